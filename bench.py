@@ -4,6 +4,7 @@
   python bench.py --gpus 1 --steps K --warmup W
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   # + what the last timed step returned, DIR/*.npy
 
 Workload (BASELINE.json configs[1], one GPU; configs[2] = the same, 1024 problems per rank):
 1024 independent planning problems per GPU, trees pre-grown (untimed) to 10,000 nodes; one
@@ -265,6 +266,39 @@ def _connect_rows(args, scenarios, capi, sc, P, seed, first_id, device):
     return rows
 
 
+DUMP_TREES = 64                           # problems whose trees --dump-outputs writes (fixed, seeded sample)
+DUMP_SEED = 20240611
+DUMP_LIMIT = 64 << 20                     # bytes, all files together
+
+
+def dump_outputs(out_dir, gpu, status, counts, prefix=""):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float64 .npy files (every value exact):
+    the per-problem status that solve() returned, the per-problem counters (the 64-bit checksum, which folds every iteration's
+    nearest index, q_new bits and verdict, as two 32-bit halves), and the trees of a fixed, seeded sample of problems."""
+    import numpy as np
+    P = gpu.n_problems
+    sample = np.sort(np.random.default_rng(DUMP_SEED).choice(P, size=min(DUMP_TREES, P), replace=False))
+    trees = [gpu.tree(int(p)) for p in sample]
+    ck = counts["checksum"].astype(np.uint64)
+    arrays = {
+        "status": status, "iterations": counts["iterations"], "nodes": counts["nodes"], "accepted": counts["accepted"],
+        "goal_node": counts["goal_node"], "stop_reason": counts["stop_reason"],
+        "checksum_hi": ck >> np.uint64(32), "checksum_lo": ck & np.uint64(0xFFFFFFFF),
+        "tree_problems": sample,
+        "tree_states": np.stack([s for s, _ in trees]), "tree_parents": np.stack([p for _, p in trees]),
+    }
+    for name, a in arrays.items():
+        if a.dtype.kind in "ui":
+            assert int(np.abs(a.astype(np.int64)).max(initial=0)) < 2 ** 53, name   # float64 holds it exactly
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -284,7 +318,13 @@ def main():
     ap.add_argument("--rank-check", type=int, default=2, help="N > 1: problems of its own shard every rank checks against the oracle")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (stream kernel, all-binary64 resident kernel)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step returned (see dump_outputs) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -354,7 +394,7 @@ def main():
     kernel_ms = 0.0
     launches = 0
     for _ in range(args.steps):
-        gpu.solve(args.iters, freeze=True)
+        status = gpu.solve(args.iters, freeze=True)
         t = gpu.last_timing()           # HIP events on the library's own stream
         kernel_ms += t["kernel_ms"]
         launches += t["launches"]
@@ -365,6 +405,8 @@ def main():
     assert done == P * args.iters * (args.steps + args.warmup)
     iters_timed = P * args.iters * args.steps
     kname = KNAME[gpu.last_timing()["kernel"]]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, gpu, status, c2, "" if world == 1 else "rank%d_" % rank)
 
     def side_run(kernel, steps=2):
         """the same workload through another kernel kind (rank 0, N = 1 only)"""

@@ -13,7 +13,7 @@
  * (tests/golden/make_golden.py) and (ii) published ChaCha test vectors for the
  * RNG block function.  Equivalence with a rustc-built oxmpl is unverified.
  *
- * Reference lines followed (relative to /root/reference):
+ * Reference lines followed (relative to the root of the oxmpl workspace, v0.4.1):
  *   oxmpl/src/geometric/planners/rrt.rs:24-27,75-83,90-128,140-227
  *   oxmpl/src/base/spaces/real_vector_state_space.rs:65-129,137-186,233-253
  *   oxmpl/src/base/states/real_vector_state.rs:5-13

@@ -4,7 +4,7 @@
 // reference's evaluation order; the translation unit is built with -ffp-contract=off so
 // that `from + (to - from) * t` keeps its three roundings (the reference, Rust, never fuses).
 //
-// Reference lines (relative to /root/reference):
+// Reference lines (relative to the root of the oxmpl workspace, v0.4.1):
 //   distance      oxmpl/src/base/spaces/real_vector_state_space.rs:137-155
 //   interpolate   oxmpl/src/base/spaces/real_vector_state_space.rs:161-186
 //   sample        oxmpl/src/base/spaces/real_vector_state_space.rs:233-249, rrt.rs:177-184

@@ -1,7 +1,7 @@
 """Synthetic workloads named by BASELINE.json's configs (inputs only; no planner logic).
 
 config 1: README quick-start, R^2, disc obstacle r=2 at the origin, start (-5,-5), goal (5,5) r=0.5
-          (/root/reference README.md:147-171, oxmpl-js/examples/simple_2d_planning.js:8-41)
+          (oxmpl README.md:147-171, oxmpl-js/examples/simple_2d_planning.js:8-41)
 wall    : the reference's own RRT test scene (oxmpl/tests/rrt_rvss_tests.rs:109-159)
 config 2: R^3, [0,10]^3, 64 random spheres, start (.5,.5,.5), goal ball (9.5,9.5,9.5) r=0.5
 config 4: SE(2) RRTConnect (BASELINE.json configs[3]): [0,10]^2 x [-PI,PI), 64 random quadrilaterals = 256 segments,

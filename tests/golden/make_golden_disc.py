@@ -2,7 +2,7 @@
 """Golden vectors for the disc goal sampler (OXHIP_GOAL_SAMPLE_UNIFORM_DISC): an independent pure-Python restatement, run only
 to (re)generate tests/golden/rrt_disc_golden.json.
 
-What it restates: GoalSampleableRegion::sample_goal of the reference's test fixture, /root/reference/oxmpl/tests/rrt_rvss_tests.rs:55-66
+What it restates: GoalSampleableRegion::sample_goal of the reference's test fixture, oxmpl/tests/rrt_rvss_tests.rs:55-66
 (angle = rng.random_range(0.0..2.0 * PI); radius = self.radius * rng.random::<f64>().sqrt(); centre + radius (cos, sin)), with rand
 0.9's transforms (random_range: the 52-bit [1, 2) - 1 form; random::<f64>(): (u64 >> 11) * 2^-53 -- restated from memory, the crate
 is not in the image: PARITY UNPINNED as everywhere) and the build's portable sin / cos (ox_sincos: Cody-Waite reduction by pi/2 in

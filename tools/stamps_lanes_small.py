@@ -1,5 +1,5 @@
 import os, sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oxmpl_amd import capi, scenarios
 sc = scenarios.config2()
 for N in (500, 2000):
