@@ -69,11 +69,24 @@ typedef enum oxhip_planner_kind {
 
 /* State space of a batch.  oxmpl has RealVectorStateSpace, SO2StateSpace and SO3StateSpace; SE(2) is not in the
  * reference (docs/BACKLOG.md:12-14) and is assembled here from the first two (see rrt_connect_se2.hip):
- * state (x, y, theta), distance = 1.0 * d_xy + 0.5 * d_theta, extent = extent_xy + 0.5 * PI. */
+ * state (x, y, theta), distance = 1.0 * d_xy + 0.5 * d_theta, extent = extent_xy + 0.5 * PI.
+ * SO(3) is SO3StateSpace itself (rrt_so3.hip): states are quaternions (x, y, z, w) -- normalising them is the caller's job, as
+ * in the reference -- and the config's bounds are REINTERPRETED: bounds[0..3] = the centre quaternion, bounds[4] = max_angle
+ * (so3_state_space.rs:57-76: negative = OXHIP_ERR_ZERO_VOLUME, the mirror of StateSpaceError; clamped to PI; NaN reads as PI,
+ * as f64::min has it; the unbounded space is centre (0, 0, 0, 1) and max_angle PI); bounds[5..] are ignored.
+ * distance = abs_dot > 1 - 1e-9 ? 0 : acos(abs_dot); interpolate = LERP + normalise above |dot| 0.9995, else SLERP; extent
+ * 0.5 * PI.  acos / sin are the portable routines ox_acos / ox_sincos (below one ulp; the CPU test suite restates them), so
+ * against a rustc-built oxmpl (libm) a run is within a few ulp per evaluation, not bit-exact: PARITY UNPINNED.
+ * Validity: oxhip_rrt_batch_set_spheres with 4-wide centres, read as cones in the SO(3) metric -- a state is valid iff
+ * distance(centre, q) > radius for every cone (strict; the ForbiddenConeChecker of oxmpl/tests/rrt_so3ss_tests.rs:46-56). */
 typedef enum oxhip_space_kind {
     OXHIP_SPACE_REAL_VECTOR = 0,  /* RealVectorStateSpace(dim)  oxmpl/src/base/spaces/real_vector_state_space.rs */
-    OXHIP_SPACE_SE2 = 1           /* R^2 x SO(2): dim must be 3, bounds = (x), (y), (theta: clamped to [-PI, PI]);
+    OXHIP_SPACE_SE2 = 1,          /* R^2 x SO(2): dim must be 3, bounds = (x), (y), (theta: clamped to [-PI, PI]);
                                      planner must be OXHIP_PLANNER_RRT_CONNECT; validity = oxhip_rrt_batch_set_segments */
+    OXHIP_SPACE_SO3 = 2           /* SO3StateSpace  oxmpl/src/base/spaces/so3_state_space.rs: dim must be 4, bounds as above;
+                                     planner must be OXHIP_PLANNER_RRT with kernel OXHIP_KERNEL_AUTO or OXHIP_KERNEL_STREAM (both run
+                                     rrt_so3.hip); goal = ball in the SO(3) distance, sample_goal = OXHIP_GOAL_SAMPLE_CENTRE;
+                                     validity = cones (oxhip_rrt_batch_set_spheres; set_boxes is OXHIP_ERR_BAD_ARG) */
 } oxhip_space_kind;
 
 /* GoalSampleableRegion::sample_goal of the ball goal (goal.rs:35-41; the trait leaves the distribution to the implementor).
@@ -102,7 +115,8 @@ typedef enum oxhip_debug_flag {
     OXHIP_DEBUG_STAR_TWO_PASS = 32,       /* rrt_star_wire.hip: neighbour lists by a second search instead of the counting pass's chunks */
     OXHIP_DEBUG_STAR_ONE_SEGMENT = 64,    /* rrt_star_wire.hip: one edge-check segment, no overlap with the wiring stream */
     OXHIP_DEBUG_SE2_NO_SEGMENT_GRID = 128,/* rrt_connect_se2.hip / rrt_connect.hip: every interpolated state is tested against every segment / sphere (no grid lookup) */
-    OXHIP_DEBUG_SE2_SMALL_LDS = 256       /* rrt_connect_se2.hip: the shape for batches larger than the chip (512-node shadows, segments from HBM / L2) whatever the batch size */
+    OXHIP_DEBUG_SE2_SMALL_LDS = 256,      /* rrt_connect_se2.hip: the shape for batches larger than the chip (512-node shadows, segments from HBM / L2) whatever the batch size */
+    OXHIP_DEBUG_SO3_SERIAL_SAMPLER = 512  /* rrt_so3.hip: sample_uniform attempt by attempt on one lane instead of 64 attempts side by side */
 } oxhip_debug_flag;
 
 typedef enum oxhip_kernel_kind {
@@ -273,7 +287,8 @@ int32_t oxhip_interpolate_batch(int32_t device, uint32_t dim, const double* from
                                 const double* t, uint32_t n, double* out);
 
 /* StateValidityChecker::is_valid for n states and RRT::check_motion (rrt.rs:90-116) for n
- * (from,to) pairs against the batch's current sphere/box field and space resolution. */
+ * (from,to) pairs against the batch's current sphere/box field and space resolution (SE(2): segments; SO(3): cones,
+ * interpolated as the SO(3) space does). */
 int32_t oxhip_rrt_batch_is_valid(oxhip_rrt_batch* b, const double* states, uint32_t n, uint8_t* out);
 int32_t oxhip_rrt_batch_check_motion(oxhip_rrt_batch* b, const double* from, const double* to,
                                      uint32_t n, uint8_t* out);
@@ -287,6 +302,12 @@ int32_t oxhip_f64_op_batch(int32_t device, uint32_t op, const double* a, const d
  * op 0: out[i] = (se2_distance(a_i, b_i), so2_normalise(a_i.theta), so2_distance(a_i.theta, b_i.theta))
  * op 1: out[i] = se2_interpolate(a_i, b_i, t[i])        (so2_state_space.rs:97-122, so2_state.rs:33-37) */
 int32_t oxhip_se2_op_batch(int32_t device, uint32_t op, const double* a, const double* b, const double* t, uint32_t n,
+                           double* out);
+/* SO(3) arithmetic self-test hooks (so3_state_space.rs:101-159), n rows of quaternions (x, y, z, w):
+ * op 0: out[i] = distance(a_i, b_i)                       out[n]
+ * op 1: out[i] = interpolate(a_i, b_i, t[i]), t in [0, 1]  out[n][4]
+ * op 2: out[i] = ox_acos(a[i]), a read as n scalars (b and t may be NULL)   out[n] */
+int32_t oxhip_so3_op_batch(int32_t device, uint32_t op, const double* a, const double* b, const double* t, uint32_t n,
                            double* out);
 /* device RNG self-test: the first n u64 words of the (seed, stream) ChaCha12 stream */
 int32_t oxhip_rng_u64_batch(int32_t device, uint64_t seed, uint64_t stream, uint32_t n, uint64_t* out);

@@ -85,6 +85,83 @@ class SphereBoxValidityChecker:
         self.boxes = [([float(v) for v in lo], [float(v) for v in hi]) for lo, hi in boxes]
 
 
+class SO3State:
+    """oxmpl_py.base.SO3State (oxmpl-py/src/base/so3_state.rs): a rotation as the quaternion (x, y, z, w).  Not normalised
+    on construction, as in the reference (oxmpl/src/base/states/so3_state.rs:21-30)."""
+
+    def __init__(self, x, y, z, w):
+        self.x, self.y, self.z, self.w = float(x), float(y), float(z), float(w)
+
+    @staticmethod
+    def identity():
+        return SO3State(0.0, 0.0, 0.0, 1.0)
+
+    @property
+    def values(self):
+        return [self.x, self.y, self.z, self.w]
+
+    def __eq__(self, other):
+        return isinstance(other, SO3State) and self.values == other.values
+
+    def __repr__(self):
+        return "<SO3State x=%r, y=%r, z=%r, w=%r>" % (self.x, self.y, self.z, self.w)
+
+
+class SO3StateSpace:
+    """oxmpl_py.base.SO3StateSpace (oxmpl-py/src/base/so3_state_space.rs): SO3StateSpace(bounds=None | (SO3State, max_angle)).
+    None: the identity and PI, every rotation.  A negative max_angle is ValueError (StateSpaceError::InvalidAngularDistance);
+    max_angle is clamped to PI (oxmpl/src/base/spaces/so3_state_space.rs:57-76).  `distance` is evaluated by the HIP library."""
+
+    def __init__(self, bounds=None):
+        if bounds is None:
+            centre, max_angle = SO3State.identity(), math.pi
+        else:
+            centre, max_angle = bounds
+            if not isinstance(centre, SO3State):
+                raise TypeError("bounds must be (SO3State, max_angle)")
+            max_angle = float(max_angle)
+            if max_angle < 0.0:
+                raise ValueError("Invalid angular distance: %s must not be negative." % max_angle)
+            max_angle = math.pi if max_angle != max_angle else min(max_angle, math.pi)
+        self.bounds = (centre, max_angle)
+        self.dimension = 4
+        self.longest_valid_segment_fraction = 0.05
+
+    def distance(self, state1, state2):
+        a = np.array([state1.values], dtype=np.float64)
+        b = np.array([state2.values], dtype=np.float64)
+        return float(capi.so3_op_batch(0, a, b)[0])
+
+    def get_maximum_extent(self):
+        return 0.5 * math.pi
+
+    def set_longest_valid_segment_fraction(self, fraction):
+        if 0.0 < fraction <= 1.0:
+            self.longest_valid_segment_fraction = float(fraction)
+        elif fraction <= 0.0:
+            self.longest_valid_segment_fraction = 0.0
+        else:
+            self.longest_valid_segment_fraction = 1.0
+
+    def config_bounds(self):
+        """the C ABI's reading of oxhip_rrt_config.bounds for SO(3): (cx, cy, cz, cw, max_angle)"""
+        return self.bounds[0].values + [self.bounds[1]]
+
+
+class SO3ConeValidityChecker:
+    """Device-describable StateValidityChecker of SO(3): a state is valid iff distance(centre, q) > radius for every cone
+    (strict) -- the ForbiddenConeChecker of oxmpl/tests/rrt_so3ss_tests.rs:46-56, one or more of them.  Pass it to
+    RRT.setup() with an SO(3) ProblemDefinition."""
+
+    def __init__(self, cones=()):
+        self.cones = []
+        for centre, radius in cones:
+            c = centre.values if isinstance(centre, SO3State) else [float(v) for v in centre]
+            if len(c) != 4:
+                raise ValueError("a cone's centre is a quaternion (x, y, z, w)")
+            self.cones.append((list(c), float(radius)))
+
+
 class ProblemDefinition:
     """oxmpl_py.base.ProblemDefinition (oxmpl-py/src/base/problem_definition.rs:43-75)"""
 
@@ -102,6 +179,18 @@ class ProblemDefinition:
             raise TypeError("the GPU path needs a ball goal: an object with `target` and `radius` attributes")
         if len(start_state.values) != space.dimension or len(goal.target.values) != space.dimension:
             raise ValueError("state dimension does not match the space")
+        return ProblemDefinition(space, start_state, goal)
+
+    @staticmethod
+    def from_so3(space, start_state, goal):
+        """oxmpl_py ProblemDefinition.from_so3 (oxmpl-py/src/base/problem_definition.rs:105-131).  `goal`: any object with a
+        `target` (SO3State) and a `radius`; is_satisfied(s) = distance(s, target) <= radius, sample_goal() = target."""
+        if not isinstance(space, SO3StateSpace):
+            raise TypeError("space must be an SO3StateSpace")
+        if not hasattr(goal, "target") or not hasattr(goal, "radius"):
+            raise TypeError("the GPU path needs a ball goal: an object with `target` and `radius` attributes")
+        if not isinstance(start_state, SO3State) or not isinstance(goal.target, SO3State):
+            raise TypeError("start_state and goal.target must be SO3State")
         return ProblemDefinition(space, start_state, goal)
 
 

@@ -25,10 +25,11 @@ DEBUG_PAIR_TO_WHOLE_TREE, DEBUG_AUDIT, DEBUG_ALL_WHOLE_TREE, DEBUG_ONE_LANE_ROUN
 DEBUG_STAR_TWO_PASS, DEBUG_STAR_ONE_SEGMENT = 32, 64
 DEBUG_SE2_NO_SEGMENT_GRID = 128
 DEBUG_SE2_SMALL_LDS = 256
+DEBUG_SO3_SERIAL_SAMPLER = 512
 ABI_VERSION = 2
 STAMP_WORDS = 64
 PLANNER_RRT, PLANNER_RRT_CONNECT, PLANNER_RRT_STAR = 0, 1, 2
-SPACE_REAL_VECTOR, SPACE_SE2 = 0, 1
+SPACE_REAL_VECTOR, SPACE_SE2, SPACE_SO3 = 0, 1, 2
 
 # every symbol include/oxmpl_hip.h declares (tests check the library exports them all)
 EXPORTS = [
@@ -40,7 +41,7 @@ EXPORTS = [
     "oxhip_rrt_batch_last_timing", "oxhip_rrt_batch_enable_stamps", "oxhip_rrt_batch_get_stamps",
     "oxhip_nn_argmin_batch", "oxhip_distance_batch",
     "oxhip_interpolate_batch", "oxhip_rrt_batch_is_valid", "oxhip_rrt_batch_check_motion",
-    "oxhip_f64_op_batch", "oxhip_se2_op_batch", "oxhip_rng_u64_batch",
+    "oxhip_f64_op_batch", "oxhip_se2_op_batch", "oxhip_so3_op_batch", "oxhip_rng_u64_batch",
     "oxhip_prm_create", "oxhip_prm_destroy", "oxhip_prm_set_spheres", "oxhip_prm_set_boxes", "oxhip_prm_setup",
     "oxhip_prm_set_problem", "oxhip_prm_construct_roadmap", "oxhip_prm_get_sizes", "oxhip_prm_get_roadmap",
     "oxhip_prm_solve", "oxhip_prm_get_query_sets", "oxhip_prm_last_timing", "oxhip_prm_knn_exact_rows",
@@ -115,6 +116,7 @@ def lib():
         L.oxhip_rrt_batch_set_boxes.argtypes = [C.c_void_p, _dp, _dp, C.c_uint32]
         L.oxhip_rrt_batch_set_segments.argtypes = [C.c_void_p, _dp, C.c_uint32, C.c_double]
         L.oxhip_se2_op_batch.argtypes = [C.c_int32, C.c_uint32, _dp, _dp, _dp, C.c_uint32, _dp]
+        L.oxhip_so3_op_batch.argtypes = [C.c_int32, C.c_uint32, _dp, _dp, _dp, C.c_uint32, _dp]
         L.oxhip_rrt_batch_setup.argtypes = [C.c_void_p, _dp, _dp, _dp]
         L.oxhip_rrt_batch_set_tree.argtypes = [C.c_void_p, C.c_uint32, _dp, _i32p, C.c_uint32]
         L.oxhip_rrt_batch_solve.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_uint32, _i32p]
@@ -185,7 +187,11 @@ def _p(a, t=_dp):
 
 class RRTBatch:
     """P independent oxmpl RRT planners (RealVectorStateSpace, ball goal, sphere/box validity)
-    grown on one GPU.  Thin wrapper of the oxhip_rrt_batch_* entry points."""
+    grown on one GPU.  Thin wrapper of the oxhip_rrt_batch_* entry points.
+
+    space=SPACE_SO3 (dim 4, quaternions (x, y, z, w)): `bounds` is (cx, cy, cz, cw, max_angle) -- SO3StateSpace's centre
+    quaternion and cone of freedom, as include/oxmpl_hip.h reinterprets the config's bounds -- and set_spheres takes the
+    forbidden cones (centre quaternion, radius in the SO(3) distance)."""
 
     def __init__(self, dim, bounds, max_distance, goal_bias, n_problems, max_nodes=10000,
                  lvs_fraction=0.05, stop_at_goal=True, seed=0, first_problem_id=0, device=0,
@@ -195,7 +201,11 @@ class RRTBatch:
         cfg.struct_size = C.sizeof(Config)
         cfg.dim = dim
         b = _f64(bounds).reshape(-1)
-        if b.size != 2 * dim:
+        if space == SPACE_SO3:
+            if b.size != 5:
+                raise OxhipError(ERR_BAD_ARG, "SO(3) bounds are (cx, cy, cz, cw, max_angle)")
+            b = np.concatenate([b, np.zeros(2 * dim - 5 if dim >= 3 else 0)])
+        elif b.size != 2 * dim:
             raise OxhipError(ERR_BAD_ARG, "bounds must hold dim (lo,hi) pairs")  # StateSpaceError::DimensionMismatch
         for i, v in enumerate(b[:2 * MAX_DIM]):  # dim > MAX_DIM is rejected by the library
             cfg.bounds[i] = v
@@ -385,6 +395,21 @@ def se2_op_batch(op, a, b, t=None, device=0):
     out = np.empty_like(a)
     tt = None if t is None else _f64(t).reshape(-1)
     _check(lib().oxhip_se2_op_batch(device, op, _p(a), _p(b), None if tt is None else _p(tt), a.shape[0], _p(out)))
+    return out
+
+
+def so3_op_batch(op, a, b=None, t=None, device=0):
+    """SO(3) arithmetic on the device: op 0 distance(a_i, b_i) -> [n]; op 1 interpolate(a_i, b_i, t_i) -> [n, 4];
+    op 2 ox_acos(a_i) of n scalars -> [n]"""
+    if op == 2:
+        a = _f64(a).reshape(-1)
+        out = np.empty(a.size, dtype=np.float64)
+        _check(lib().oxhip_so3_op_batch(device, op, _p(a), None, None, a.size, _p(out)))
+        return out
+    a, b = _f64(a).reshape(-1, 4), _f64(b).reshape(-1, 4)
+    out = np.empty((a.shape[0], 4) if op == 1 else a.shape[0], dtype=np.float64)
+    tt = None if t is None else _f64(t).reshape(-1)
+    _check(lib().oxhip_so3_op_batch(device, op, _p(a), _p(b), None if tt is None else _p(tt), a.shape[0], _p(out)))
     return out
 
 

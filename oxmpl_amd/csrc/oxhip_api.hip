@@ -171,8 +171,29 @@ int32_t oxhip_rrt_batch_create(const oxhip_rrt_config* cfg, oxhip_rrt_batch** ou
         return fail(OXHIP_ERR_BAD_ARG, "the disc sampler is built for RRT / RRT* on the stream, lane-per-query and cell-grid kernels");
     double fraction = cfg->lvs_fraction, res = 0.0;
     double th_lo = 0.0, th_hi = 0.0;
-    if (cfg->space > OXHIP_SPACE_SE2) return fail(OXHIP_ERR_BAD_ARG, "unknown space kind");
-    if (cfg->space == OXHIP_SPACE_SE2) {
+    double so3_max_angle = 0.0;
+    if (cfg->space > OXHIP_SPACE_SO3) return fail(OXHIP_ERR_BAD_ARG, "unknown space kind");
+    if (cfg->space == OXHIP_SPACE_SO3) {
+        if (cfg->dim != 4) return fail(OXHIP_ERR_BAD_ARG, "SO(3) states are quaternions (x, y, z, w): dim must be 4");
+        if (cfg->planner != OXHIP_PLANNER_RRT) return fail(OXHIP_ERR_BAD_ARG, "SO(3) is built for RRT only");
+        if (cfg->kernel != OXHIP_KERNEL_AUTO && cfg->kernel != OXHIP_KERNEL_STREAM)
+            return fail(OXHIP_ERR_BAD_ARG, "SO(3) RRT runs on rrt_so3.hip: kernel must be OXHIP_KERNEL_AUTO or OXHIP_KERNEL_STREAM");
+        for (uint32_t k = 0; k < 4; ++k)
+            if (!(std::fabs(cfg->bounds[k]) <= kMaxMagnitude)) return fail(OXHIP_ERR_BAD_ARG, "SO(3) centre not finite or beyond 1e150");
+        // SO3StateSpace::new (so3_state_space.rs:57-76): a negative max_angle is StateSpaceError::InvalidAngularDistance;
+        // max_angle.min(PI) (NaN gives PI, as f64::min does)
+        const double pi = 3.14159265358979323846;
+        so3_max_angle = cfg->bounds[4];
+        if (so3_max_angle < 0.0) return fail(OXHIP_ERR_ZERO_VOLUME, "SO(3): max_angle must not be negative");
+        so3_max_angle = std::isnan(so3_max_angle) ? pi : std::fmin(so3_max_angle, pi);
+        // extent = 0.5 * PI (so3_state_space.rs:81-84); lvsl = extent * fraction (:234-236); res = lvsl * 0.1 (rrt.rs:97)
+        if (fraction > 0.0 && fraction <= 1.0) {} else if (fraction <= 0.0) fraction = 0.0; else fraction = 1.0;
+        const double lvsl = 0.5 * pi * fraction;
+        res = lvsl * 0.1;
+        if (!(res > 0.0)) return fail(OXHIP_ERR_BAD_ARG, "longest valid segment length is 0: check_motion would never terminate");
+        // no SO(3) distance exceeds 0.5 * PI (acos of |dot| >= 0), so that bounds the step count of any motion
+        if (0.5 * pi / res > 1e6) return fail(OXHIP_ERR_BAD_ARG, "more than 1e6 validity checks per edge");
+    } else if (cfg->space == OXHIP_SPACE_SE2) {
         if (cfg->dim != 3) return fail(OXHIP_ERR_BAD_ARG, "SE(2) states are (x, y, theta): dim must be 3");
         if (cfg->planner != OXHIP_PLANNER_RRT_CONNECT) return fail(OXHIP_ERR_BAD_ARG, "SE(2) is built for RRTConnect only");
         // SO2StateSpace::new (so2_state_space.rs:57-72): lo >= hi is InvalidBound; bounds clamped to [-PI, PI]
@@ -193,7 +214,7 @@ int32_t oxhip_rrt_batch_create(const oxhip_rrt_config* cfg, oxhip_rrt_batch** ou
         int32_t sr = space_resolution(cfg->dim, cfg->bounds, fraction, res);
         if (sr != OXHIP_OK) return sr;
     }
-    if (cfg->max_distance / res > 1e6) return fail(OXHIP_ERR_BAD_ARG, "more than 1e6 validity checks per edge");
+    if (cfg->space != OXHIP_SPACE_SO3 && cfg->max_distance / res > 1e6) return fail(OXHIP_ERR_BAD_ARG, "more than 1e6 validity checks per edge");
 
     int32_t st = select_device(cfg->device);
     if (st != OXHIP_OK) return st;
@@ -211,6 +232,10 @@ int32_t oxhip_rrt_batch_create(const oxhip_rrt_config* cfg, oxhip_rrt_batch** ou
         dp.scale[k] = dp.hi[k] - dp.lo[k];
     }
     if (cfg->space == OXHIP_SPACE_SE2) { dp.lo[2] = th_lo; dp.hi[2] = th_hi; dp.scale[2] = th_hi - th_lo; }
+    if (cfg->space == OXHIP_SPACE_SO3) {
+        for (uint32_t k = 0; k < 4; ++k) { dp.so3_centre[k] = cfg->bounds[k]; dp.lo[k] = dp.hi[k] = dp.scale[k] = 0.0; }
+        dp.so3_max_angle = so3_max_angle;
+    }
     dp.space = cfg->space;
     dp.max_distance = cfg->max_distance;
     dp.res = res;
@@ -316,6 +341,7 @@ int32_t oxhip_rrt_batch_create(const oxhip_rrt_config* cfg, oxhip_rrt_batch** ou
     dp.goal_c = b->goal_c.p; dp.goal_thr = b->goal_thr.p; dp.goal_r = b->goal_r.p;
 
     uint32_t kind = cfg->kernel;
+    if (cfg->space == OXHIP_SPACE_SO3) kind = OXHIP_KERNEL_STREAM;   // rrt_so3.hip (its one kernel, reported as the streaming kind)
     if (cfg->planner != OXHIP_PLANNER_RRT) kind = b->star_wired ? (b->star_geo_cells ? OXHIP_KERNEL_CELLS : OXHIP_KERNEL_LANES) : OXHIP_KERNEL_STREAM;
     if (kind == OXHIP_KERNEL_AUTO)
     {
@@ -374,7 +400,7 @@ int32_t oxhip_rrt_batch_create(const oxhip_rrt_config* cfg, oxhip_rrt_batch** ou
     }
     b->kernel_kind = kind;
     b->last_kind = kind;
-    if ((cfg->planner == OXHIP_PLANNER_RRT && kind == OXHIP_KERNEL_STREAM) || cfg->planner == OXHIP_PLANNER_RRT_STAR) {   // (RRT*: star_shadow's)
+    if ((cfg->planner == OXHIP_PLANNER_RRT && kind == OXHIP_KERNEL_STREAM && cfg->space != OXHIP_SPACE_SO3) || cfg->planner == OXHIP_PLANNER_RRT_STAR) {   // (RRT*: star_shadow's)
         // the streaming kernels screen their scans over an fl32 shadow of the tree, which they maintain themselves
         hipError_t e2 = b->tree32.alloc((size_t)P * dim * cap);
         if (e2 == hipSuccess) e2 = b->shadow_state.alloc((size_t)P * 2);
@@ -424,6 +450,10 @@ int32_t oxhip_rrt_batch_set_spheres(oxhip_rrt_batch* b, const double* centres, c
     if ((st = upload(b->sph_c, c, b->stream)) != OXHIP_OK) return st;
     if ((st = upload(b->sph_thr, thr, b->stream)) != OXHIP_OK) return st;
     b->dp.n_spheres = n; b->dp.sph_c = b->sph_c.p; b->dp.sph_thr = b->sph_thr.p;
+    if (b->cfg.space == OXHIP_SPACE_SO3) {   // cones: distance(centre, q) > radius in the SO(3) metric, compared with the radius itself
+        if ((st = upload(b->sph_r, std::vector<double>(radii, radii + n), b->stream)) != OXHIP_OK) return st;
+        b->dp.sph_r = b->sph_r.p;
+    }
     b->sph_centres.assign(centres, centres + (size_t)n * dim);
     b->sph_radii.assign(radii, radii + n);
     b->filt_dirty = true;
@@ -433,6 +463,7 @@ int32_t oxhip_rrt_batch_set_spheres(oxhip_rrt_batch* b, const double* centres, c
 int32_t oxhip_rrt_batch_set_boxes(oxhip_rrt_batch* b, const double* lo, const double* hi, uint32_t n) {
     if (!b || (n && (!lo || !hi))) return fail(OXHIP_ERR_BAD_ARG, "null argument");
     if (b->cfg.space == OXHIP_SPACE_SE2) return fail(OXHIP_ERR_BAD_ARG, "SE(2) batches take oxhip_rrt_batch_set_segments");
+    if (b->cfg.space == OXHIP_SPACE_SO3) return fail(OXHIP_ERR_BAD_ARG, "SO(3) batches take cones (oxhip_rrt_batch_set_spheres)");
     int32_t st = select_device(b->cfg.device);
     if (st != OXHIP_OK) return st;
     const uint32_t dim = b->cfg.dim;
@@ -490,8 +521,8 @@ int32_t oxhip_rrt_batch_setup(oxhip_rrt_batch* b, const double* starts, const do
     b->starts.assign(starts, starts + (size_t)P * dim);
     b->filt_dirty = true;
     std::vector<double> thr(P);
-    // R^n: satisfied iff d2 <= T(radius); SE(2): the compound distance is compared with the radius itself
-    for (uint32_t p = 0; p < P; ++p) thr[p] = b->cfg.space == OXHIP_SPACE_SE2 ? goal_radii[p] : sqrt_le_threshold(goal_radii[p]);
+    // R^n: satisfied iff d2 <= T(radius); SE(2) / SO(3): the space's distance is compared with the radius itself
+    for (uint32_t p = 0; p < P; ++p) thr[p] = b->cfg.space != OXHIP_SPACE_REAL_VECTOR ? goal_radii[p] : sqrt_le_threshold(goal_radii[p]);
     std::vector<ProblemState> states(P);
     for (auto& s : states) {
         s = ProblemState{};
@@ -752,7 +783,7 @@ int32_t oxhip_rrt_batch_solve(oxhip_rrt_batch* b, uint64_t max_iterations, doubl
     int32_t st = select_device(b->cfg.device);
     if (st != OXHIP_OK) return st;
     if (b->cfg.planner != OXHIP_PLANNER_RRT && freeze) return fail(OXHIP_ERR_BAD_ARG, "freeze is for the RRT planner");
-    if ((st = refresh_filter(b)) != OXHIP_OK) return st;
+    if (b->cfg.space != OXHIP_SPACE_SO3 && (st = refresh_filter(b)) != OXHIP_OK) return st;   // (rrt_so3.hip tests every cone)
     if (std::isnan(timeout_s) || timeout_s < 0.0)   // Duration cannot be negative; from_secs_f32 (oxmpl-py rrt.rs:112) panics on both
         return fail(OXHIP_ERR_BAD_ARG, "timeout_s is NaN or negative (0 or +inf = no wall-clock limit)");
     const bool has_timeout = timeout_s > 0.0 && std::isfinite(timeout_s);
@@ -778,6 +809,7 @@ int32_t oxhip_rrt_batch_solve(oxhip_rrt_batch* b, uint64_t max_iterations, doubl
         b->last_kind = kind;
         HIP_TRY(hipEventRecord(b->ev0, b->stream));
         if (b->cfg.space == OXHIP_SPACE_SE2) launch_rrt_connect_se2(b->dp, b->stream);
+        else if (b->cfg.space == OXHIP_SPACE_SO3) launch_rrt_so3(b->dp, b->stream);
         else if (b->cfg.planner == OXHIP_PLANNER_RRT_CONNECT) launch_rrt_connect(b->dp, b->stream);
         else if (b->cfg.planner == OXHIP_PLANNER_RRT_STAR && b->star_wired) {
             // geometry: exactly RRT's loop on the same stream (rrt_star_wire.hip's header); then wire the new nodes
@@ -1103,6 +1135,7 @@ int32_t oxhip_rrt_batch_is_valid(oxhip_rrt_batch* b, const double* states, uint3
     OX_TRY(to_device(ds, states, (size_t)n * b->cfg.dim, b->stream));
     HIP_TRY(dout.alloc(n));
     if (b->cfg.space == OXHIP_SPACE_SE2) launch_se2_is_valid(b->dp, ds.p, n, dout.p, b->stream);
+    else if (b->cfg.space == OXHIP_SPACE_SO3) launch_so3_is_valid(b->dp, ds.p, n, dout.p, b->stream);
     else launch_is_valid(b->dp, ds.p, n, dout.p, b->stream);
     HIP_TRY(hipGetLastError());
     return to_host(out, dout, n, b->stream);
@@ -1118,6 +1151,7 @@ int32_t oxhip_rrt_batch_check_motion(oxhip_rrt_batch* b, const double* from, con
     OX_TRY(to_device(db, to, (size_t)n * b->cfg.dim, b->stream));
     HIP_TRY(dout.alloc(n));
     if (b->cfg.space == OXHIP_SPACE_SE2) launch_se2_check_motion(b->dp, da.p, db.p, n, dout.p, b->stream);
+    else if (b->cfg.space == OXHIP_SPACE_SO3) launch_so3_check_motion(b->dp, da.p, db.p, n, dout.p, b->stream);
     else launch_check_motion(b->dp, da.p, db.p, n, dout.p, b->stream);
     HIP_TRY(hipGetLastError());
     return to_host(out, dout, n, b->stream);
@@ -1159,6 +1193,26 @@ int32_t oxhip_se2_op_batch(int32_t device, uint32_t op, const double* a, const d
     launch_se2_op(op, da.p, db.p, dt.p, n, dout.p, ts.s);
     HIP_TRY(hipGetLastError());
     return to_host(out, dout, (size_t)3 * n, ts.s);
+}
+
+int32_t oxhip_so3_op_batch(int32_t device, uint32_t op, const double* a, const double* b, const double* t, uint32_t n,
+                           double* out) {
+    if (!a || !out || op > 2 || (op <= 1 && !b) || (op == 1 && !t)) return fail(OXHIP_ERR_BAD_ARG, "bad argument");
+    if (n == 0) return OXHIP_OK;
+    OX_TRY(select_device(device));
+    TmpStream ts;
+    HIP_TRY(oxhip_stream_acquire(device, &ts.s));
+    ts.device = device;
+    const size_t w = op == 2 ? 1 : 4;          // doubles per row of a (and b)
+    const size_t w_out = op == 1 ? 4 : 1;      // ... of out
+    DevBuf<double> da, db, dt, dout;
+    OX_TRY(to_device(da, a, w * n, ts.s));
+    if (op <= 1) OX_TRY(to_device(db, b, (size_t)4 * n, ts.s));
+    if (op == 1) OX_TRY(to_device(dt, t, n, ts.s));
+    HIP_TRY(dout.alloc(w_out * n));
+    launch_so3_op(op, da.p, db.p, dt.p, n, dout.p, ts.s);
+    HIP_TRY(hipGetLastError());
+    return to_host(out, dout, w_out * n, ts.s);
 }
 
 int32_t oxhip_rng_u64_batch(int32_t device, uint64_t seed, uint64_t stream, uint32_t n, uint64_t* out) {

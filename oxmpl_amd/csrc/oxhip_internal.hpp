@@ -35,6 +35,12 @@ void launch_se2_op(uint32_t op, const double* a, const double* b, const double* 
 void launch_se2_is_valid(const DevParams& p, const double* states, uint32_t n, uint8_t* out, hipStream_t s);
 void launch_se2_check_motion(const DevParams& p, const double* from, const double* to, uint32_t n, uint8_t* out, hipStream_t s);
 
+// rrt_so3.hip: RRT over SO3StateSpace with the forbidden-cone checker, one wave per problem
+void launch_rrt_so3(const DevParams& p, hipStream_t stream);
+void launch_so3_op(uint32_t op, const double* a, const double* b, const double* t, uint32_t n, double* out, hipStream_t s);
+void launch_so3_is_valid(const DevParams& p, const double* states, uint32_t n, uint8_t* out, hipStream_t s);
+void launch_so3_check_motion(const DevParams& p, const double* from, const double* to, uint32_t n, uint8_t* out, hipStream_t s);
+
 // rrt_star.hip: RRT* (rrt_star.rs), one 256-thread workgroup per problem
 void launch_rrt_star(const DevParams& p, hipStream_t stream);
 

@@ -157,6 +157,9 @@ struct DevParams {
     const uint64_t* sph_grid;
     uint32_t sph_grid_G;
     const uint64_t* star_sph_grid;   // the same for RRT*'s edge checks: filter balls of motions up to search_radius long (null: none)
+    // SO(3) only (rrt_so3.hip): SO3StateSpace's bounds (centre quaternion, max_angle clamped to PI); the cones are sph_c / sph_r
+    double so3_centre[4];
+    double so3_max_angle;
 };
 
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }

@@ -1,0 +1,317 @@
+// rrt_so3.hip -- RRT (oxmpl/src/geometric/planners/rrt.rs:170-225) over SO3StateSpace (unit quaternions,
+// oxmpl/src/base/spaces/so3_state_space.rs) with the forbidden-cone checker of the reference's SO(3) fixture
+// (oxmpl/tests/rrt_so3ss_tests.rs:46-56).  Arithmetic: so3_device.hpp.
+//
+// ONE WAVE PER PROBLEM (a 64-thread workgroup, four per CU -- the shape of rrt_connect.hip / rrt_connect_se2.hip): an
+// iteration is a chain of dependent steps, so what counts is the length of that chain.  The tree lives in HBM as SoA
+// [4][cap] (every store lands there) and its first kSo3N nodes are mirrored in LDS; the cones are staged in LDS when they
+// fit.  Per iteration:
+//   sample    lane j evaluates rejection attempt j of sample_uniform (so3_state_space.rs:201-231) -- words 1 + 4j .. 4j + 4
+//             after the Bernoulli word -- and a ballot takes the first accepted attempt (so3_sample below)
+//   nearest   each lane computes the exact distance (acos included) of its strided nodes, strict '<' in ascending index
+//             order, then the wave's lexicographic (distance, index) minimum: the reference's argmin with the lowest index
+//             among ties.  No binary32 screen: the distance is not a norm, and parity needs none.
+//   steer     interpolate(q_near, q_rand, max_distance / min_dist) when min_dist > max_distance  (rrt.rs:199-208)
+//   motion    the interpolated states of check_motion (rrt.rs:90-116) are dealt to the lanes, 64 per pass
+//   insert    lane 0 stores node n (HBM + LDS mirror), then the goal test distance(q_new, target) <= radius
+// The checksum is the per-iteration polynomial of ABI 2 (rrt_device.hpp, iter_digest) over the four coordinates.
+#include "oxhip_internal.hpp"
+#include "rrt_device.hpp"
+#include "so3_device.hpp"
+
+namespace oxhip {
+
+constexpr int kSo3N = 1024;        // tree nodes mirrored in LDS (32 B each); beyond that nodes are read from HBM / L2
+constexpr int kSo3LdsCones = 32;   // cones staged in LDS; more are read from HBM / L2
+
+template <int NC>
+struct So3Shared {
+    uint32_t rng_buf[16][64];   // the sampler's window: 64 ChaCha12 blocks = 512 words
+    double4 node[kSo3N];        // (x, y, z, w) of the first kSo3N nodes
+    double cone_c[4][NC];       // cone centres, SoA (the layout of DevParams::sph_c)
+    double cone_r[NC];          // cone radii as given
+};
+static_assert(sizeof(So3Shared<kSo3LdsCones>) <= 40960, "four problems per CU");
+
+__device__ __forceinline__ double so3_readlane(double v, int l) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
+    return __hiloint2double(hi, lo);
+}
+
+// rand 0.9 random_range(-1.0..1.0) from one word: (bits >> 12 | 1.0) - 1.0, times scale 2.0, plus -1.0; false when rand would
+// draw again (res >= 1.0: not reachable for this range -- the largest value is 1 - 2^-51 -- but stated as rand states it)
+__device__ __forceinline__ bool so3_range_word(uint64_t w, double& res) {
+    const double v01 = __longlong_as_double((long long)((w >> 12) | 0x3FF0000000000000ull)) - 1.0;
+    res = v01 * 2.0;
+    res = res + -1.0;
+    return res < 1.0;
+}
+
+// one rejection attempt of so3_state_space.rs:213-229 from its four coordinates; true when accepted (q written)
+__device__ __forceinline__ bool so3_attempt(const double v[4], const double centre[4], double max_angle, double q[4]) {
+    const double x2 = v[0] * v[0], y2 = v[1] * v[1], z2 = v[2] * v[2], w2 = v[3] * v[3];
+    double ns = x2 + y2;
+    ns = ns + z2;
+    ns = ns + w2;
+    if (!(ns > 1e-9 && ns < 1.0)) return false;
+    const double norm = sqrt(ns);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) q[k] = v[k] / norm;
+    return so3_distance(centre, q) <= max_angle;
+}
+
+// sample_uniform by one lane after the other, word by word (random_range redraws included)
+__device__ __forceinline__ void so3_sample_serial(RngWindow& rng, const DevParams& p, double q[4]) {
+    for (;;) {
+        double v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            while (!so3_range_word(rng.next<false>(), v[k])) {}
+        if (so3_attempt(v, p.so3_centre, p.so3_max_angle, q)) return;
+    }
+}
+
+// rrt.rs:177-184 with SO3StateSpace::sample_uniform and the ball goal's sample_goal (the target, no draw).  Wave-uniform result.
+// Lane j evaluates attempt j of the round (its four words follow the 4 j words of the attempts before it); the first accepted
+// attempt wins and the stream moves past it.  A round without an accepted attempt moves 256 words on and tries the next 64.  A
+// range redraw at or before the winner (or the test switch OXHIP_DEBUG_SO3_SERIAL_SAMPLER) hands the sample to the serial form.
+__device__ __forceinline__ void so3_sample(RngWindow& rng, const DevParams& p, const double target[4], uint32_t lane, double q[4]) {
+    bool goal;
+    if (p.p_int == ~0ull) goal = true;              // Bernoulli ALWAYS_TRUE: no draw
+    else goal = rng.next<false>() < p.p_int;        // one u64
+    if (goal || p.so3_max_angle < 1e-9) {           // the target / the centre of a degenerate space (so3_state_space.rs:204-206)
+        const double* src = goal ? target : p.so3_centre;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] = src[k];
+        return;
+    }
+    if (p.dbg_flags & OXHIP_DEBUG_SO3_SERIAL_SAMPLER) { so3_sample_serial(rng, p, q); return; }
+    for (;;) {
+        const uint64_t pos = rng.pos;
+        if ((pos >> 3) - rng.base_blk >= 64 || pos + 256 > (rng.base_blk + 64) * 8) {   // the window must hold the round's 256 words
+            rng.base_blk = uni64(pos >> 3);
+            uint32_t o[16];
+            chacha12_block(rng.seed, rng.base_blk + lane, rng.stream, o);
+#pragma unroll
+            for (int w = 0; w < 16; ++w) rng.buf[w][lane] = o[w];
+        }
+        const uint32_t rel0 = (uint32_t)(pos - rng.base_blk * 8) + 4u * lane;
+        double v[4];
+        bool redraw = false;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t a = rel0 + (uint32_t)k, bl = a >> 3, w = (a & 7u) * 2u;
+            const uint64_t word = ((uint64_t)rng.buf[w + 1][bl] << 32) | rng.buf[w][bl];
+            redraw = redraw || !so3_range_word(word, v[k]);
+        }
+        double qa[4] = {0.0, 0.0, 0.0, 0.0};
+        const bool acc = !redraw && so3_attempt(v, p.so3_centre, p.so3_max_angle, qa);
+        const uint64_t am = __ballot(acc), rm = __ballot(redraw);
+        const uint32_t L = am ? (uint32_t)__builtin_ctzll(am) : 64u;
+        const uint64_t upto = L >= 63u ? ~0ull : (2ull << L) - 1ull;
+        if (rm & upto) { so3_sample_serial(rng, p, q); return; }   // (rng.pos is still the round's start)
+        if (am == 0) { rng.pos = uni64(pos + 256); continue; }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] = so3_readlane(qa[k], (int)L);
+        rng.pos = uni64(pos + 4ull * (L + 1u));
+        return;
+    }
+}
+
+// check_motion (rrt.rs:90-116) by one wave: lane s tests state s + 1 of the steps 1 ..= nsteps (or `to` alone when nsteps <= 1)
+// against every cone; returns the wave-uniform verdict "some state is invalid".  is_valid is pure, so testing a whole pass of
+// states equals the reference's first-invalid early exit.
+__device__ __forceinline__ bool so3_motion_invalid_wave(const double* cc, uint32_t stride, const double* cr, uint32_t nc,
+                                                        const double from[4], const double to[4], double res, uint32_t lane) {
+    if (nc == 0) return false;
+    const uint32_t nsteps = num_steps_u32(so3_distance(from, to), res);
+    const uint32_t S = nsteps <= 1u ? 1u : nsteps;
+    const double dn = (double)nsteps;
+    for (uint32_t s0 = 0; s0 < S; s0 += 64u) {
+        const uint32_t s = s0 + lane;
+        bool bad = false;
+        if (s < S) {
+            double st[4] = {to[0], to[1], to[2], to[3]};
+            if (nsteps > 1u) so3_interpolate(from, to, (double)(s + 1u) / dn, st);
+            bad = so3_cone_hit(cc, stride, cr, nc, st);
+        }
+        if (__ballot(bad) != 0) return true;
+        if (s0 + 64u < s0) break;   // (no wrap at 2^32)
+    }
+    return false;
+}
+
+template <bool LDS_CONES>
+__global__ __launch_bounds__(64) void rrt_so3_kernel(DevParams p) {
+    const uint32_t prob = blockIdx.x, lane = threadIdx.x;
+    __shared__ So3Shared<LDS_CONES ? kSo3LdsCones : 1> sh;
+    ProblemState st = p.state[prob];
+    if (p.stop_at_goal && st.goal_node >= 0) return;   // already solved: solve() is idempotent
+    const uint32_t nc = p.n_spheres;
+    const double* cc = p.sph_c;
+    const double* cr = p.sph_r;
+    uint32_t stride = nc;
+    if (LDS_CONES) {   // the checker's table at LDS latency
+        for (uint32_t i = lane; i < nc; i += 64u) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) sh.cone_c[k][i] = p.sph_c[(size_t)k * nc + i];
+            sh.cone_r[i] = p.sph_r[i];
+        }
+        cc = &sh.cone_c[0][0];
+        cr = sh.cone_r;
+        stride = (uint32_t)kSo3LdsCones;
+    }
+    const size_t cap = p.cap;
+    double* tree = p.tree + (size_t)prob * 4 * cap;
+    int32_t* parent = p.parent + (size_t)prob * cap;
+    const double target[4] = {p.goal_c[(size_t)prob * 4], p.goal_c[(size_t)prob * 4 + 1], p.goal_c[(size_t)prob * 4 + 2],
+                              p.goal_c[(size_t)prob * 4 + 3]};
+    const double goal_radius = p.goal_thr[prob];   // the radius itself: the goal test compares the SO(3) distance
+
+    uint32_t n = st.n_nodes;
+    const uint32_t n_lds0 = n < (uint32_t)kSo3N ? n : (uint32_t)kSo3N;
+    for (uint32_t i = lane; i < n_lds0; i += 64u)   // a solve call continues the tree an earlier one (or set_tree) left in HBM
+        sh.node[i] = make_double4(tree[i], tree[cap + i], tree[2 * cap + i], tree[3 * cap + i]);
+    RngWindow rng;
+    rng.init(sh.rng_buf, p.seed, p.first_problem_id + prob, st.draws);
+    __syncthreads();
+
+    int32_t stop = 1;   // OXHIP_STOP_ITERATIONS
+    uint64_t h = uni64(st.checksum);
+    for (uint64_t it = 0; it < p.budget; ++it) {
+        if (!p.freeze && n >= p.max_nodes) { stop = 2; break; }
+
+        // 2. sample (rrt.rs:177-184)
+        double q[4];
+        so3_sample(rng, p, target, lane, q);
+
+        // 3. nearest neighbour (rrt.rs:187-196): lexicographic (distance, index) minimum; a NaN distance of node 0 keeps node 0
+        //    (every later comparison with it fails), a NaN elsewhere never wins
+        const uint32_t n_lds = n < (uint32_t)kSo3N ? n : (uint32_t)kSo3N;
+        Exact e{__builtin_inf(), 0xFFFFFFFFu};
+        double d0 = 0.0;
+        for (uint32_t i = lane; i < n_lds; i += 64u) {
+            const double4 c4 = sh.node[i];
+            const double c[4] = {c4.x, c4.y, c4.z, c4.w};
+            const double d = so3_distance(c, q);
+            if (i == 0) d0 = d;
+            if (d < e.dist) { e.dist = d; e.idx = i; }
+        }
+        for (uint32_t i = n_lds + lane; i < n; i += 64u) {   // nodes beyond the mirror (indices keep ascending within a lane)
+            const double c[4] = {tree[i], tree[cap + i], tree[2 * cap + i], tree[3 * cap + i]};
+            const double d = so3_distance(c, q);
+            if (d < e.dist) { e.dist = d; e.idx = i; }
+        }
+        e = exact_wave_reduce(e);
+        d0 = so3_readlane(d0, 0);
+        uint32_t nearest = e.idx;
+        double min_dist = e.dist;
+        if (d0 != d0 || nearest == 0xFFFFFFFFu) { nearest = 0; min_dist = d0; }
+        nearest = uni(nearest);
+        double q_near[4];
+        if (nearest < (uint32_t)kSo3N) {
+            const double4 c4 = sh.node[nearest];
+            q_near[0] = c4.x; q_near[1] = c4.y; q_near[2] = c4.z; q_near[3] = c4.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) q_near[k] = tree[(size_t)k * cap + nearest];
+        }
+
+        // 4. steer (rrt.rs:199-208)
+        double q_new[4];
+        if (min_dist > p.max_distance) {
+            const double t = p.max_distance / min_dist;
+            so3_interpolate(q_near, q, t, q_new);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) q_new[k] = q[k];
+        }
+
+        // 5. check_motion (rrt.rs:211 -> :90-116)
+        const bool ok = !so3_motion_invalid_wave(cc, stride, cr, nc, q_near, q_new, p.res, lane);
+
+        h = chk_push(h, iter_digest<4>(nearest, q_new, 4, ok));
+        st.iterations++;
+
+        bool hit = false;
+        if (ok) {
+            st.accepted++;
+            if (!p.freeze) {
+                // 6. insert (rrt.rs:213-217)
+                if (lane == 0) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) tree[(size_t)k * cap + n] = q_new[k];
+                    parent[n] = (int32_t)nearest;
+                    if (n < (uint32_t)kSo3N) sh.node[n] = make_double4(q_new[0], q_new[1], q_new[2], q_new[3]);
+                }
+                // the next scan is this wave's own and LDS is in order per wave (the fences keep the compiler from moving the store)
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                ++n;
+                // 7. goal test (rrt.rs:220-223)
+                if (so3_distance(q_new, target) <= goal_radius) {
+                    if (st.goal_node < 0) st.goal_node = (int32_t)(n - 1);
+                    hit = true;
+                }
+            }
+        }
+        if (hit && p.stop_at_goal) { stop = 0; break; }
+    }
+    if (lane == 0) {
+        st.checksum = h;
+        st.n_nodes = n;
+        st.draws = rng.pos;
+        st.stop_reason = stop;
+        p.state[prob] = st;
+    }
+}
+
+void launch_rrt_so3(const DevParams& p, hipStream_t stream) {
+    const dim3 grid(p.n_problems), block(64);
+    if (p.n_spheres <= (uint32_t)kSo3LdsCones) hipLaunchKernelGGL(rrt_so3_kernel<true>, grid, block, 0, stream, p);
+    else hipLaunchKernelGGL(rrt_so3_kernel<false>, grid, block, 0, stream, p);
+}
+
+// ---- stand-alone primitives (parity tests of the SO(3) arithmetic and of the checker)
+__global__ void so3_op_kernel(uint32_t op, const double* a, const double* b, const double* t, uint32_t n, double* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (op == 2) { out[i] = ox_acos(a[i]); return; }
+    const double x[4] = {a[4 * (size_t)i], a[4 * (size_t)i + 1], a[4 * (size_t)i + 2], a[4 * (size_t)i + 3]};
+    const double y[4] = {b[4 * (size_t)i], b[4 * (size_t)i + 1], b[4 * (size_t)i + 2], b[4 * (size_t)i + 3]};
+    if (op == 0) { out[i] = so3_distance(x, y); return; }
+    double o[4];
+    so3_interpolate(x, y, t[i], o);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) out[4 * (size_t)i + k] = o[k];
+}
+void launch_so3_op(uint32_t op, const double* a, const double* b, const double* t, uint32_t n, double* out, hipStream_t s) {
+    hipLaunchKernelGGL(so3_op_kernel, dim3((n + 255) / 256), dim3(256), 0, s, op, a, b, t, n, out);
+}
+
+__global__ void so3_is_valid_kernel(DevParams p, const double* states, uint32_t n, uint8_t* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double s[4] = {states[4 * (size_t)i], states[4 * (size_t)i + 1], states[4 * (size_t)i + 2], states[4 * (size_t)i + 3]};
+    out[i] = so3_cone_hit(p.sph_c, p.n_spheres, p.sph_r, p.n_spheres, s) ? 0 : 1;
+}
+void launch_so3_is_valid(const DevParams& p, const double* states, uint32_t n, uint8_t* out, hipStream_t s) {
+    hipLaunchKernelGGL(so3_is_valid_kernel, dim3((n + 255) / 256), dim3(256), 0, s, p, states, n, out);
+}
+
+// one wave per motion
+__global__ __launch_bounds__(256) void so3_check_motion_kernel(DevParams p, const double* from, const double* to, uint32_t n,
+                                                                uint8_t* out) {
+    const uint32_t m = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (m >= n) return;
+    const double f[4] = {from[4 * (size_t)m], from[4 * (size_t)m + 1], from[4 * (size_t)m + 2], from[4 * (size_t)m + 3]};
+    const double g[4] = {to[4 * (size_t)m], to[4 * (size_t)m + 1], to[4 * (size_t)m + 2], to[4 * (size_t)m + 3]};
+    const bool any = so3_motion_invalid_wave(p.sph_c, p.n_spheres, p.sph_r, p.n_spheres, f, g, p.res, lane);
+    if (lane == 0) out[m] = any ? 0 : 1;
+}
+void launch_so3_check_motion(const DevParams& p, const double* from, const double* to, uint32_t n, uint8_t* out, hipStream_t s) {
+    hipLaunchKernelGGL(so3_check_motion_kernel, dim3((n + 3) / 4), dim3(256), 0, s, p, from, to, n, out);
+}
+
+}  // namespace oxhip

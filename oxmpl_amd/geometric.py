@@ -10,7 +10,8 @@ drop-in for users of the reference's Python API.
 import numpy as np
 
 from . import capi
-from .base import Path, ProblemDefinition, RealVectorState, SphereBoxValidityChecker
+from .base import (Path, ProblemDefinition, RealVectorState, SO3ConeValidityChecker, SO3State, SO3StateSpace,
+                   SphereBoxValidityChecker)
 
 _MESSAGES = {  # Display strings of PlanningError (oxmpl/src/base/error.rs:110-136)
     capi.ERR_TIMEOUT: "No solution found within timeout.",
@@ -45,7 +46,9 @@ class RRT:
 
     def setup(self, validity_checker):
         """Planner::setup (rrt.rs:140-156).  The reference takes a Python callable here; the GPU path
-        takes a SphereBoxValidityChecker (see oxmpl_amd.base)."""
+        takes a SphereBoxValidityChecker (see oxmpl_amd.base), or an SO3ConeValidityChecker for an SO(3) problem (RRT only)."""
+        if isinstance(self._pd.space, SO3StateSpace):
+            return self._setup_so3(validity_checker)
         if not isinstance(validity_checker, SphereBoxValidityChecker):
             raise TypeError("the GPU path cannot call a Python function per interpolated state; "
                             "describe the obstacles with oxmpl_amd.base.SphereBoxValidityChecker")
@@ -68,6 +71,29 @@ class RRT:
         self._batch = b
         self._checker = validity_checker
 
+    def _setup_so3(self, validity_checker):
+        if self._PLANNER != capi.PLANNER_RRT:
+            raise TypeError("SO(3) is built for RRT only")
+        if not isinstance(validity_checker, SO3ConeValidityChecker):
+            raise TypeError("the GPU path cannot call a Python function per interpolated state; "
+                            "describe the forbidden cones with oxmpl_amd.base.SO3ConeValidityChecker")
+        pd = self._pd
+        if self._batch is not None:
+            self._batch.close()
+        try:
+            b = capi.RRTBatch(4, pd.space.config_bounds(), self.max_distance, self.goal_bias, 1,
+                              lvs_fraction=pd.space.longest_valid_segment_fraction, stop_at_goal=True, planner=capi.PLANNER_RRT,
+                              space=capi.SPACE_SO3, **self._opts)
+        except capi.OxhipError as e:
+            if e.status in (capi.ERR_ZERO_VOLUME, capi.ERR_BAD_ARG):
+                raise ValueError(str(e)) from None
+            raise
+        if validity_checker.cones:
+            b.set_spheres([c for c, _ in validity_checker.cones], [r for _, r in validity_checker.cones])
+        b.setup(pd.start_state.values, pd.goal.target.values, float(pd.goal.radius))
+        self._batch = b
+        self._checker = validity_checker
+
     def solve(self, timeout_secs):
         """Planner::solve (rrt.rs:158-227); errors surface as Exception(message) like the reference
         (oxmpl-py/src/geometric/rrt.rs:117)."""
@@ -83,6 +109,8 @@ class RRT:
         st = self._batch.solve(1 << 40, timeout_s=timeout_secs)
         if st[0] != capi.OK:
             raise Exception(_MESSAGES.get(int(st[0]), capi.status_string(int(st[0]))))
+        if isinstance(self._pd.space, SO3StateSpace):
+            return Path([SO3State(*row) for row in self._batch.path(0)])
         return Path([RealVectorState(row) for row in self._batch.path(0)])
 
     def is_state_valid(self, state):

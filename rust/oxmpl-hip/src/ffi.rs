@@ -32,6 +32,8 @@ pub const OXHIP_PLANNER_RRT_STAR: u32 = 2;
 pub const OXHIP_KERNEL_AUTO: u32 = 0;
 pub const OXHIP_SPACE_REAL_VECTOR: u32 = 0;
 pub const OXHIP_SPACE_SE2: u32 = 1;
+/// SO3StateSpace (rrt_so3.hip): dim 4, quaternions (x, y, z, w); bounds[0..4] = centre quaternion, bounds[4] = max_angle
+pub const OXHIP_SPACE_SO3: u32 = 2;
 // oxhip_goal_sampler: what GoalSampleableRegion::sample_goal draws (goal.rs:35-41)
 pub const OXHIP_GOAL_SAMPLE_CENTRE: u32 = 0;
 pub const OXHIP_GOAL_SAMPLE_UNIFORM_DISC: u32 = 1;
@@ -184,6 +186,8 @@ extern "C" {
     ) -> i32;
     pub fn oxhip_distance_batch(device: i32, dim: u32, a: *const f64, b: *const f64, n: u32, out: *mut f64) -> i32;
     pub fn oxhip_interpolate_batch(device: i32, dim: u32, from: *const f64, to: *const f64, t: *const f64, n: u32, out: *mut f64) -> i32;
+    /// SO(3) self-test hook: op 0 distance, op 1 interpolate, op 2 ox_acos (so3_state_space.rs:101-159)
+    pub fn oxhip_so3_op_batch(device: i32, op: u32, a: *const f64, b: *const f64, t: *const f64, n: u32, out: *mut f64) -> i32;
 
     // ---- PRM (prm.rs)
     pub fn oxhip_prm_create(cfg: *const OxhipPrmConfig, out: *mut *mut OxhipPrm) -> i32;

@@ -33,8 +33,8 @@ use oxmpl::base::error::PlanningError;
 use oxmpl::base::goal::GoalSampleableRegion;
 use oxmpl::base::planner::{Path, Planner};
 use oxmpl::base::problem_definition::ProblemDefinition;
-use oxmpl::base::space::{RealVectorStateSpace, StateSpace};
-use oxmpl::base::state::RealVectorState;
+use oxmpl::base::space::{RealVectorStateSpace, SO3StateSpace, StateSpace};
+use oxmpl::base::state::{RealVectorState, SO3State};
 use oxmpl::base::validity::StateValidityChecker;
 
 type Pd<G> = ProblemDefinition<RealVectorState, RealVectorStateSpace, G>;
@@ -530,4 +530,56 @@ impl<D: DeviceValidityChecker, G: DeviceGoal> Planner<RealVectorState, RealVecto
         }
         Ok(Path(flat.chunks(dim).map(|c| RealVectorState::new(c.to_vec())).collect()))
     }
+}
+
+// ---- SO(3) (rrt_so3.hip): RRT over SO3StateSpace with forbidden cones.  Minimal for now: the configuration and the
+// device's distance; a `Planner<SO3State, SO3StateSpace, G>` implementation in the shape of HipRRT is the next step.
+
+/// `oxhip_rrt_config` of an SO(3) RRT batch of one problem: RRT::new(max_distance, goal_bias) over `space`.  The config's
+/// bounds carry SO3StateSpace::bounds (centre quaternion, max_angle); `lvs_fraction` is the space's
+/// longest_valid_segment_fraction (a private field of SO3StateSpace, 0.05 unless set).  Cones go in through
+/// `oxhip_rrt_batch_set_spheres` with 4-wide centres.
+pub fn so3_rrt_config(space: &SO3StateSpace, max_distance: f64, goal_bias: f64, lvs_fraction: f64, options: &HipOptions) -> ffi::OxhipRrtConfig {
+    let (centre, max_angle) = &space.bounds;
+    let mut bounds = [0.0f64; 2 * ffi::OXHIP_MAX_DIM];
+    bounds[0] = centre.x;
+    bounds[1] = centre.y;
+    bounds[2] = centre.z;
+    bounds[3] = centre.w;
+    bounds[4] = *max_angle;
+    ffi::OxhipRrtConfig {
+        struct_size: ffi::OXHIP_RRT_CONFIG_SIZE as u32,
+        dim: 4,
+        bounds,
+        max_distance,
+        goal_bias,
+        lvs_fraction,
+        n_problems: 1,
+        max_nodes: options.max_nodes,
+        stop_at_goal: 1,
+        kernel: ffi::OXHIP_KERNEL_AUTO,
+        seed: options.seed,
+        first_problem_id: options.stream,
+        device: options.device,
+        planner: ffi::OXHIP_PLANNER_RRT,
+        search_radius: 0.0,
+        space: ffi::OXHIP_SPACE_SO3,
+        goal_sampler: ffi::OXHIP_GOAL_SAMPLE_CENTRE,
+        debug_flags: 0,
+        star_pool_share: 0,
+        frozen_split: 0,
+        reserved: 0,
+    }
+}
+
+/// SO3StateSpace::distance evaluated by the device (ox_acos: within one ulp of libm's acos), for checking a binding
+pub fn so3_device_distance(device: i32, a: &SO3State, b: &SO3State) -> Result<f64, String> {
+    let qa = [a.x, a.y, a.z, a.w];
+    let qb = [b.x, b.y, b.z, b.w];
+    let mut out = 0.0f64;
+    let st = unsafe { ffi::oxhip_so3_op_batch(device, 0, qa.as_ptr(), qb.as_ptr(), ptr::null(), 1, &mut out) };
+    if st != ffi::OXHIP_OK {
+        return Err(last_error());
+    }
+    Ok(out)
 }
