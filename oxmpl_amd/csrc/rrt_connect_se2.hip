@@ -301,6 +301,14 @@ __device__ __forceinline__ double readlane_f64(double v, int l) {
     return __hiloint2double(hi, lo);
 }
 constexpr float kSe2PiUp = 3.14159274f;   // fl32(PI), which is > PI
+// The screen's magnitude guard (the R^n kernels' ScreenMargins::usable): beyond binary32's range fl32(x) is +-inf, and the
+// difference of two same-signed infinities is NaN -- an estimate no threshold test can place.  Nor can +inf: a node whose square
+// overflowed fails `d^ <= thr` whenever another node's estimate is finite, though it may be the nearer one.  Below 2^62 every fl32
+// coordinate is at most 2^62, every difference below 2^63, dx^2 + dy^2 below 2^127: every estimate is finite.  So the screen runs
+// only when the largest |x|, |y| of the trees (Se2Range::mag, +inf when a coordinate is beyond binary32) and of the query are
+// below 2^62; otherwise the query takes the exact path.  (The "far" filler of unused shadow slots may still square to +inf: it is
+// no node.)
+constexpr float kSe2MagMax = 0x1p62f;
 __device__ __forceinline__ float se2_screen(const float4 s, float qx, float qy, float qt) {
     const float dx = s.x - qx, dy = s.y - qy;
     const float r = __builtin_amdgcn_sqrtf(__builtin_fmaf(dy, dy, dx * dx));
@@ -327,7 +335,8 @@ __device__ __forceinline__ void se2_nearest(const Se2Tree& tree, uint32_t n, con
                                             uint32_t& nearest, double& min_dist, double q_near[3]) {
     const float qx = (float)q[0], qy = (float)q[1], qt = (float)q[2];
     const uint32_t ns = n < tree.N ? n : tree.N;
-    const bool screen = rg.theta_ok && fabsf(qt) <= kSe2PiUp;
+    const float mag = fmaxf(rg.mag, fmaxf(fabsf(qx), fabsf(qy)));
+    const bool screen = rg.theta_ok && fabsf(qt) <= kSe2PiUp && mag < kSe2MagMax;
     float thr = __builtin_inff();
     bool slow = !screen || n > ns;
     float b1 = __builtin_inff(), b2 = __builtin_inff();
@@ -351,7 +360,6 @@ __device__ __forceinline__ void se2_nearest(const Se2Tree& tree, uint32_t n, con
         }
         if (!slow && i1 != 0xFFFFFFFFu) tree.load(i1, c);   // in flight across the reduction: almost always it is the lane's only candidate
         const float m = __uint_as_float(wave_min_u32(__float_as_uint(b1)));   // (estimates are >= +0: their bit patterns order like they do)
-        const float mag = fmaxf(rg.mag, fmaxf(fabsf(qx), fabsf(qy)));
         thr = m + (mag + 3.2f) * (2.02f * 32.0f * 0x1p-24f);
         slow = slow || __ballot(b2 <= thr) != 0;
     }
@@ -490,7 +498,8 @@ __device__ __forceinline__ void se2_round(const DevParams& p, const double* segs
     const Se2Tree tree{e2 ? t_e2.g : t_spec.g, e2 ? t_e2.sh : t_spec.sh, t_spec.cap, t_spec.N};
     const uint32_t n = e2 ? n_e2 : n_spec;
     const float qx = (float)q[0], qy = (float)q[1], qt = (float)q[2];
-    bool slow = !rg.theta_ok || !(fabsf(qt) <= kSe2PiUp) || n > tree.N || (p.n_segs != 0u && p.seg_grid == nullptr);
+    const float mag = fmaxf(rg.mag, fmaxf(fabsf(qx), fabsf(qy)));
+    bool slow = !rg.theta_ok || !(fabsf(qt) <= kSe2PiUp) || !(mag < kSe2MagMax) || n > tree.N || (p.n_segs != 0u && p.seg_grid == nullptr);
     const uint32_t ns = n < tree.N ? n : tree.N;
     const uint32_t ns_max = n_spec > n_e2 && pend ? (n_spec < tree.N ? n_spec : tree.N) : (pend ? (n_e2 < tree.N ? n_e2 : tree.N) : ns);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // (this wave's stores first: se2_nearest)
@@ -508,7 +517,6 @@ __device__ __forceinline__ void se2_round(const DevParams& p, const double* segs
     double c[3] = {0.0, 0.0, 0.0};
     if (i1 != 0xFFFFFFFFu) tree.load(i1, c);
     const float m = __uint_as_float(group8_min_u32(__float_as_uint(b1)));
-    const float mag = fmaxf(rg.mag, fmaxf(fabsf(qx), fabsf(qy)));
     const float thr = m + (mag + 3.2f) * (2.02f * 32.0f * 0x1p-24f);
     slow = slow || (__ballot(b2 <= thr) & gm) != 0;
     const bool cand = b1 <= thr;
@@ -554,7 +562,8 @@ __device__ __forceinline__ void se2_round(const DevParams& p, const double* segs
     if (STAMP) { const uint64_t t3 = se2_clock<STAMP>(); acc[1] += t1 - t0; acc[2] += t2 - t1; acc[3] += t3 - t2; acc[9] += 1; }
 }
 
-// shadow of the first nodes of a tree an earlier launch (or setup) left in HBM; folds them into the screen's range
+// shadow of the first nodes of a tree an earlier launch (or setup) left in HBM; folds them into the screen's range (a coordinate
+// beyond binary32 makes mag +inf: kSe2MagMax then keeps every query of the launch on the exact path)
 __device__ __forceinline__ void se2_shadow_load(const Se2Tree& tree, uint32_t n, uint32_t lane, Se2Range& rg) {
     float mag = 0.0f;
     bool ok = true;

@@ -65,6 +65,15 @@ def wall():
                 boxes=(np.array([[4.75, 2.0]]), np.array([[5.25, 8.0]])))
 
 
+# (scale, offset) frames of the SE(2) scenes' (x, y) plane, headings left as they are (tests/test_gpu_se2.py, tools/fuzz_parity.py).
+# Offsets (at 4e6 a binary32 coordinate is off by up to 1/8: the screen separates little) and 1e-12 (the heading term decides);
+# 1e18 and (2.4e18, -1.2e19) keep |x|, |y| below 2^64 while node distances cross sqrt(FLT_MAX) = 1.8e19, where binary32 squares
+# overflow; 1e36 has finite binary32 coordinates; 1e38 puts the start inside binary32's range and the goal beyond it; 1e40, 1e100
+# and offset 1e39 lie wholly beyond it.  Offset 1e39 needs a scale of its own: at unit scale x + 10 == x in binary64.
+SE2_FRAMES = [(1.0, 1.0e3), (1.0, 1.0e6), (1.0, 4.0e6), (1.0, -5.0e4), (1.0e-12, 0.0), (1.0e18, 0.0), (2.4e18, -1.2e19),
+              (1.0e36, 0.0), (1.0e38, 0.0), (1.0e40, 0.0), (1.0e100, 0.0), (1.0e28, 1.0e39)]
+
+
 def config2():
     start, goal = [0.5, 0.5, 0.5], [9.5, 9.5, 9.5]
     return dict(dim=3, bounds=[(0.0, 10.0)] * 3, max_distance=0.5, goal_bias=0.05, lvs_fraction=0.05,

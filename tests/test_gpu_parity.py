@@ -878,3 +878,127 @@ def test_rrt_connect_rarely_taken_paths_of_the_one_wave_kernel():
             o.solve(budget)
             _assert_same_connect(g, p, o, c, gc)
         g.close()
+
+
+# RRTConnect in moved and scaled frames: R^2 / R^3 with spheres only (the motion check looks them up in the sphere grid, cell =
+# (x - lo) G / w), the same with one box (no grid), and R^5
+def _connect_scene(name, boxed):
+    if name == "r3":
+        sc = dict(scenarios.config2())
+    else:
+        dim = 2 if name == "r2" else 5
+        start, goal = [0.5] * dim, [9.5] * dim
+        sph = scenarios.sphere_field(seed=0x5EED0011 + dim, n=40 if dim == 2 else 60, dim=dim, rmin=0.3 if dim == 2 else 1.2,
+                                     rmax=0.8 if dim == 2 else 2.2, keep_clear=[start, goal])
+        sc = dict(dim=dim, bounds=[(0.0, 10.0)] * dim, max_distance=0.5 if dim == 2 else 0.9, goal_bias=0.05, lvs_fraction=0.05,
+                  start=start, goal_centre=goal, goal_radius=0.5, spheres=sph, boxes=None)
+    if boxed:
+        sc["boxes"] = (np.array([[4.4] * sc["dim"]]), np.array([[5.6] * sc["dim"]]))
+    return sc
+
+
+def _connect_frame(sc, scale, offset):
+    t = lambda v: np.asarray(v, dtype=np.float64) * scale + offset
+    c, r = sc["spheres"]
+    out = dict(sc, bounds=[(float(t(lo)), float(t(hi))) for lo, hi in sc["bounds"]], max_distance=sc["max_distance"] * scale,
+               start=list(t(sc["start"])), goal_centre=list(t(sc["goal_centre"])), goal_radius=sc["goal_radius"] * scale,
+               spheres=(t(c), np.asarray(r, dtype=np.float64) * scale))
+    if sc["boxes"] is not None:
+        out["boxes"] = (t(sc["boxes"][0]), t(sc["boxes"][1]))
+    return out
+
+
+@pytest.mark.parametrize("scale,offset", [(1.0, 1.0e3), (1.0, 1.0e6), (1.0, -5.0e4), (1.0e-12, 0.0), (1.0e18, 0.0), (1.0e60, 0.0),
+                                          (1.0e40, 0.0)], ids=lambda v: "%g" % v)
+@pytest.mark.parametrize("name,boxed", [("r2", False), ("r3", False), ("r2", True), ("r3", True), ("r5", False)],
+                         ids=["r2", "r3", "r2-box", "r3-box", "r5"])
+def test_rrt_connect_translated_and_scaled_spaces(name, boxed, scale, offset):
+    """rrt_connect.hip's counterpart of test_rrt_translated_and_scaled_spaces: both trees, merged path, checksum, iterations and
+    stop reason equal the oracle's far from the origin, at 1e-12, at 1e18 and 1e60, and beyond binary32 (1e40: the magnitude the
+    known-step-count test folds in is +inf there)"""
+    sc = _connect_frame(_connect_scene(name, boxed), scale, offset)
+    P, budget, max_nodes = 4, 1500, 800
+    gpu = scenarios.make_batch(sc, P, max_nodes, True, 23, 60, 0, 0, capi.PLANNER_RRT_CONNECT)
+    gpu.solve(budget)
+    c, gc = gpu.counts(), gpu.goal_counts()
+    for p in range(P):
+        o = _oracle_connect(sc, 23, 60 + p, max_nodes)
+        o.solve(budget)
+        assert int(c["stop_reason"][p]) == o.stop_reason
+        _assert_same_connect(gpu, p, o, c, gc)
+        assert o.num_nodes(0) + o.num_nodes(1) > 20   # the scene still lets the trees grow
+    gpu.close()
+
+
+def _host_adv_steps(max_distance, res):
+    """oxhip_api.hip's rule, restated: an Advanced extend's step count is the constant ceil(max_distance / res) when that ratio
+    is farther than 1e-6 from an integer; returns (adv_steps or 0, adv_slack)"""
+    r = max_distance / res
+    c = math.ceil(r)
+    gap = min(r - (c - 1.0), c - r)
+    if math.isfinite(r) and 1.0 <= c < 4294967295.0 and gap > 1e-6:
+        return int(c), 0.5 * gap * res
+    return 0, 0.0
+
+
+def _rv_res(bounds, fraction):
+    acc = 0.0
+    for lo, hi in bounds:
+        w = hi - lo
+        acc = acc + w * w
+    return math.sqrt(acc) * fraction * 0.1
+
+
+def test_rrt_connect_known_step_count_boundary():
+    """The constant step count of an Advanced extend (adv_steps, taken when (mag + max |q| + 1 + max_distance) 2^-45 < adv_slack).
+    (1) max_distance / res just beyond and just inside the host's 1e-6 gap from an integer, on both sides of it, at offsets where
+    that condition holds for every query, for part of them and for none: parity with the oracle (which always takes
+    ceil(distance / res)) around the boundary of the rule.  (2) Far from the origin (1e10, -3e10) the rounding of an Advanced
+    motion's length exceeds the gap, so ceil(distance / res) really differs from adv_steps for many motions, and among 1,200 thin
+    spheres the states a motion check tests decide its verdict: a kernel that took the constant there would part from the oracle."""
+    base = _connect_scene("r2", False)
+    res = _rv_res(base["bounds"], base["lvs_fraction"])   # (translation leaves the widths, and so res, as they are)
+    k, P, budget = 7, 6, 1500
+
+    def run(sc, n_problems):
+        assert _rv_res(sc["bounds"], sc["lvs_fraction"]) == res
+        gpu = scenarios.make_batch(sc, n_problems, 600, True, 13, 7, 0, 0, capi.PLANNER_RRT_CONNECT)
+        gpu.solve(budget)
+        c, gc = gpu.counts(), gpu.goal_counts()
+        oracles = []
+        for p in range(n_problems):
+            o = _oracle_connect(sc, 13, 7 + p, 600)
+            o.solve(budget)
+            assert int(c["stop_reason"][p]) == o.stop_reason
+            _assert_same_connect(gpu, p, o, c, gc)
+            oracles.append(o)
+        gpu.close()
+        return oracles
+
+    host = []
+    for g in (1.25e-6, -1.25e-6, 0.8e-6, -0.8e-6):
+        md = (k + g) * res
+        steps, slack = _host_adv_steps(md, res)
+        host.append(steps)
+        # mag (the goal tree starts at offset + 9.5) + max |q| spans 2 offset + [9.5, 20]: the condition holds for every query
+        # below T - 10, for part of them at T - 7.5, for none above T - 4.75
+        T = (0.5 * abs(g) * res * 2.0 ** 45 - 1.0 - md) / 2.0
+        for off in (0.5 * T, T - 7.5, 1.5 * T):
+            run(_connect_frame(dict(base, max_distance=md), 1.0, float(round(off))), P)   # (integral: the widths stay exactly 10)
+    assert host == [k + 1, k, 0, 0]   # (the construction: the constant just beyond the gap on either side of k, none inside it)
+    # (2) thin obstacles far out
+    start, goal = [0.5, 0.5], [9.5, 9.5]
+    thin = dict(base, spheres=scenarios.sphere_field(seed=0x5EED0021, n=1200, dim=2, lo=0.5, hi=9.5, rmin=0.02, rmax=0.04,
+                                                     keep_clear=[start, goal]))
+    differ = 0
+    for g in (1.25e-6, -1.25e-6):
+        md = (k + g) * res
+        steps, _ = _host_adv_steps(md, res)
+        for off in (1.0e10, -3.0e10):
+            for o in run(_connect_frame(dict(thin, max_distance=md), 1.0, off), 12):
+                for w in (0, 1):
+                    st, par = o.tree(w)
+                    for i in range(1, len(par)):
+                        d = orc.distance(st[par[i]], st[i])
+                        differ += abs(d - md) < 1e-3 and math.ceil(d / res) != steps
+    assert differ > 0   # Advanced motions whose step count is not the constant were taken (and many more were tested)

@@ -10,7 +10,7 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
-from oxmpl_amd import capi  # noqa: E402
+from oxmpl_amd import capi, scenarios  # noqa: E402
 from oracle import oracle_py as orc  # noqa: E402
 
 rng = np.random.default_rng(1)   # re-seeded by sweep()
@@ -40,6 +40,9 @@ def case_rv(planner):
     dim = int(rng.choice([1, 2, 2, 3, 3, 3, 4, 6, 8]))
     lo = float(rng.choice([0.0, -10.0, 100.0, -1e6]))
     hi = lo + float(rng.choice([1.0, 10.0, 20.0, 1e3]))
+    if planner == capi.PLANNER_RRT_CONNECT:   # RRTConnect: tiny and huge spaces too (1e60: beyond binary32)
+        s = float(rng.choice([1.0, 1.0, 1.0, 1e-12, 1e18, 1e60]))
+        lo, hi = lo * s, hi * s
     w = hi - lo
     bounds = [(lo, hi)] * dim
     md = float(rng.choice([0.02, 0.05, 0.1, 0.3])) * w
@@ -202,12 +205,20 @@ def case_se2():
     # (round 3) the lookup grid switched off in a quarter of the cases; the solve cut into launches that end inside a sampled block
     flags = capi.DEBUG_SE2_NO_SEGMENT_GRID if rng.integers(0, 4) == 0 else 0
     cuts = sorted(int(v) for v in rng.integers(1, iters, size=int(rng.integers(0, 3))))
+    # the (x, y) frame: the identity half the time; the heading stays as it is
+    frames = scenarios.SE2_FRAMES
+    scale, offset = frames[int(rng.integers(0, len(frames)))] if rng.random() < 0.5 else (1.0, 0.0)
+    segs = segs * scale + offset
+    start[:2] = [v * scale + offset for v in start[:2]]
+    goal[:2] = [v * scale + offset for v in goal[:2]]
+    md, clear, gr = md * scale, clear * scale, 0.4 * scale
+    xy = [(offset, 10.0 * scale + offset)] * 2
     desc = dict(planner="se2", nseg=nseg, th=th, md=md, gb=gb, seed=seed, pid0=pid0, clear=clear, nprob=nprob, iters=iters,
-                max_nodes=max_nodes, flags=flags, cuts=cuts)
-    g = capi.RRTBatch(3, [(0.0, 10.0), (0.0, 10.0), th], md, gb, nprob, max_nodes, 0.05, True, seed, pid0, 0, 0,
+                max_nodes=max_nodes, flags=flags, cuts=cuts, scale=scale, offset=offset)
+    g = capi.RRTBatch(3, xy + [th], md, gb, nprob, max_nodes, 0.05, True, seed, pid0, 0, 0,
                       capi.PLANNER_RRT_CONNECT, 0.0, capi.SPACE_SE2, debug_flags=flags)
     g.set_segments(segs, clear)
-    g.setup(start, goal, 0.4)
+    g.setup(start, goal, gr)
     done = 0
     for cut in cuts + [iters]:
         if cut > done:
@@ -215,9 +226,9 @@ def case_se2():
             done = cut
     c, gc = g.counts(), g.goal_counts()
     for p in range(nprob):
-        o = orc.OracleSE2Connect([(0.0, 10.0), (0.0, 10.0)], th, md, gb, 0.05, max_nodes, seed, pid0 + p)
+        o = orc.OracleSE2Connect(xy, th, md, gb, 0.05, max_nodes, seed, pid0 + p)
         o.set_segments(segs, clear)
-        o.setup(start, goal, 0.4)
+        o.setup(start, goal, gr)
         o.solve(iters)
         ok = int(c["checksum"][p]) == o.checksum and int(c["iterations"][p]) == o.iterations
         for w_, (gs, gp) in enumerate((g.tree(p), g.goal_tree(p))):
