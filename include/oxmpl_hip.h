@@ -83,10 +83,12 @@ typedef enum oxhip_space_kind {
     OXHIP_SPACE_REAL_VECTOR = 0,  /* RealVectorStateSpace(dim)  oxmpl/src/base/spaces/real_vector_state_space.rs */
     OXHIP_SPACE_SE2 = 1,          /* R^2 x SO(2): dim must be 3, bounds = (x), (y), (theta: clamped to [-PI, PI]);
                                      planner must be OXHIP_PLANNER_RRT_CONNECT; validity = oxhip_rrt_batch_set_segments */
-    OXHIP_SPACE_SO3 = 2           /* SO3StateSpace  oxmpl/src/base/spaces/so3_state_space.rs: dim must be 4, bounds as above;
-                                     planner must be OXHIP_PLANNER_RRT with kernel OXHIP_KERNEL_AUTO or OXHIP_KERNEL_STREAM (both run
-                                     rrt_so3.hip); goal = ball in the SO(3) distance, sample_goal = OXHIP_GOAL_SAMPLE_CENTRE;
-                                     validity = cones (oxhip_rrt_batch_set_spheres; set_boxes is OXHIP_ERR_BAD_ARG) */
+    OXHIP_SPACE_SO3 = 2           /* SO3StateSpace  oxmpl/src/base/spaces/so3_state_space.rs: dim must be 4, bounds as above.
+                                     RRT batches: planner must be OXHIP_PLANNER_RRT with kernel OXHIP_KERNEL_AUTO or OXHIP_KERNEL_STREAM
+                                     (both run rrt_so3.hip); goal = ball in the SO(3) distance, sample_goal = OXHIP_GOAL_SAMPLE_CENTRE;
+                                     validity = cones (oxhip_rrt_batch_set_spheres; set_boxes is OXHIP_ERR_BAD_ARG).
+                                     PRM (oxhip_prm_config.space, prm_so3.hip): radius rule only (knn_k must be 0); cones by
+                                     oxhip_prm_set_spheres (set_boxes is OXHIP_ERR_BAD_ARG); goal = ball in the SO(3) distance */
 } oxhip_space_kind;
 
 /* GoalSampleableRegion::sample_goal of the ball goal (goal.rs:35-41; the trait leaves the distribution to the implementor).
@@ -318,7 +320,15 @@ int32_t oxhip_rng_u64_batch(int32_t device, uint64_t seed, uint64_t stream, uint
  * its roadmap for `timeout` seconds of wall clock with an OS-seeded RNG; the device path adds the
  * deterministic caps max_milestones / max_samples (checked where the reference reads its clock,
  * prm.rs:118) and a ChaCha12 stream (seed, stream) restarted by setup().  For a given final milestone
- * count the roadmap does not depend on how construction was batched. */
+ * count the roadmap does not depend on how construction was batched.
+ *
+ * space = OXHIP_SPACE_SO3: PRM over SO3StateSpace (prm_so3.hip).  dim must be 4 and the bounds are read as for an SO(3) RRT
+ * batch: bounds[0..3] = centre quaternion, bounds[4] = max_angle (negative: OXHIP_ERR_ZERO_VOLUME; NaN reads as PI; clamped to
+ * PI); lvs_fraction as there (res = 0.5 PI fraction 0.1).  States, start, goal centre and path rows are quaternions
+ * (x, y, z, w).  oxhip_prm_set_spheres takes cones -- valid iff distance(centre, q) > radius for every cone (strict) --
+ * and oxhip_prm_set_boxes and knn_k > 0 are OXHIP_ERR_BAD_ARG.  n_samples counts sample_uniform calls (accepted rejection
+ * attempts).  Edges: distance < connection_radius (strict), check_motion with SO(3) interpolation; a radius above PI / 2 connects
+ * every pair.  acos / sin are ox_acos / ox_sincos: PARITY UNPINNED against a libm-built oxmpl, as for SO(3) RRT. */
 typedef struct oxhip_prm_config {
     uint32_t struct_size;               /* = sizeof(oxhip_prm_config) */
     uint32_t dim;                       /* 1..OXHIP_MAX_DIM */
@@ -337,7 +347,8 @@ typedef struct oxhip_prm_config {
                                            (prm.rs:131-138).  k > 0: the k-nearest variant (BASELINE.json configs[4]: "all-pairs k-NN"): it connects
                                            to its k nearest earlier milestones, ordered by (distance, index), visited in ascending index order;
                                            check_motion and everything else as prm.rs.  The query's start connections keep the radius rule */
-    uint32_t reserved;                  /* 0 */
+    uint32_t space;                     /* oxhip_space_kind: OXHIP_SPACE_REAL_VECTOR (0) or OXHIP_SPACE_SO3; anything else is
+                                           OXHIP_ERR_BAD_ARG (this field was `reserved`, ignored, before) */
 } oxhip_prm_config;
 
 typedef struct oxhip_prm oxhip_prm;

@@ -65,7 +65,7 @@ class PrmConfig(C.Structure):
         ("struct_size", C.c_uint32), ("dim", C.c_uint32), ("bounds", C.c_double * (2 * MAX_DIM)),
         ("timeout", C.c_double), ("connection_radius", C.c_double), ("lvs_fraction", C.c_double),
         ("max_milestones", C.c_uint32), ("device", C.c_int32), ("max_samples", C.c_uint64),
-        ("seed", C.c_uint64), ("stream", C.c_uint64), ("knn_k", C.c_uint32), ("reserved", C.c_uint32),
+        ("seed", C.c_uint64), ("stream", C.c_uint64), ("knn_k", C.c_uint32), ("space", C.c_uint32),
     ]
 
 
@@ -414,15 +414,21 @@ def so3_op_batch(op, a, b=None, t=None, device=0):
 
 
 class PRMRoadmap:
-    """oxmpl's PRM (prm.rs) on one GPU: roadmap construction and queries.  Thin wrapper of oxhip_prm_*."""
+    """oxmpl's PRM (prm.rs) on one GPU: roadmap construction and queries.  Thin wrapper of oxhip_prm_*.
+
+    space=SPACE_SO3 (dim 4, quaternions (x, y, z, w)): `bounds` is (cx, cy, cz, cw, max_angle), as for RRTBatch, and
+    set_spheres takes the forbidden cones (centre quaternion, radius in the SO(3) distance)."""
 
     def __init__(self, dim, bounds, connection_radius, max_milestones, timeout=0.0, lvs_fraction=0.05,
-                 max_samples=0, seed=0, stream=0, device=0, knn_k=0):
+                 max_samples=0, seed=0, stream=0, device=0, knn_k=0, space=SPACE_REAL_VECTOR):
         cfg = PrmConfig()
         cfg.struct_size = C.sizeof(PrmConfig)
         cfg.dim = dim
         b = _f64(bounds).reshape(-1)
-        if b.size != 2 * dim:
+        if space == SPACE_SO3:
+            if b.size != 5:
+                raise OxhipError(ERR_BAD_ARG, "SO(3) bounds are (cx, cy, cz, cw, max_angle)")
+        elif b.size != 2 * dim:
             raise OxhipError(ERR_BAD_ARG, "bounds must hold dim (lo,hi) pairs")
         for i, v in enumerate(b[:2 * MAX_DIM]):
             cfg.bounds[i] = v
@@ -430,7 +436,8 @@ class PRMRoadmap:
         cfg.max_milestones, cfg.device, cfg.max_samples = max_milestones, device, max_samples
         cfg.seed, cfg.stream = seed, stream
         cfg.knn_k = knn_k   # 0: radius connection (the reference); k > 0: connect to the k nearest earlier milestones
-        self.dim = dim
+        cfg.space = space
+        self.dim, self.space = dim, space
         self._h = C.c_void_p()
         _check(lib().oxhip_prm_create(C.byref(cfg), C.byref(self._h)))
 

@@ -178,21 +178,8 @@ int32_t oxhip_rrt_batch_create(const oxhip_rrt_config* cfg, oxhip_rrt_batch** ou
         if (cfg->planner != OXHIP_PLANNER_RRT) return fail(OXHIP_ERR_BAD_ARG, "SO(3) is built for RRT only");
         if (cfg->kernel != OXHIP_KERNEL_AUTO && cfg->kernel != OXHIP_KERNEL_STREAM)
             return fail(OXHIP_ERR_BAD_ARG, "SO(3) RRT runs on rrt_so3.hip: kernel must be OXHIP_KERNEL_AUTO or OXHIP_KERNEL_STREAM");
-        for (uint32_t k = 0; k < 4; ++k)
-            if (!(std::fabs(cfg->bounds[k]) <= kMaxMagnitude)) return fail(OXHIP_ERR_BAD_ARG, "SO(3) centre not finite or beyond 1e150");
-        // SO3StateSpace::new (so3_state_space.rs:57-76): a negative max_angle is StateSpaceError::InvalidAngularDistance;
-        // max_angle.min(PI) (NaN gives PI, as f64::min does)
-        const double pi = 3.14159265358979323846;
-        so3_max_angle = cfg->bounds[4];
-        if (so3_max_angle < 0.0) return fail(OXHIP_ERR_ZERO_VOLUME, "SO(3): max_angle must not be negative");
-        so3_max_angle = std::isnan(so3_max_angle) ? pi : std::fmin(so3_max_angle, pi);
-        // extent = 0.5 * PI (so3_state_space.rs:81-84); lvsl = extent * fraction (:234-236); res = lvsl * 0.1 (rrt.rs:97)
-        if (fraction > 0.0 && fraction <= 1.0) {} else if (fraction <= 0.0) fraction = 0.0; else fraction = 1.0;
-        const double lvsl = 0.5 * pi * fraction;
-        res = lvsl * 0.1;
-        if (!(res > 0.0)) return fail(OXHIP_ERR_BAD_ARG, "longest valid segment length is 0: check_motion would never terminate");
-        // no SO(3) distance exceeds 0.5 * PI (acos of |dot| >= 0), so that bounds the step count of any motion
-        if (0.5 * pi / res > 1e6) return fail(OXHIP_ERR_BAD_ARG, "more than 1e6 validity checks per edge");
+        int32_t sr = so3_space_resolution(cfg->dim, cfg->bounds, fraction, res, so3_max_angle);   // centre, max_angle, fraction
+        if (sr != OXHIP_OK) return sr;
     } else if (cfg->space == OXHIP_SPACE_SE2) {
         if (cfg->dim != 3) return fail(OXHIP_ERR_BAD_ARG, "SE(2) states are (x, y, theta): dim must be 3");
         if (cfg->planner != OXHIP_PLANNER_RRT_CONNECT) return fail(OXHIP_ERR_BAD_ARG, "SE(2) is built for RRTConnect only");

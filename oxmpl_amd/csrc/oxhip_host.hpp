@@ -154,4 +154,25 @@ inline int32_t space_resolution(uint32_t dim, const double* bounds, double& frac
     return OXHIP_OK;
 }
 
+// SO3StateSpace::new + get_longest_valid_segment_length for a config whose bounds carry (cx, cy, cz, cw, max_angle)
+// (include/oxmpl_hip.h, OXHIP_SPACE_SO3): validates the centre and max_angle as so3_state_space.rs:57-76 does (a negative
+// max_angle is StateSpaceError::InvalidAngularDistance; max_angle.min(PI), NaN giving PI as f64::min does), clamps the fraction
+// (:234-236) and returns res = 0.5 * PI * fraction * 0.1 (extent 0.5 * PI, :81-84; rrt.rs:97, prm.rs:168).  No SO(3) distance
+// exceeds 0.5 * PI, which bounds the step count of every motion.
+inline int32_t so3_space_resolution(uint32_t dim, const double* bounds, double& fraction, double& res, double& max_angle) {
+    if (dim != 4) return fail(OXHIP_ERR_BAD_ARG, "SO(3) states are quaternions (x, y, z, w): dim must be 4");
+    for (uint32_t k = 0; k < 4; ++k)
+        if (!(std::fabs(bounds[k]) <= kMaxMagnitude)) return fail(OXHIP_ERR_BAD_ARG, "SO(3) centre not finite or beyond 1e150");
+    const double pi = 3.14159265358979323846;
+    max_angle = bounds[4];
+    if (max_angle < 0.0) return fail(OXHIP_ERR_ZERO_VOLUME, "SO(3): max_angle must not be negative");
+    max_angle = std::isnan(max_angle) ? pi : std::fmin(max_angle, pi);
+    if (fraction > 0.0 && fraction <= 1.0) {} else if (fraction <= 0.0) fraction = 0.0; else fraction = 1.0;
+    const double lvsl = 0.5 * pi * fraction;
+    res = lvsl * 0.1;
+    if (!(res > 0.0)) return fail(OXHIP_ERR_BAD_ARG, "longest valid segment length is 0: check_motion would never terminate");
+    if (0.5 * pi / res > 1e6) return fail(OXHIP_ERR_BAD_ARG, "more than 1e6 validity checks per edge");
+    return OXHIP_OK;
+}
+
 }  // namespace oxhip

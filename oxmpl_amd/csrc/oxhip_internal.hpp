@@ -129,5 +129,26 @@ void launch_prm_csr(const uint64_t* sorted, uint32_t n_keys, uint32_t n_nodes, u
                     uint32_t* nbrs, hipStream_t s);
 void launch_prm_query(const DevParams& p, const PrmArgs& a, uint32_t n, const PrmQuery& q, double thr, uint8_t* flags,
                       uint32_t* start_valid, hipStream_t s);
+uint32_t prm_key_shift(uint32_t cap);   // directed keys are (u << shift) | v
+
+// prm_so3.hip: PRM over SO3StateSpace with forbidden cones; the sort / CSR above are shared
+struct PrmSo3Spec {           // one round of the SO(3) sampler: m rejection attempts, attempt a at stream word pos0 + 4 a
+    uint64_t pos0;
+    uint32_t m;
+    uint32_t pad;
+    double* tmp;             // [m][4] the valid attempts' quaternions
+    uint64_t* vbits;         // [ceil(m/64)] ballots of "accepted and valid" (a milestone)
+    uint64_t* abits;         // [ceil(m/64)] ballots of "accepted" (a sample_uniform call returned)
+    uint32_t* voff;          // [ceil(m/64)] per-wave milestone counts, then their exclusive prefix
+    uint32_t* acnt;          // [ceil(m/64)] per-wave sample counts
+    uint32_t* redraw_flag;   // set when random_range would have drawn again (unreachable for -1..1): the host refuses the round
+    PrmState* result;        // the state after this round
+};
+void launch_prm_so3_sample(const DevParams& p, const PrmArgs& a, const PrmSo3Spec& sp, uint32_t n0, hipStream_t s);
+// candidates (j, i < j) with distance < r, j in [j0, j1): |dot| > hi is in, |dot| < lo is out, in between the exact distance
+void launch_prm_so3_pairs(const PrmArgs& a, uint32_t j0, uint32_t j1, double lo, double hi, double r, hipStream_t s);
+void launch_prm_so3_edges(const DevParams& p, const PrmArgs& a, uint32_t n_cand, hipStream_t s);
+void launch_prm_so3_query(const DevParams& p, const PrmArgs& a, uint32_t n, const PrmQuery& q, double r, uint8_t* flags,
+                          uint32_t* start_valid, hipStream_t s);
 
 }  // namespace oxhip

@@ -5,6 +5,7 @@
 // reconstruct_path (prm.rs:189-208) on the CSR roadmap it copies back once per construction.  Start
 // validity, start connections and goal milestones (prm.rs:243-264) are computed on the device.
 // There is no CPU fallback: without a HIP device every computing entry point fails.
+// space = OXHIP_SPACE_SO3 runs the same phases with the kernels of prm_so3.hip.
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -21,6 +22,8 @@ struct oxhip_prm {
     DevParams dp{};           // space, resolution and validity field (the RRT fields stay zero)
     PrmArgs args{};
     double thr_conn = -1.0;   // d2 <= thr_conn  <=>  distance < connection_radius
+    bool so3 = false;         // OXHIP_SPACE_SO3: quaternion milestones, cones, prm_so3.hip
+    double so3_lo = -1.0, so3_hi = -1.0;   // |dot| bands of the SO(3) radius test (so3_radius_bands)
     hipStream_t stream = nullptr;
     hipEvent_t ev[6] = {};
     DevBuf<double> ms, sph_c, sph_thr, sph_r, box_lo, box_hi;
@@ -45,6 +48,8 @@ struct oxhip_prm {
     DevBuf<double> spec_tmp;
     DevBuf<uint64_t> spec_vbits;
     DevBuf<uint32_t> spec_off, spec_flag;
+    DevBuf<uint64_t> spec_abits;   // SO(3) sampler: accepted-attempt ballots and counts
+    DevBuf<uint32_t> spec_acnt;
     double valid_rate = 1.0;   // running estimate of P(sample is valid), sizes the rounds
     bool is_setup = false;
     PrmQuery query{};
@@ -83,7 +88,7 @@ int32_t set_query(oxhip_prm* h, const double* start, const double* goal_centre, 
     h->query = PrmQuery{};
     std::memcpy(h->query.start, start, dim * sizeof(double));
     std::memcpy(h->query.goal_c, goal_centre, dim * sizeof(double));
-    h->query.goal_thr = sqrt_le_threshold(goal_radius);
+    h->query.goal_thr = h->so3 ? goal_radius : sqrt_le_threshold(goal_radius);   // SO(3): the distance is compared with the radius itself
     return OXHIP_OK;
 }
 
@@ -143,6 +148,57 @@ int32_t sample_until(oxhip_prm* h, PrmState& st, uint32_t target, uint64_t max_s
     return OXHIP_OK;
 }
 
+// The SO(3) sampler (prm_so3.hip): rounds of m rejection attempts, attempt a at stream word pos0 + 4 a, sized by the observed
+// rate of milestones per attempt.  random_range(-1.0..1.0) cannot draw again (its largest value is 1 - 2^-51), so a flagged round
+// would mean the word positions are wrong: it is refused, never shifted.
+int32_t sample_until_so3(oxhip_prm* h, PrmState& st, uint32_t target, uint64_t max_samples) {
+    constexpr uint64_t kRoundMax = 1ull << 22;
+    h->args.n_target = target;
+    h->args.max_samples = max_samples;
+    while (st.n_milestones < target && st.n_samples < max_samples) {
+        const uint32_t need = target - st.n_milestones;
+        uint64_t want = (uint64_t)((double)need / h->valid_rate * 1.02) + 256;
+        want = std::min(want, kRoundMax);
+        const uint32_t m = (uint32_t)want, nw = (m + 63) / 64;
+        if (h->spec_tmp.n < (size_t)m * 4) HIP_TRY(h->spec_tmp.alloc((size_t)m * 4));
+        if (h->spec_vbits.n < nw) {
+            HIP_TRY(h->spec_vbits.alloc(nw)); HIP_TRY(h->spec_off.alloc(nw)); HIP_TRY(h->spec_abits.alloc(nw)); HIP_TRY(h->spec_acnt.alloc(nw));
+        }
+        if (h->spec_flag.n == 0) HIP_TRY(h->spec_flag.alloc(1));
+        HIP_TRY(hipMemsetAsync(h->spec_flag.p, 0, sizeof(uint32_t), h->stream));
+        PrmSo3Spec sp{};
+        sp.pos0 = st.draws; sp.m = m;
+        sp.tmp = h->spec_tmp.p; sp.vbits = h->spec_vbits.p; sp.abits = h->spec_abits.p; sp.voff = h->spec_off.p; sp.acnt = h->spec_acnt.p;
+        sp.redraw_flag = h->spec_flag.p; sp.result = h->state.p;
+        launch_prm_so3_sample(h->dp, h->args, sp, st.n_milestones, h->stream);
+        HIP_TRY(hipGetLastError());
+        PrmState after{};
+        uint32_t flag = 0;
+        HIP_TRY(hipMemcpyAsync(&after, h->state.p, sizeof(PrmState), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(&flag, h->spec_flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (flag != 0) return fail(OXHIP_ERR_HIP, "SO(3) sampler: random_range(-1.0..1.0) drew again, which cannot happen; round refused");
+        const double got = (double)(after.n_milestones - st.n_milestones);
+        h->valid_rate = std::max(1e-6, std::min(1.0, (got + 1.0) / ((double)m + 1.0)));
+        st = after;
+    }
+    return OXHIP_OK;
+}
+
+// |dot| bands of "distance < r" (DESIGN.md section 15).  distance = |dot| > 1 - 1e-9 ? 0 : ox_acos(|dot|), ox_acos within
+// delta = 2^-52 relative of the true acos (below one ulp; the CPU suite checks 2^-50 against libm), acos
+// strictly decreasing.  hi >= cos(r (1 - 2^-40)): |dot| > hi gives ox_acos < acos(hi) (1 + delta) < r, or the 1 - 1e-9 shortcut's 0.
+// lo <= cos(r (1 + 2^-40)) and lo <= 1 - 1e-9: |dot| < lo gives ox_acos > acos(lo) (1 - delta) > r.  libm's cos is within one ulp
+// (2^-53 here) and each margin operation rounds once, both far inside the 2^-50 added.  Between lo and hi: the exact distance.
+// No distance exceeds fl(PI / 2) (ox_acos(0) and, below |dot| 2^-55, pio2_hi - (x - pio2_lo) rounds to pio2_hi), so a radius
+// above it takes every pair: hi = lo = -1.  r <= 0 takes none (the caller skips the search).
+void so3_radius_bands(double r, double& lo, double& hi) {
+    const double pio2 = 1.57079632679489655800e+00;
+    if (!(r <= pio2)) { lo = hi = -1.0; return; }
+    hi = std::cos(r * (1.0 - 0x1p-40)) + 0x1p-50;
+    lo = std::fmin(std::cos(r * (1.0 + 0x1p-40)) - 0x1p-50, 1.0 - 1e-9);
+}
+
 // host copy of the roadmap for get_roadmap and the breadth-first query (once per construction)
 int32_t fetch_roadmap(oxhip_prm* h) {
     if (h->host_copy) return OXHIP_OK;
@@ -176,11 +232,22 @@ int32_t oxhip_prm_create(const oxhip_prm_config* cfg, oxhip_prm** out) {
     if (cfg->max_milestones == 0 || cfg->max_milestones > (1u << 26))
         return fail(OXHIP_ERR_BAD_ARG, "max_milestones must be in 1..2^26");
     if (std::isnan(cfg->connection_radius)) return fail(OXHIP_ERR_BAD_ARG, "connection_radius is NaN");
-    double fraction = cfg->lvs_fraction, res = 0.0;
-    OX_TRY(space_resolution(cfg->dim, cfg->bounds, fraction, res));
-    // the longest motion PRM ever checks is shorter than the connection radius
-    if (std::isfinite(cfg->connection_radius) && cfg->connection_radius / res > 1e6)
-        return fail(OXHIP_ERR_BAD_ARG, "more than 1e6 validity checks per edge");
+    if (cfg->space != OXHIP_SPACE_REAL_VECTOR && cfg->space != OXHIP_SPACE_SO3)
+        return fail(OXHIP_ERR_BAD_ARG, "PRM space must be OXHIP_SPACE_REAL_VECTOR (0) or OXHIP_SPACE_SO3");
+    const bool so3 = cfg->space == OXHIP_SPACE_SO3;
+    double fraction = cfg->lvs_fraction, res = 0.0, so3_max_angle = 0.0;
+    if (so3) {
+        OX_TRY(so3_space_resolution(cfg->dim, cfg->bounds, fraction, res, so3_max_angle));
+        if (cfg->knn_k) return fail(OXHIP_ERR_BAD_ARG, "SO(3) PRM connects by radius only: knn_k must be 0");
+        // no SO(3) motion is longer than PI / 2, whatever the radius
+        if (std::fmin(cfg->connection_radius, 0.5 * 3.14159265358979323846) / res > 1e6)
+            return fail(OXHIP_ERR_BAD_ARG, "more than 1e6 validity checks per edge");
+    } else {
+        OX_TRY(space_resolution(cfg->dim, cfg->bounds, fraction, res));
+        // the longest motion PRM ever checks is shorter than the connection radius
+        if (std::isfinite(cfg->connection_radius) && cfg->connection_radius / res > 1e6)
+            return fail(OXHIP_ERR_BAD_ARG, "more than 1e6 validity checks per edge");
+    }
     OX_TRY(select_device(cfg->device));
 
     auto* h = new oxhip_prm();
@@ -190,14 +257,22 @@ int32_t oxhip_prm_create(const oxhip_prm_config* cfg, oxhip_prm** out) {
     const uint32_t cap = ((cfg->max_milestones + 1023u) / 1024u) * 1024u;
     DevParams& dp = h->dp;
     dp.dim = dim;
-    for (uint32_t k = 0; k < dim; ++k) {
-        dp.lo[k] = cfg->bounds[2 * k];
-        dp.hi[k] = cfg->bounds[2 * k + 1];
-        dp.scale[k] = dp.hi[k] - dp.lo[k];
+    h->so3 = so3;
+    if (so3) {   // the bounds are (cx, cy, cz, cw, max_angle); lo / hi / scale stay zero
+        for (uint32_t k = 0; k < 4; ++k) dp.so3_centre[k] = cfg->bounds[k];
+        dp.so3_max_angle = so3_max_angle;
+        dp.space = OXHIP_SPACE_SO3;
+        so3_radius_bands(cfg->connection_radius, h->so3_lo, h->so3_hi);
+    } else {
+        for (uint32_t k = 0; k < dim; ++k) {
+            dp.lo[k] = cfg->bounds[2 * k];
+            dp.hi[k] = cfg->bounds[2 * k + 1];
+            dp.scale[k] = dp.hi[k] - dp.lo[k];
+        }
     }
     dp.res = res;
     dp.seed = cfg->seed;
-    for (uint32_t k = 0; k < 2 * dim; ++k) h->maxabs = std::fmax(h->maxabs, std::fabs(cfg->bounds[k]));
+    if (!so3) for (uint32_t k = 0; k < 2 * dim; ++k) h->maxabs = std::fmax(h->maxabs, std::fabs(cfg->bounds[k]));
     dp.filt_abs = 1e-9 * h->maxabs;
     h->thr_conn = sqrt_lt_threshold(cfg->connection_radius);
 
@@ -206,7 +281,7 @@ int32_t oxhip_prm_create(const oxhip_prm_config* cfg, oxhip_prm** out) {
     chk(oxhip_stream_acquire(cfg->device, &h->stream));
     for (auto& ev : h->ev) chk(hipEventCreate(&ev));
     chk(h->ms.alloc((size_t)dim * cap));
-    chk(h->ms32.alloc((size_t)dim * cap));
+    if (!so3) chk(h->ms32.alloc((size_t)dim * cap));   // (the SO(3) pair search screens nothing)
     chk(h->state.alloc(1));
     chk(h->flags.alloc(cap));
     chk(h->start_valid.alloc(1));
@@ -252,6 +327,7 @@ int32_t oxhip_prm_set_spheres(oxhip_prm* h, const double* centres, const double*
     OX_TRY(upload(h->sph_thr, thr, h->stream));
     OX_TRY(upload(h->sph_r, std::vector<double>(radii, radii + n), h->stream));
     h->dp.n_spheres = n; h->dp.sph_c = h->sph_c.p; h->dp.sph_thr = h->sph_thr.p; h->dp.sph_r = h->sph_r.p;
+    if (h->so3) return OXHIP_OK;   // cones: distance(centre, q) > radius, compared with sph_r itself
     h->maxabs = 1.0;
     for (uint32_t k = 0; k < 2 * dim; ++k) h->maxabs = std::fmax(h->maxabs, std::fabs(h->cfg.bounds[k]));
     for (double v : c) h->maxabs = std::fmax(h->maxabs, std::fabs(v));
@@ -261,6 +337,7 @@ int32_t oxhip_prm_set_spheres(oxhip_prm* h, const double* centres, const double*
 
 int32_t oxhip_prm_set_boxes(oxhip_prm* h, const double* lo, const double* hi, uint32_t n) {
     if (!h || (n && (!lo || !hi))) return fail(OXHIP_ERR_BAD_ARG, "null argument");
+    if (h->so3) return fail(OXHIP_ERR_BAD_ARG, "SO(3) PRM takes cones (oxhip_prm_set_spheres with 4-wide centres), not boxes");
     OX_TRY(select_device(h->cfg.device));
     const uint32_t dim = h->cfg.dim;
     std::vector<double> l((size_t)dim * n), u((size_t)dim * n);
@@ -317,13 +394,14 @@ int32_t oxhip_prm_construct_roadmap(oxhip_prm* h) {
     for (;;) {
         // ---- 1. sample until `target` milestones
         HIP_TRY(hipEventRecord(h->ev[0], h->stream));
-        OX_TRY(sample_until(h, st, target, max_samples));
+        OX_TRY(h->so3 ? sample_until_so3(h, st, target, max_samples) : sample_until(h, st, target, max_samples));
         HIP_TRY(hipEventRecord(h->ev[1], h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
         h->t_ms[0] += elapsed_ms(h->ev[0], h->ev[1]);
         const uint32_t n_now = st.n_milestones;
         // ---- 2. pairs (j in [n_done, n_now), i < j) within the connection radius
-        if (n_now > n_done && n_now >= 2 && (h->thr_conn >= 0.0 || h->cfg.knn_k)) {
+        const bool any_pair = h->so3 ? h->cfg.connection_radius > 0.0 : (h->thr_conn >= 0.0 || h->cfg.knn_k);
+        if (n_now > n_done && n_now >= 2 && any_pair) {
             if (h->cand.n == 0) {
                 HIP_TRY(h->cand.alloc(std::min<size_t>(std::max<size_t>(1u << 20, (size_t)64 * n_max), (size_t)1 << 28)));
                 h->args.cand = h->cand.p;
@@ -358,7 +436,8 @@ int32_t oxhip_prm_construct_roadmap(oxhip_prm* h) {
                 st.n_cand = 0;
                 OX_TRY(write_state(h, st));
                 HIP_TRY(hipEventRecord(h->ev[2], h->stream));
-                if (knn_k) launch_prm_pairs(h->dp, h->args, n_done, n_now, std::numeric_limits<double>::infinity(), h->stream, h->knn_thr.p, h->knn_thr32.p);
+                if (h->so3) launch_prm_so3_pairs(h->args, n_done, n_now, h->so3_lo, h->so3_hi, h->cfg.connection_radius, h->stream);
+                else if (knn_k) launch_prm_pairs(h->dp, h->args, n_done, n_now, std::numeric_limits<double>::infinity(), h->stream, h->knn_thr.p, h->knn_thr32.p);
                 else launch_prm_pairs(h->dp, h->args, n_done, n_now, h->thr_conn, h->stream);
                 HIP_TRY(hipGetLastError());
                 HIP_TRY(hipEventRecord(h->ev[3], h->stream));
@@ -427,7 +506,8 @@ int32_t oxhip_prm_construct_roadmap(oxhip_prm* h) {
                 h->args.keys = h->keys.p;
             }
             HIP_TRY(hipEventRecord(h->ev[2], h->stream));
-            launch_prm_edges(h->dp, h->args, (uint32_t)st.n_cand, h->stream);
+            if (h->so3) launch_prm_so3_edges(h->dp, h->args, (uint32_t)st.n_cand, h->stream);
+            else launch_prm_edges(h->dp, h->args, (uint32_t)st.n_cand, h->stream);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipEventRecord(h->ev[3], h->stream));
             OX_TRY(read_state(h, st));
@@ -515,7 +595,8 @@ int32_t oxhip_prm_solve(oxhip_prm* h, double timeout_s, double* path, uint32_t c
     DevParams qdp = h->dp;   // the start may lie anywhere: widen the filter's absolute margin for this launch
     for (uint32_t k = 0; k < dim; ++k) qdp.filt_abs = std::fmax(qdp.filt_abs, 1e-9 * std::fabs(h->query.start[k]));
     HIP_TRY(hipEventRecord(h->ev[0], h->stream));
-    launch_prm_query(qdp, h->args, n, h->query, h->thr_conn, h->flags.p, h->start_valid.p, h->stream);
+    if (h->so3) launch_prm_so3_query(h->dp, h->args, n, h->query, h->cfg.connection_radius, h->flags.p, h->start_valid.p, h->stream);
+    else launch_prm_query(qdp, h->args, n, h->query, h->thr_conn, h->flags.p, h->start_valid.p, h->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(h->ev[1], h->stream));
     std::vector<uint8_t> flags(n);

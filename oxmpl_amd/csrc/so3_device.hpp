@@ -68,6 +68,28 @@ __device__ __forceinline__ void so3_interpolate(const double from[4], const doub
     }
 }
 
+// rand 0.9 random_range(-1.0..1.0) from one word: (bits >> 12 | 1.0) - 1.0, times scale 2.0, plus -1.0; false when rand would
+// draw again (res >= 1.0: not reachable for this range -- the largest value is 1 - 2^-51 -- but stated as rand states it)
+__device__ __forceinline__ bool so3_range_word(uint64_t w, double& res) {
+    const double v01 = __longlong_as_double((long long)((w >> 12) | 0x3FF0000000000000ull)) - 1.0;
+    res = v01 * 2.0;
+    res = res + -1.0;
+    return res < 1.0;
+}
+
+// one rejection attempt of so3_state_space.rs:213-229 from its four coordinates; true when accepted (q written)
+__device__ __forceinline__ bool so3_attempt(const double v[4], const double centre[4], double max_angle, double q[4]) {
+    const double x2 = v[0] * v[0], y2 = v[1] * v[1], z2 = v[2] * v[2], w2 = v[3] * v[3];
+    double ns = x2 + y2;
+    ns = ns + z2;
+    ns = ns + w2;
+    if (!(ns > 1e-9 && ns < 1.0)) return false;
+    const double norm = sqrt(ns);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) q[k] = v[k] / norm;
+    return so3_distance(centre, q) <= max_angle;
+}
+
 // is state s inside one of the n cones (centres SoA [4][stride], radii r[n])?  valid iff distance(centre, s) > radius (strict)
 __device__ __forceinline__ bool so3_cone_hit(const double* cc, uint32_t stride, const double* cr, uint32_t n, const double s[4]) {
     bool hit = false;

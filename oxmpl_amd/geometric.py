@@ -169,7 +169,10 @@ class PRM:
         self._prm = None
 
     def setup(self, validity_checker):
-        """Planner::setup (prm.rs:217-225): stores problem and checker, clears the roadmap"""
+        """Planner::setup (prm.rs:217-225): stores problem and checker, clears the roadmap.  An SO(3) problem takes an
+        SO3ConeValidityChecker (the radius rule; milestones and path states are SO3State)."""
+        if isinstance(self._pd.space, SO3StateSpace):
+            return self._setup_so3(validity_checker)
         if not isinstance(validity_checker, SphereBoxValidityChecker):
             raise TypeError("the GPU path cannot call a Python function per interpolated state; "
                             "describe the obstacles with oxmpl_amd.base.SphereBoxValidityChecker")
@@ -189,6 +192,28 @@ class PRM:
             g.set_boxes([lo for lo, _ in validity_checker.boxes], [hi for _, hi in validity_checker.boxes])
         g.setup(pd.start_state.values, pd.goal.target.values, float(pd.goal.radius))
         self._prm = g
+
+    def _setup_so3(self, validity_checker):
+        if not isinstance(validity_checker, SO3ConeValidityChecker):
+            raise TypeError("the GPU path cannot call a Python function per interpolated state; "
+                            "describe the forbidden cones with oxmpl_amd.base.SO3ConeValidityChecker")
+        pd = self._pd
+        if self._prm is not None:
+            self._prm.close()
+        try:
+            g = capi.PRMRoadmap(4, pd.space.config_bounds(), self.connection_radius, timeout=self.timeout,
+                                lvs_fraction=pd.space.longest_valid_segment_fraction, space=capi.SPACE_SO3, **self._opts)
+        except capi.OxhipError as e:
+            if e.status in (capi.ERR_ZERO_VOLUME, capi.ERR_BAD_ARG):
+                raise ValueError(str(e)) from None
+            raise
+        if validity_checker.cones:
+            g.set_spheres([c for c, _ in validity_checker.cones], [r for _, r in validity_checker.cones])
+        g.setup(pd.start_state.values, pd.goal.target.values, float(pd.goal.radius))
+        self._prm = g
+
+    def _state(self, row):
+        return SO3State(*row) if isinstance(self._pd.space, SO3StateSpace) else RealVectorState(row)
 
     def set_problem_definition(self, problem_definition):
         """PRM::set_problem_definition (prm.rs:88-90): new start / goal on the roadmap already built"""
@@ -212,12 +237,15 @@ class PRM:
         st, path = self._prm.solve(float(timeout_secs))
         if st != capi.OK:
             raise Exception(_MESSAGES.get(int(st), capi.status_string(int(st))))
-        return Path([RealVectorState(row) for row in path])
+        return Path([self._state(row) for row in path])
 
     def get_roadmap(self):
         """PRM::get_roadmap (prm.rs:82-84) as (states, offsets, neighbours): node i's edges are
-        neighbours[offsets[i]:offsets[i+1]]"""
-        return self._prm.roadmap()
+        neighbours[offsets[i]:offsets[i+1]].  SO(3) problems: states is a list of SO3State."""
+        states, offsets, nbrs = self._prm.roadmap()
+        if isinstance(self._pd.space, SO3StateSpace):
+            states = [SO3State(*row) for row in states]
+        return states, offsets, nbrs
 
     @property
     def num_milestones(self):

@@ -108,7 +108,8 @@ pub struct OxhipPrmConfig {
     pub seed: u64,
     pub stream: u64,
     pub knn_k: u32,
-    pub reserved: u32,
+    /// `oxhip_space_kind`: OXHIP_SPACE_REAL_VECTOR or OXHIP_SPACE_SO3 (anything else is OXHIP_ERR_BAD_ARG)
+    pub space: u32,
 }
 
 /// (field, byte offset, byte size) of `oxhip_prm_config`
@@ -125,7 +126,7 @@ pub const OXHIP_PRM_CONFIG_LAYOUT: &[(&str, usize, usize)] = &[
     ("seed", 176, 8),
     ("stream", 184, 8),
     ("knn_k", 192, 4),
-    ("reserved", 196, 4),
+    ("space", 196, 4),
 ];
 pub const OXHIP_PRM_CONFIG_SIZE: usize = 200;
 
@@ -238,6 +239,6 @@ mod tests {
             [struct_size, dim, bounds, max_distance, goal_bias, lvs_fraction, n_problems, max_nodes, stop_at_goal, kernel,
              seed, first_problem_id, device, planner, search_radius, space, goal_sampler, debug_flags, star_pool_share, frozen_split, reserved]);
         check_layout!(OxhipPrmConfig, OXHIP_PRM_CONFIG_LAYOUT, OXHIP_PRM_CONFIG_SIZE,
-            [struct_size, dim, bounds, timeout, connection_radius, lvs_fraction, max_milestones, device, max_samples, seed, stream, knn_k, reserved]);
+            [struct_size, dim, bounds, timeout, connection_radius, lvs_fraction, max_milestones, device, max_samples, seed, stream, knn_k, space]);
     }
 }

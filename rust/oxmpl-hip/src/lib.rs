@@ -572,6 +572,34 @@ pub fn so3_rrt_config(space: &SO3StateSpace, max_distance: f64, goal_bias: f64, 
     }
 }
 
+/// `oxhip_prm_config` of an SO(3) roadmap: PRM::new(timeout, connection_radius) over `space` (prm_so3.hip).  The bounds carry
+/// SO3StateSpace::bounds (centre quaternion, max_angle) as in `so3_rrt_config`; cones go in through `oxhip_prm_set_spheres`
+/// with 4-wide centres; the radius rule only (knn_k = 0).  `options.max_nodes` caps the milestones.
+pub fn so3_prm_config(space: &SO3StateSpace, timeout: f64, connection_radius: f64, lvs_fraction: f64, options: &HipOptions) -> ffi::OxhipPrmConfig {
+    let (centre, max_angle) = &space.bounds;
+    let mut bounds = [0.0f64; 2 * ffi::OXHIP_MAX_DIM];
+    bounds[0] = centre.x;
+    bounds[1] = centre.y;
+    bounds[2] = centre.z;
+    bounds[3] = centre.w;
+    bounds[4] = *max_angle;
+    ffi::OxhipPrmConfig {
+        struct_size: ffi::OXHIP_PRM_CONFIG_SIZE as u32,
+        dim: 4,
+        bounds,
+        timeout,
+        connection_radius,
+        lvs_fraction,
+        max_milestones: options.max_nodes,
+        device: options.device,
+        max_samples: 0,
+        seed: options.seed,
+        stream: options.stream,
+        knn_k: 0,
+        space: ffi::OXHIP_SPACE_SO3,
+    }
+}
+
 /// SO3StateSpace::distance evaluated by the device (ox_acos: within one ulp of libm's acos), for checking a binding
 pub fn so3_device_distance(device: i32, a: &SO3State, b: &SO3State) -> Result<f64, String> {
     let qa = [a.x, a.y, a.z, a.w];
