@@ -5,6 +5,12 @@
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
   python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   # + what the last timed step returned, DIR/*.npy
+  python bench.py --gpus 1 --steps K --warmup W --full               # + every check and side measurement below
+
+A plain run does only what the headline needs: set up (grow the trees), warm up, time the steps, dump if asked, print the line
+(`roofline` included: it is this run's rate next to committed profile constants).  `--full` adds what takes runs of its own:
+`cpu_baseline` and the oracle check, the `secondary*` rows, the device-to-device copy peak (`hbm_copy_peak_GBps`) and, with N > 1,
+every rank's oracle check of its own shard.  `--no-cpu-baseline` / `--no-secondary` leave parts of that out again.
 
 Workload (BASELINE.json configs[1], one GPU; configs[2] = the same, 1024 problems per rank):
 1024 independent planning problems per GPU, trees pre-grown (untimed) to 10,000 nodes; one
@@ -25,12 +31,12 @@ the tree in the register file: its `peak` is the measured rate of its own screen
 figure SURVEY.md 8(d) defines (24 B x tree size per iteration) is kept as `hbm_equivalent_GBps`; for the stream kernel it is the
 bound itself.
 
-`cpu_baseline` times the CPU oracle (our C restatement of oxmpl's loop, kind "port") on a bounded sample of
+`cpu_baseline` (--full) times the CPU oracle (our C restatement of oxmpl's loop, kind "port") on a bounded sample of
 the same workload on this host's cores -- and the run is only accepted if the GPU's per-problem node
 counts, iteration counts and checksums (every iteration folds nearest index, q_new bits and verdict) equal
 the oracle's on that sample, after the grow phase and after the frozen iterations.
 
-`secondary` / `secondary_lanes` / `secondary_f64`: the same steps through the stream kernel, the lane-per-query kernel and the
+`secondary` / `secondary_lanes` / `secondary_f64` (--full): the same steps through the stream kernel, the lane-per-query kernel and the
 all-binary64 resident kernel (checksums of all 1024 problems must equal the main run's).  `secondary_rrt_star`: the RRT* row on the same scene and batch size, 1024 trees grown
 to 10,000 nodes; the checker grows problem 0 with the CPU oracle as well and refuses the line unless parents after rewiring,
 costs and checksum are identical.  `secondary_rrt_connect`: the RRTConnect rows -- BASELINE.json configs[3], SE(2) among
@@ -315,9 +321,12 @@ def main():
                          "of the N > 1 branch on a box with fewer GPUs than ranks)")
     ap.add_argument("--device-map", default="", help="comma-separated HIP device per local rank (default: local rank r -> device r); "
                                                      "'0,0' runs two ranks on GPU 0")
-    ap.add_argument("--rank-check", type=int, default=2, help="N > 1: problems of its own shard every rank checks against the oracle")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (stream kernel, all-binary64 resident kernel)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline and oracle checks, the secondary rows and the copy-bandwidth probe (off: headline only)")
+    ap.add_argument("--rank-check", type=int, default=2, help="--full, N > 1: problems of its own shard every rank checks against the oracle")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and the oracle checks")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary measurements (other kernels, RRT*, "
+                                                                "RRTConnect, copy bandwidth)")
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
                     help="after the timed steps, write what the last timed step returned (see dump_outputs) as DIR/<name>.npy")
     args = ap.parse_args()
@@ -325,6 +334,7 @@ def main():
         ap.error("--steps must be at least 1")
     if args.warmup < 0:
         ap.error("--warmup must not be negative")
+    cpu_check = args.full and not args.no_cpu_baseline        # the oracle legs: cpu_baseline, rank checks, secondary rows' checks
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -387,7 +397,7 @@ def main():
     snap = None   # (frozen iterations per problem, counters) at a point the CPU check can afford to reach
     for w in range(args.warmup):
         gpu.solve(args.iters, freeze=True)
-        if not args.no_cpu_baseline and (w + 1) * args.iters <= 400000:
+        if cpu_check and (w + 1) * args.iters <= 400000:
             snap = ((w + 1) * args.iters, gpu.counts())   # untimed: warm-up
     barrier()
     t0 = time.perf_counter()
@@ -428,9 +438,10 @@ def main():
             raise SystemExit("bench.py: kernel kind %d disagrees with the main run's checksums: refusing to report" % kernel)
         return ms2 / steps, same
 
+    secondary = args.full and world == 1 and not args.no_secondary
     secondary_stream = secondary_f64 = secondary_lanes = None
     copy_gbs = None
-    if world == 1 and not args.no_secondary:
+    if secondary:
         copy_gbs = copy_peak_gbs(torch, torch.device("cuda", device))
         if kname != "stream":
             ms, same = side_run(capi.KERNEL_STREAM)
@@ -469,7 +480,7 @@ def main():
     # size, search radius 1: 1024 trees grown to 10,000 nodes; problem 0 is grown by the CPU oracle too and its parents after
     # rewiring, costs and checksum must be identical, or nothing is printed
     secondary_star = None
-    if world == 1 and not args.no_secondary:
+    if secondary:
         import numpy as np
         star = scenarios.make_batch(sc, P, N_NODES, stop_at_goal=False, seed=seed, first_problem_id=first_id, device=device,
                                     kernel=capi.KERNEL_AUTO, planner=capi.PLANNER_RRT_STAR, search_radius=1.0)
@@ -478,7 +489,7 @@ def main():
         st_c = star.counts()
         assert (st_c["nodes"] == N_NODES).all()
         verified = None
-        if not args.no_cpu_baseline:
+        if cpu_check:
             from oracle import oracle_py as orc
             o = orc.OracleRRTStar(sc["dim"], sc["bounds"], sc["max_distance"], sc["goal_bias"], 1.0, sc["lvs_fraction"], N_NODES, False,
                                   seed, first_id)
@@ -499,7 +510,7 @@ def main():
         star.close()
 
     secondary_connect = None
-    if world == 1 and not args.no_secondary:
+    if secondary:
         secondary_connect = _connect_rows(args, scenarios, capi, sc, P, seed, first_id, device)
 
     def check_point():
@@ -516,7 +527,7 @@ def main():
     # N > 1: every rank checks the LAST `rank_check` problems of its own shard against the oracle (same rule as the N = 1 run:
     # no agreement, no line) -- after the timed region, outside every bracket
     checked = 0
-    if world > 1 and not args.no_cpu_baseline and args.rank_check > 0:
+    if world > 1 and cpu_check and args.rank_check > 0:
         k = min(args.rank_check, P)
         point = check_point()
         oracle_check(sc, seed, first_id, k, min(k, host_cores()[1]), point[0], c, point[1], offset=P - k)
@@ -574,7 +585,7 @@ def main():
             "value": value, "unit": "iterations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": t_max / args.steps * 1e3, "higher_is_better": True,
             "scaling": "strong" if args.strong_total else "weak",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
             "config": {"workload": "configs[1]: R^3 RRT, 64 random spheres, %d problem instances per MI355X, "
                                    "steady@10k (trees pre-grown to 10000 nodes, inserts suppressed)" % P,
                        "problems_per_gpu": P, "iterations_per_problem_per_step": args.iters, "tree_nodes": N_NODES,
@@ -621,7 +632,7 @@ def main():
             out["secondary_rrt_star"] = secondary_star
         if secondary_connect:
             out["secondary_rrt_connect"] = secondary_connect
-        if not args.no_cpu_baseline and world == 1:  # the contract: rank 0, N = 1 only
+        if cpu_check and world == 1:  # the contract: rank 0, N = 1 only
             point = check_point()
             out["cpu_baseline"] = cpu_baseline_and_check(sc, seed, first_id, P, point[0], c, point[1])
         print(json.dumps(out))

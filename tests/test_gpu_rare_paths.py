@@ -165,7 +165,7 @@ def test_rank7_shard_of_configs2():
 def test_bench_py_n2_branch_runs_with_two_ranks_on_one_gpu(tmp_path):
     """bench.py's N > 1 branch, executed: two ranks (torch.distributed.run, gloo for the barriers and the one all-gather -- both ranks
     share GPU 0, which RCCL refuses), each rank its own shard of problem ids, each checking two of its problems against the oracle
-    before rank 0 prints.  A functional run, not a scaling point."""
+    (--full) before rank 0 prints.  A functional run, not a scaling point."""
     import socket
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -173,7 +173,7 @@ def test_bench_py_n2_branch_runs_with_two_ranks_on_one_gpu(tmp_path):
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--problems", "64", "--iters", "512", "--backend", "gloo", "--device-map", "0,0"]
+           "--problems", "64", "--iters", "512", "--backend", "gloo", "--device-map", "0,0", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
