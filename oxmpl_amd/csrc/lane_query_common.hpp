@@ -62,4 +62,14 @@ struct LMargins {
     bool usable;      // H small enough for binary32 products
 };
 
+// E of the dot-product screen (rrt_lanes.hip's error model) for a magnitude bound h relative to c0.  u H^2 D (3D + 9) holds while
+// binary32 results are normal; below 2^-126 a rounding errs by up to 2^-150 whatever the value, so each of the D + 1 binary32
+// roundings of s' (cc and the D fused multiply-adds) adds 2^-150 and the conversions fl32(x - c0), fl32(q - c0) add 2^-150 per
+// coordinate, at most 4 D H 2^-149 in d^2 -- below (D + 1) 2^-150 for H < 1/8, and below the 1.0001 slack of the first term
+// above: (D + 1) 2^-149 covers both.  (Without it a scene of extent ~1e-22 gets screen values whose rounding is coarser than
+// E, and a screen verdict can name the wrong nearest node.)  1e-290: binary64 underflow of h * h and |b|^2.
+__device__ __forceinline__ double lanes_screen_e(double h, int dim) {
+    return 0x1p-24 * h * h * (double)(dim * (3 * dim + 9)) * 1.0001 + 1e-290 + (double)(dim + 1) * 0x1p-149;
+}
+
 }  // namespace oxhip

@@ -565,9 +565,8 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
             h = fmax(h, fabs(p.goal_c[(size_t)(live ? prob : 0u) * DIM + k] - c0[k]));
         }
         h = unid(h) * 1.001;   // interpolation rounding over any chain of inserts
-        const double u = 0x1p-24;
         mg.usable = h < 1e15 && fabs(c0[0]) < 1e300;
-        mg.e2 = 2.0 * (u * h * h * (double)(D * (3 * D + 9)) * 1.0001 + 1e-290);
+        mg.e2 = 2.0 * lanes_screen_e(h, D);
     }
     __syncthreads();   // the launch's only barrier: the obstacle tables are in LDS
     if (!live) return;

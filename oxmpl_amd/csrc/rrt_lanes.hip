@@ -323,7 +323,7 @@ __global__ __launch_bounds__(kLanesThreads) void rrt_lanes_kernel(DevParams p) {
             }
             h = unid(h) * 1.001;
             const bool usable = h < 1e15 && fabs(c0[0]) < 1e300;
-            e4f = usable ? f32_up(2.5 * (0x1p-24 * h * h * (double)(D * (3 * D + 9)) * 1.0001 + 1e-290)) : __builtin_inff();
+            e4f = usable ? f32_up(2.5 * lanes_screen_e(h, D)) : __builtin_inff();
         }
 
         uint32_t seen_sampled = 0;
@@ -608,15 +608,14 @@ __global__ __launch_bounds__(kLanesThreads) void rrt_lanes_kernel(DevParams p) {
             h = fmax(h, fabs(goal_c[k] - c0[k]));
         }
         h = unid(h) * 1.001;   // interpolation rounding over any chain of inserts
-        const double u = 0x1p-24;
         mg.usable = h < 1e15 && fabs(c0[0]) < 1e300;  // also false for NaN / inf
-        mg.e2 = 2.0 * (u * h * h * (double)(D * (3 * D + 9)) * 1.0001 + 1e-290);
+        mg.e2 = 2.0 * lanes_screen_e(h, D);
         // the spheres for the binary32 pre-filter of the motion check: same error model with H_f = max(H, |centre - c0|)
         double hs = 0.0;
 #pragma unroll
         for (int k = 0; k < D; ++k) hs = fmax(hs, lane < ns64 ? fabs(oc[k] - c0[k]) : 0.0);
         const double hf = fmax(h, wave_max_f64pos(hs));
-        const double ef = 2.0 * (u * hf * hf * (double)(D * (3 * D + 9)) * 1.0001 + 1e-290);
+        const double ef = 2.0 * lanes_screen_e(hf, D);
         double sq = 0.0;
 #pragma unroll
         for (int k = 0; k < D; ++k) {

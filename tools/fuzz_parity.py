@@ -37,12 +37,15 @@ def random_field(dim, lo, hi):
 
 
 def case_rv(planner):
-    dim = int(rng.choice([1, 2, 2, 3, 3, 3, 4, 6, 8]))
+    dim = int(rng.choice([1, 2, 2, 3, 3, 3, 4, 5, 6, 7, 8]))
     lo = float(rng.choice([0.0, -10.0, 100.0, -1e6]))
     hi = lo + float(rng.choice([1.0, 10.0, 20.0, 1e3]))
     if planner == capi.PLANNER_RRT_CONNECT:   # RRTConnect: tiny and huge spaces too (1e60: beyond binary32)
         s = float(rng.choice([1.0, 1.0, 1.0, 1e-12, 1e18, 1e60]))
         lo, hi = lo * s, hi * s
+    elif planner in (capi.PLANNER_RRT, capi.PLANNER_RRT_STAR):   # RRT / RRT*: the same, plus binary32 squares underflowing (1e-20),
+        s = float(rng.choice([1.0, 1.0, 1.0, 1e-12, 1e18, 1e60, 1e-20, 1e-40, 1e-158]))   # subnormal binary32 coordinates (1e-40)
+        lo, hi = lo * s, hi * s                                                        # and subnormal binary64 squares (1e-158)
     w = hi - lo
     bounds = [(lo, hi)] * dim
     md = float(rng.choice([0.02, 0.05, 0.1, 0.3])) * w
