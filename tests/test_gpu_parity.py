@@ -383,7 +383,7 @@ def test_long_motion_checks_are_not_a_stalled_pipeline(kernel):
     (boxes are stepped, never filtered): the resident kernels' resolver then works for longer than the watchdog of the
     waves waiting on it, which must read its heartbeat instead of reporting a stalled hand-off."""
     if kernel == capi.KERNEL_AUTO:
-        pytest.skip("a batch of three runs the lane-per-query kernel under KERNEL_AUTO: the [lanes] case")
+        pytest.skip("KERNEL_AUTO runs the cell-grid kernel for R^2 batches of any size: the [cells] case")
     # (the cell-grid kernel has no hand-off to stall -- one wave does everything -- and steps every lane's motion in lockstep: a third
     #  of the states keeps its case to the time of the others)
     states = 1.0e5 if kernel == capi.KERNEL_CELLS else 3.0e5

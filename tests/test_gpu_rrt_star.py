@@ -22,8 +22,8 @@ DESIGN = {"kernel": capi.KERNEL_AUTO}
 
 @pytest.fixture(autouse=True, params=["decoupled", "decoupled_lanes", "one_kernel"])
 def star_design(request):
-    # decoupled: geometry by rrt_cells.hip (what KERNEL_AUTO runs for batches of more than 256 problems in R^2 / R^3) + rrt_star_wire.hip;
-    # decoupled_lanes: geometry by rrt_lanes.hip (KERNEL_AUTO's choice for small batches and R^4 .. R^6)
+    # decoupled: geometry by rrt_cells.hip (what KERNEL_AUTO runs in R^2 / R^3 at any batch size) + rrt_star_wire.hip;
+    # decoupled_lanes: geometry by rrt_lanes.hip (KERNEL_AUTO's choice in R^4 .. R^6)
     DESIGN["kernel"] = {"decoupled": capi.KERNEL_CELLS, "decoupled_lanes": capi.KERNEL_LANES, "one_kernel": capi.KERNEL_STREAM}[request.param]
     yield request.param
     DESIGN["kernel"] = capi.KERNEL_AUTO
