@@ -78,17 +78,43 @@ typedef enum oxhip_planner_kind {
  * 0.5 * PI.  acos / sin are the portable routines ox_acos / ox_sincos (below one ulp; the CPU test suite restates them), so
  * against a rustc-built oxmpl (libm) a run is within a few ulp per evaluation, not bit-exact: PARITY UNPINNED.
  * Validity: oxhip_rrt_batch_set_spheres with 4-wide centres, read as cones in the SO(3) metric -- a state is valid iff
- * distance(centre, q) > radius for every cone (strict; the ForbiddenConeChecker of oxmpl/tests/rrt_so3ss_tests.rs:46-56). */
+ * distance(centre, q) > radius for every cone (strict; the ForbiddenConeChecker of oxmpl/tests/rrt_so3ss_tests.rs:46-56).
+ *
+ * SE(3) = R^3 x SO(3) is not in the reference either (docs/BACKLOG.md:12-14); it is assembled from the reference's
+ * RealVectorStateSpace and SO3StateSpace the way SE(2) was, with OMPL's SE(3) weights (rrt_connect_se3.hip).  Every operation is
+ * unfused binary64 in the order written here:
+ *   state        dim = 7: (x, y, z, qx, qy, qz, qw), AoS; normalising the quaternion is the caller's job, as for SO(3)
+ *   bounds       bounds[0..5] = (lo, hi) of x, y, z, validated as RealVectorStateSpace::new(3, ..) (OXHIP_ERR_UNBOUNDED,
+ *                OXHIP_ERR_ZERO_VOLUME); bounds[6..9] = the rotation's centre quaternion, bounds[10] = max_angle, read exactly as
+ *                an SO(3) batch reads bounds[0..4]; bounds[11..15] are ignored
+ *   distance     1.0 * distance_R3(xyz) + 1.0 * distance_SO3(q): the two component distances, then one add
+ *   interpolate  xyz: from + (to - from) * t; q: SO(3)'s interpolate; the same t
+ *   sample       x, y, z in that order by random_range(lo..hi), then SO(3)'s rejection sampler (four random_range(-1.0..1.0)
+ *                words per attempt)
+ *   extent       extent_R3 + 0.5 * PI; lvsl = extent * fraction; check_motion steps of lvsl * 0.1 (more than 1e6 validity
+ *                checks per edge are refused)
+ *   goal         distance(s, target) <= radius; sample_goal = the target (OXHIP_GOAL_SAMPLE_CENTRE, no draw)
+ *   validity     a rigid body of B spheres (c_b, r_b) given in the body frame (oxhip_rrt_batch_set_body; default: one sphere of
+ *                radius 0 at the origin, a point) among N world spheres (o_j, r_j) (oxhip_rrt_batch_set_spheres, 3-wide centres).
+ *                Body sphere b sits at p = rot(q, c_b) + (x, y, z); the state is valid iff sqrt(|p - o_j|^2) > r_b + r_j for
+ *                every pair (strict; |.|^2 summed x, y, z in order; r_b + r_j is one add).  Bounds are not part of validity.
+ *   rot(q, v)    u = (qx, qy, qz), w = qw:  t = 2 * (u x v);  rot = (v + w * t) + (u x t), component by component, every
+ *                cross product component evaluated as a*b - c*d:  (u x v)_x = uy*vz - uz*vy, _y = uz*vx - ux*vz, _z = ux*vy - uy*vx
+ *   planner      RRTConnect (rrt_connect.rs:86-309) as for the other RRTConnect rows; PARITY UNPINNED (nothing to compare with). */
 typedef enum oxhip_space_kind {
     OXHIP_SPACE_REAL_VECTOR = 0,  /* RealVectorStateSpace(dim)  oxmpl/src/base/spaces/real_vector_state_space.rs */
     OXHIP_SPACE_SE2 = 1,          /* R^2 x SO(2): dim must be 3, bounds = (x), (y), (theta: clamped to [-PI, PI]);
                                      planner must be OXHIP_PLANNER_RRT_CONNECT; validity = oxhip_rrt_batch_set_segments */
-    OXHIP_SPACE_SO3 = 2           /* SO3StateSpace  oxmpl/src/base/spaces/so3_state_space.rs: dim must be 4, bounds as above.
+    OXHIP_SPACE_SO3 = 2,          /* SO3StateSpace  oxmpl/src/base/spaces/so3_state_space.rs: dim must be 4, bounds as above.
                                      RRT batches: planner must be OXHIP_PLANNER_RRT with kernel OXHIP_KERNEL_AUTO or OXHIP_KERNEL_STREAM
                                      (both run rrt_so3.hip); goal = ball in the SO(3) distance, sample_goal = OXHIP_GOAL_SAMPLE_CENTRE;
                                      validity = cones (oxhip_rrt_batch_set_spheres; set_boxes is OXHIP_ERR_BAD_ARG).
                                      PRM (oxhip_prm_config.space, prm_so3.hip): radius rule only (knn_k must be 0); cones by
                                      oxhip_prm_set_spheres (set_boxes is OXHIP_ERR_BAD_ARG); goal = ball in the SO(3) distance */
+    OXHIP_SPACE_SE3 = 3           /* R^3 x SO(3), see above: dim must be 7; planner must be OXHIP_PLANNER_RRT_CONNECT with kernel
+                                     OXHIP_KERNEL_AUTO or OXHIP_KERNEL_STREAM (both run rrt_connect_se3.hip); goal sampler CENTRE;
+                                     validity = oxhip_rrt_batch_set_body + oxhip_rrt_batch_set_spheres (set_boxes and
+                                     set_segments are OXHIP_ERR_BAD_ARG).  Not a PRM space. */
 } oxhip_space_kind;
 
 /* GoalSampleableRegion::sample_goal of the ball goal (goal.rs:35-41; the trait leaves the distribution to the implementor).
@@ -120,7 +146,9 @@ typedef enum oxhip_debug_flag {
     OXHIP_DEBUG_STAR_ONE_SEGMENT = 64,    /* rrt_star_wire.hip: one edge-check segment, no overlap with the wiring stream */
     OXHIP_DEBUG_SE2_NO_SEGMENT_GRID = 128,/* rrt_connect_se2.hip / rrt_connect.hip: every interpolated state is tested against every segment / sphere (no grid lookup) */
     OXHIP_DEBUG_SE2_SMALL_LDS = 256,      /* rrt_connect_se2.hip: the shape for batches larger than the chip (512-node shadows, segments from HBM / L2) whatever the batch size */
-    OXHIP_DEBUG_SO3_SERIAL_SAMPLER = 512  /* rrt_so3.hip: sample_uniform attempt by attempt on one lane instead of 64 attempts side by side */
+    OXHIP_DEBUG_SO3_SERIAL_SAMPLER = 512, /* rrt_so3.hip, rrt_connect_se3.hip: sample_uniform attempt by attempt on one lane instead of 64 attempts side by side */
+    OXHIP_DEBUG_SE3_BRANCHY_SWEEP = 1024  /* rrt_connect_se3.hip: the motion check decides every (body sphere, obstacle) pair as it meets it (the first kernel's sweep)
+                                             instead of sweeping without a branch and deciding only the pairs it could not clear */
 } oxhip_debug_flag;
 
 typedef enum oxhip_kernel_kind {
@@ -202,6 +230,11 @@ int32_t oxhip_rrt_batch_set_boxes(oxhip_rrt_batch* b, const double* lo /*[n][dim
  * oxhip_rrt_batch_check_motion test a state against its cell's segments only -- the same verdicts, by construction. */
 int32_t oxhip_rrt_batch_set_segments(oxhip_rrt_batch* b, const double* segments /*[n][4]*/, uint32_t n,
                                      double clearance);
+
+/* SE(3) batches only (OXHIP_ERR_BAD_ARG otherwise).  The rigid body: n spheres, 1 <= n <= 16, centres in the body frame and radii
+ * (finite, >= 0).  Replaces any earlier body; a new batch has one sphere of radius 0 at the origin.  The obstacles are the world
+ * spheres of oxhip_rrt_batch_set_spheres (centres [n][3]). */
+int32_t oxhip_rrt_batch_set_body(oxhip_rrt_batch* b, const double* centres /*[n][3]*/, const double* radii /*[n]*/, uint32_t n);
 
 /* Planner::setup (rrt.rs:140-156) for every problem: clears the tree, pushes start_states[0]
  * (validity of the start is NOT checked, as in the reference), resets counters and the RNG
@@ -317,6 +350,12 @@ int32_t oxhip_se2_op_batch(int32_t device, uint32_t op, const double* a, const d
  * op 1: out[i] = interpolate(a_i, b_i, t[i]), t in [0, 1]  out[n][4]
  * op 2: out[i] = ox_acos(a[i]), a read as n scalars (b and t may be NULL)   out[n] */
 int32_t oxhip_so3_op_batch(int32_t device, uint32_t op, const double* a, const double* b, const double* t, uint32_t n,
+                           double* out);
+/* SE(3) arithmetic self-test hooks (OXHIP_SPACE_SE3), n rows of (x, y, z, qx, qy, qz, qw) in a and b:
+ * op 0: out[i] = distance(a_i, b_i)                                              out[n]
+ * op 1: out[i] = interpolate(a_i, b_i, t[i])                                     out[n][7]
+ * op 2: out[i] = rot(q of a_i, first three of b_i) + xyz of a_i (t may be NULL)  out[n][3] */
+int32_t oxhip_se3_op_batch(int32_t device, uint32_t op, const double* a, const double* b, const double* t, uint32_t n,
                            double* out);
 /* device RNG self-test: the first n u64 words of the (seed, stream) ChaCha12 stream */
 int32_t oxhip_rng_u64_batch(int32_t device, uint64_t seed, uint64_t stream, uint32_t n, uint64_t* out);

@@ -1,5 +1,5 @@
 """oxmpl_amd -- MI355X-native batched RRT hot path for oxmpl (rossng/oxmpl), with the rows built next to it:
-RRTConnect (R^n and SE(2)), RRT* and PRM.
+RRTConnect (R^n, SE(2) and SE(3)), RRT* and PRM.
 
 The product is `lib/liboxmpl_hip.so` (hand-written HIP for gfx950 behind the C ABI of
 include/oxmpl_hip.h).  This package is the thin Python host side: a ctypes binding

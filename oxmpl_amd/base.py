@@ -162,6 +162,87 @@ class SO3ConeValidityChecker:
             self.cones.append((list(c), float(radius)))
 
 
+class SE3State:
+    """A rigid-body pose: position (x, y, z) and a rotation (SO3State).  The reference has no SE(3) state yet
+    (docs/BACKLOG.md:12-14); this is the compound of its RealVectorState and SO3State.  `values` is the C ABI's row
+    (x, y, z, qx, qy, qz, qw)."""
+
+    def __init__(self, x, y, z, rotation):
+        if not isinstance(rotation, SO3State):
+            raise TypeError("rotation must be an SO3State")
+        self.x, self.y, self.z, self.rotation = float(x), float(y), float(z), rotation
+
+    @staticmethod
+    def from_values(row):
+        row = [float(v) for v in row]
+        if len(row) != 7:
+            raise ValueError("an SE(3) row is (x, y, z, qx, qy, qz, qw)")
+        return SE3State(row[0], row[1], row[2], SO3State(*row[3:]))
+
+    @property
+    def values(self):
+        return [self.x, self.y, self.z] + self.rotation.values
+
+    def __eq__(self, other):
+        return isinstance(other, SE3State) and self.values == other.values
+
+    def __repr__(self):
+        return "<SE3State x=%r, y=%r, z=%r, rotation=%r>" % (self.x, self.y, self.z, self.rotation)
+
+
+class SE3StateSpace:
+    """SE(3) = R^3 x SO(3), assembled from the reference's RealVectorStateSpace(3) and SO3StateSpace with OMPL's weights
+    (include/oxmpl_hip.h, OXHIP_SPACE_SE3): SE3StateSpace(bounds_xyz, rotation_bounds=None | (SO3State, max_angle)).
+    distance = distance_R3 + distance_SO3, evaluated by the HIP library; extent = extent_R3 + 0.5 * PI."""
+
+    def __init__(self, bounds_xyz, rotation_bounds=None):
+        self.position = RealVectorStateSpace(3, bounds_xyz)
+        self.rotation = SO3StateSpace(rotation_bounds)
+        self.dimension = 7
+        self.longest_valid_segment_fraction = 0.05
+
+    def distance(self, state1, state2):
+        a = np.array([state1.values], dtype=np.float64)
+        b = np.array([state2.values], dtype=np.float64)
+        return float(capi.se3_op_batch(0, a, b)[0])
+
+    def get_maximum_extent(self):
+        return self.position.get_maximum_extent() + 0.5 * math.pi
+
+    def set_longest_valid_segment_fraction(self, fraction):
+        if 0.0 < fraction <= 1.0:
+            self.longest_valid_segment_fraction = float(fraction)
+        elif fraction <= 0.0:
+            self.longest_valid_segment_fraction = 0.0
+        else:
+            self.longest_valid_segment_fraction = 1.0
+
+    def config_bounds(self):
+        """the C ABI's reading of oxhip_rrt_config.bounds for SE(3): the (lo, hi) pairs of x, y, z, then (cx, cy, cz, cw, max_angle)"""
+        return [v for pair in self.position.bounds for v in pair] + self.rotation.config_bounds()
+
+
+class SE3RigidBodyValidityChecker:
+    """Device-describable StateValidityChecker of SE(3): a rigid body of spheres (centre in the body frame, radius; 1 .. 16 of
+    them, default a point at the origin) among world spheres.  A state is valid iff every body sphere, carried to
+    rot(q, centre) + (x, y, z), lies strictly outside every obstacle: distance > r_body + r_obstacle.  Pass it to
+    RRTConnect.setup() with an SE(3) ProblemDefinition."""
+
+    def __init__(self, body=None, obstacles=()):
+        body = [([0.0, 0.0, 0.0], 0.0)] if body is None else list(body)
+        if not 1 <= len(body) <= capi.SE3_MAX_BODY:
+            raise ValueError("a body has 1 .. %d spheres" % capi.SE3_MAX_BODY)
+        self.body, self.obstacles = [], []
+        for name, src, dst in (("body", body, self.body), ("obstacle", obstacles, self.obstacles)):
+            for centre, radius in src:
+                c = [float(v) for v in centre]
+                if len(c) != 3:
+                    raise ValueError("a %s sphere's centre is (x, y, z)" % name)
+                dst.append((c, float(radius)))
+        if any(not (r >= 0.0 and math.isfinite(r)) for _, r in self.body):
+            raise ValueError("a body sphere's radius must be finite and >= 0")
+
+
 class ProblemDefinition:
     """oxmpl_py.base.ProblemDefinition (oxmpl-py/src/base/problem_definition.rs:43-75)"""
 
@@ -191,6 +272,18 @@ class ProblemDefinition:
             raise TypeError("the GPU path needs a ball goal: an object with `target` and `radius` attributes")
         if not isinstance(start_state, SO3State) or not isinstance(goal.target, SO3State):
             raise TypeError("start_state and goal.target must be SO3State")
+        return ProblemDefinition(space, start_state, goal)
+
+    @staticmethod
+    def from_se3(space, start_state, goal):
+        """`goal`: any object with a `target` (SE3State) and a `radius`; is_satisfied(s) = distance(s, target) <= radius in the
+        SE(3) distance, sample_goal() = target."""
+        if not isinstance(space, SE3StateSpace):
+            raise TypeError("space must be an SE3StateSpace")
+        if not hasattr(goal, "target") or not hasattr(goal, "radius"):
+            raise TypeError("the GPU path needs a ball goal: an object with `target` and `radius` attributes")
+        if not isinstance(start_state, SE3State) or not isinstance(goal.target, SE3State):
+            raise TypeError("start_state and goal.target must be SE3State")
         return ProblemDefinition(space, start_state, goal)
 
 

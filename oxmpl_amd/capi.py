@@ -26,22 +26,24 @@ DEBUG_STAR_TWO_PASS, DEBUG_STAR_ONE_SEGMENT = 32, 64
 DEBUG_SE2_NO_SEGMENT_GRID = 128
 DEBUG_SE2_SMALL_LDS = 256
 DEBUG_SO3_SERIAL_SAMPLER = 512
+DEBUG_SE3_BRANCHY_SWEEP = 1024
 ABI_VERSION = 2
 STAMP_WORDS = 64
 PLANNER_RRT, PLANNER_RRT_CONNECT, PLANNER_RRT_STAR = 0, 1, 2
-SPACE_REAL_VECTOR, SPACE_SE2, SPACE_SO3 = 0, 1, 2
+SPACE_REAL_VECTOR, SPACE_SE2, SPACE_SO3, SPACE_SE3 = 0, 1, 2, 3
+SE3_MAX_BODY = 16
 
 # every symbol include/oxmpl_hip.h declares (tests check the library exports them all)
 EXPORTS = [
     "oxhip_abi_version", "oxhip_status_string", "oxhip_last_error_string", "oxhip_device_count",
     "oxhip_rrt_batch_create", "oxhip_rrt_batch_destroy", "oxhip_rrt_batch_set_spheres",
-    "oxhip_rrt_batch_set_boxes", "oxhip_rrt_batch_set_segments", "oxhip_rrt_batch_setup", "oxhip_rrt_batch_set_tree", "oxhip_rrt_batch_solve",
+    "oxhip_rrt_batch_set_boxes", "oxhip_rrt_batch_set_segments", "oxhip_rrt_batch_set_body", "oxhip_rrt_batch_setup", "oxhip_rrt_batch_set_tree", "oxhip_rrt_batch_solve",
     "oxhip_rrt_batch_get_counts", "oxhip_rrt_batch_get_tree", "oxhip_rrt_batch_get_path",
     "oxhip_rrt_batch_get_goal_counts", "oxhip_rrt_batch_get_goal_tree", "oxhip_rrt_batch_get_costs",
     "oxhip_rrt_batch_last_timing", "oxhip_rrt_batch_enable_stamps", "oxhip_rrt_batch_get_stamps",
     "oxhip_nn_argmin_batch", "oxhip_distance_batch",
     "oxhip_interpolate_batch", "oxhip_rrt_batch_is_valid", "oxhip_rrt_batch_check_motion",
-    "oxhip_f64_op_batch", "oxhip_se2_op_batch", "oxhip_so3_op_batch", "oxhip_rng_u64_batch",
+    "oxhip_f64_op_batch", "oxhip_se2_op_batch", "oxhip_so3_op_batch", "oxhip_se3_op_batch", "oxhip_rng_u64_batch",
     "oxhip_prm_create", "oxhip_prm_destroy", "oxhip_prm_set_spheres", "oxhip_prm_set_boxes", "oxhip_prm_setup",
     "oxhip_prm_set_problem", "oxhip_prm_construct_roadmap", "oxhip_prm_get_sizes", "oxhip_prm_get_roadmap",
     "oxhip_prm_solve", "oxhip_prm_get_query_sets", "oxhip_prm_last_timing", "oxhip_prm_knn_exact_rows",
@@ -117,6 +119,8 @@ def lib():
         L.oxhip_rrt_batch_set_segments.argtypes = [C.c_void_p, _dp, C.c_uint32, C.c_double]
         L.oxhip_se2_op_batch.argtypes = [C.c_int32, C.c_uint32, _dp, _dp, _dp, C.c_uint32, _dp]
         L.oxhip_so3_op_batch.argtypes = [C.c_int32, C.c_uint32, _dp, _dp, _dp, C.c_uint32, _dp]
+        L.oxhip_rrt_batch_set_body.argtypes = [C.c_void_p, _dp, _dp, C.c_uint32]
+        L.oxhip_se3_op_batch.argtypes = [C.c_int32, C.c_uint32, _dp, _dp, _dp, C.c_uint32, _dp]
         L.oxhip_rrt_batch_setup.argtypes = [C.c_void_p, _dp, _dp, _dp]
         L.oxhip_rrt_batch_set_tree.argtypes = [C.c_void_p, C.c_uint32, _dp, _i32p, C.c_uint32]
         L.oxhip_rrt_batch_solve.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_uint32, _i32p]
@@ -191,7 +195,11 @@ class RRTBatch:
 
     space=SPACE_SO3 (dim 4, quaternions (x, y, z, w)): `bounds` is (cx, cy, cz, cw, max_angle) -- SO3StateSpace's centre
     quaternion and cone of freedom, as include/oxmpl_hip.h reinterprets the config's bounds -- and set_spheres takes the
-    forbidden cones (centre quaternion, radius in the SO(3) distance)."""
+    forbidden cones (centre quaternion, radius in the SO(3) distance).
+
+    space=SPACE_SE3 (dim 7, states (x, y, z, qx, qy, qz, qw); planner=PLANNER_RRT_CONNECT): `bounds` holds eleven values, the
+    (lo, hi) pairs of x, y, z and then (cx, cy, cz, cw, max_angle) of the rotation; set_body gives the rigid body's spheres
+    and set_spheres the world's (3-wide centres)."""
 
     def __init__(self, dim, bounds, max_distance, goal_bias, n_problems, max_nodes=10000,
                  lvs_fraction=0.05, stop_at_goal=True, seed=0, first_problem_id=0, device=0,
@@ -205,6 +213,9 @@ class RRTBatch:
             if b.size != 5:
                 raise OxhipError(ERR_BAD_ARG, "SO(3) bounds are (cx, cy, cz, cw, max_angle)")
             b = np.concatenate([b, np.zeros(2 * dim - 5 if dim >= 3 else 0)])
+        elif space == SPACE_SE3:
+            if b.size != 11:
+                raise OxhipError(ERR_BAD_ARG, "SE(3) bounds are (x lo, x hi, y lo, y hi, z lo, z hi, cx, cy, cz, cw, max_angle)")
         elif b.size != 2 * dim:
             raise OxhipError(ERR_BAD_ARG, "bounds must hold dim (lo,hi) pairs")  # StateSpaceError::DimensionMismatch
         for i, v in enumerate(b[:2 * MAX_DIM]):  # dim > MAX_DIM is rejected by the library
@@ -218,7 +229,7 @@ class RRTBatch:
         cfg.space = space
         cfg.goal_sampler, cfg.debug_flags, cfg.star_pool_share = goal_sampler, debug_flags, star_pool_share
         cfg.frozen_split = frozen_split
-        self.planner = planner
+        self.planner, self.space = planner, space
         self.dim, self.n_problems, self.max_nodes = dim, n_problems, max_nodes
         self._h = C.c_void_p()
         _check(lib().oxhip_rrt_batch_create(C.byref(cfg), C.byref(self._h)))
@@ -232,7 +243,7 @@ class RRTBatch:
 
     def set_spheres(self, centres, radii):
         r = _f64(radii).reshape(-1)
-        c = _f64(centres, (r.size, self.dim))
+        c = _f64(centres, (r.size, 3 if self.space == SPACE_SE3 else self.dim))
         _check(lib().oxhip_rrt_batch_set_spheres(self._h, _p(c), _p(r), r.size))
 
     def set_boxes(self, lo, hi):
@@ -244,6 +255,14 @@ class RRTBatch:
         """SE(2) batches: the segment-soup checker (disc robot of radius `clearance`)"""
         s = _f64(segments).reshape(-1, 4)
         _check(lib().oxhip_rrt_batch_set_segments(self._h, _p(s), s.shape[0], clearance))
+
+    def set_body(self, centres, radii):
+        """SE(3) batches: the rigid body's spheres (1 .. 16), centres [n][3] in the body frame"""
+        r = _f64(radii).reshape(-1)
+        c = _f64(centres).reshape(-1, 3)
+        if c.shape[0] != r.size:
+            raise OxhipError(ERR_BAD_ARG, "one radius per body sphere")
+        _check(lib().oxhip_rrt_batch_set_body(self._h, _p(c), _p(r), r.size))
 
     def setup(self, starts, goal_centres, goal_radii):
         P = self.n_problems
@@ -410,6 +429,17 @@ def so3_op_batch(op, a, b=None, t=None, device=0):
     out = np.empty((a.shape[0], 4) if op == 1 else a.shape[0], dtype=np.float64)
     tt = None if t is None else _f64(t).reshape(-1)
     _check(lib().oxhip_so3_op_batch(device, op, _p(a), _p(b), None if tt is None else _p(tt), a.shape[0], _p(out)))
+    return out
+
+
+def se3_op_batch(op, a, b, t=None, device=0):
+    """rows (x, y, z, qx, qy, qz, qw).  op 0: distance(a, b) [n]; op 1: interpolate(a, b, t) [n][7];
+    op 2: rot(q of a, first three of b) + xyz of a [n][3]"""
+    a = _f64(a).reshape(-1, 7)
+    b = _f64(b, a.shape)
+    tt = None if t is None else _f64(t, (a.shape[0],))
+    out = np.empty(a.shape[0] if op == 0 else (a.shape[0], 7 if op == 1 else 3), dtype=np.float64)
+    _check(lib().oxhip_se3_op_batch(device, op, _p(a), _p(b), None if tt is None else _p(tt), a.shape[0], _p(out)))
     return out
 
 

@@ -73,6 +73,8 @@ struct oxhip_rrt_batch {
     DevBuf<double> tree_b;   // RRTConnect goal trees
     DevBuf<double> segs;            // SE(2): segment soup
     DevBuf<uint16_t> seg_grid;      // ... and the cells' segment lists (rrt_connect_se2.hip, seg_grid_kernel)
+    DevBuf<double> se3_body;        // SE(3): the body's spheres, SoA [4][kSe3MaxBody] (rrt_connect_se3.hip)
+    Se3Args se3{};
     DevBuf<uint64_t> conn_grid;     // RRTConnect in R^2 / R^3: the spheres that reach each cell of the bounds' grid (rrt_connect.hip)
     DevBuf<double> conn_filt;
     DevBuf<double> cost, nb_dist;   // RRT*: cost-to-come, neighbour scratch
@@ -172,7 +174,24 @@ int32_t oxhip_rrt_batch_create(const oxhip_rrt_config* cfg, oxhip_rrt_batch** ou
     double fraction = cfg->lvs_fraction, res = 0.0;
     double th_lo = 0.0, th_hi = 0.0;
     double so3_max_angle = 0.0;
-    if (cfg->space > OXHIP_SPACE_SO3) return fail(OXHIP_ERR_BAD_ARG, "unknown space kind");
+    if (cfg->space > OXHIP_SPACE_SE3) return fail(OXHIP_ERR_BAD_ARG, "unknown space kind");
+    if (cfg->space == OXHIP_SPACE_SE3) {
+        if (cfg->dim != 7) return fail(OXHIP_ERR_BAD_ARG, "SE(3) states are (x, y, z, qx, qy, qz, qw): dim must be 7");
+        if (cfg->planner != OXHIP_PLANNER_RRT_CONNECT) return fail(OXHIP_ERR_BAD_ARG, "SE(3) is built for RRTConnect only");
+        if (cfg->kernel != OXHIP_KERNEL_AUTO && cfg->kernel != OXHIP_KERNEL_STREAM)
+            return fail(OXHIP_ERR_BAD_ARG, "SE(3) RRTConnect runs on rrt_connect_se3.hip: kernel must be OXHIP_KERNEL_AUTO or OXHIP_KERNEL_STREAM");
+        if (cfg->goal_sampler != OXHIP_GOAL_SAMPLE_CENTRE) return fail(OXHIP_ERR_BAD_ARG, "SE(3): the goal sampler must be OXHIP_GOAL_SAMPLE_CENTRE");
+        // (x, y, z) as RealVectorStateSpace::new(3, ..) (validates, clamps the fraction); rotation bounds as SO3StateSpace::new;
+        // extent = extent_xyz + 0.5 * PI; lvsl = extent * fraction; res = lvsl * 0.1
+        int32_t sr = space_resolution(3, cfg->bounds, fraction, res);
+        if (sr != OXHIP_OK) return sr;
+        if ((sr = so3_rotation_bounds(cfg->bounds + 6, so3_max_angle)) != OXHIP_OK) return sr;
+        double acc = 0.0;
+        for (uint32_t k = 0; k < 3; ++k) { double w = cfg->bounds[2 * k + 1] - cfg->bounds[2 * k]; double sq = w * w; acc = acc + sq; }
+        const double extent = std::sqrt(acc) + 0.5 * 3.14159265358979323846;
+        const double lvsl = extent * fraction;
+        res = lvsl * 0.1;
+    } else
     if (cfg->space == OXHIP_SPACE_SO3) {
         if (cfg->dim != 4) return fail(OXHIP_ERR_BAD_ARG, "SO(3) states are quaternions (x, y, z, w): dim must be 4");
         if (cfg->planner != OXHIP_PLANNER_RRT) return fail(OXHIP_ERR_BAD_ARG, "SO(3) is built for RRT only");
@@ -221,6 +240,11 @@ int32_t oxhip_rrt_batch_create(const oxhip_rrt_config* cfg, oxhip_rrt_batch** ou
     if (cfg->space == OXHIP_SPACE_SE2) { dp.lo[2] = th_lo; dp.hi[2] = th_hi; dp.scale[2] = th_hi - th_lo; }
     if (cfg->space == OXHIP_SPACE_SO3) {
         for (uint32_t k = 0; k < 4; ++k) { dp.so3_centre[k] = cfg->bounds[k]; dp.lo[k] = dp.hi[k] = dp.scale[k] = 0.0; }
+        dp.so3_max_angle = so3_max_angle;
+    }
+    if (cfg->space == OXHIP_SPACE_SE3) {   // lo / hi / scale [0..3) are (x, y, z); the rotation's bounds travel as SO(3)'s do
+        for (uint32_t k = 3; k < 7; ++k) dp.lo[k] = dp.hi[k] = dp.scale[k] = 0.0;
+        for (uint32_t k = 0; k < 4; ++k) dp.so3_centre[k] = cfg->bounds[6 + k];
         dp.so3_max_angle = so3_max_angle;
     }
     dp.space = cfg->space;
@@ -314,6 +338,11 @@ int32_t oxhip_rrt_batch_create(const oxhip_rrt_config* cfg, oxhip_rrt_batch** ou
     chk(b->goal_c.alloc((size_t)P * dim));
     chk(b->goal_thr.alloc(P));
     chk(b->goal_r.alloc(P));
+    if (cfg->space == OXHIP_SPACE_SE3 && e == hipSuccess) {   // the default body: one sphere of radius 0 at the origin (a point)
+        if (upload(b->se3_body, std::vector<double>(4 * (size_t)kSe3MaxBody, 0.0), b->stream) != OXHIP_OK) e = hipErrorOutOfMemory;
+        b->se3.body = b->se3_body.p;
+        b->se3.n_body = 1;
+    }
     if (e != hipSuccess) {
         std::string msg = std::string("device allocation failed: ") + hipGetErrorString(e);
         oxhip_rrt_batch_destroy(b);
@@ -424,7 +453,7 @@ int32_t oxhip_rrt_batch_set_spheres(oxhip_rrt_batch* b, const double* centres, c
     if (b->cfg.space == OXHIP_SPACE_SE2) return fail(OXHIP_ERR_BAD_ARG, "SE(2) batches take oxhip_rrt_batch_set_segments");
     int32_t st = select_device(b->cfg.device);
     if (st != OXHIP_OK) return st;
-    const uint32_t dim = b->cfg.dim;
+    const uint32_t dim = b->cfg.space == OXHIP_SPACE_SE3 ? 3u : b->cfg.dim;   // SE(3): world spheres, 3-wide centres
     std::vector<double> c((size_t)dim * n), thr(n);
     for (uint32_t j = 0; j < n; ++j) {
         for (uint32_t k = 0; k < dim; ++k) {
@@ -437,7 +466,7 @@ int32_t oxhip_rrt_batch_set_spheres(oxhip_rrt_batch* b, const double* centres, c
     if ((st = upload(b->sph_c, c, b->stream)) != OXHIP_OK) return st;
     if ((st = upload(b->sph_thr, thr, b->stream)) != OXHIP_OK) return st;
     b->dp.n_spheres = n; b->dp.sph_c = b->sph_c.p; b->dp.sph_thr = b->sph_thr.p;
-    if (b->cfg.space == OXHIP_SPACE_SO3) {   // cones: distance(centre, q) > radius in the SO(3) metric, compared with the radius itself
+    if (b->cfg.space == OXHIP_SPACE_SO3 || b->cfg.space == OXHIP_SPACE_SE3) {   // cones: distance(centre, q) > radius in the SO(3) metric, compared with the radius itself; SE(3): r_b + r_j
         if ((st = upload(b->sph_r, std::vector<double>(radii, radii + n), b->stream)) != OXHIP_OK) return st;
         b->dp.sph_r = b->sph_r.p;
     }
@@ -451,6 +480,7 @@ int32_t oxhip_rrt_batch_set_boxes(oxhip_rrt_batch* b, const double* lo, const do
     if (!b || (n && (!lo || !hi))) return fail(OXHIP_ERR_BAD_ARG, "null argument");
     if (b->cfg.space == OXHIP_SPACE_SE2) return fail(OXHIP_ERR_BAD_ARG, "SE(2) batches take oxhip_rrt_batch_set_segments");
     if (b->cfg.space == OXHIP_SPACE_SO3) return fail(OXHIP_ERR_BAD_ARG, "SO(3) batches take cones (oxhip_rrt_batch_set_spheres)");
+    if (b->cfg.space == OXHIP_SPACE_SE3) return fail(OXHIP_ERR_BAD_ARG, "SE(3) batches take sphere obstacles (oxhip_rrt_batch_set_spheres)");
     int32_t st = select_device(b->cfg.device);
     if (st != OXHIP_OK) return st;
     const uint32_t dim = b->cfg.dim;
@@ -490,6 +520,28 @@ int32_t oxhip_rrt_batch_set_segments(oxhip_rrt_batch* b, const double* segments,
         launch_seg_grid(b->dp, b->seg_grid.p, clearance, b->stream);
         b->dp.seg_grid = b->seg_grid.p;
     }
+    return OXHIP_OK;
+}
+
+int32_t oxhip_rrt_batch_set_body(oxhip_rrt_batch* b, const double* centres, const double* radii, uint32_t n) {
+    if (!b || !centres || !radii) return fail(OXHIP_ERR_BAD_ARG, "null argument");
+    if (b->cfg.space != OXHIP_SPACE_SE3) return fail(OXHIP_ERR_BAD_ARG, "a body describes the SE(3) checker");
+    if (n == 0 || n > (uint32_t)kSe3MaxBody) return fail(OXHIP_ERR_BAD_ARG, "a body has 1 .. 16 spheres");
+    std::vector<double> v(4 * (size_t)kSe3MaxBody, 0.0);   // SoA [4][kSe3MaxBody]
+    for (uint32_t j = 0; j < n; ++j) {
+        for (uint32_t k = 0; k < 3; ++k) {
+            const double c = centres[(size_t)j * 3 + k];
+            if (!(std::fabs(c) <= kMaxMagnitude)) return fail(OXHIP_ERR_BAD_ARG, "body sphere centre not finite / too large");
+            v[(size_t)k * kSe3MaxBody + j] = c;
+        }
+        if (!(radii[j] >= 0.0 && radii[j] <= kMaxMagnitude)) return fail(OXHIP_ERR_BAD_ARG, "body sphere radius must be finite and >= 0");
+        v[3 * (size_t)kSe3MaxBody + j] = radii[j];
+    }
+    int32_t st = select_device(b->cfg.device);
+    if (st != OXHIP_OK) return st;
+    if ((st = upload(b->se3_body, v, b->stream)) != OXHIP_OK) return st;
+    b->se3.body = b->se3_body.p;
+    b->se3.n_body = n;
     return OXHIP_OK;
 }
 
@@ -770,7 +822,7 @@ int32_t oxhip_rrt_batch_solve(oxhip_rrt_batch* b, uint64_t max_iterations, doubl
     int32_t st = select_device(b->cfg.device);
     if (st != OXHIP_OK) return st;
     if (b->cfg.planner != OXHIP_PLANNER_RRT && freeze) return fail(OXHIP_ERR_BAD_ARG, "freeze is for the RRT planner");
-    if (b->cfg.space != OXHIP_SPACE_SO3 && (st = refresh_filter(b)) != OXHIP_OK) return st;   // (rrt_so3.hip tests every cone)
+    if (b->cfg.space != OXHIP_SPACE_SO3 && b->cfg.space != OXHIP_SPACE_SE3 && (st = refresh_filter(b)) != OXHIP_OK) return st;   // (rrt_so3.hip tests every cone, rrt_connect_se3.hip every sphere)
     if (std::isnan(timeout_s) || timeout_s < 0.0)   // Duration cannot be negative; from_secs_f32 (oxmpl-py rrt.rs:112) panics on both
         return fail(OXHIP_ERR_BAD_ARG, "timeout_s is NaN or negative (0 or +inf = no wall-clock limit)");
     const bool has_timeout = timeout_s > 0.0 && std::isfinite(timeout_s);
@@ -797,6 +849,7 @@ int32_t oxhip_rrt_batch_solve(oxhip_rrt_batch* b, uint64_t max_iterations, doubl
         HIP_TRY(hipEventRecord(b->ev0, b->stream));
         if (b->cfg.space == OXHIP_SPACE_SE2) launch_rrt_connect_se2(b->dp, b->stream);
         else if (b->cfg.space == OXHIP_SPACE_SO3) launch_rrt_so3(b->dp, b->stream);
+        else if (b->cfg.space == OXHIP_SPACE_SE3) launch_rrt_connect_se3(b->dp, b->se3, b->stream);
         else if (b->cfg.planner == OXHIP_PLANNER_RRT_CONNECT) launch_rrt_connect(b->dp, b->stream);
         else if (b->cfg.planner == OXHIP_PLANNER_RRT_STAR && b->star_wired) {
             // geometry: exactly RRT's loop on the same stream (rrt_star_wire.hip's header); then wire the new nodes
@@ -1123,6 +1176,7 @@ int32_t oxhip_rrt_batch_is_valid(oxhip_rrt_batch* b, const double* states, uint3
     HIP_TRY(dout.alloc(n));
     if (b->cfg.space == OXHIP_SPACE_SE2) launch_se2_is_valid(b->dp, ds.p, n, dout.p, b->stream);
     else if (b->cfg.space == OXHIP_SPACE_SO3) launch_so3_is_valid(b->dp, ds.p, n, dout.p, b->stream);
+    else if (b->cfg.space == OXHIP_SPACE_SE3) launch_se3_is_valid(b->dp, b->se3, ds.p, n, dout.p, b->stream);
     else launch_is_valid(b->dp, ds.p, n, dout.p, b->stream);
     HIP_TRY(hipGetLastError());
     return to_host(out, dout, n, b->stream);
@@ -1139,6 +1193,7 @@ int32_t oxhip_rrt_batch_check_motion(oxhip_rrt_batch* b, const double* from, con
     HIP_TRY(dout.alloc(n));
     if (b->cfg.space == OXHIP_SPACE_SE2) launch_se2_check_motion(b->dp, da.p, db.p, n, dout.p, b->stream);
     else if (b->cfg.space == OXHIP_SPACE_SO3) launch_so3_check_motion(b->dp, da.p, db.p, n, dout.p, b->stream);
+    else if (b->cfg.space == OXHIP_SPACE_SE3) launch_se3_check_motion(b->dp, b->se3, da.p, db.p, n, dout.p, b->stream);
     else launch_check_motion(b->dp, da.p, db.p, n, dout.p, b->stream);
     HIP_TRY(hipGetLastError());
     return to_host(out, dout, n, b->stream);
@@ -1198,6 +1253,25 @@ int32_t oxhip_so3_op_batch(int32_t device, uint32_t op, const double* a, const d
     if (op == 1) OX_TRY(to_device(dt, t, n, ts.s));
     HIP_TRY(dout.alloc(w_out * n));
     launch_so3_op(op, da.p, db.p, dt.p, n, dout.p, ts.s);
+    HIP_TRY(hipGetLastError());
+    return to_host(out, dout, w_out * n, ts.s);
+}
+
+int32_t oxhip_se3_op_batch(int32_t device, uint32_t op, const double* a, const double* b, const double* t, uint32_t n,
+                           double* out) {
+    if (!a || !b || !out || op > 2 || (op == 1 && !t)) return fail(OXHIP_ERR_BAD_ARG, "bad argument");
+    if (n == 0) return OXHIP_OK;
+    OX_TRY(select_device(device));
+    TmpStream ts;
+    HIP_TRY(oxhip_stream_acquire(device, &ts.s));
+    ts.device = device;
+    const size_t w_out = op == 0 ? 1 : (op == 1 ? 7 : 3);   // doubles per row of out
+    DevBuf<double> da, db, dt, dout;
+    OX_TRY(to_device(da, a, (size_t)7 * n, ts.s));
+    OX_TRY(to_device(db, b, (size_t)7 * n, ts.s));
+    if (op == 1) OX_TRY(to_device(dt, t, n, ts.s));
+    HIP_TRY(dout.alloc(w_out * n));
+    launch_se3_op(op, da.p, db.p, dt.p, n, dout.p, ts.s);
     HIP_TRY(hipGetLastError());
     return to_host(out, dout, w_out * n, ts.s);
 }

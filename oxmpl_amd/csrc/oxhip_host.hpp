@@ -159,14 +159,21 @@ inline int32_t space_resolution(uint32_t dim, const double* bounds, double& frac
 // max_angle is StateSpaceError::InvalidAngularDistance; max_angle.min(PI), NaN giving PI as f64::min does), clamps the fraction
 // (:234-236) and returns res = 0.5 * PI * fraction * 0.1 (extent 0.5 * PI, :81-84; rrt.rs:97, prm.rs:168).  No SO(3) distance
 // exceeds 0.5 * PI, which bounds the step count of every motion.
-inline int32_t so3_space_resolution(uint32_t dim, const double* bounds, double& fraction, double& res, double& max_angle) {
-    if (dim != 4) return fail(OXHIP_ERR_BAD_ARG, "SO(3) states are quaternions (x, y, z, w): dim must be 4");
+// (the centre / max_angle part, shared with SE(3), whose bounds carry the same five values behind the (x, y, z) bounds)
+inline int32_t so3_rotation_bounds(const double* bounds, double& max_angle) {
     for (uint32_t k = 0; k < 4; ++k)
         if (!(std::fabs(bounds[k]) <= kMaxMagnitude)) return fail(OXHIP_ERR_BAD_ARG, "SO(3) centre not finite or beyond 1e150");
     const double pi = 3.14159265358979323846;
     max_angle = bounds[4];
     if (max_angle < 0.0) return fail(OXHIP_ERR_ZERO_VOLUME, "SO(3): max_angle must not be negative");
     max_angle = std::isnan(max_angle) ? pi : std::fmin(max_angle, pi);
+    return OXHIP_OK;
+}
+inline int32_t so3_space_resolution(uint32_t dim, const double* bounds, double& fraction, double& res, double& max_angle) {
+    if (dim != 4) return fail(OXHIP_ERR_BAD_ARG, "SO(3) states are quaternions (x, y, z, w): dim must be 4");
+    const double pi = 3.14159265358979323846;
+    int32_t rb = so3_rotation_bounds(bounds, max_angle);
+    if (rb != OXHIP_OK) return rb;
     if (fraction > 0.0 && fraction <= 1.0) {} else if (fraction <= 0.0) fraction = 0.0; else fraction = 1.0;
     const double lvsl = 0.5 * pi * fraction;
     res = lvsl * 0.1;

@@ -41,6 +41,18 @@ void launch_so3_op(uint32_t op, const double* a, const double* b, const double* 
 void launch_so3_is_valid(const DevParams& p, const double* states, uint32_t n, uint8_t* out, hipStream_t s);
 void launch_so3_check_motion(const DevParams& p, const double* from, const double* to, uint32_t n, uint8_t* out, hipStream_t s);
 
+// rrt_connect_se3.hip: RRTConnect over SE(3), a rigid body of spheres among sphere obstacles (sph_c [3][n], sph_r), one wave per problem
+constexpr int kSe3MaxBody = 16;
+struct Se3Args {             // this kernel family's own arguments, next to DevParams
+    const double* body;      // [4][kSe3MaxBody] SoA (cx, cy, cz, r) of the body's spheres in the body frame
+    uint32_t n_body, pad;
+};
+void launch_rrt_connect_se3(const DevParams& p, const Se3Args& a, hipStream_t stream);
+uint32_t se3_lds_obstacles();                                             // obstacles the kernel stages in LDS (more are read from HBM)
+void launch_se3_op(uint32_t op, const double* a, const double* b, const double* t, uint32_t n, double* out, hipStream_t s);
+void launch_se3_is_valid(const DevParams& p, const Se3Args& a, const double* states, uint32_t n, uint8_t* out, hipStream_t s);
+void launch_se3_check_motion(const DevParams& p, const Se3Args& a, const double* from, const double* to, uint32_t n, uint8_t* out, hipStream_t s);
+
 // rrt_star.hip: RRT* (rrt_star.rs), one 256-thread workgroup per problem
 void launch_rrt_star(const DevParams& p, hipStream_t stream);
 

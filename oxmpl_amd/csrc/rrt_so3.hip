@@ -18,6 +18,7 @@
 #include "oxhip_internal.hpp"
 #include "rrt_device.hpp"
 #include "so3_device.hpp"
+#include "so3_sampler.hpp"
 
 namespace oxhip {
 
@@ -33,67 +34,18 @@ struct So3Shared {
 };
 static_assert(sizeof(So3Shared<kSo3LdsCones>) <= 40960, "four problems per CU");
 
-__device__ __forceinline__ double so3_readlane(double v, int l) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
-
-// sample_uniform by one lane after the other, word by word (random_range redraws included)
-__device__ __forceinline__ void so3_sample_serial(RngWindow& rng, const DevParams& p, double q[4]) {
-    for (;;) {
-        double v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            while (!so3_range_word(rng.next<false>(), v[k])) {}
-        if (so3_attempt(v, p.so3_centre, p.so3_max_angle, q)) return;
-    }
-}
-
-// rrt.rs:177-184 with SO3StateSpace::sample_uniform and the ball goal's sample_goal (the target, no draw).  Wave-uniform result.
-// Lane j evaluates attempt j of the round (its four words follow the 4 j words of the attempts before it); the first accepted
-// attempt wins and the stream moves past it.  A round without an accepted attempt moves 256 words on and tries the next 64.  A
-// range redraw at or before the winner (or the test switch OXHIP_DEBUG_SO3_SERIAL_SAMPLER) hands the sample to the serial form.
+// rrt.rs:177-184 with SO3StateSpace::sample_uniform (so3_sampler.hpp: 64 rejection attempts side by side) and the ball goal's
+// sample_goal (the target, no draw).  Wave-uniform result.
 __device__ __forceinline__ void so3_sample(RngWindow& rng, const DevParams& p, const double target[4], uint32_t lane, double q[4]) {
     bool goal;
     if (p.p_int == ~0ull) goal = true;              // Bernoulli ALWAYS_TRUE: no draw
     else goal = rng.next<false>() < p.p_int;        // one u64
-    if (goal || p.so3_max_angle < 1e-9) {           // the target / the centre of a degenerate space (so3_state_space.rs:204-206)
-        const double* src = goal ? target : p.so3_centre;
+    if (goal) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) q[k] = src[k];
+        for (int k = 0; k < 4; ++k) q[k] = target[k];
         return;
     }
-    if (p.dbg_flags & OXHIP_DEBUG_SO3_SERIAL_SAMPLER) { so3_sample_serial(rng, p, q); return; }
-    for (;;) {
-        const uint64_t pos = rng.pos;
-        if ((pos >> 3) - rng.base_blk >= 64 || pos + 256 > (rng.base_blk + 64) * 8) {   // the window must hold the round's 256 words
-            rng.base_blk = uni64(pos >> 3);
-            uint32_t o[16];
-            chacha12_block(rng.seed, rng.base_blk + lane, rng.stream, o);
-#pragma unroll
-            for (int w = 0; w < 16; ++w) rng.buf[w][lane] = o[w];
-        }
-        const uint32_t rel0 = (uint32_t)(pos - rng.base_blk * 8) + 4u * lane;
-        double v[4];
-        bool redraw = false;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t a = rel0 + (uint32_t)k, bl = a >> 3, w = (a & 7u) * 2u;
-            const uint64_t word = ((uint64_t)rng.buf[w + 1][bl] << 32) | rng.buf[w][bl];
-            redraw = redraw || !so3_range_word(word, v[k]);
-        }
-        double qa[4] = {0.0, 0.0, 0.0, 0.0};
-        const bool acc = !redraw && so3_attempt(v, p.so3_centre, p.so3_max_angle, qa);
-        const uint64_t am = __ballot(acc), rm = __ballot(redraw);
-        const uint32_t L = am ? (uint32_t)__builtin_ctzll(am) : 64u;
-        const uint64_t upto = L >= 63u ? ~0ull : (2ull << L) - 1ull;
-        if (rm & upto) { so3_sample_serial(rng, p, q); return; }   // (rng.pos is still the round's start)
-        if (am == 0) { rng.pos = uni64(pos + 256); continue; }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) q[k] = so3_readlane(qa[k], (int)L);
-        rng.pos = uni64(pos + 4ull * (L + 1u));
-        return;
-    }
+    so3_sample_uniform_wave(rng, p, lane, q);
 }
 
 // check_motion (rrt.rs:90-116) by one wave: lane s tests state s + 1 of the steps 1 ..= nsteps (or `to` alone when nsteps <= 1)

@@ -10,8 +10,8 @@ drop-in for users of the reference's Python API.
 import numpy as np
 
 from . import capi
-from .base import (Path, ProblemDefinition, RealVectorState, SO3ConeValidityChecker, SO3State, SO3StateSpace,
-                   SphereBoxValidityChecker)
+from .base import (Path, ProblemDefinition, RealVectorState, SE3RigidBodyValidityChecker, SE3State, SE3StateSpace,
+                   SO3ConeValidityChecker, SO3State, SO3StateSpace, SphereBoxValidityChecker)
 
 _MESSAGES = {  # Display strings of PlanningError (oxmpl/src/base/error.rs:110-136)
     capi.ERR_TIMEOUT: "No solution found within timeout.",
@@ -49,6 +49,8 @@ class RRT:
         takes a SphereBoxValidityChecker (see oxmpl_amd.base), or an SO3ConeValidityChecker for an SO(3) problem (RRT only)."""
         if isinstance(self._pd.space, SO3StateSpace):
             return self._setup_so3(validity_checker)
+        if isinstance(self._pd.space, SE3StateSpace):
+            return self._setup_se3(validity_checker)
         if not isinstance(validity_checker, SphereBoxValidityChecker):
             raise TypeError("the GPU path cannot call a Python function per interpolated state; "
                             "describe the obstacles with oxmpl_amd.base.SphereBoxValidityChecker")
@@ -94,6 +96,30 @@ class RRT:
         self._batch = b
         self._checker = validity_checker
 
+    def _setup_se3(self, validity_checker):
+        if self._PLANNER != capi.PLANNER_RRT_CONNECT:
+            raise TypeError("SE(3) is built for RRTConnect only")
+        if not isinstance(validity_checker, SE3RigidBodyValidityChecker):
+            raise TypeError("the GPU path cannot call a Python function per interpolated state; "
+                            "describe the body and the obstacles with oxmpl_amd.base.SE3RigidBodyValidityChecker")
+        pd = self._pd
+        if self._batch is not None:
+            self._batch.close()
+        try:
+            b = capi.RRTBatch(7, pd.space.config_bounds(), self.max_distance, self.goal_bias, 1,
+                              lvs_fraction=pd.space.longest_valid_segment_fraction, stop_at_goal=True,
+                              planner=capi.PLANNER_RRT_CONNECT, space=capi.SPACE_SE3, **self._opts)
+        except capi.OxhipError as e:
+            if e.status in (capi.ERR_UNBOUNDED, capi.ERR_ZERO_VOLUME, capi.ERR_BAD_ARG):
+                raise ValueError(str(e)) from None
+            raise
+        b.set_body([c for c, _ in validity_checker.body], [r for _, r in validity_checker.body])
+        if validity_checker.obstacles:
+            b.set_spheres([c for c, _ in validity_checker.obstacles], [r for _, r in validity_checker.obstacles])
+        b.setup(pd.start_state.values, pd.goal.target.values, float(pd.goal.radius))
+        self._batch = b
+        self._checker = validity_checker
+
     def solve(self, timeout_secs):
         """Planner::solve (rrt.rs:158-227); errors surface as Exception(message) like the reference
         (oxmpl-py/src/geometric/rrt.rs:117)."""
@@ -111,6 +137,8 @@ class RRT:
             raise Exception(_MESSAGES.get(int(st[0]), capi.status_string(int(st[0]))))
         if isinstance(self._pd.space, SO3StateSpace):
             return Path([SO3State(*row) for row in self._batch.path(0)])
+        if isinstance(self._pd.space, SE3StateSpace):
+            return Path([SE3State.from_values(row) for row in self._batch.path(0)])
         return Path([RealVectorState(row) for row in self._batch.path(0)])
 
     def is_state_valid(self, state):

@@ -6,6 +6,8 @@ wall    : the reference's own RRT test scene (oxmpl/tests/rrt_rvss_tests.rs:109-
 config 2: R^3, [0,10]^3, 64 random spheres, start (.5,.5,.5), goal ball (9.5,9.5,9.5) r=0.5
 config 4: SE(2) RRTConnect (BASELINE.json configs[3]): [0,10]^2 x [-PI,PI), 64 random quadrilaterals = 256 segments,
           disc robot of radius 0.15, start (0.5,0.5,0), goal ball (9.5,9.5,1.5) r=0.5
+se3 field / slot: SE(3) RRTConnect: [-5,5]^3 x SO(3), a rod of five spheres among 64 random spheres
+          (field) or through the one open row of a wall of 110 spheres (slot)
 config 5: PRM (BASELINE.json configs[4]): R^6, [0,10]^6, 32 random hyperspheres, 50,000 milestones,
           connection radius 2.0, start (1,..,1), goal ball (9,..,9) r=1.5
 """
@@ -121,6 +123,75 @@ def make_se2_batch(sc, n_problems, max_nodes=10000, seed=42, first_problem_id=0,
     b = RRTBatch(3, sc["bounds"], sc["max_distance"], sc["goal_bias"], n_problems, max_nodes, sc["lvs_fraction"], True,
                  seed, first_problem_id, device, KERNEL_AUTO, PLANNER_RRT_CONNECT, 0.0, SPACE_SE2)
     b.set_segments(sc["segments"], sc["clearance"])
+    b.setup(sc["start"], sc["goal_centre"], sc["goal_radius"])
+    return b
+
+
+def se3_rod():
+    """a rod of five spheres of radius 0.25 at body x = -1, -0.5, 0, 0.5, 1: (centres [5][3], radii [5])"""
+    return np.array([[-1.0 + 0.5 * i, 0.0, 0.0] for i in range(5)]), np.full(5, 0.25)
+
+
+def _se3_scene(start_xyz, goal_xyz, spheres):
+    h = 0.5 ** 0.5   # a quarter turn about y either way: (0, +-sin(PI/4), 0, cos(PI/4)), by a square root alone
+    return dict(dim=7, bounds=[(-5.0, 5.0)] * 3, rotation_bounds=None, max_distance=1.0, goal_bias=0.05, lvs_fraction=0.05,
+                start=list(start_xyz) + [0.0, h, 0.0, h], goal_centre=list(goal_xyz) + [0.0, -h, 0.0, h], goal_radius=0.25,
+                body=se3_rod(), spheres=spheres, boxes=None)
+
+
+def se3_field(seed=0x5EED0018, n=64):
+    """n random spheres, radius U[0.3, 0.9), centres U[-4.5, 4.5)^3, none within radius + 1.6 of the start (-4, -4, -4) or
+    the target (4, 4, 4).  SplitMix64 + the 52-bit transform, the recipe of sphere_field with its own margin."""
+    start, goal = [-4.0, -4.0, -4.0], [4.0, 4.0, 4.0]
+    st = seed
+
+    def u(a, b):
+        nonlocal st
+        st, z = _splitmix64(st)
+        bits = (z >> 12) | 0x3FF0000000000000
+        v = struct.unpack("<d", struct.pack("<Q", bits))[0] - 1.0
+        return v * (b - a) + a
+
+    cs, rs = [], []
+    while len(rs) < n:
+        c = [u(-4.5, 4.5) for _ in range(3)]
+        r = u(0.3, 0.9)
+        ok = True
+        for p in (start, goal):
+            acc = 0.0
+            for x, y in zip(c, p):
+                acc = acc + (x - y) * (x - y)
+            if not (acc ** 0.5 > r + 1.6):
+                ok = False
+        if ok:
+            cs.append(c)
+            rs.append(r)
+    return _se3_scene(start, goal, (np.array(cs, dtype=np.float64).reshape(-1, 3), np.array(rs, dtype=np.float64)))
+
+
+def se3_slot():
+    """a wall of spheres of radius 0.62 at (0, iy, iz), iy, iz in -5 .. 5, the row iz = 0 left out (110 spheres): the rod
+    passes only while it lies near the plane z = 0, so the orientation decides validity"""
+    cs = [[0.0, float(iy), float(iz)] for iy in range(-5, 6) for iz in range(-5, 6) if iz != 0]
+    return _se3_scene([-4.0, 0.0, 3.0], [4.0, 0.0, -3.0], (np.array(cs, dtype=np.float64), np.full(len(cs), 0.62)))
+
+
+def se3_config_bounds(sc):
+    """the eleven values oxmpl_amd.capi.RRTBatch takes for SPACE_SE3"""
+    rb = sc.get("rotation_bounds")
+    rot = [0.0, 0.0, 0.0, 1.0, 3.141592653589793] if rb is None else list(rb[0]) + [rb[1]]
+    return [v for pair in sc["bounds"] for v in pair] + rot
+
+
+def make_se3_batch(sc, n_problems, max_nodes=10000, seed=42, first_problem_id=0, device=0, debug_flags=0):
+    """RRTConnect over SE(3) for a scene dict (se3_field / se3_slot; oxmpl_amd.capi.SPACE_SE3), set up and ready to solve."""
+    from .capi import RRTBatch, KERNEL_AUTO, PLANNER_RRT_CONNECT, SPACE_SE3
+    b = RRTBatch(7, se3_config_bounds(sc), sc["max_distance"], sc["goal_bias"], n_problems, max_nodes, sc["lvs_fraction"], True,
+                 seed, first_problem_id, device, KERNEL_AUTO, PLANNER_RRT_CONNECT, 0.0, SPACE_SE3, debug_flags=debug_flags)
+    if sc.get("body") is not None:
+        b.set_body(*sc["body"])
+    if sc["spheres"] is not None and len(sc["spheres"][1]):
+        b.set_spheres(*sc["spheres"])
     b.setup(sc["start"], sc["goal_centre"], sc["goal_radius"])
     return b
 

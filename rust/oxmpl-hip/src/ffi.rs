@@ -34,6 +34,7 @@ pub const OXHIP_SPACE_REAL_VECTOR: u32 = 0;
 pub const OXHIP_SPACE_SE2: u32 = 1;
 /// SO3StateSpace (rrt_so3.hip): dim 4, quaternions (x, y, z, w); bounds[0..4] = centre quaternion, bounds[4] = max_angle
 pub const OXHIP_SPACE_SO3: u32 = 2;
+pub const OXHIP_SPACE_SE3: u32 = 3;
 // oxhip_goal_sampler: what GoalSampleableRegion::sample_goal draws (goal.rs:35-41)
 pub const OXHIP_GOAL_SAMPLE_CENTRE: u32 = 0;
 pub const OXHIP_GOAL_SAMPLE_UNIFORM_DISC: u32 = 1;
@@ -153,6 +154,7 @@ extern "C" {
     pub fn oxhip_rrt_batch_set_spheres(b: *mut OxhipRrtBatch, centres: *const f64, radii: *const f64, n: u32) -> i32;
     pub fn oxhip_rrt_batch_set_boxes(b: *mut OxhipRrtBatch, lo: *const f64, hi: *const f64, n: u32) -> i32;
     pub fn oxhip_rrt_batch_set_segments(b: *mut OxhipRrtBatch, segments: *const f64, n: u32, clearance: f64) -> i32;
+    pub fn oxhip_rrt_batch_set_body(b: *mut OxhipRrtBatch, centres: *const f64, radii: *const f64, n: u32) -> i32;
     pub fn oxhip_rrt_batch_setup(b: *mut OxhipRrtBatch, starts: *const f64, goal_centres: *const f64, goal_radii: *const f64) -> i32;
     pub fn oxhip_rrt_batch_set_tree(b: *mut OxhipRrtBatch, problem: u32, states: *const f64, parents: *const i32, n_nodes: u32) -> i32;
     pub fn oxhip_rrt_batch_solve(b: *mut OxhipRrtBatch, max_iterations: u64, timeout_s: f64, freeze: u32, status_out: *mut i32) -> i32;
@@ -189,6 +191,7 @@ extern "C" {
     pub fn oxhip_interpolate_batch(device: i32, dim: u32, from: *const f64, to: *const f64, t: *const f64, n: u32, out: *mut f64) -> i32;
     /// SO(3) self-test hook: op 0 distance, op 1 interpolate, op 2 ox_acos (so3_state_space.rs:101-159)
     pub fn oxhip_so3_op_batch(device: i32, op: u32, a: *const f64, b: *const f64, t: *const f64, n: u32, out: *mut f64) -> i32;
+    pub fn oxhip_se3_op_batch(device: i32, op: u32, a: *const f64, b: *const f64, t: *const f64, n: u32, out: *mut f64) -> i32;
 
     // ---- PRM (prm.rs)
     pub fn oxhip_prm_create(cfg: *const OxhipPrmConfig, out: *mut *mut OxhipPrm) -> i32;
