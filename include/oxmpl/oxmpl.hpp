@@ -368,6 +368,51 @@ class PRM {
         return path;
     }
 
+    // Many problem definitions on the roadmap already built, in one device call (oxhip_prm_solve_batch: start connections, goal
+    // test, breadth-first search and path extraction on the GPU): per problem what set_problem_definition + solve would return.
+    // The planner's own problem definition is left as it is.  Every problem must share the planner's space.
+    std::vector<Result<base::Path, base::PlanningError>> solve_batch(const std::vector<std::shared_ptr<base::ProblemDefinition>>& problems,
+                                                                     std::chrono::duration<double> timeout_) {
+        std::vector<Result<base::Path, base::PlanningError>> out;
+        out.reserve(problems.size());
+        const std::size_t q = problems.size();
+        if (!prm_ || !pd_) {
+            for (std::size_t i = 0; i < q; ++i) out.emplace_back(base::PlanningError::PlannerUninitialised);
+            return out;
+        }
+        const std::size_t dim = pd_->space->dimension;
+        std::vector<double> starts, centres, radii;
+        for (const auto& pd : problems) {
+            const bool fits = pd && pd->goal && !pd->start_states.empty() && pd->start_states[0].values.size() == dim;
+            const auto target = fits ? pd->goal->target() : pd_->goal->target();
+            if (!fits || target.values.size() != dim) {
+                for (std::size_t i = 0; i < q; ++i) out.emplace_back(base::PlanningError::PlannerUninitialised);
+                return out;
+            }
+            starts.insert(starts.end(), pd->start_states[0].values.begin(), pd->start_states[0].values.end());
+            centres.insert(centres.end(), target.values.begin(), target.values.end());
+            radii.push_back(pd->goal->radius());
+        }
+        std::vector<int32_t> status(q ? q : 1);
+        int32_t st = oxhip_prm_solve_batch(prm_, (uint32_t)q, starts.data(), centres.data(), radii.data(), timeout_.count(), 0, status.data());
+        std::vector<uint64_t> off(q + 1);
+        uint64_t total = 0;
+        if (st == OXHIP_OK) st = oxhip_prm_batch_get_paths(prm_, off.data(), nullptr, nullptr, 0, &total);
+        std::vector<double> flat((std::size_t)total * dim + 1);
+        if (st == OXHIP_OK) st = oxhip_prm_batch_get_paths(prm_, off.data(), nullptr, flat.data(), total, &total);
+        for (std::size_t i = 0; i < q; ++i) {
+            if (st != OXHIP_OK || status[i] != OXHIP_OK) {
+                out.emplace_back(to_error(st != OXHIP_OK ? st : status[i]));
+                continue;
+            }
+            base::Path path;
+            for (uint64_t r = off[i]; r < off[i + 1]; ++r)
+                path.states.emplace_back(std::vector<double>(flat.begin() + r * dim, flat.begin() + (r + 1) * dim));
+            out.emplace_back(std::move(path));
+        }
+        return out;
+    }
+
     // PRM::get_roadmap (prm.rs:82-84): milestone count and, per node, its `edges`
     uint32_t num_milestones() const {
         uint32_t n = 0;

@@ -433,6 +433,41 @@ int32_t oxhip_prm_last_timing(oxhip_prm* prm, double* phase_ms /*[6]*/, uint64_t
  * searched exactly instead (diagnostic: results do not depend on it) */
 int32_t oxhip_prm_knn_exact_rows(oxhip_prm* prm, uint32_t* rows);
 
+/* ---- a batch of queries on one roadmap, search included, on the device (prm_batch.hip) ----
+ * n_queries (start, ball goal) pairs on the roadmap as it stands, each answered exactly -- bit for bit, status for status -- as
+ * set_problem + solve answer it: start validity, start connections and goal milestones (prm.rs:243-264), the breadth-first
+ * search (:270-301) and reconstruct_path (:189-208) all run on the device, one workgroup per query.  Per query:
+ * OXHIP_ERR_INVALID_START_STATE, OXHIP_ERR_NO_SOLUTION_FOUND (no start connection, no goal milestone, or the search ran dry),
+ * OXHIP_OK, or OXHIP_ERR_TIMEOUT.  chunk_queries: queries per device round, 0 = automatic (bounds the workspace: 9 bytes per
+ * query and milestone, at most 1 GiB); results never depend on it.  timeout_s as the single solve reads it (<= 0, inf, NaN:
+ * none); the clock is read between rounds: a query is either answered completely or OXHIP_ERR_TIMEOUT with length 0, and the
+ * timed-out queries are a suffix of the batch (the first round always runs).  The call itself returns OXHIP_OK whatever the
+ * queries' statuses, OXHIP_ERR_PLANNER_UNINITIALISED without setup(), OXHIP_ERR_UNSAMPLED_STATE_SPACE on an empty roadmap,
+ * OXHIP_ERR_BAD_ARG for null pointers or a start / goal centre that set_problem would refuse; n_queries = 0 is OXHIP_OK.
+ * The batch neither reads nor writes the handle's own problem definition or the last solve's query sets.  setup() (which
+ * clears the roadmap) drops the batch's results -- the getters then return OXHIP_ERR_UNSAMPLED_STATE_SPACE, as they do before
+ * the first batch; a new batch replaces them. */
+int32_t oxhip_prm_solve_batch(oxhip_prm* prm, uint32_t n_queries, const double* starts /*[Q][dim]*/,
+                              const double* goal_centres /*[Q][dim]*/, const double* goal_radii /*[Q]*/, double timeout_s,
+                              uint32_t chunk_queries, int32_t* status_out /*[Q] or NULL*/);
+/* per query of the last batch: status, path length in states (0 unless OXHIP_OK), the goal milestone reached (-1 unless
+ * OXHIP_OK), |start_connections|, |goal_indices| (both 0 for an invalid start or a timed-out query, as after the single
+ * solve).  Any pointer may be NULL. */
+int32_t oxhip_prm_batch_get_results(oxhip_prm* prm, int32_t* status, uint32_t* path_len, int32_t* goal_node,
+                                    uint32_t* n_start, uint32_t* n_goal);
+/* all paths of the last batch in one copy: query q's path is rows offsets[q] .. offsets[q+1]; nodes = milestone index of
+ * each row (0xFFFFFFFF for the start state, row 0 of every path); states = the rows themselves [total_rows][dim].
+ * OXHIP_ERR_CAPACITY when cap_rows is too small; *total_rows and offsets are still written.  Any pointer may be NULL. */
+int32_t oxhip_prm_batch_get_paths(oxhip_prm* prm, uint64_t* offsets /*[Q+1]*/, uint32_t* nodes, double* states,
+                                  uint64_t cap_rows, uint64_t* total_rows);
+/* start_connections / goal_indices of query `query` of the last batch, as the single-query getter returns them (the
+ * flag kernel runs again for that query: the sets are not stored per query) */
+int32_t oxhip_prm_batch_get_query_sets(oxhip_prm* prm, uint32_t query, uint32_t* start_connections, uint32_t cap_start,
+                                       uint32_t* n_start, uint32_t* goal_indices, uint32_t cap_goal, uint32_t* n_goal);
+/* HIP-event times (ms) of the last batch, summed over its rounds: phase_ms[4] = {flag kernel, search kernel, path
+ * extraction, device-to-host copies}; the number of rounds */
+int32_t oxhip_prm_batch_last_timing(oxhip_prm* prm, double* phase_ms /*[4]*/, uint32_t* rounds);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,6 +47,8 @@ EXPORTS = [
     "oxhip_prm_create", "oxhip_prm_destroy", "oxhip_prm_set_spheres", "oxhip_prm_set_boxes", "oxhip_prm_setup",
     "oxhip_prm_set_problem", "oxhip_prm_construct_roadmap", "oxhip_prm_get_sizes", "oxhip_prm_get_roadmap",
     "oxhip_prm_solve", "oxhip_prm_get_query_sets", "oxhip_prm_last_timing", "oxhip_prm_knn_exact_rows",
+    "oxhip_prm_solve_batch", "oxhip_prm_batch_get_results", "oxhip_prm_batch_get_paths", "oxhip_prm_batch_get_query_sets",
+    "oxhip_prm_batch_last_timing",
 ]
 
 
@@ -153,6 +155,11 @@ def lib():
         L.oxhip_prm_get_query_sets.argtypes = [C.c_void_p, _u32p, C.c_uint32, _u32p, _u32p, C.c_uint32, _u32p]
         L.oxhip_prm_last_timing.argtypes = [C.c_void_p, _dp, _u64p, _u32p]
         L.oxhip_prm_knn_exact_rows.argtypes = [C.c_void_p, _u32p]
+        L.oxhip_prm_solve_batch.argtypes = [C.c_void_p, C.c_uint32, _dp, _dp, _dp, C.c_double, C.c_uint32, _i32p]
+        L.oxhip_prm_batch_get_results.argtypes = [C.c_void_p, _i32p, _u32p, _i32p, _u32p, _u32p]
+        L.oxhip_prm_batch_get_paths.argtypes = [C.c_void_p, _u64p, _u32p, _dp, C.c_uint64, _u64p]
+        L.oxhip_prm_batch_get_query_sets.argtypes = [C.c_void_p, C.c_uint32, _u32p, C.c_uint32, _u32p, _u32p, C.c_uint32, _u32p]
+        L.oxhip_prm_batch_last_timing.argtypes = [C.c_void_p, _dp, _u32p]
         for name in EXPORTS:
             if name not in ("oxhip_status_string", "oxhip_last_error_string"):
                 getattr(L, name).restype = C.c_int32
@@ -548,3 +555,51 @@ class PRMRoadmap:
         c, r = C.c_uint64(), C.c_uint32()
         _check(lib().oxhip_prm_last_timing(self._h, _p(ms), C.byref(c), C.byref(r)))
         return dict(phase_ms=[float(v) for v in ms], candidates=c.value, redraw_batches=r.value)
+
+    # ---- a batch of queries on the roadmap as it stands: flags, breadth-first search and paths on the device
+
+    def solve_batch(self, starts, goal_centres, goal_radii, timeout_s=0.0, chunk_queries=0):
+        """Q (start, ball goal) queries in one call, each answered exactly as set_problem + solve answer it.
+        Returns the per-query statuses [Q] (OK, ERR_INVALID_START_STATE, ERR_NO_SOLUTION_FOUND, ERR_TIMEOUT)."""
+        r = _f64(goal_radii).reshape(-1)
+        s, g = _f64(starts, (r.size, self.dim)), _f64(goal_centres, (r.size, self.dim))
+        status = np.zeros(max(r.size, 1), dtype=np.int32)
+        _check(lib().oxhip_prm_solve_batch(self._h, r.size, _p(s), _p(g), _p(r), timeout_s, chunk_queries, _p(status, _i32p)))
+        self._batch_q = r.size
+        return status[:r.size]
+
+    def batch_results(self):
+        """dict(status, path_len, goal_node, n_start, n_goal), one entry per query of the last batch"""
+        q = getattr(self, "_batch_q", 0)
+        st, gn = np.zeros(max(q, 1), dtype=np.int32), np.zeros(max(q, 1), dtype=np.int32)
+        ln, ns, ng = (np.zeros(max(q, 1), dtype=np.uint32) for _ in range(3))
+        _check(lib().oxhip_prm_batch_get_results(self._h, _p(st, _i32p), _p(ln, _u32p), _p(gn, _i32p), _p(ns, _u32p), _p(ng, _u32p)))
+        return dict(status=st[:q], path_len=ln[:q], goal_node=gn[:q], n_start=ns[:q], n_goal=ng[:q])
+
+    def batch_paths(self):
+        """(offsets [Q+1] u64, nodes [rows] u32, states [rows][dim]): query q's path is rows offsets[q] .. offsets[q+1]"""
+        q = getattr(self, "_batch_q", 0)
+        offsets = np.zeros(q + 1, dtype=np.uint64)
+        total = C.c_uint64()
+        _check(lib().oxhip_prm_batch_get_paths(self._h, _p(offsets, _u64p), None, None, 0, C.byref(total)))
+        nodes = np.zeros(max(total.value, 1), dtype=np.uint32)
+        states = np.zeros((max(total.value, 1), self.dim), dtype=np.float64)
+        _check(lib().oxhip_prm_batch_get_paths(self._h, _p(offsets, _u64p), _p(nodes, _u32p), _p(states), total.value, C.byref(total)))
+        return offsets, nodes[:total.value], states[:total.value]
+
+    def batch_query_sets(self, query):
+        """(start_connections, goal_indices) of query `query` of the last batch"""
+        ns, ng = C.c_uint32(), C.c_uint32()
+        _check(lib().oxhip_prm_batch_get_query_sets(self._h, query, None, 0, C.byref(ns), None, 0, C.byref(ng)))
+        sc = np.zeros(max(ns.value, 1), dtype=np.uint32)
+        gi = np.zeros(max(ng.value, 1), dtype=np.uint32)
+        _check(lib().oxhip_prm_batch_get_query_sets(self._h, query, _p(sc, _u32p), ns.value, C.byref(ns), _p(gi, _u32p), ng.value,
+                                                    C.byref(ng)))
+        return sc[:ns.value], gi[:ng.value]
+
+    def batch_last_timing(self):
+        """dict(phase_ms=[flags, search, paths, copies], rounds) of the last batch"""
+        ms = np.zeros(4, dtype=np.float64)
+        r = C.c_uint32()
+        _check(lib().oxhip_prm_batch_last_timing(self._h, _p(ms), C.byref(r)))
+        return dict(phase_ms=[float(v) for v in ms], rounds=r.value)

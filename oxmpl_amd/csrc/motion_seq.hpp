@@ -20,8 +20,9 @@ __device__ __forceinline__ bool state_valid_seq(const DevParams& p, const double
 // is dropped before the step loop (h = dist/2 with a relative 1e-6 and an absolute 1e-9 * |coordinates|
 // margin, orders of magnitude above the few-ulp rounding of interpolate; the filter never decides a
 // motion invalid).  Typically 2-3 of 32 spheres survive, which is what makes this phase cheap.
+// (filt_abs: the filter's absolute margin, DevParams::filt_abs unless the caller has a wider one for this motion)
 template <int D>
-__device__ __forceinline__ bool motion_valid_seq(const DevParams& p, const double from[D], const double to[D]) {
+__device__ __forceinline__ bool motion_valid_seq(const DevParams& p, const double from[D], const double to[D], double filt_abs) {
     if (p.n_spheres + p.n_boxes == 0) return true;
     const double dist = sqrt(dist2<D>(from, to, D));
     const uint32_t nsteps = num_steps_u32(dist, p.res);
@@ -29,7 +30,7 @@ __device__ __forceinline__ bool motion_valid_seq(const DevParams& p, const doubl
     const double dn = (double)nsteps;
     double mid[D];
     lerp<D>(from, to, 0.5, mid, D);
-    const double h = 0.5 * dist * (1.0 + 1e-6) + p.filt_abs;
+    const double h = 0.5 * dist * (1.0 + 1e-6) + filt_abs;
     for (uint32_t w0 = 0; w0 < p.n_spheres; w0 += 64) {
         const uint32_t cnt = p.n_spheres - w0 < 64u ? p.n_spheres - w0 : 64u;
         uint64_t mask = 0;
@@ -60,6 +61,11 @@ __device__ __forceinline__ bool motion_valid_seq(const DevParams& p, const doubl
         }
     }
     return true;
+}
+
+template <int D>
+__device__ __forceinline__ bool motion_valid_seq(const DevParams& p, const double from[D], const double to[D]) {
+    return motion_valid_seq<D>(p, from, to, p.filt_abs);
 }
 
 }  // namespace oxhip

@@ -163,4 +163,32 @@ void launch_prm_so3_edges(const DevParams& p, const PrmArgs& a, uint32_t n_cand,
 void launch_prm_so3_query(const DevParams& p, const PrmArgs& a, uint32_t n, const PrmQuery& q, double r, uint8_t* flags,
                           uint32_t* start_valid, hipStream_t s);
 
+// prm_batch.hip: a batch of queries on the constructed roadmap, breadth-first search and path extraction on the device
+// (DESIGN.md section 17).  One round answers the queries [q0, q0 + n_chunk) of the batch; row c of a per-round array is query q0 + c.
+struct PrmBatchArgs {
+    const double* ms;            // milestones, AoS [n][dim]
+    const uint32_t* offsets;     // CSR of the roadmap: node u's neighbours are nbrs[offsets[u] .. offsets[u + 1]), ascending
+    const uint32_t* nbrs;
+    const double* starts;        // [n_queries][dim]   (whole batch)
+    const double* goals;         // [n_queries][dim]
+    const double* goal_thr;      // [n_queries] satisfied iff d2 <= goal_thr (SO(3): distance <= goal_thr)
+    const double* filt;          // [n_queries] the midpoint filter's absolute margin with this query's start in play (R^n)
+    uint8_t* flags;              // [n_chunk][stride] bit 0: start connection, bit 1: goal milestone
+    uint32_t* start_valid;       // [n_chunk]
+    uint32_t* parent;            // [n_chunk][stride] 0xFFFFFFFF before the search; claim while a level is expanded; then the parent
+    uint32_t* queue;             // [n_chunk][stride] the levels back to back: the order in which the reference's FIFO dequeues
+    int32_t* status;             // [n_chunk] results of the round
+    uint32_t* path_len;
+    int32_t* goal_node;
+    uint32_t* n_start;
+    uint32_t* n_goal;
+    uint32_t n, stride, dim, q0, n_chunk, pad;
+};
+void launch_prm_batch_flags(const DevParams& p, const PrmBatchArgs& b, double thr, hipStream_t s);
+void launch_prm_batch_so3_flags(const DevParams& p, const PrmBatchArgs& b, double r, hipStream_t s);
+uint32_t prm_batch_group(uint32_t n, uint64_t n_edge_entries);   // lanes per level node, from the roadmap's mean degree
+void launch_prm_batch_search(const PrmBatchArgs& b, uint32_t group, hipStream_t s);
+// row_off[c]: first row of query c's path within nodes / rows (this round's rows)
+void launch_prm_batch_paths(const PrmBatchArgs& b, const uint64_t* row_off, uint32_t* nodes, double* rows, hipStream_t s);
+
 }  // namespace oxhip

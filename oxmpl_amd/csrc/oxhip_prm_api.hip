@@ -4,6 +4,8 @@
 // the construction phases of prm_kernels.hip, and runs the breadth-first query (prm.rs:270-307) and
 // reconstruct_path (prm.rs:189-208) on the CSR roadmap it copies back once per construction.  Start
 // validity, start connections and goal milestones (prm.rs:243-264) are computed on the device.
+// oxhip_prm_solve_batch (the end of this file; prm_batch.hip) answers many queries in one call with the search
+// and the path extraction on the device as well; it needs no host copy of the roadmap.
 // There is no CPU fallback: without a HIP device every computing entry point fails.
 // space = OXHIP_SPACE_SO3 runs the same phases with the kernels of prm_so3.hip.
 #include <algorithm>
@@ -64,6 +66,20 @@ struct oxhip_prm {
     // phase timings of the last construct / solve (ms): sample, pairs, edges, sort+csr, query kernel, bfs (host)
     double t_ms[6] = {};
     uint64_t n_candidates = 0;
+    // last oxhip_prm_solve_batch: its queries, per-query results and all paths; per-round device workspace
+    bool batch_valid = false;
+    uint32_t batch_rounds = 0;
+    double batch_ms[4] = {};   // flag kernels, search kernels, path extraction, device-to-host copies
+    std::vector<double> b_starts, b_goals, b_thr, b_filt;       // as uploaded: [Q][dim], [Q][dim], [Q], [Q]
+    std::vector<int32_t> b_status, b_goal_node;
+    std::vector<uint32_t> b_len, b_nstart, b_ngoal, b_nodes;
+    std::vector<uint64_t> b_off;                                // [Q + 1] row offsets of the paths
+    std::vector<double> b_rows;
+    DevBuf<double> bd_starts, bd_goals, bd_thr, bd_filt, bd_rows;
+    DevBuf<uint8_t> bd_flags;
+    DevBuf<uint32_t> bd_start_valid, bd_parent, bd_queue, bd_res, bd_nodes;
+    DevBuf<uint64_t> bd_off;
+    hipEvent_t bev[7] = {};
 };
 
 namespace {
@@ -103,6 +119,7 @@ void clear_roadmap(oxhip_prm* h) {
     h->h_states.clear();
     h->start_conn.clear();
     h->goal_idx.clear();
+    h->batch_valid = false;   // the batch's results are about the roadmap that just went
 }
 
 // Draw samples until `target` milestones exist or `max_samples` were drawn.  Rounds of the parallel sampler
@@ -280,6 +297,7 @@ int32_t oxhip_prm_create(const oxhip_prm_config* cfg, oxhip_prm** out) {
     auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
     chk(oxhip_stream_acquire(cfg->device, &h->stream));
     for (auto& ev : h->ev) chk(hipEventCreate(&ev));
+    for (auto& ev : h->bev) chk(hipEventCreate(&ev));
     chk(h->ms.alloc((size_t)dim * cap));
     if (!so3) chk(h->ms32.alloc((size_t)dim * cap));   // (the SO(3) pair search screens nothing)
     chk(h->state.alloc(1));
@@ -305,6 +323,7 @@ int32_t oxhip_prm_destroy(oxhip_prm* h) {
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (auto& ev : h->ev) if (ev) (void)hipEventDestroy(ev);
+    for (auto& ev : h->bev) if (ev) (void)hipEventDestroy(ev);
     if (h->stream) oxhip_stream_release(h->cfg.device, h->stream);
     delete h;
     return OXHIP_OK;
@@ -676,6 +695,206 @@ int32_t oxhip_prm_last_timing(oxhip_prm* h, double* phase_ms, uint64_t* n_candid
     if (phase_ms) for (int i = 0; i < 6; ++i) phase_ms[i] = h->t_ms[i];
     if (n_candidates) *n_candidates = h->n_candidates;
     if (redraw_batches) *redraw_batches = h->redraw_batches;
+    return OXHIP_OK;
+}
+
+}  // extern "C"
+
+// ---- a batch of queries on the roadmap as it stands: prm.rs:243-307 per query, all of it on the device
+
+namespace {
+
+// the arguments of one round of the last batch: queries [q0, q0 + n_chunk) in the workspace rows [0, n_chunk)
+PrmBatchArgs batch_args(oxhip_prm* h, uint32_t q0, uint32_t n_chunk, uint32_t res_cap) {
+    PrmBatchArgs b{};
+    b.ms = h->ms.p; b.offsets = h->offsets.p; b.nbrs = h->nbrs.p;
+    b.starts = h->bd_starts.p; b.goals = h->bd_goals.p; b.goal_thr = h->bd_thr.p; b.filt = h->bd_filt.p;
+    b.flags = h->bd_flags.p; b.start_valid = h->bd_start_valid.p; b.parent = h->bd_parent.p; b.queue = h->bd_queue.p;
+    b.status = (int32_t*)h->bd_res.p; b.path_len = h->bd_res.p + res_cap; b.goal_node = (int32_t*)(h->bd_res.p + 2 * (size_t)res_cap);
+    b.n_start = h->bd_res.p + 3 * (size_t)res_cap; b.n_goal = h->bd_res.p + 4 * (size_t)res_cap;
+    b.n = h->n; b.stride = (h->n + 63u) & ~63u; b.dim = h->cfg.dim; b.q0 = q0; b.n_chunk = n_chunk;
+    return b;
+}
+
+void launch_batch_flags(oxhip_prm* h, const PrmBatchArgs& b) {
+    if (h->so3) launch_prm_batch_so3_flags(h->dp, b, h->cfg.connection_radius, h->stream);
+    else launch_prm_batch_flags(h->dp, b, h->thr_conn, h->stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t oxhip_prm_solve_batch(oxhip_prm* h, uint32_t n_queries, const double* starts, const double* goal_centres, const double* goal_radii,
+                              double timeout_s, uint32_t chunk_queries, int32_t* status_out) {
+    if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
+    if (n_queries && (!starts || !goal_centres || !goal_radii)) return fail(OXHIP_ERR_BAD_ARG, "null argument");
+    if (!h->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");      // prm.rs:229-236
+    if (h->n == 0) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "construct_roadmap() left no milestones");  // prm.rs:239-241
+    const uint32_t Q = n_queries, n = h->n, dim = h->cfg.dim;
+    for (size_t k = 0; k < (size_t)Q * dim; ++k)   // as oxhip_prm_set_problem validates one
+        if (!(std::fabs(starts[k]) <= kMaxMagnitude) || !(std::fabs(goal_centres[k]) <= kMaxMagnitude))
+            return fail(OXHIP_ERR_BAD_ARG, "start / goal centre not finite or beyond 1e150");
+    OX_TRY(select_device(h->cfg.device));
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool has_timeout = timeout_s > 0.0 && std::isfinite(timeout_s);
+    h->batch_valid = false;
+    h->batch_rounds = 0;
+    for (double& t : h->batch_ms) t = 0.0;
+    h->b_starts.assign(starts, starts + (size_t)Q * dim);
+    h->b_goals.assign(goal_centres, goal_centres + (size_t)Q * dim);
+    h->b_thr.resize(Q);
+    h->b_filt.resize(Q);
+    for (uint32_t q = 0; q < Q; ++q) {
+        h->b_thr[q] = h->so3 ? goal_radii[q] : sqrt_le_threshold(goal_radii[q]);
+        double f = h->dp.filt_abs;   // the start may lie anywhere: the filter's absolute margin with this start in play
+        for (uint32_t k = 0; k < dim; ++k) f = std::fmax(f, 1e-9 * std::fabs(starts[(size_t)q * dim + k]));
+        h->b_filt[q] = f;
+    }
+    h->b_status.assign(Q, OXHIP_ERR_TIMEOUT);
+    h->b_goal_node.assign(Q, -1);
+    h->b_len.assign(Q, 0);
+    h->b_nstart.assign(Q, 0);
+    h->b_ngoal.assign(Q, 0);
+    h->b_off.assign((size_t)Q + 1, 0);
+    h->b_nodes.clear();
+    h->b_rows.clear();
+    if (Q) {
+        // 9 bytes per query and milestone: the round is sized to keep the workspace within 1 GiB
+        const uint32_t stride = (n + 63u) & ~63u;
+        uint32_t chunk = chunk_queries ? chunk_queries : (uint32_t)std::max<uint64_t>(1, (1ull << 30) / (9ull * stride));
+        chunk = std::min(std::min(chunk, Q), 65535u);
+        if (h->bd_starts.n < (size_t)Q * dim) { HIP_TRY(h->bd_starts.alloc((size_t)Q * dim)); HIP_TRY(h->bd_goals.alloc((size_t)Q * dim)); }
+        if (h->bd_thr.n < Q) { HIP_TRY(h->bd_thr.alloc(Q)); HIP_TRY(h->bd_filt.alloc(Q)); }
+        if (h->bd_flags.n < (size_t)chunk * stride) {
+            HIP_TRY(h->bd_flags.alloc((size_t)chunk * stride));
+            HIP_TRY(h->bd_parent.alloc((size_t)chunk * stride));
+            HIP_TRY(h->bd_queue.alloc((size_t)chunk * stride));
+        }
+        if (h->bd_start_valid.n < chunk) {
+            HIP_TRY(h->bd_start_valid.alloc(chunk)); HIP_TRY(h->bd_res.alloc(5 * (size_t)chunk)); HIP_TRY(h->bd_off.alloc(chunk));
+        }
+        HIP_TRY(hipMemcpyAsync(h->bd_starts.p, h->b_starts.data(), (size_t)Q * dim * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->bd_goals.p, h->b_goals.data(), (size_t)Q * dim * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->bd_thr.p, h->b_thr.data(), (size_t)Q * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->bd_filt.p, h->b_filt.data(), (size_t)Q * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        const uint32_t group = prm_batch_group(n, h->n_keys);
+        std::vector<uint32_t> res(5 * (size_t)chunk);
+        std::vector<uint64_t> off(chunk);
+        uint32_t answered = 0;
+        for (uint32_t q0 = 0; q0 < Q; q0 += chunk) {
+            // the clock is read between rounds: the queries of the rounds not begun keep OXHIP_ERR_TIMEOUT
+            if (q0 && has_timeout && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > timeout_s) break;
+            const uint32_t c = std::min(chunk, Q - q0);
+            const PrmBatchArgs b = batch_args(h, q0, c, chunk);
+            HIP_TRY(hipMemsetAsync(h->bd_parent.p, 0xFF, (size_t)c * stride * sizeof(uint32_t), h->stream));
+            HIP_TRY(hipEventRecord(h->bev[0], h->stream));
+            launch_batch_flags(h, b);
+            HIP_TRY(hipEventRecord(h->bev[1], h->stream));
+            launch_prm_batch_search(b, group, h->stream);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(h->bev[2], h->stream));
+            HIP_TRY(hipMemcpyAsync(res.data(), h->bd_res.p, 5 * (size_t)chunk * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipEventRecord(h->bev[3], h->stream));
+            HIP_TRY(hipStreamSynchronize(h->stream));
+            h->batch_ms[0] += elapsed_ms(h->bev[0], h->bev[1]);
+            h->batch_ms[1] += elapsed_ms(h->bev[1], h->bev[2]);
+            h->batch_ms[3] += elapsed_ms(h->bev[2], h->bev[3]);
+            uint64_t rows = 0;
+            const uint64_t row0 = h->b_off[q0];
+            for (uint32_t i = 0; i < c; ++i) {
+                h->b_status[q0 + i] = (int32_t)res[i];
+                h->b_len[q0 + i] = res[chunk + i];
+                h->b_goal_node[q0 + i] = (int32_t)res[2 * (size_t)chunk + i];
+                h->b_nstart[q0 + i] = res[3 * (size_t)chunk + i];
+                h->b_ngoal[q0 + i] = res[4 * (size_t)chunk + i];
+                off[i] = rows;
+                rows += res[chunk + i];
+                h->b_off[q0 + i + 1] = row0 + rows;
+            }
+            if (rows) {
+                if (h->bd_nodes.n < rows) { HIP_TRY(h->bd_nodes.alloc((size_t)rows)); HIP_TRY(h->bd_rows.alloc((size_t)rows * dim)); }
+                h->b_nodes.resize((size_t)(row0 + rows));
+                h->b_rows.resize((size_t)(row0 + rows) * dim);
+                HIP_TRY(hipMemcpyAsync(h->bd_off.p, off.data(), (size_t)c * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+                HIP_TRY(hipEventRecord(h->bev[4], h->stream));
+                launch_prm_batch_paths(b, h->bd_off.p, h->bd_nodes.p, h->bd_rows.p, h->stream);
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipEventRecord(h->bev[5], h->stream));
+                HIP_TRY(hipMemcpyAsync(h->b_nodes.data() + row0, h->bd_nodes.p, (size_t)rows * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+                HIP_TRY(hipMemcpyAsync(h->b_rows.data() + (size_t)row0 * dim, h->bd_rows.p, (size_t)rows * dim * sizeof(double), hipMemcpyDeviceToHost,
+                                       h->stream));
+                HIP_TRY(hipEventRecord(h->bev[6], h->stream));
+                HIP_TRY(hipStreamSynchronize(h->stream));
+                h->batch_ms[2] += elapsed_ms(h->bev[4], h->bev[5]);
+                h->batch_ms[3] += elapsed_ms(h->bev[5], h->bev[6]);
+            }
+            ++h->batch_rounds;
+            answered = q0 + c;
+        }
+        for (uint32_t q = answered + 1; q <= Q; ++q) h->b_off[q] = h->b_off[answered];   // (the rounds not begun add no rows)
+    }
+    h->batch_valid = true;
+    if (status_out) for (uint32_t q = 0; q < Q; ++q) status_out[q] = h->b_status[q];
+    return OXHIP_OK;
+}
+
+int32_t oxhip_prm_batch_get_results(oxhip_prm* h, int32_t* status, uint32_t* path_len, int32_t* goal_node, uint32_t* n_start, uint32_t* n_goal) {
+    if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
+    if (!h->batch_valid) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "no batch was solved on this roadmap");
+    const size_t Q = h->b_status.size();
+    if (status && Q) std::memcpy(status, h->b_status.data(), Q * sizeof(int32_t));
+    if (path_len && Q) std::memcpy(path_len, h->b_len.data(), Q * sizeof(uint32_t));
+    if (goal_node && Q) std::memcpy(goal_node, h->b_goal_node.data(), Q * sizeof(int32_t));
+    if (n_start && Q) std::memcpy(n_start, h->b_nstart.data(), Q * sizeof(uint32_t));
+    if (n_goal && Q) std::memcpy(n_goal, h->b_ngoal.data(), Q * sizeof(uint32_t));
+    return OXHIP_OK;
+}
+
+int32_t oxhip_prm_batch_get_paths(oxhip_prm* h, uint64_t* offsets, uint32_t* nodes, double* states, uint64_t cap_rows, uint64_t* total_rows) {
+    if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
+    if (!h->batch_valid) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "no batch was solved on this roadmap");
+    const uint64_t total = h->b_nodes.size();
+    if (total_rows) *total_rows = total;
+    if (offsets) std::memcpy(offsets, h->b_off.data(), h->b_off.size() * sizeof(uint64_t));
+    if ((nodes || states) && cap_rows < total) return fail(OXHIP_ERR_CAPACITY, "path buffers too small");
+    if (nodes && total) std::memcpy(nodes, h->b_nodes.data(), (size_t)total * sizeof(uint32_t));
+    if (states && total) std::memcpy(states, h->b_rows.data(), h->b_rows.size() * sizeof(double));
+    return OXHIP_OK;
+}
+
+int32_t oxhip_prm_batch_get_query_sets(oxhip_prm* h, uint32_t query, uint32_t* start_connections, uint32_t cap_start, uint32_t* n_start,
+                                       uint32_t* goal_indices, uint32_t cap_goal, uint32_t* n_goal) {
+    if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
+    if (!h->batch_valid) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "no batch was solved on this roadmap");
+    if (query >= h->b_status.size()) return fail(OXHIP_ERR_BAD_ARG, "query index beyond the last batch");
+    const uint32_t ns = h->b_nstart[query], ng = h->b_ngoal[query];
+    if (n_start) *n_start = ns;
+    if (n_goal) *n_goal = ng;
+    if (start_connections && cap_start < ns) return fail(OXHIP_ERR_CAPACITY, "start_connections buffer too small");
+    if (goal_indices && cap_goal < ng) return fail(OXHIP_ERR_CAPACITY, "goal_indices buffer too small");
+    if ((!start_connections && !goal_indices) || (ns == 0 && ng == 0)) return OXHIP_OK;
+    // the sets are not kept per query: the flag kernel runs again for this one (same kernel, same bits) into workspace row 0
+    OX_TRY(select_device(h->cfg.device));
+    const uint32_t n = h->n;
+    const PrmBatchArgs b = batch_args(h, query, 1, (uint32_t)(h->bd_res.n / 5));
+    launch_batch_flags(h, b);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint8_t> flags(n);
+    HIP_TRY(hipMemcpyAsync(flags.data(), h->bd_flags.p, n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    uint32_t is = 0, ig = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if ((flags[i] & 1) && start_connections && is < ns) start_connections[is++] = i;
+        if ((flags[i] & 2) && goal_indices && ig < ng) goal_indices[ig++] = i;
+    }
+    return OXHIP_OK;
+}
+
+int32_t oxhip_prm_batch_last_timing(oxhip_prm* h, double* phase_ms, uint32_t* rounds) {
+    if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
+    if (phase_ms) for (int i = 0; i < 4; ++i) phase_ms[i] = h->batch_ms[i];
+    if (rounds) *rounds = h->batch_rounds;
     return OXHIP_OK;
 }
 

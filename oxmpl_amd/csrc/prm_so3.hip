@@ -16,6 +16,7 @@
 #include "oxhip_internal.hpp"
 #include "rrt_device.hpp"
 #include "so3_device.hpp"
+#include "so3_motion_seq.hpp"
 
 namespace oxhip {
 
@@ -245,29 +246,6 @@ __global__ __launch_bounds__(kSo3PairThreads) void prm_so3_pairs_kernel(PrmArgs 
 // 3. check_motion per candidate pair (from = the newer milestone j, to = the older one i: prm.rs:134)
 
 constexpr int kSo3LdsCones = 64;
-
-struct So3Cones {           // what the edge and query kernels read of DevParams (the whole struct costs SGPRs)
-    const double* c;        // centres SoA [4][n]
-    const double* r;        // radii [n]
-    uint32_t n;
-    double res;             // check_motion's step length
-};
-
-// check_motion (prm.rs:161-187, the discretisation of rrt.rs:90-116) by one thread; is_valid is pure, so stopping at the first
-// invalid state is the reference's early return
-__device__ __forceinline__ bool so3_motion_valid_seq(const double* cc, uint32_t stride, const double* cr, uint32_t nc, const double from[4],
-                                                     const double to[4], double res) {
-    if (nc == 0) return true;
-    const uint32_t nsteps = num_steps_u32(so3_distance(from, to), res);
-    if (nsteps <= 1u) return !so3_cone_hit(cc, stride, cr, nc, to);
-    const double dn = (double)nsteps;
-    for (uint32_t s = 1; s <= nsteps; ++s) {   // nsteps <= 0.5 PI / res <= 1e6 (checked at create)
-        double st[4];
-        so3_interpolate(from, to, (double)s / dn, st);
-        if (so3_cone_hit(cc, stride, cr, nc, st)) return false;
-    }
-    return true;
-}
 
 template <bool LDS_CONES>
 __global__ __launch_bounds__(256) void prm_so3_edge_kernel(So3Cones p, const uint2* __restrict__ cand, const double* __restrict__ ms,

@@ -267,6 +267,36 @@ class PRM:
             raise Exception(_MESSAGES.get(int(st), capi.status_string(int(st))))
         return Path([self._state(row) for row in path])
 
+    def solve_batch(self, problem_definitions, timeout_secs):
+        """Many problem definitions on the roadmap already built, in one device call (oxhip_prm_solve_batch: start
+        connections, goal test, breadth-first search and path extraction on the GPU).  Returns a list with, per problem, what
+        set_problem_definition + solve would give: a Path, or an Exception instance carrying the reference's message for that
+        status -- returned, not raised, so one start in collision does not hide a thousand answers.  The planner's own problem
+        definition is left as it is.  All problems must share the planner's space."""
+        if self._prm is None:
+            raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
+        pds = list(problem_definitions)
+        for pd in pds:
+            if not isinstance(pd, ProblemDefinition):
+                raise TypeError("problem_definitions must hold ProblemDefinition objects")
+            if type(pd.space) is not type(self._pd.space) or len(pd.start_state.values) != len(self._pd.start_state.values):
+                raise ValueError("every problem of a batch must share the planner's state space")
+        try:
+            status = self._prm.solve_batch([pd.start_state.values for pd in pds], [pd.goal.target.values for pd in pds],
+                                           [float(pd.goal.radius) for pd in pds], float(timeout_secs))
+        except capi.OxhipError as e:
+            if e.status in _MESSAGES:
+                raise Exception(_MESSAGES[e.status]) from None
+            raise
+        offsets, _, rows = self._prm.batch_paths()
+        out = []
+        for q, st in enumerate(status):
+            if st != capi.OK:
+                out.append(Exception(_MESSAGES.get(int(st), capi.status_string(int(st)))))
+            else:
+                out.append(Path([self._state(row) for row in rows[int(offsets[q]):int(offsets[q + 1])]]))
+        return out
+
     def get_roadmap(self):
         """PRM::get_roadmap (prm.rs:82-84) as (states, offsets, neighbours): node i's edges are
         neighbours[offsets[i]:offsets[i+1]].  SO(3) problems: states is a list of SO3State."""

@@ -215,6 +215,30 @@ extern "C" {
     ) -> i32;
     pub fn oxhip_prm_last_timing(p: *mut OxhipPrm, phase_ms: *mut f64, n_candidates: *mut u64, redraw_batches: *mut u32) -> i32;
     pub fn oxhip_prm_knn_exact_rows(p: *mut OxhipPrm, rows: *mut u32) -> i32;
+    // a batch of queries on the roadmap as it stands: flags, breadth-first search and paths on the device (prm_batch.hip)
+    pub fn oxhip_prm_solve_batch(
+        p: *mut OxhipPrm,
+        n_queries: u32,
+        starts: *const f64,
+        goal_centres: *const f64,
+        goal_radii: *const f64,
+        timeout_s: f64,
+        chunk_queries: u32,
+        status_out: *mut i32,
+    ) -> i32;
+    pub fn oxhip_prm_batch_get_results(p: *mut OxhipPrm, status: *mut i32, path_len: *mut u32, goal_node: *mut i32, n_start: *mut u32, n_goal: *mut u32) -> i32;
+    pub fn oxhip_prm_batch_get_paths(p: *mut OxhipPrm, offsets: *mut u64, nodes: *mut u32, states: *mut f64, cap_rows: u64, total_rows: *mut u64) -> i32;
+    pub fn oxhip_prm_batch_get_query_sets(
+        p: *mut OxhipPrm,
+        query: u32,
+        start_connections: *mut u32,
+        cap_start: u32,
+        n_start: *mut u32,
+        goal_indices: *mut u32,
+        cap_goal: u32,
+        n_goal: *mut u32,
+    ) -> i32;
+    pub fn oxhip_prm_batch_last_timing(p: *mut OxhipPrm, phase_ms: *mut f64, rounds: *mut u32) -> i32;
 }
 
 #[cfg(test)]

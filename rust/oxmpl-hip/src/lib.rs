@@ -449,6 +449,47 @@ impl<D: DeviceValidityChecker, G: DeviceGoal> HipPRM<D, G> {
             })
             .collect()
     }
+
+    /// Many problem definitions on the roadmap already built, in one device call (`oxhip_prm_solve_batch`): per problem what
+    /// `set_problem_definition` + `solve` would return, the breadth-first search included on the GPU.  The planner's own
+    /// problem definition is left as it is.
+    pub fn solve_batch(&mut self, problems: &[Arc<Pd<G>>], timeout: Duration) -> Vec<Result<Path<RealVectorState>, PlanningError>> {
+        let dim = match (&self.problem_def, self.prm.is_null()) {
+            (Some(pd), false) => pd.space.dimension,
+            _ => return problems.iter().map(|_| Err(PlanningError::PlannerUninitialised)).collect(), // prm.rs:229-236
+        };
+        let q = problems.len();
+        let (mut starts, mut centres, mut radii) = (Vec::with_capacity(q * dim), Vec::with_capacity(q * dim), Vec::with_capacity(q));
+        for pd in problems {
+            let (centre, radius) = pd.goal.ball();
+            assert!(pd.start_states[0].values.len() == dim && centre.len() == dim, "solve_batch: every problem must share the planner's space");
+            starts.extend_from_slice(&pd.start_states[0].values);
+            centres.extend_from_slice(&centre);
+            radii.push(radius);
+        }
+        let mut status = vec![0i32; q.max(1)];
+        let st = unsafe {
+            ffi::oxhip_prm_solve_batch(self.prm, q as u32, starts.as_ptr(), centres.as_ptr(), radii.as_ptr(), timeout.as_secs_f64(), 0, status.as_mut_ptr())
+        };
+        if st != ffi::OXHIP_OK {
+            return problems.iter().map(|_| Err(to_planning_error(st))).collect();
+        }
+        let mut offsets = vec![0u64; q + 1];
+        let mut total = 0u64;
+        unsafe { ffi::oxhip_prm_batch_get_paths(self.prm, offsets.as_mut_ptr(), ptr::null_mut(), ptr::null_mut(), 0, &mut total) };
+        let mut flat = vec![0.0f64; (total as usize * dim).max(1)];
+        let st = unsafe { ffi::oxhip_prm_batch_get_paths(self.prm, offsets.as_mut_ptr(), ptr::null_mut(), flat.as_mut_ptr(), total, &mut total) };
+        assert_eq!(st, ffi::OXHIP_OK, "batch_get_paths: {}", last_error());
+        (0..q)
+            .map(|i| {
+                if status[i] != ffi::OXHIP_OK {
+                    return Err(to_planning_error(status[i]));
+                }
+                let rows = &flat[offsets[i] as usize * dim..offsets[i + 1] as usize * dim];
+                Ok(Path(rows.chunks(dim).map(|c| RealVectorState::new(c.to_vec())).collect()))
+            })
+            .collect()
+    }
 }
 
 impl<D: DeviceValidityChecker, G: DeviceGoal> Drop for HipPRM<D, G> {
