@@ -228,6 +228,27 @@ class RRT {
         return path;
     }
 
+    // The last solution, shortcut over its own waypoints on the device (oxhip_rrt_batch_simplify_paths: the cheapest chain of
+    // waypoints whose links pass the planner's own check_motion; max_span bounds how many waypoints a link may skip over, 0 =
+    // no bound).  Not part of the reference's surface.  NoSolutionFound when there is no solution.
+    Result<base::Path, base::PlanningError> simplify_solution(uint32_t max_span = 0) {
+        if (!batch_ || last_status_ != OXHIP_OK) return base::PlanningError::PlannerUninitialised;
+        const int32_t st = oxhip_rrt_batch_simplify_paths(batch_, max_span, 0);
+        if (st == OXHIP_ERR_PLANNER_UNINITIALISED) return base::PlanningError::PlannerUninitialised;
+        if (st != OXHIP_OK) return base::PlanningError::NoSolutionFound;
+        uint64_t off[2] = {0, 0}, total = 0;
+        (void)oxhip_rrt_batch_get_simplified_paths(batch_, off, nullptr, nullptr, 0, &total);
+        if (total == 0) return base::PlanningError::NoSolutionFound;
+        const std::size_t dim = pd_->space->dimension;
+        std::vector<double> flat((std::size_t)total * dim);
+        if (oxhip_rrt_batch_get_simplified_paths(batch_, off, flat.data(), nullptr, total, &total) != OXHIP_OK)
+            return base::PlanningError::NoSolutionFound;
+        base::Path path;
+        for (uint64_t i = 0; i < total; ++i)
+            path.states.emplace_back(std::vector<double>(flat.begin() + i * dim, flat.begin() + (i + 1) * dim));
+        return path;
+    }
+
     // batched StateValidityChecker::is_valid / RRT::check_motion on the device (test helpers)
     bool is_valid(const base::RealVectorState& s) const {
         uint8_t ok = 0;

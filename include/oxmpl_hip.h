@@ -290,6 +290,50 @@ int32_t oxhip_rrt_batch_get_goal_tree(oxhip_rrt_batch* b, uint32_t problem, doub
 int32_t oxhip_rrt_batch_get_costs(oxhip_rrt_batch* b, uint32_t problem, double* costs, uint32_t cap_nodes,
                                   uint32_t* n_nodes);
 
+/* ---- the whole batch's solution paths, extracted and shortcut on the device (path_simplify.hip) ----
+ * extract_paths walks the parent chain of every problem whose goal_node >= 0 on the device (RRTConnect: plus the goal-tree
+ * chain, spliced as get_path splices it) and keeps the rows in path order behind a per-problem offset; an unsolved problem has
+ * length 0.  Every space and planner a batch can hold.  get_paths hands everything out in one copy: problem p's path is rows
+ * offsets[p] .. offsets[p+1] of `states`, and those rows equal oxhip_rrt_batch_get_path(p) bit for bit.  offsets / states may be
+ * NULL; *total_out is always set, and cap_states < total is OXHIP_ERR_CAPACITY (the way get_path uses `len`).
+ *
+ * simplify_paths extracts the paths if that has not been done and shortcuts every one of them over its own waypoints.  The
+ * semantics are this build's (the reference has no path simplifier).  Raw path p_0 .. p_{L-1}, span S = L - 1 when
+ * max_span == 0, else min(max_span, L - 1); max_span == 1 leaves the path as it is.
+ *   valid(i, j)   j == i + 1: true without a check (the planner accepted that edge; a goal-tree edge was checked in the other
+ *                 direction).  2 <= j - i <= S: the batch's check_motion(from = p_i, to = p_j) -- the verdict of
+ *                 oxhip_rrt_batch_check_motion on the same two rows.
+ *   cost          cost[0] = 0; cost[j] = min over i in [j - S, j - 1] with valid(i, j) of fl(cost[i] + distance(p_i, p_j)), i
+ *                 scanned ascending with strict '<' (ties keep the lowest i); distance is the space's own, in the bits of
+ *                 oxhip_distance_batch / oxhip_so3_op_batch op 0.
+ *   outputs       the simplified path is the parent chain from L - 1; simplified_cost = cost[L - 1]; raw_cost is the
+ *                 left-to-right sum over adjacent edges.  Hence simplified_cost <= raw_cost exactly, and both ends are kept.
+ * Built for OXHIP_SPACE_REAL_VECTOR (dim 2 .. 8, spheres and boxes, RRT / RRTConnect / RRT*) and OXHIP_SPACE_SO3; SE(2) and
+ * SE(3) batches return OXHIP_ERR_BAD_ARG ("not built").  chunk_problems: problems per device round, 0 = automatic (a round's
+ * bit matrices stay within 1 GiB; a single path whose matrix is larger is OXHIP_ERR_CAPACITY: pass a max_span); results never
+ * depend on it.  get_simplified_paths: problem p's simplified states are rows offsets[p] .. offsets[p+1] of `states`, `indices`
+ * their positions in the raw path; any of the three may be NULL.  get_simplify_results: per problem raw_cost, simplified_cost
+ * and the number of motion checks evaluated (0 for an unsolved problem); any pointer may be NULL.
+ *
+ * The results belong to the trees as they stood at the call: a later setup, solve or set_tree discards them, and the getters
+ * then return OXHIP_ERR_BAD_ARG ("no extracted / simplified paths"), as they do before the first call.  Without setup():
+ * OXHIP_ERR_PLANNER_UNINITIALISED.  Neither call changes trees, counts or checksums. */
+int32_t oxhip_rrt_batch_extract_paths(oxhip_rrt_batch* b);
+int32_t oxhip_rrt_batch_get_paths(oxhip_rrt_batch* b, uint64_t* offsets /*[P+1]*/, double* states /*[total][dim]*/,
+                                  uint64_t cap_states, uint64_t* total_out);
+int32_t oxhip_rrt_batch_simplify_paths(oxhip_rrt_batch* b, uint32_t max_span, uint32_t chunk_problems);
+int32_t oxhip_rrt_batch_get_simplified_paths(oxhip_rrt_batch* b, uint64_t* offsets /*[P+1]*/, double* states /*[total][dim]*/,
+                                             uint32_t* indices /*[total]*/, uint64_t cap_states, uint64_t* total_out);
+int32_t oxhip_rrt_batch_get_simplify_results(oxhip_rrt_batch* b, double* raw_cost /*[P]*/, double* simplified_cost /*[P]*/,
+                                             uint64_t* checks /*[P]*/);
+/* test hook: valid(i, j) of problem `problem`'s extracted path as the pair kernel evaluates it, out[i * L + j] for i < j within
+ * the span (0 elsewhere), L * L bytes; *len_out = L; cap_bytes < L * L is OXHIP_ERR_CAPACITY */
+int32_t oxhip_rrt_batch_path_valid_matrix(oxhip_rrt_batch* b, uint32_t problem, uint32_t max_span, uint8_t* out,
+                                          uint64_t cap_bytes, uint32_t* len_out);
+/* HIP-event times (ms) of the last extract_paths (both kernels) and of the last simplify_paths (pair matrix, DP), and its rounds */
+int32_t oxhip_rrt_batch_paths_last_timing(oxhip_rrt_batch* b, double* extract_ms, double* pairs_ms, double* dp_ms,
+                                          uint32_t* rounds);
+
 /* HIP-event time (ms) of the kernels of the last solve call, their launch count, and which
  * kernel ran (oxhip_kernel_kind). */
 int32_t oxhip_rrt_batch_last_timing(oxhip_rrt_batch* b, double* kernel_ms, uint32_t* launches,

@@ -49,6 +49,9 @@ EXPORTS = [
     "oxhip_prm_solve", "oxhip_prm_get_query_sets", "oxhip_prm_last_timing", "oxhip_prm_knn_exact_rows",
     "oxhip_prm_solve_batch", "oxhip_prm_batch_get_results", "oxhip_prm_batch_get_paths", "oxhip_prm_batch_get_query_sets",
     "oxhip_prm_batch_last_timing",
+    "oxhip_rrt_batch_extract_paths", "oxhip_rrt_batch_get_paths", "oxhip_rrt_batch_simplify_paths",
+    "oxhip_rrt_batch_get_simplified_paths", "oxhip_rrt_batch_get_simplify_results", "oxhip_rrt_batch_path_valid_matrix",
+    "oxhip_rrt_batch_paths_last_timing",
 ]
 
 
@@ -160,6 +163,13 @@ def lib():
         L.oxhip_prm_batch_get_paths.argtypes = [C.c_void_p, _u64p, _u32p, _dp, C.c_uint64, _u64p]
         L.oxhip_prm_batch_get_query_sets.argtypes = [C.c_void_p, C.c_uint32, _u32p, C.c_uint32, _u32p, _u32p, C.c_uint32, _u32p]
         L.oxhip_prm_batch_last_timing.argtypes = [C.c_void_p, _dp, _u32p]
+        L.oxhip_rrt_batch_extract_paths.argtypes = [C.c_void_p]
+        L.oxhip_rrt_batch_get_paths.argtypes = [C.c_void_p, _u64p, _dp, C.c_uint64, _u64p]
+        L.oxhip_rrt_batch_simplify_paths.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+        L.oxhip_rrt_batch_get_simplified_paths.argtypes = [C.c_void_p, _u64p, _dp, _u32p, C.c_uint64, _u64p]
+        L.oxhip_rrt_batch_get_simplify_results.argtypes = [C.c_void_p, _dp, _dp, _u64p]
+        L.oxhip_rrt_batch_path_valid_matrix.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, _u8p, C.c_uint64, _u32p]
+        L.oxhip_rrt_batch_paths_last_timing.argtypes = [C.c_void_p, _dp, _dp, _dp, _u32p]
         for name in EXPORTS:
             if name not in ("oxhip_status_string", "oxhip_last_error_string"):
                 getattr(L, name).restype = C.c_int32
@@ -342,6 +352,62 @@ class RRTBatch:
         if ln.value:
             _check(lib().oxhip_rrt_batch_get_path(self._h, problem, _p(out), ln.value, C.byref(ln)))
         return out
+
+    # ---- the whole batch's paths: extraction and shortcutting on the device
+
+    def extract_paths(self):
+        """Walk every solved problem's parent chain on the device; paths() then hands all of them out in one copy."""
+        _check(lib().oxhip_rrt_batch_extract_paths(self._h))
+
+    def paths(self):
+        """(offsets [P+1] u64, rows [total][dim]): problem p's path is rows offsets[p] .. offsets[p+1], bit for bit path(p)"""
+        offsets = np.zeros(self.n_problems + 1, dtype=np.uint64)
+        total = C.c_uint64()
+        st = lib().oxhip_rrt_batch_get_paths(self._h, _p(offsets, _u64p), None, 0, C.byref(total))
+        if st not in (OK, ERR_CAPACITY):
+            _check(st)
+        rows = np.zeros((max(total.value, 1), self.dim), dtype=np.float64)
+        _check(lib().oxhip_rrt_batch_get_paths(self._h, _p(offsets, _u64p), _p(rows), total.value, C.byref(total)))
+        return offsets, rows[:total.value]
+
+    def simplify_paths(self, max_span=0, chunk_problems=0):
+        """Shortcut every path over its own waypoints (include/oxmpl_hip.h states the semantics); extracts the paths first
+        if that has not been done.  chunk_problems: problems per device round (test-only; results never depend on it)."""
+        _check(lib().oxhip_rrt_batch_simplify_paths(self._h, int(max_span), int(chunk_problems)))
+
+    def simplified_paths(self):
+        """(offsets [P+1] u64, rows [total][dim], indices [total] u32 into the raw path, raw_cost [P], simplified_cost [P],
+        checks [P] u64)"""
+        P = self.n_problems
+        offsets = np.zeros(P + 1, dtype=np.uint64)
+        total = C.c_uint64()
+        st = lib().oxhip_rrt_batch_get_simplified_paths(self._h, _p(offsets, _u64p), None, None, 0, C.byref(total))
+        if st not in (OK, ERR_CAPACITY):
+            _check(st)
+        rows = np.zeros((max(total.value, 1), self.dim), dtype=np.float64)
+        idx = np.zeros(max(total.value, 1), dtype=np.uint32)
+        _check(lib().oxhip_rrt_batch_get_simplified_paths(self._h, _p(offsets, _u64p), _p(rows), _p(idx, _u32p), total.value,
+                                                          C.byref(total)))
+        raw, simp, checks = np.zeros(P), np.zeros(P), np.zeros(P, dtype=np.uint64)
+        _check(lib().oxhip_rrt_batch_get_simplify_results(self._h, _p(raw), _p(simp), _p(checks, _u64p)))
+        return offsets, rows[:total.value], idx[:total.value], raw, simp, checks
+
+    def path_valid_matrix(self, problem, max_span=0):
+        """test hook: valid(i, j) of the extracted path of `problem` as the pair kernel evaluates it, [L][L] bool (i < j)"""
+        ln = C.c_uint32()
+        st = lib().oxhip_rrt_batch_path_valid_matrix(self._h, problem, int(max_span), None, 0, C.byref(ln))
+        if st not in (OK, ERR_CAPACITY):
+            _check(st)
+        L = ln.value
+        out = np.zeros(max(L * L, 1), dtype=np.uint8)
+        _check(lib().oxhip_rrt_batch_path_valid_matrix(self._h, problem, int(max_span), _p(out, _u8p), L * L, C.byref(ln)))
+        return out[:L * L].reshape(L, L).astype(bool)
+
+    def paths_last_timing(self):
+        """dict(extract_ms, pairs_ms, dp_ms, rounds): HIP-event times of the last extract_paths / simplify_paths"""
+        e, pr, dp, r = C.c_double(), C.c_double(), C.c_double(), C.c_uint32()
+        _check(lib().oxhip_rrt_batch_paths_last_timing(self._h, C.byref(e), C.byref(pr), C.byref(dp), C.byref(r)))
+        return dict(extract_ms=e.value, pairs_ms=pr.value, dp_ms=dp.value, rounds=r.value)
 
     def last_timing(self):
         ms, launches, kind = C.c_double(), C.c_uint32(), C.c_uint32()

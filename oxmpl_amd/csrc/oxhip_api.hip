@@ -103,7 +103,23 @@ struct oxhip_rrt_batch {
     uint32_t last_launches = 0;
     uint32_t kernel_kind = OXHIP_KERNEL_STREAM;   // the kind a launch uses (KERNEL_AUTO: resolved per launch, see solve)
     uint32_t last_kind = OXHIP_KERNEL_STREAM;     // what the last launch ran
+    // path_simplify.hip: the batch's solution paths as extract_paths / simplify_paths left them.  They belong to the trees as they
+    // stood at that call: setup / solve / set_tree drop them (drop_paths).
+    bool paths_ok = false, simp_ok = false;
+    std::vector<uint64_t> path_off;               // [P + 1] host copy of the row offsets
+    std::vector<uint32_t> h_path_len;             // [P]
+    DevBuf<uint64_t> d_path_off, sp_woff, sp_bits, sp_checks;
+    DevBuf<uint32_t> path_len, path_len_a, sp_par, sp_idx, sp_len;
+    DevBuf<double> path_rows, sp_cost, sp_raw, sp_simp;
+    double paths_ms[3] = {0.0, 0.0, 0.0};         // extraction kernels, pair matrix, DP of the last calls
+    uint32_t paths_rounds = 0;
 };
+static void drop_paths(oxhip_rrt_batch* b) { b->paths_ok = b->simp_ok = false; }
+template <typename T>
+static hipError_t grow(DevBuf<T>& buf, size_t count) {   // keeps a buffer that is large enough (a round reuses the last one's)
+    if (buf.p && buf.n >= count) return hipSuccess;
+    return buf.alloc(count ? count : 1);
+}
 
 extern "C" {
 
@@ -548,6 +564,7 @@ int32_t oxhip_rrt_batch_set_body(oxhip_rrt_batch* b, const double* centres, cons
 int32_t oxhip_rrt_batch_setup(oxhip_rrt_batch* b, const double* starts, const double* goal_centres,
                               const double* goal_radii) {
     if (!b || !starts || !goal_centres || !goal_radii) return fail(OXHIP_ERR_BAD_ARG, "null argument");
+    drop_paths(b);
     int32_t st = select_device(b->cfg.device);
     if (st != OXHIP_OK) return st;
     const uint32_t P = b->cfg.n_problems, dim = b->cfg.dim, cap = b->dp.cap;
@@ -689,6 +706,7 @@ static int32_t read_states(oxhip_rrt_batch* b, std::vector<ProblemState>& states
 int32_t oxhip_rrt_batch_set_tree(oxhip_rrt_batch* b, uint32_t problem, const double* states_in, const int32_t* parents_in,
                                  uint32_t n) {
     if (!b || !states_in || !parents_in) return fail(OXHIP_ERR_BAD_ARG, "null argument");
+    drop_paths(b);
     if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
     if (problem >= b->cfg.n_problems) return fail(OXHIP_ERR_BAD_ARG, "problem index out of range");
     if (n == 0 || n > b->cfg.max_nodes) return fail(OXHIP_ERR_BAD_ARG, "n_nodes must be in 1..max_nodes");
@@ -818,6 +836,7 @@ static int32_t wire_new_nodes(oxhip_rrt_batch* b) {
 int32_t oxhip_rrt_batch_solve(oxhip_rrt_batch* b, uint64_t max_iterations, double timeout_s, uint32_t freeze,
                               int32_t* status_out) {
     if (!b) return fail(OXHIP_ERR_BAD_ARG, "null batch");
+    drop_paths(b);
     if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");  // rrt.rs:160-163
     int32_t st = select_device(b->cfg.device);
     if (st != OXHIP_OK) return st;
@@ -1059,6 +1078,248 @@ int32_t oxhip_rrt_batch_get_costs(oxhip_rrt_batch* b, uint32_t problem, double* 
     if (n > cap_nodes) return fail(OXHIP_ERR_CAPACITY, "cost buffer too small");
     HIP_TRY(hipMemcpyAsync(costs, b->cost.p + (size_t)problem * b->dp.cap, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
+    return OXHIP_OK;
+}
+
+// ------------------------------------------------------------------ the whole batch's paths (path_simplify.hip)
+
+int32_t oxhip_rrt_batch_extract_paths(oxhip_rrt_batch* b) {
+    if (!b) return fail(OXHIP_ERR_BAD_ARG, "null batch");
+    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
+    OX_TRY(select_device(b->cfg.device));
+    drop_paths(b);
+    const uint32_t P = b->cfg.n_problems, dim = b->cfg.dim;
+    HIP_TRY(grow(b->path_len, P));
+    HIP_TRY(grow(b->path_len_a, P));
+    HIP_TRY(grow(b->d_path_off, (size_t)P + 1));
+    PathArgs a{b->d_path_off.p, b->path_len.p, b->path_len_a.p, nullptr};
+    // lengths first, one prefix sum, then the rows
+    HIP_TRY(hipEventRecord(b->ev0, b->stream));
+    launch_path_len(b->dp, a, b->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(b->ev1, b->stream));
+    b->h_path_len.resize(P);
+    HIP_TRY(hipMemcpyAsync(b->h_path_len.data(), b->path_len.p, (size_t)P * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+    b->paths_ms[0] = ms;
+    b->path_off.assign((size_t)P + 1, 0);
+    for (uint32_t p = 0; p < P; ++p) {
+        if (b->h_path_len[p] == 0xFFFFFFFFu) return fail(OXHIP_ERR_HIP, "parent chain is cyclic or leaves the tree (corrupt tree)");
+        b->path_off[p + 1] = b->path_off[p] + b->h_path_len[p];
+    }
+    const uint64_t total = b->path_off[P];
+    HIP_TRY(grow(b->path_rows, (size_t)total * dim));
+    HIP_TRY(hipMemcpyAsync(b->d_path_off.p, b->path_off.data(), ((size_t)P + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, b->stream));
+    a.rows = b->path_rows.p;
+    HIP_TRY(hipEventRecord(b->ev0, b->stream));
+    launch_path_rows(b->dp, a, b->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(b->ev1, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+    b->paths_ms[0] += ms;
+    b->paths_ok = true;
+    return OXHIP_OK;
+}
+
+int32_t oxhip_rrt_batch_get_paths(oxhip_rrt_batch* b, uint64_t* offsets_out, double* states_out, uint64_t cap_states, uint64_t* total_out) {
+    if (!b || !total_out) return fail(OXHIP_ERR_BAD_ARG, "null argument");
+    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
+    if (!b->paths_ok) return fail(OXHIP_ERR_BAD_ARG, "no extracted paths: call oxhip_rrt_batch_extract_paths after the last setup / solve / set_tree");
+    OX_TRY(select_device(b->cfg.device));
+    const uint32_t P = b->cfg.n_problems;
+    const uint64_t total = b->path_off[P];
+    *total_out = total;
+    if (offsets_out) std::memcpy(offsets_out, b->path_off.data(), ((size_t)P + 1) * sizeof(uint64_t));
+    if (total > cap_states) return fail(OXHIP_ERR_CAPACITY, "path buffer too small");
+    if (!states_out || total == 0) return OXHIP_OK;
+    HIP_TRY(hipMemcpyAsync(states_out, b->path_rows.p, (size_t)total * b->cfg.dim * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return OXHIP_OK;
+}
+
+// what a round of the pair matrix may take: 1 GiB of bits
+static constexpr uint64_t kPairWordsMax = (1ull << 30) / sizeof(uint64_t);
+
+// the batch's parameters as the pair kernel reads them (R^n: the radii and the absolute margin of motion_seq.hpp's midpoint filter)
+static int32_t pair_params(oxhip_rrt_batch* b, double& filt_base) {
+    filt_base = 0.0;
+    if (b->cfg.space != OXHIP_SPACE_REAL_VECTOR) return OXHIP_OK;
+    if (b->dp.n_spheres != 0) {
+        OX_TRY(upload(b->sph_r, b->sph_radii, b->stream));
+        b->dp.sph_r = b->sph_r.p;
+    }
+    double maxabs = 1.0;
+    for (uint32_t k = 0; k < 2 * b->cfg.dim; ++k) maxabs = std::fmax(maxabs, std::fabs(b->cfg.bounds[k]));
+    for (double v : b->sph_centres) maxabs = std::fmax(maxabs, std::fabs(v));
+    filt_base = 1e-9 * maxabs;
+    return OXHIP_OK;
+}
+
+static int32_t simplify_supported(const oxhip_rrt_batch* b) {
+    if (b->cfg.space == OXHIP_SPACE_SE2 || b->cfg.space == OXHIP_SPACE_SE3)
+        return fail(OXHIP_ERR_BAD_ARG, "simplify_paths is not built for SE(2) / SE(3) batches (their motion checks live inside their planners' kernels)");
+    if (b->cfg.space == OXHIP_SPACE_REAL_VECTOR && b->cfg.dim < 2)
+        return fail(OXHIP_ERR_BAD_ARG, "simplify_paths is not built for dim 1 (R^2 .. R^8 and SO(3))");
+    return OXHIP_OK;
+}
+
+int32_t oxhip_rrt_batch_simplify_paths(oxhip_rrt_batch* b, uint32_t max_span, uint32_t chunk_problems) {
+    if (!b) return fail(OXHIP_ERR_BAD_ARG, "null batch");
+    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
+    OX_TRY(simplify_supported(b));
+    OX_TRY(select_device(b->cfg.device));
+    b->simp_ok = false;
+    if (!b->paths_ok) OX_TRY(oxhip_rrt_batch_extract_paths(b));
+    const uint32_t P = b->cfg.n_problems;
+    const uint64_t total = b->path_off[P];
+    double filt_base = 0.0;
+    OX_TRY(pair_params(b, filt_base));
+    HIP_TRY(grow(b->sp_cost, total));
+    HIP_TRY(grow(b->sp_par, total));
+    HIP_TRY(grow(b->sp_idx, total));
+    HIP_TRY(grow(b->sp_len, P));
+    HIP_TRY(grow(b->sp_raw, P));
+    HIP_TRY(grow(b->sp_simp, P));
+    HIP_TRY(grow(b->sp_checks, P));
+    const SimplifyOut out{b->sp_cost.p, b->sp_par.p, b->sp_idx.p, b->sp_len.p, b->sp_raw.p, b->sp_simp.p, b->sp_checks.p};
+    hipEvent_t ev2 = nullptr;
+    HIP_TRY(hipEventCreate(&ev2));
+    struct EvGuard { hipEvent_t e; ~EvGuard() { (void)hipEventDestroy(e); } } guard{ev2};
+    b->paths_ms[1] = b->paths_ms[2] = 0.0;
+    b->paths_rounds = 0;
+    std::vector<uint64_t> woff;
+    for (uint32_t q0 = 0; q0 < P;) {
+        // a round: as many problems as the bit workspace (and the caller's override) allows, at least one
+        woff.assign(1, 0);
+        uint32_t q1 = q0;
+        while (q1 < P && (chunk_problems == 0 || q1 - q0 < chunk_problems)) {
+            const uint64_t w = path_pair_words(b->h_path_len[q1], max_span);
+            if (w > kPairWordsMax) return fail(OXHIP_ERR_CAPACITY, "a path's pair matrix exceeds the 1 GiB workspace: pass a max_span");
+            if (q1 > q0 && woff.back() + w > kPairWordsMax) break;
+            woff.push_back(woff.back() + w);
+            ++q1;
+        }
+        const uint32_t n_chunk = q1 - q0;
+        HIP_TRY(grow(b->sp_woff, (size_t)n_chunk + 1));
+        HIP_TRY(grow(b->sp_bits, woff.back()));
+        HIP_TRY(hipMemcpyAsync(b->sp_woff.p, woff.data(), woff.size() * sizeof(uint64_t), hipMemcpyHostToDevice, b->stream));
+        const PairArgs a{b->d_path_off.p, b->path_len.p, b->path_rows.p, b->sp_woff.p, b->sp_bits.p, woff.back(), q0, n_chunk, max_span, 0, filt_base};
+        HIP_TRY(hipEventRecord(b->ev0, b->stream));
+        launch_path_pairs(b->dp, a, b->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(b->ev1, b->stream));
+        launch_path_dp(b->dp, a, out, b->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ev2, b->stream));
+        HIP_TRY(hipStreamSynchronize(b->stream));   // (woff is rebuilt by the next round)
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+        b->paths_ms[1] += ms;
+        HIP_TRY(hipEventElapsedTime(&ms, b->ev1, ev2));
+        b->paths_ms[2] += ms;
+        b->paths_rounds++;
+        q0 = q1;
+    }
+    b->simp_ok = true;
+    return OXHIP_OK;
+}
+
+int32_t oxhip_rrt_batch_get_simplified_paths(oxhip_rrt_batch* b, uint64_t* offsets_out, double* states_out, uint32_t* indices_out,
+                                             uint64_t cap_states, uint64_t* total_out) {
+    if (!b || !total_out) return fail(OXHIP_ERR_BAD_ARG, "null argument");
+    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
+    if (!b->simp_ok || !b->paths_ok)
+        return fail(OXHIP_ERR_BAD_ARG, "no simplified paths: call oxhip_rrt_batch_simplify_paths after the last setup / solve / set_tree");
+    OX_TRY(select_device(b->cfg.device));
+    const uint32_t P = b->cfg.n_problems, dim = b->cfg.dim;
+    std::vector<uint32_t> slen(P);
+    HIP_TRY(hipMemcpyAsync(slen.data(), b->sp_len.p, (size_t)P * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    std::vector<uint64_t> soff((size_t)P + 1, 0);
+    for (uint32_t p = 0; p < P; ++p) soff[p + 1] = soff[p] + slen[p];
+    const uint64_t total = soff[P];
+    *total_out = total;
+    if (offsets_out) std::memcpy(offsets_out, soff.data(), soff.size() * sizeof(uint64_t));
+    if (total > cap_states) return fail(OXHIP_ERR_CAPACITY, "path buffer too small");
+    if ((!states_out && !indices_out) || total == 0) return OXHIP_OK;
+    // one copy of the raw rows and of the index lists; the simplified rows are gathered from them
+    const uint64_t raw_total = b->path_off[P];
+    std::vector<uint32_t> idx(raw_total);
+    std::vector<double> rows;
+    HIP_TRY(hipMemcpyAsync(idx.data(), b->sp_idx.p, (size_t)raw_total * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+    if (states_out) {
+        rows.resize((size_t)raw_total * dim);
+        HIP_TRY(hipMemcpyAsync(rows.data(), b->path_rows.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    for (uint32_t p = 0; p < P; ++p)
+        for (uint32_t t = 0; t < slen[p]; ++t) {
+            const uint32_t i = idx[b->path_off[p] + t];
+            if (indices_out) indices_out[soff[p] + t] = i;
+            if (states_out) std::memcpy(states_out + (soff[p] + t) * dim, rows.data() + (b->path_off[p] + i) * dim, dim * sizeof(double));
+        }
+    return OXHIP_OK;
+}
+
+int32_t oxhip_rrt_batch_get_simplify_results(oxhip_rrt_batch* b, double* raw_cost, double* simplified_cost, uint64_t* checks) {
+    if (!b) return fail(OXHIP_ERR_BAD_ARG, "null batch");
+    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
+    if (!b->simp_ok || !b->paths_ok)
+        return fail(OXHIP_ERR_BAD_ARG, "no simplified paths: call oxhip_rrt_batch_simplify_paths after the last setup / solve / set_tree");
+    OX_TRY(select_device(b->cfg.device));
+    const size_t P = b->cfg.n_problems;
+    if (raw_cost) HIP_TRY(hipMemcpyAsync(raw_cost, b->sp_raw.p, P * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (simplified_cost) HIP_TRY(hipMemcpyAsync(simplified_cost, b->sp_simp.p, P * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (checks) HIP_TRY(hipMemcpyAsync(checks, b->sp_checks.p, P * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return OXHIP_OK;
+}
+
+int32_t oxhip_rrt_batch_path_valid_matrix(oxhip_rrt_batch* b, uint32_t problem, uint32_t max_span, uint8_t* out, uint64_t cap_bytes,
+                                          uint32_t* len_out) {
+    if (!b || !len_out) return fail(OXHIP_ERR_BAD_ARG, "null argument");
+    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
+    if (problem >= b->cfg.n_problems) return fail(OXHIP_ERR_BAD_ARG, "problem index out of range");
+    OX_TRY(simplify_supported(b));
+    if (!b->paths_ok) return fail(OXHIP_ERR_BAD_ARG, "no extracted paths: call oxhip_rrt_batch_extract_paths after the last setup / solve / set_tree");
+    OX_TRY(select_device(b->cfg.device));
+    const uint32_t L = b->h_path_len[problem];
+    *len_out = L;
+    if ((uint64_t)L * L > cap_bytes) return fail(OXHIP_ERR_CAPACITY, "matrix buffer too small");
+    if (!out || L == 0) return OXHIP_OK;
+    const uint64_t words = path_pair_words(L, max_span);
+    if (words > kPairWordsMax) return fail(OXHIP_ERR_CAPACITY, "a path's pair matrix exceeds the 1 GiB workspace: pass a max_span");
+    double filt_base = 0.0;
+    OX_TRY(pair_params(b, filt_base));
+    // the pair kernel on a round of this one problem (its own buffers: a simplified result stays as it is)
+    DevBuf<uint64_t> d_woff, d_bits;
+    const uint64_t woff[2] = {0, words};
+    OX_TRY(to_device(d_woff, woff, 2, b->stream));
+    HIP_TRY(d_bits.alloc(words ? words : 1));
+    const PairArgs a{b->d_path_off.p, b->path_len.p, b->path_rows.p, d_woff.p, d_bits.p, words, problem, 1, max_span, 0, filt_base};
+    launch_path_pairs(b->dp, a, b->stream);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint64_t> bits(words);
+    OX_TRY(to_host(bits.data(), d_bits, words, b->stream));
+    const uint32_t S = max_span == 0 || max_span > L - 1 ? L - 1 : max_span;
+    std::memset(out, 0, (size_t)L * L);
+    for (uint32_t i = 0; i + 1 < L; ++i)
+        for (uint32_t d = 1; d <= S && i + d < L; ++d) {
+            const uint64_t slot = (uint64_t)(d - 2) * L + i;
+            out[(size_t)i * L + i + d] = d == 1 ? 1 : (uint8_t)((bits[slot >> 6] >> (slot & 63)) & 1u);
+        }
+    return OXHIP_OK;
+}
+
+int32_t oxhip_rrt_batch_paths_last_timing(oxhip_rrt_batch* b, double* extract_ms, double* pairs_ms, double* dp_ms, uint32_t* rounds) {
+    if (!b) return fail(OXHIP_ERR_BAD_ARG, "null batch");
+    if (extract_ms) *extract_ms = b->paths_ms[0];
+    if (pairs_ms) *pairs_ms = b->paths_ms[1];
+    if (dp_ms) *dp_ms = b->paths_ms[2];
+    if (rounds) *rounds = b->paths_rounds;
     return OXHIP_OK;
 }
 

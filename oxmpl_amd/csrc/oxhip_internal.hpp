@@ -191,4 +191,37 @@ void launch_prm_batch_search(const PrmBatchArgs& b, uint32_t group, hipStream_t 
 // row_off[c]: first row of query c's path within nodes / rows (this round's rows)
 void launch_prm_batch_paths(const PrmBatchArgs& b, const uint64_t* row_off, uint32_t* nodes, double* rows, hipStream_t s);
 
+// path_simplify.hip: the solution paths of an RRT / RRTConnect / RRT* batch, extracted and shortcut on the device (DESIGN.md
+// section 18).  Problem p's raw path is rows off[p] .. off[p] + len[p] of `rows`.
+struct PathArgs {
+    const uint64_t* off;         // [P + 1] first row of every problem's path (read by the rows kernel only)
+    uint32_t* len;               // [P] states of the path, 0 = unsolved (0xFFFFFFFF from the length kernel: corrupt chain)
+    uint32_t* len_a;             // [P] of which from the start tree
+    double* rows;                // [total][dim]
+};
+struct PairArgs {                // one round: the problems [q0, q0 + n_chunk)
+    const uint64_t* off;
+    const uint32_t* len;
+    const double* rows;
+    const uint64_t* woff;        // [n_chunk + 1] first word of every problem's bit matrix within `bits`
+    uint64_t* bits;              // bit (d - 2) * L + i of a problem: check_motion(p_i, p_{i + d}), 2 <= d <= span
+    uint64_t n_words;
+    uint32_t q0, n_chunk, max_span, pad;
+    double filt_base;            // the midpoint filter's absolute margin from the bounds and the sphere centres (R^n)
+};
+struct SimplifyOut {
+    double* cost;                // [total] per raw state: cost of the best chain from p_0
+    uint32_t* par;               // [total] ... and the state before it on that chain
+    uint32_t* idx;               // [total] the simplified path's indices into the raw path, at the raw path's offset
+    uint32_t* simp_len;          // [P]
+    double* raw_cost;            // [P]
+    double* simp_cost;           // [P]
+    uint64_t* checks;            // [P] motion checks evaluated
+};
+void launch_path_len(const DevParams& p, const PathArgs& a, hipStream_t s);
+void launch_path_rows(const DevParams& p, const PathArgs& a, hipStream_t s);
+uint64_t path_pair_words(uint32_t len, uint32_t max_span);   // 64-bit words of one problem's bit matrix
+void launch_path_pairs(const DevParams& p, const PairArgs& a, hipStream_t s);
+void launch_path_dp(const DevParams& p, const PairArgs& a, const SimplifyOut& o, hipStream_t s);
+
 }  // namespace oxhip

@@ -141,6 +141,23 @@ class RRT:
             return Path([SE3State.from_values(row) for row in self._batch.path(0)])
         return Path([RealVectorState(row) for row in self._batch.path(0)])
 
+    def simplify_solution(self, max_span=0):
+        """The last solution, shortcut over its own waypoints on the device (the cheapest chain of
+        waypoints whose links pass the planner's own check_motion; `max_span` bounds how many waypoints a link may skip over,
+        0 = no bound) -> Path.  Not part of the reference's surface.  Raises the reference-style Exception when there is no
+        solution, TypeError on SE(3), for which the shortcut is not built."""
+        if self._batch is None:
+            raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
+        if isinstance(self._pd.space, SE3StateSpace):
+            raise TypeError("simplify_solution is not built for SE(3)")
+        if int(self._batch.counts()["goal_node"][0]) < 0:
+            raise Exception(_MESSAGES[capi.ERR_NO_SOLUTION_FOUND])
+        self._batch.simplify_paths(int(max_span))
+        rows = self._batch.simplified_paths()[1]
+        if isinstance(self._pd.space, SO3StateSpace):
+            return Path([SO3State(*row) for row in rows])
+        return Path([RealVectorState(row) for row in rows])
+
     def is_state_valid(self, state):
         """the checker's predicate, evaluated on the device (the reference calls the user's callable)"""
         return bool(self._batch.is_valid(np.array([state.values]))[0])

@@ -173,6 +173,14 @@ extern "C" {
     pub fn oxhip_rrt_batch_get_goal_tree(b: *mut OxhipRrtBatch, problem: u32, states: *mut f64, parents: *mut i32, cap_nodes: u32, n_nodes: *mut u32) -> i32;
     pub fn oxhip_rrt_batch_get_costs(b: *mut OxhipRrtBatch, problem: u32, costs: *mut f64, cap_nodes: u32, n_nodes: *mut u32) -> i32;
     pub fn oxhip_rrt_batch_last_timing(b: *mut OxhipRrtBatch, kernel_ms: *mut f64, launches: *mut u32, kernel_kind: *mut u32) -> i32;
+    // the whole batch's solution paths, extracted and shortcut on the device (path_simplify.hip)
+    pub fn oxhip_rrt_batch_extract_paths(b: *mut OxhipRrtBatch) -> i32;
+    pub fn oxhip_rrt_batch_get_paths(b: *mut OxhipRrtBatch, offsets: *mut u64, states: *mut f64, cap_states: u64, total_out: *mut u64) -> i32;
+    pub fn oxhip_rrt_batch_simplify_paths(b: *mut OxhipRrtBatch, max_span: u32, chunk_problems: u32) -> i32;
+    pub fn oxhip_rrt_batch_get_simplified_paths(b: *mut OxhipRrtBatch, offsets: *mut u64, states: *mut f64, indices: *mut u32, cap_states: u64, total_out: *mut u64) -> i32;
+    pub fn oxhip_rrt_batch_get_simplify_results(b: *mut OxhipRrtBatch, raw_cost: *mut f64, simplified_cost: *mut f64, checks: *mut u64) -> i32;
+    pub fn oxhip_rrt_batch_path_valid_matrix(b: *mut OxhipRrtBatch, problem: u32, max_span: u32, out: *mut u8, cap_bytes: u64, len_out: *mut u32) -> i32;
+    pub fn oxhip_rrt_batch_paths_last_timing(b: *mut OxhipRrtBatch, extract_ms: *mut f64, pairs_ms: *mut f64, dp_ms: *mut f64, rounds: *mut u32) -> i32;
     pub fn oxhip_rrt_batch_is_valid(b: *mut OxhipRrtBatch, states: *const f64, n: u32, out: *mut u8) -> i32;
     pub fn oxhip_rrt_batch_check_motion(b: *mut OxhipRrtBatch, from: *const f64, to: *const f64, n: u32, out: *mut u8) -> i32;
 

@@ -239,6 +239,33 @@ impl<D: DeviceValidityChecker, G: DeviceGoal> HipRRT<D, G> {
         let states = flat.chunks(dim).map(|c| RealVectorState::new(c.to_vec())).collect();
         Some((states, parents))
     }
+
+    /// The last solution, shortcut over its own waypoints on the device (`oxhip_rrt_batch_simplify_paths`: the cheapest
+    /// chain of waypoints whose links pass the planner's own `check_motion`; `max_span` bounds how many waypoints a link
+    /// may skip over, 0 = no bound).  Not part of the reference's surface.  `NoSolutionFound` when there is no solution.
+    pub fn simplify_solution(&mut self, max_span: u32) -> Result<Path<RealVectorState>, PlanningError> {
+        let pd = match (&self.problem_def, self.batch.is_null()) {
+            (Some(pd), false) => pd.clone(),
+            _ => return Err(PlanningError::PlannerUninitialised),
+        };
+        let rc = unsafe { ffi::oxhip_rrt_batch_simplify_paths(self.batch, max_span, 0) };
+        if rc != ffi::OXHIP_OK {
+            return Err(to_planning_error(rc));
+        }
+        let dim = pd.space.dimension;
+        let mut offsets = [0u64; 2];
+        let mut total = 0u64;
+        unsafe { ffi::oxhip_rrt_batch_get_simplified_paths(self.batch, offsets.as_mut_ptr(), ptr::null_mut(), ptr::null_mut(), 0, &mut total) };
+        if total == 0 {
+            return Err(PlanningError::NoSolutionFound);
+        }
+        let mut flat = vec![0.0f64; total as usize * dim];
+        let rc = unsafe { ffi::oxhip_rrt_batch_get_simplified_paths(self.batch, offsets.as_mut_ptr(), flat.as_mut_ptr(), ptr::null_mut(), total, &mut total) };
+        if rc != ffi::OXHIP_OK {
+            return Err(to_planning_error(rc));
+        }
+        Ok(Path(flat.chunks(dim).map(|c| RealVectorState::new(c.to_vec())).collect()))
+    }
 }
 
 impl<D: DeviceValidityChecker, G: DeviceGoal> Drop for HipRRT<D, G> {
