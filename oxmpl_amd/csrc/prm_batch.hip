@@ -79,7 +79,6 @@ constexpr uint32_t kNoGoal = 0xFFFFFFFFu;
 __device__ __forceinline__ uint32_t ld_l2(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_l2(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-__device__ __forceinline__ uint64_t lanes_below(uint32_t lane) { return (1ull << lane) - 1ull; }
 
 // 1024 threads per query: the search is a chain of dependent loads (edge list -> claim word), and with one workgroup per query
 // the waves of that workgroup are all the latency hiding a query has
@@ -137,7 +136,7 @@ __global__ __launch_bounds__(kSearchThreads) void prm_batch_search_kernel(PrmBat
                 const uint32_t f = i < i1 ? flags[i] : 0u;
                 const uint64_t bal = __ballot(f & 1u);
                 if (f & 1u) {
-                    const uint32_t pos = base + (uint32_t)__popcll(bal & lanes_below(lane));
+                    const uint32_t pos = base + (uint32_t)__popcll(bal & below_mask(lane));
                     st_l2(queue + pos, i);
                     st_l2(parent + i, kRoot);
                     if (LDS_VISITED) atomicOr(&visited[i >> 5], 1u << (i & 31u));
@@ -217,7 +216,7 @@ __global__ __launch_bounds__(kSearchThreads) void prm_batch_search_kernel(PrmBat
                             }
                             const uint64_t bal = __ballot(own) & gmask;
                             if (own) {
-                                const uint32_t pos = at + (uint32_t)__popcll(bal & lanes_below(lane));
+                                const uint32_t pos = at + (uint32_t)__popcll(bal & below_mask(lane));
                                 st_l2(queue + pos, v);
                                 st_l2(parent + v, u);
                                 if (LDS_VISITED) atomicOr(&visited[v >> 5], 1u << (v & 31u));

@@ -139,7 +139,7 @@ __global__ __launch_bounds__(kSampleBatch) void prm_sample_kernel(DevParams p, P
             before += (uint32_t)w < wave ? c : 0u;
             total += c;
         }
-        const uint32_t rank = before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        const uint32_t rank = before + (uint32_t)__popcll(bal & below_mask(lane));
         const bool keep = valid && n + rank < a.n_target;
         if (keep) {
 #pragma unroll
@@ -269,7 +269,7 @@ __global__ __launch_bounds__(kSpecThreads) void prm_sample_compact_kernel(PrmArg
     if (s >= sp.m) return;
     const uint64_t bal = sp.vbits[s >> 6];
     if (!((bal >> lane) & 1ull)) return;
-    const uint32_t dst = n0 + sp.wave_off[s >> 6] + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+    const uint32_t dst = n0 + sp.wave_off[s >> 6] + (uint32_t)__popcll(bal & below_mask(lane));
     if (dst >= a.n_target) return;
 #pragma unroll
     for (int k = 0; k < DIM; ++k) a.ms[(size_t)dst * DIM + k] = sp.tmp[(size_t)s * DIM + k];
@@ -386,7 +386,7 @@ __device__ __forceinline__ void pairs_one_i(const PrmArgs& a, PairStage& st, uin
 #pragma unroll
         for (int r = 0; r < kPairR; ++r) {
             const uint64_t m = __ballot(h[r]);
-            if (h[r]) st.buf[st.cnt + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = make_uint2(jr[r], i);
+            if (h[r]) st.buf[st.cnt + (uint32_t)__popcll(m & below_mask(lane))] = make_uint2(jr[r], i);
             st.cnt += (uint32_t)__popcll(m);
         }
         if (st.cnt > (uint32_t)(kStage - 64 * kPairR)) stage_flush(a, st, lane);  // room for one more full i
@@ -491,7 +491,7 @@ __global__ __launch_bounds__(256) void prm_edge_kernel(DevParams p, PrmArgs a, u
     if (lane == 0) base = atomicAdd(&a.state->n_keys, 2u * (uint32_t)__popcll(bal));
     base = uni(base);
     if (ok) {
-        const uint32_t slot = base + 2u * (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        const uint32_t slot = base + 2u * (uint32_t)__popcll(bal & below_mask(lane));
         a.keys[slot] = ((uint64_t)pr.x << key_shift) | pr.y;       // i in j's list
         a.keys[slot + 1] = ((uint64_t)pr.y << key_shift) | pr.x;   // j in i's list (prm.rs:143-145)
     }

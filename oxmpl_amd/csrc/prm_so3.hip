@@ -143,7 +143,7 @@ __global__ __launch_bounds__(kSo3SpecThreads) void prm_so3_sample_compact_kernel
     if (s >= sp.m) return;
     const uint64_t bal = sp.vbits[s >> 6];
     if (!((bal >> lane) & 1ull)) return;
-    const uint32_t dst = n0 + sp.voff[s >> 6] + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+    const uint32_t dst = n0 + sp.voff[s >> 6] + (uint32_t)__popcll(bal & below_mask(lane));
     if (dst >= sp.result->n_milestones) return;
 #pragma unroll
     for (int k = 0; k < 4; ++k) a.ms[(size_t)dst * 4 + k] = sp.tmp[(size_t)s * 4 + k];
@@ -210,7 +210,7 @@ __device__ __forceinline__ void so3_pairs_range(const PrmArgs& a, So3Stage& st, 
 #pragma unroll
             for (int q = 0; q < kSo3PairR; ++q) {
                 const uint64_t m = __ballot(in[q]);
-                if (in[q]) st.buf[st.cnt + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = make_uint2(jr[q], i);
+                if (in[q]) st.buf[st.cnt + (uint32_t)__popcll(m & below_mask(lane))] = make_uint2(jr[q], i);
                 st.cnt += (uint32_t)__popcll(m);
             }
             if (st.cnt > (uint32_t)(kSo3Stage - 64 * kSo3PairR)) so3_stage_flush(a, st, lane);   // room for one more i
@@ -286,7 +286,7 @@ __global__ __launch_bounds__(256) void prm_so3_edge_kernel(So3Cones p, const uin
     if (lane == 0) base = atomicAdd(n_keys, 2u * (uint32_t)__popcll(bal));
     base = uni(base);
     if (ok) {
-        const uint32_t slot = base + 2u * (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        const uint32_t slot = base + 2u * (uint32_t)__popcll(bal & below_mask(lane));
         keys[slot] = ((uint64_t)pr.x << key_shift) | pr.y;       // i in j's list
         keys[slot + 1] = ((uint64_t)pr.y << key_shift) | pr.x;   // j in i's list (prm.rs:143-145)
     }

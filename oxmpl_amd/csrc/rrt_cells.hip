@@ -31,6 +31,7 @@
 #include "rrt_device.hpp"
 #include "rrt_resident_common.hpp"
 #include "lane_query_common.hpp"
+#include "lane_sampler.hpp"
 
 namespace oxhip {
 
@@ -291,92 +292,19 @@ __device__ __forceinline__ void grid_store(CellMeta& m, const CellGrid& g, uint3
     }
 }
 
-// Lane-parallel sampling of m <= 64 consecutive queries (rrt.rs:177-184 + rvss.rs:233-249; sample_batch of
-// rrt_resident_common.hpp with this kernel's ring).  STORE = false only advances the stream position (the fast-forward of
-// cells_prepare_kernel).  Returns false, nothing written, when a range draw was rejected or the window is too short.
-template <int DIM, bool STORE>
-__device__ __forceinline__ bool cells_sample(RngWindow& rng, const DevParams& p, const double* goal_c, double goal_radius, uint32_t m, uint32_t lane,
-                                             CellsWaveLds<DIM>* sh, uint32_t js) {
-    const uint64_t win_lo = rng.base_blk * 8;
-    const uint64_t pos0 = rng.pos;
-    if (pos0 < win_lo || pos0 + (uint64_t)m * (1 + DIM) > win_lo + 512) return false;
-    const uint32_t rel0 = (uint32_t)(pos0 - win_lo);
-    const bool act = lane < m;
-    const bool always_goal = p.p_int == ~0ull;
-    const bool disc = DIM == 2 && p.goal_sampler == OXHIP_GOAL_SAMPLE_UNIFORM_DISC;
-    const uint32_t gw = disc ? 2u : 0u;   // words a goal sample draws after its Bernoulli word
-    auto word = [&](uint32_t rel) -> uint64_t {
-        const uint32_t a = rel0 + rel, bl = a >> 3, w = (a & 7u) * 2u;
-        return ((uint64_t)rng.buf[w + 1][bl] << 32) | rng.buf[w][bl];
-    };
-    uint64_t goal_mask = always_goal ? ~0ull : 0ull;
-    uint32_t off = act ? gw * lane : 0u;   // (every query is a goal sample: gw words each)
-    if (!always_goal) {
-        const uint64_t below = below_mask(lane);
-        for (uint32_t round = 0; round <= m; ++round) {
-            off = act ? (1u + DIM) * lane - ((uint32_t)DIM - gw) * (uint32_t)__popcll(goal_mask & below) : 0u;
-            const uint64_t now = __ballot(act && word(off) < p.p_int);
-            if (now == goal_mask) break;
-            goal_mask = now;
-        }
-    }
-    const bool goal = (goal_mask >> lane) & 1ull;
-    double q[DIM];
-    bool redraw = false;
-#pragma unroll
-    for (int k = 0; k < DIM; ++k) {
-        const uint64_t bits = (word(act && !goal ? off + 1u + (uint32_t)k : 0u) >> 12) | 0x3FF0000000000000ull;
-        const double v01 = __longlong_as_double((long long)bits) - 1.0;
-        double res = v01 * p.scale[k];
-        res = res + p.lo[k];
-        redraw = redraw || !(res < p.hi[k]);
-        q[k] = goal ? goal_c[k] : res;
-    }
-    redraw = redraw && !goal;
-    if (DIM == 2 && disc) {   // the disc sampler's two words follow the Bernoulli word (if one was drawn)
-        const uint32_t base = act && goal ? off + (always_goal ? 0u : 1u) : 0u;
-        double gx, gy;
-        const bool okd = goal_disc_sample(word(base), word(base + 1u), goal_c, goal_radius, gx, gy);
-        if (goal) { q[0] = gx; q[DIM >= 2 ? 1 : 0] = gy; redraw = !okd; }
-    }
-    if (__ballot(act && redraw) != 0) return false;
-    const uint32_t cnt = always_goal ? gw : (goal ? 1u + gw : 1u + (uint32_t)DIM);
-    if (STORE && act) {
-        const uint32_t slot = (js + lane) & 63u;
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) sh->q[k][slot] = q[k];
-        sh->pos_after[slot] = pos0 + off + cnt;
-    }
-    rng.pos = pos0 + (uint32_t)__builtin_amdgcn_readlane((int)(off + cnt), (int)(m - 1));
-    return true;
-}
-
-// draw (STORE) or skip the queries [js, js + m): window refill, the lane-parallel sampler, the sequential fallback
+// draw (STORE) or skip the queries [js, js + m) (lane_sampler.hpp); STORE = false only advances the stream position: the
+// fast-forward of a split frozen launch.  No slack in the hold: a fresh window of 512 words serves two rounds of 64 uniform
+// samples in R^3 most of the time -- any slack means ChaCha blocks computed twice.
 template <int DIM, bool STORE>
 __device__ __forceinline__ void cells_sample_block(RngWindow& rng, const DevParams& p, const double* goal_c, double goal_radius, uint32_t m, uint32_t lane,
                                                    CellsWaveLds<DIM>* sh, uint32_t js) {
-    // (exactly what cells_sample asks of the window: a fresh window of 512 words serves two rounds of 64 uniform samples in R^3
-    //  most of the time -- any slack here means ChaCha blocks computed twice)
-    const uint64_t need_hi = rng.pos + (uint64_t)m * (1 + DIM);
-    if ((rng.pos >> 3) - rng.base_blk >= 64 || need_hi > (rng.base_blk + 64) * 8) {
-        rng.base_blk = uni64(rng.pos >> 3);
-        uint32_t o[16];
-        chacha12_block(rng.seed, rng.base_blk + lane, rng.stream, o);
+    sample_block64<DIM, true>(rng, p, DIM, goal_c, goal_radius, m, lane, 0u, [&](uint32_t b, const double (&q)[DIM], uint64_t pos_after) {
+        if (!STORE) return;
+        const uint32_t slot = (js + b) & 63u;
 #pragma unroll
-        for (int w = 0; w < 16; ++w) rng.buf[w][lane] = o[w];
-    }
-    if (!cells_sample<DIM, STORE>(rng, p, goal_c, goal_radius, m, lane, sh, js)) {
-        for (uint32_t b = 0; b < m; ++b) {   // (never expected) a redraw, or a batch past the window: one by one
-            double qn[DIM];
-            sample_state<DIM, false>(rng, p, DIM, goal_c, qn, goal_radius);
-            if (STORE && lane == 0) {
-                const uint32_t slot = (js + b) & 63u;
-#pragma unroll
-                for (int k = 0; k < DIM; ++k) sh->q[k][slot] = qn[k];
-                sh->pos_after[slot] = rng.pos;
-            }
-        }
-    }
+        for (int k = 0; k < DIM; ++k) sh->q[k][slot] = q[k];
+        sh->pos_after[slot] = pos_after;
+    });
 }
 
 // inclusive prefix sum over the wave (DPP: shifts within the rows of 16, then the row totals)

@@ -11,6 +11,7 @@
 // problem: four barriers per extend and a wave-serial sampler made an iteration 5.8-6.7 us; this kernel's is a third of that.
 #include "oxhip_internal.hpp"
 #include "rrt_device.hpp"
+#include "lane_sampler.hpp"
 
 namespace oxhip {
 
@@ -50,86 +51,15 @@ struct ConnTree {
 // what the constant step count of an Advanced extend depends on (wave-uniform, kept current by every insert)
 struct ConnRange { float mag; };   // largest |coordinate| of any node of either tree
 
-__device__ __forceinline__ double conn_readlane_f64(double v, int l) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
-
-// Lane-parallel sampling of m <= 64 consecutive iterations (rrt_connect.rs:258-262 + rvss.rs:233-249; the scheme of rrt_cells.hip's
-// cells_sample): lane j draws iteration j.  Where its words start depends on how many of the iterations before it sampled the goal
-// (one word instead of 1 + dim), so the goal mask is iterated to its fixed point.  Returns false, nothing written, when a range draw
-// was rejected or the window is too short.
-template <int D>
-__device__ __forceinline__ bool conn_sample64(RngWindow& rng, const DevParams& p, int dim, const double* goal_c, uint32_t m, uint32_t lane,
-                                              ConnShared<D>& sh) {
-    const uint32_t per = 1u + (uint32_t)dim;
-    const uint64_t win_lo = rng.base_blk * 8;
-    const uint64_t pos0 = rng.pos;
-    if (pos0 < win_lo || pos0 + (uint64_t)m * per > win_lo + 512) return false;
-    const uint32_t rel0 = (uint32_t)(pos0 - win_lo);
-    const bool act = lane < m;
-    const bool always_goal = p.p_int == ~0ull;   // Bernoulli ALWAYS_TRUE: no draw at all
-    auto word = [&](uint32_t rel) -> uint64_t {
-        const uint32_t a = rel0 + rel, bl = a >> 3, w = (a & 7u) * 2u;
-        return ((uint64_t)rng.buf[w + 1][bl] << 32) | rng.buf[w][bl];
-    };
-    uint64_t goal_mask = always_goal ? ~0ull : 0ull;
-    uint32_t off = 0u;
-    if (!always_goal) {
-        const uint64_t below = (1ull << lane) - 1ull;
-        for (uint32_t round = 0; round <= m; ++round) {
-            off = act ? per * lane - (uint32_t)dim * (uint32_t)__popcll(goal_mask & below) : 0u;
-            const uint64_t now = __ballot(act && word(off) < p.p_int);
-            if (now == goal_mask) break;
-            goal_mask = now;
-        }
-    }
-    const bool goal = (goal_mask >> lane) & 1ull;
-    double q[D];
-    bool redraw = false;
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        if (k < dim) {
-            const uint64_t bits = (word(act && !goal ? off + 1u + (uint32_t)k : 0u) >> 12) | 0x3FF0000000000000ull;
-            const double v01 = __longlong_as_double((long long)bits) - 1.0;
-            double res = v01 * p.scale[k];
-            res = res + p.lo[k];
-            redraw = redraw || !(res < p.hi[k]);
-            q[k] = goal ? goal_c[k] : res;
-        }
-    }
-    if (__ballot(act && redraw && !goal) != 0) return false;
-    const uint32_t cnt = always_goal ? 0u : (goal ? 1u : per);
-    if (act) {
-#pragma unroll
-        for (int k = 0; k < D; ++k) if (k < dim) sh.q[k][lane] = q[k];
-        sh.pos_after[lane] = pos0 + off + cnt;
-    }
-    rng.pos = pos0 + (uint32_t)__builtin_amdgcn_readlane((int)(off + cnt), (int)(m - 1));
-    return true;
-}
+// the samples of the next m <= 64 iterations (rrt_connect.rs:258-262; lane_sampler.hpp), iteration b of the block in slot b
 template <int D>
 __device__ __forceinline__ void conn_sample_block(RngWindow& rng, const DevParams& p, int dim, const double* goal_c, uint32_t m, uint32_t lane,
                                                   ConnShared<D>& sh) {
-    const uint64_t need_hi = rng.pos + (uint64_t)m * (1u + (uint32_t)dim);
-    if ((rng.pos >> 3) - rng.base_blk >= 64 || need_hi > (rng.base_blk + 64) * 8) {
-        rng.base_blk = uni64(rng.pos >> 3);
-        uint32_t o[16];
-        chacha12_block(rng.seed, rng.base_blk + lane, rng.stream, o);
+    sample_block64<D, false>(rng, p, dim, goal_c, 0.0, m, lane, 0u, [&](uint32_t b, const double (&q)[D], uint64_t pos_after) {
 #pragma unroll
-        for (int w = 0; w < 16; ++w) rng.buf[w][lane] = o[w];
-    }
-    if (!conn_sample64<D>(rng, p, dim, goal_c, m, lane, sh)) {
-        for (uint32_t b = 0; b < m; ++b) {   // (never expected) a redraw: one by one
-            double qn[D];
-            sample_state<D, false>(rng, p, dim, goal_c, qn);
-            if (lane == 0) {
-#pragma unroll
-                for (int k = 0; k < D; ++k) if (k < dim) sh.q[k][b] = qn[k];
-                sh.pos_after[b] = rng.pos;
-            }
-        }
-    }
+        for (int k = 0; k < D; ++k) if (k < dim) sh.q[k][b] = q[k];
+        sh.pos_after[b] = pos_after;
+    });
 }
 
 // nearest node of rrt_connect.rs:128-136: d2 compare with second-smallest tracking, exact post-sqrt fallback on a near-tie.  A lane
@@ -207,7 +137,7 @@ __device__ __forceinline__ void conn_nearest(const ConnTree<D>& tree, int dim, u
     }
     const int L = __builtin_ctzll(__ballot(mine_x == nearest) | (1ull << 63));   // the lane that holds the winner (a node belongs to one lane)
 #pragma unroll
-    for (int k = 0; k < D; ++k) if (k < dim) q_near[k] = conn_readlane_f64(bc[k], L);
+    for (int k = 0; k < D; ++k) if (k < dim) q_near[k] = readlane_f64(bc[k], L);
 }
 
 // The obstacle table as the motion check reads it: staged in LDS (OBS_LDS: a typed LDS pointer -- a DevParams field that was
@@ -298,14 +228,14 @@ __device__ __forceinline__ bool conn_motion_invalid(const ConnObs& ob, const Dev
 #pragma unroll
                 for (int s = 0; s < 8; ++s) {
                     double st[D];
-                    lerp<D>(from, to, conn_readlane_f64(tl, s), st, dim);
+                    lerp<D>(from, to, readlane_f64(tl, s), st, dim);
                     bad |= ((uint32_t)s < S && !(dist2<D>(a, st, dim) > thr)) ? 1u : 0u;
                 }
             } else if (S <= 8u) {
 #pragma unroll
                 for (int s = 0; s < 8; ++s) {
                     double st[D];
-                    lerp<D>(from, to, conn_readlane_f64(tl, s), st, dim);
+                    lerp<D>(from, to, readlane_f64(tl, s), st, dim);
                     const uint32_t hit_s = !(dist2<D>(a, st, dim) > thr) ? 1u : 0u;
                     uint32_t inside = 1u;
 #pragma unroll
@@ -315,13 +245,13 @@ __device__ __forceinline__ bool conn_motion_invalid(const ConnObs& ob, const Dev
             } else if (!boxes) {
                 for (uint32_t s = 0; s < S; ++s) {
                     double st[D];
-                    lerp<D>(from, to, conn_readlane_f64(tl, (int)s), st, dim);
+                    lerp<D>(from, to, readlane_f64(tl, (int)s), st, dim);
                     bad |= !(dist2<D>(a, st, dim) > thr) ? 1u : 0u;
                 }
             } else {
                 for (uint32_t s = 0; s < S; ++s) {
                     double st[D];
-                    lerp<D>(from, to, conn_readlane_f64(tl, (int)s), st, dim);
+                    lerp<D>(from, to, readlane_f64(tl, (int)s), st, dim);
                     const uint32_t hit_s = !(dist2<D>(a, st, dim) > thr) ? 1u : 0u;
                     uint32_t inside = 1u;
 #pragma unroll

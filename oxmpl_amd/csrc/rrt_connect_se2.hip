@@ -16,6 +16,7 @@
 // in a grid instead of sweeping the soup (seg_grid_kernel below).
 #include "oxhip_internal.hpp"
 #include "rrt_device.hpp"
+#include "lane_sampler.hpp"
 
 namespace oxhip {
 
@@ -209,76 +210,15 @@ static_assert(sizeof(Se2Shared<kSe2N, kSe2LdsSegs>) <= 40960, "four problems per
 static_assert(sizeof(Se2Shared<kSe2NSmall, 1>) <= 23405, "seven problems per CU");
 static_assert(kSe2N % 32 == 0 && kSe2NSmall % 32 == 0, "se2_round reads the shadow four slots of eight lanes at a time");
 
-// Lane-parallel sampling of m <= 64 consecutive iterations (rrt_connect.rs:258-262 + the SE(2) sample_uniform; the scheme of
-// rrt_cells.hip's cells_sample): lane j draws iteration j.  Where its words start depends on how many of the iterations before
-// it sampled the goal (one word instead of four), so the goal mask is iterated to its fixed point: in round r the first r lanes
-// are right.  Returns false, nothing written, when a range draw was rejected or the window is too short.
-template <class SH>
-__device__ __forceinline__ bool se2_sample64(RngWindow& rng, const DevParams& p, const double* goal_c, uint32_t m, uint32_t lane, SH& sh) {
-    const uint64_t win_lo = rng.base_blk * 8;
-    const uint64_t pos0 = rng.pos;
-    if (pos0 < win_lo || pos0 + (uint64_t)m * 4u > win_lo + 512) return false;
-    const uint32_t rel0 = (uint32_t)(pos0 - win_lo);
-    const bool act = lane < m;
-    const bool always_goal = p.p_int == ~0ull;   // Bernoulli ALWAYS_TRUE: no draw at all
-    auto word = [&](uint32_t rel) -> uint64_t {
-        const uint32_t a = rel0 + rel, bl = a >> 3, w = (a & 7u) * 2u;
-        return ((uint64_t)rng.buf[w + 1][bl] << 32) | rng.buf[w][bl];
-    };
-    uint64_t goal_mask = always_goal ? ~0ull : 0ull;
-    uint32_t off = 0u;
-    if (!always_goal) {
-        const uint64_t below = (1ull << lane) - 1ull;
-        for (uint32_t round = 0; round <= m; ++round) {
-            off = act ? 4u * lane - 3u * (uint32_t)__popcll(goal_mask & below) : 0u;
-            const uint64_t now = __ballot(act && word(off) < p.p_int);
-            if (now == goal_mask) break;
-            goal_mask = now;
-        }
-    }
-    const bool goal = (goal_mask >> lane) & 1ull;
-    double q[3];
-    bool redraw = false;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const uint64_t bits = (word(act && !goal ? off + 1u + (uint32_t)k : 0u) >> 12) | 0x3FF0000000000000ull;
-        const double v01 = __longlong_as_double((long long)bits) - 1.0;
-        double res = v01 * p.scale[k];
-        res = res + p.lo[k];
-        redraw = redraw || !(res < p.hi[k]);
-        q[k] = goal ? goal_c[k] : res;
-    }
-    if (__ballot(act && redraw && !goal) != 0) return false;
-    const uint32_t cnt = always_goal ? 0u : (goal ? 1u : 4u);
-    if (act) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) sh.q[k][lane] = q[k];
-        sh.pos_after[lane] = pos0 + off + cnt;
-    }
-    rng.pos = pos0 + (uint32_t)__builtin_amdgcn_readlane((int)(off + cnt), (int)(m - 1));
-    return true;
-}
+// the samples of the next m <= 64 iterations (rrt_connect.rs:258-262 + the SE(2) sample_uniform: random_bool, then x, y, theta by
+// random_range -- the stream of an R^3 problem; lane_sampler.hpp), iteration b of the block in slot b
 template <class SH>
 __device__ __forceinline__ void se2_sample_block(RngWindow& rng, const DevParams& p, const double* goal_c, uint32_t m, uint32_t lane, SH& sh) {
-    const uint64_t need_hi = rng.pos + (uint64_t)m * 4u;
-    if ((rng.pos >> 3) - rng.base_blk >= 64 || need_hi > (rng.base_blk + 64) * 8) {
-        rng.base_blk = uni64(rng.pos >> 3);
-        uint32_t o[16];
-        chacha12_block(rng.seed, rng.base_blk + lane, rng.stream, o);
+    sample_block64<3, false>(rng, p, 3, goal_c, 0.0, m, lane, 0u, [&](uint32_t b, const double (&q)[3], uint64_t pos_after) {
 #pragma unroll
-        for (int w = 0; w < 16; ++w) rng.buf[w][lane] = o[w];
-    }
-    if (!se2_sample64(rng, p, goal_c, m, lane, sh)) {
-        for (uint32_t b = 0; b < m; ++b) {   // (never expected) a redraw: one by one
-            double qn[3];
-            sample_state<3, false>(rng, p, 3, goal_c, qn);
-            if (lane == 0) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) sh.q[k][b] = qn[k];
-                sh.pos_after[b] = rng.pos;
-            }
-        }
-    }
+        for (int k = 0; k < 3; ++k) sh.q[k][b] = q[k];
+        sh.pos_after[b] = pos_after;
+    });
 }
 
 // One tree: the binary64 SoA arrays in HBM (every store lands there; the scan reads only its candidates back) and the binary32
@@ -296,10 +236,6 @@ struct Se2Range {
     float mag;        // largest |x|, |y| of any node of either tree
     bool theta_ok;    // every heading lies in [-PI, PI] (then the heading distance is min(|d|, 2 PI - |d|))
 };
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
 constexpr float kSe2PiUp = 3.14159274f;   // fl32(PI), which is > PI
 // The screen's magnitude guard (the R^n kernels' ScreenMargins::usable): beyond binary32's range fl32(x) is +-inf, and the
 // difference of two same-signed infinities is NaN -- an estimate no threshold test can place.  Nor can +inf: a node whose square

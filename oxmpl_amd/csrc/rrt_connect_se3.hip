@@ -254,7 +254,7 @@ __device__ __forceinline__ int se3_extend_try(const DevParams& p, SH& sh, uint32
         if (d < e.dist) { e.dist = d; e.idx = i; }
     }
     e = exact_wave_reduce(e);
-    d0 = so3_readlane(d0, 0);
+    d0 = readlane_f64(d0, 0);
     nearest = e.idx;
     double min_dist = e.dist;
     if (d0 != d0 || nearest == 0xFFFFFFFFu) { nearest = 0; min_dist = d0; }

@@ -169,6 +169,12 @@ __device__ __forceinline__ uint64_t uni64(uint64_t v) {
     return ((uint64_t)hi << 32) | lo;
 }
 __device__ __forceinline__ double unid(double v) { return __longlong_as_double((long long)uni64((uint64_t)__double_as_longlong(v))); }
+// lane l's copy of v (l wave-uniform); the result is wave-uniform
+__device__ __forceinline__ double readlane_f64(double v, int l) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ uint64_t below_mask(uint32_t lane) { return (1ull << lane) - 1ull; }   // the lanes below `lane`
 
 // ------------------------------------------------------------------ ChaCha12 (rand_chacha)
 __device__ __forceinline__ uint32_t rotl32(uint32_t v, int c) { return (v << c) | (v >> (32 - c)); }

@@ -41,6 +41,7 @@
 #include "rrt_resident_common.hpp"
 #include "lanes_reduce.hpp"
 #include "lane_query_common.hpp"
+#include "lane_sampler.hpp"
 
 namespace oxhip {
 
@@ -156,68 +157,6 @@ struct LanesShared {
     uint32_t heartbeat;                  // bumped by the resolver while it works: waiters only give up when it stands still
     uint32_t mabs_bits;                  // bits of the largest |fl32(coordinate - c0)| the scanners loaded
 };
-
-// Lane-parallel sampling of m <= 64 consecutive queries into the coordinate-major ring: sample_batch of
-// rrt_resident_common.hpp (rrt.rs:177-184 + rvss.rs:233-249) with this kernel's ring layout and the fl32 copies.
-template <int DIM>
-__device__ __forceinline__ bool sample_lanes(RngWindow& rng, const DevParams& p, const double* goal_c, double goal_radius, const double* c0, uint32_t m,
-                                             uint32_t lane, LanesShared<DIM>& sh, uint32_t js) {
-    const uint64_t win_lo = rng.base_blk * 8;
-    const uint64_t pos0 = rng.pos;
-    if (pos0 < win_lo || pos0 + (uint64_t)m * (1 + DIM) > win_lo + 512) return false;
-    const uint32_t rel0 = (uint32_t)(pos0 - win_lo);
-    const bool act = lane < m;
-    const bool always_goal = p.p_int == ~0ull;
-    const bool disc = DIM == 2 && p.goal_sampler == OXHIP_GOAL_SAMPLE_UNIFORM_DISC;
-    const uint32_t gw = disc ? 2u : 0u;   // words a goal sample draws after its Bernoulli word
-    auto word = [&](uint32_t rel) -> uint64_t {
-        const uint32_t a = rel0 + rel, bl = a >> 3, w = (a & 7u) * 2u;
-        return ((uint64_t)rng.buf[w + 1][bl] << 32) | rng.buf[w][bl];
-    };
-    uint64_t goal_mask = always_goal ? ~0ull : 0ull;
-    uint32_t off = act ? gw * lane : 0u;   // (every query is a goal sample: gw words each)
-    if (!always_goal) {
-        const uint64_t below = below_mask(lane);
-        for (uint32_t round = 0; round <= m; ++round) {
-            off = act ? (1u + DIM) * lane - ((uint32_t)DIM - gw) * (uint32_t)__popcll(goal_mask & below) : 0u;
-            const uint64_t now = __ballot(act && word(off) < p.p_int);
-            if (now == goal_mask) break;
-            goal_mask = now;
-        }
-    }
-    const bool goal = (goal_mask >> lane) & 1ull;
-    double q[DIM];
-    bool redraw = false;
-#pragma unroll
-    for (int k = 0; k < DIM; ++k) {
-        const uint64_t bits = (word(act && !goal ? off + 1u + (uint32_t)k : 0u) >> 12) | 0x3FF0000000000000ull;
-        const double v01 = __longlong_as_double((long long)bits) - 1.0;
-        double res = v01 * p.scale[k];
-        res = res + p.lo[k];
-        redraw = redraw || !(res < p.hi[k]);
-        q[k] = goal ? goal_c[k] : res;
-    }
-    redraw = redraw && !goal;
-    if (DIM == 2 && disc) {   // the disc sampler's two words follow the Bernoulli word (if one was drawn)
-        const uint32_t base = act && goal ? off + (always_goal ? 0u : 1u) : 0u;
-        double gx, gy;
-        const bool okd = goal_disc_sample(word(base), word(base + 1u), goal_c, goal_radius, gx, gy);
-        if (goal) { q[0] = gx; q[DIM >= 2 ? 1 : 0] = gy; redraw = !okd; }
-    }
-    if (__ballot(act && redraw) != 0) return false;
-    const uint32_t cnt = always_goal ? gw : (goal ? 1u + gw : 1u + (uint32_t)DIM);
-    if (act) {
-        const uint32_t slot = (js + lane) & (kQRing - 1);
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) {
-            sh.q[k][slot] = q[k];
-            sh.qf[k][slot] = -2.0f * (float)(q[k] - c0[k]);
-        }
-        sh.pos_after[slot] = pos0 + off + cnt;
-    }
-    rng.pos = pos0 + (uint32_t)__builtin_amdgcn_readlane((int)(off + cnt), (int)(m - 1));
-    return true;
-}
 
 template <int DIM, int S, int ROW>
 __device__ __forceinline__ void absorb_one(lf32x2 (&tr)[DIM][S / 2], lf32x2 (&tcc)[S / 2], bool mine, const float (&f)[DIM], float fcc) {
@@ -525,28 +464,23 @@ __global__ __launch_bounds__(kLanesThreads) void rrt_lanes_kernel(DevParams p) {
             if (m > 64u) m = 64u;
             if (m > (uint32_t)kPassQ) m -= (js + m) & (uint32_t)(kPassQ - 1);     // the scanners consume whole passes: end the batch on a pass boundary
             if (m > budget - js) m = budget - js;
-            // keep the batch's words inside the LDS window: refill (64 blocks from the current position) when short
-            const uint64_t need_hi = rng.pos + (uint64_t)m * (1 + D) + 64;
-            if ((rng.pos >> 3) - rng.base_blk >= 64 || need_hi > (rng.base_blk + 64) * 8) {
-                rng.base_blk = uni64(rng.pos >> 3);
-                uint32_t o[16];
-                chacha12_block(rng.seed, rng.base_blk + lane, rng.stream, o);
+            // the draws (lane_sampler.hpp) into the coordinate-major ring, with the scanners' fl32 copies
+            // (sample_block64's three steps spelled out: through that wrapper the R^5 and R^6 kernels spill two or three registers more)
+            auto store = [&](uint32_t b, const double (&qn)[D], uint64_t pos_after) {
+                const uint32_t slot = (js + b) & (kQRing - 1);
 #pragma unroll
-                for (int w = 0; w < 16; ++w) rng.buf[w][lane] = o[w];
-            }
-            if (!sample_lanes<DIM>(rng, p, goal_c, goal_radius, c0, m, lane, sh, js)) {
-                for (uint32_t b = 0; b < m; ++b) {  // (never expected) a redraw ran past the window: one by one
+                for (int k = 0; k < D; ++k) {
+                    sh.q[k][slot] = qn[k];
+                    sh.qf[k][slot] = -2.0f * (float)(qn[k] - c0[k]);
+                }
+                sh.pos_after[slot] = pos_after;
+            };
+            rng_window_hold(rng, (uint64_t)m * (1 + D) + 64, lane);
+            if (!sample_lanes64<D, true>(rng, p, DIM, goal_c, goal_radius, m, lane, store)) {
+                for (uint32_t b = 0; b < m; ++b) {
                     double qn[D];
                     sample_state<D, false>(rng, p, DIM, goal_c, qn, goal_radius);
-                    const uint32_t slot = (js + b) & (kQRing - 1);
-                    if (lane == 0) {
-#pragma unroll
-                        for (int k = 0; k < D; ++k) {
-                            sh.q[k][slot] = qn[k];
-                            sh.qf[k][slot] = -2.0f * (float)(qn[k] - c0[k]);
-                        }
-                        sh.pos_after[slot] = rng.pos;
-                    }
+                    if (lane == 0) store(b, qn, rng.pos);
                 }
             }
             js += m;

@@ -12,6 +12,7 @@
 #include "oxhip_internal.hpp"
 #include "rrt_device.hpp"
 #include "rrt_resident_common.hpp"
+#include "lane_sampler.hpp"
 
 namespace oxhip {
 // Coordinates of node i for the resolver.  The scanners publish only (d2, index): copying the winning slot out of a
@@ -304,27 +305,12 @@ __global__ __launch_bounds__(kPipeThreads) void rrt_resident_kernel(DevParams p)
         if (js < budget && js - jr <= (uint32_t)(kRing / 2)) {
             uint32_t m = jr + kRing - js;  // free ring slots
             if (m > budget - js) m = budget - js;
-            // keep the batch's words inside the LDS window: refill (64 blocks from the current position) when short
-            const uint64_t need_hi = rng.pos + (uint64_t)m * (1 + D) + 64;
-            if ((rng.pos >> 3) - rng.base_blk >= 64 || need_hi > (rng.base_blk + 64) * 8) {
-                rng.base_blk = uni64(rng.pos >> 3);
-                uint32_t o[16];
-                chacha12_block(rng.seed, rng.base_blk + lane, rng.stream, o);
+            sample_block64<D, false>(rng, p, DIM, goal_c, 0.0, m, lane, 64u, [&](uint32_t b, const double (&qn)[D], uint64_t pos_after) {   // lane_sampler.hpp
+                QSlot<DIM>& qs = sh.qring[(js + b) & (kRing - 1)];
 #pragma unroll
-                for (int w = 0; w < 16; ++w) rng.buf[w][lane] = o[w];
-            }
-            if (!sample_batch<DIM>(rng, p, goal_c, m, lane, sh.qring, js)) {
-                for (uint32_t b = 0; b < m; ++b) {  // (never expected) a redraw ran past the window: one by one
-                    double qn[D];
-                    sample_state<D, false>(rng, p, DIM, goal_c, qn);
-                    QSlot<DIM>& qs = sh.qring[(js + b) & (kRing - 1)];
-                    if (lane == 0) {
-#pragma unroll
-                        for (int k = 0; k < D; ++k) qs.q[k] = qn[k];
-                        qs.pos_after = rng.pos;
-                    }
-                }
-            }
+                for (int k = 0; k < D; ++k) qs.q[k] = qn[k];
+                qs.pos_after = pos_after;
+            });
             js += m;
             if (lane == 0) lds_post(&sh.sampled, js);
         }

@@ -1,19 +1,11 @@
 // rrt_resident_common.hpp -- pieces shared by the register-resident kernels (rrt_resident.hip,
 // rrt_pruned.hip): DPP reductions, the scan state, the scanner/resolver LDS ring, the tree layout,
-// steer / motion check / conservative filter, the lane-parallel sampler.
+// steer / motion check / conservative filter.
 #pragma once
 
 #include "rrt_device.hpp"
 
 namespace oxhip {
-
-
-// ---- wave64 min of an f64 with DPP (VALU only, no LDS crossbar); result is wave-uniform
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), l);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
 
 __device__ __forceinline__ double bound3(double g) {
     return __longlong_as_double((long long)((uint64_t)__double_as_longlong(g) + 3));
@@ -280,62 +272,6 @@ __device__ __forceinline__ uint32_t row_min_u32(uint32_t v) {
     v = dpp_umin_step<0x141, 0xf>(v);
     v = dpp_umin_step<0x140, 0xf>(v);
     return v;
-}
-
-// Lane-parallel sampling of m <= 64 consecutive queries (rrt.rs:177-184 + rvss.rs:233-249): lane l
-// produces query js + l.  A query starts where the earlier ones stopped drawing: a goal sample
-// takes 1 word, a uniform sample 1 + DIM.  So the word offset of lane l is
-// (1+DIM)*l - DIM*popcount(goal lanes below l): the lanes iterate "read my Bernoulli word at the
-// offset implied by the current goal mask -> ballot the new goal mask" to its fix-point (one extra
-// round per goal sample in the batch).  A rejected range draw (res >= hi, probability ~2^-53) or a
-// read past the LDS word window makes the function return false with nothing written; the caller
-// then samples that batch sequentially.
-template <int DIM, int RING = kRing, class QS = QSlot<DIM>>
-__device__ __forceinline__ bool sample_batch(RngWindow& rng, const DevParams& p, const double* goal_c, uint32_t m,
-                                             uint32_t lane, QS* qring, uint32_t js) {
-    const uint64_t win_lo = rng.base_blk * 8;
-    const uint64_t pos0 = rng.pos;
-    if (pos0 < win_lo || pos0 + (uint64_t)m * (1 + DIM) > win_lo + 512) return false;
-    const uint32_t rel0 = (uint32_t)(pos0 - win_lo);  // first word of the batch inside the window
-    const bool act = lane < m;
-    const bool always_goal = p.p_int == ~0ull;
-    auto word = [&](uint32_t rel) -> uint64_t {       // rel < 512 by the check above
-        const uint32_t a = rel0 + rel, bl = a >> 3, w = (a & 7u) * 2u;
-        return ((uint64_t)rng.buf[w + 1][bl] << 32) | rng.buf[w][bl];
-    };
-    uint64_t goal_mask = always_goal ? ~0ull : 0ull;
-    uint32_t off = 0;
-    if (!always_goal) {
-        const uint64_t below = (1ull << lane) - 1ull;
-        for (uint32_t round = 0; round <= m; ++round) {
-            off = act ? (1u + DIM) * lane - (uint32_t)DIM * (uint32_t)__popcll(goal_mask & below) : 0u;
-            const uint64_t now = __ballot(act && word(off) < p.p_int);
-            if (now == goal_mask) break;
-            goal_mask = now;
-        }
-    }
-    const bool goal = (goal_mask >> lane) & 1ull;
-    double q[DIM];
-    bool redraw = false;
-#pragma unroll
-    for (int k = 0; k < DIM; ++k) {
-        const uint64_t bits = (word(act && !goal ? off + 1u + (uint32_t)k : 0u) >> 12) | 0x3FF0000000000000ull;
-        const double v01 = __longlong_as_double((long long)bits) - 1.0;
-        double res = v01 * p.scale[k];
-        res = res + p.lo[k];
-        redraw = redraw || !(res < p.hi[k]);
-        q[k] = goal ? goal_c[k] : res;
-    }
-    if (__ballot(act && !goal && redraw) != 0) return false;
-    const uint32_t cnt = always_goal ? 0u : (goal ? 1u : 1u + (uint32_t)DIM);
-    if (act) {
-        QS& qs = qring[(js + lane) & (RING - 1)];
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) qs.q[k] = q[k];
-        qs.pos_after = pos0 + off + cnt;
-    }
-    rng.pos = pos0 + (uint32_t)__builtin_amdgcn_readlane((int)(off + cnt), (int)(m - 1));
-    return true;
 }
 
 // scan groups: kGroup slots per uniform branch, never straddling the common / heavy-only boundary

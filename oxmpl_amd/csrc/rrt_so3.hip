@@ -133,7 +133,7 @@ __global__ __launch_bounds__(64) void rrt_so3_kernel(DevParams p) {
             if (d < e.dist) { e.dist = d; e.idx = i; }
         }
         e = exact_wave_reduce(e);
-        d0 = so3_readlane(d0, 0);
+        d0 = readlane_f64(d0, 0);
         uint32_t nearest = e.idx;
         double min_dist = e.dist;
         if (d0 != d0 || nearest == 0xFFFFFFFFu) { nearest = 0; min_dist = d0; }

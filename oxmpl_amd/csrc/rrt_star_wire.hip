@@ -431,7 +431,7 @@ __global__ __launch_bounds__(64) void star_wire_kernel(DevParams p) {
             const uint32_t i = i0 + u;
             const uint4 cur = nxt;   // entries [0, 64) of node i
             const uint32_t nearest = (uint32_t)__builtin_amdgcn_readlane((int)m_near, (int)u);
-            const double dn = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(m_dn), (int)u), __builtin_amdgcn_readlane(__double2loint(m_dn), (int)u));
+            const double dn = readlane_f64(m_dn, (int)u);
             const StarEntry* list_i = list;
             const uint32_t cnt_i = cnt;
             if (u + 1 < nb) {   // the next node's first entries: requested now, used in the next trip
@@ -458,7 +458,7 @@ __global__ __launch_bounds__(64) void star_wire_kernel(DevParams p) {
                     m = __ballot(cand && c == cm);
                 }
                 const int l = __ffsll((unsigned long long)m) - 1;
-                best_c = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(c), l), __builtin_amdgcn_readlane(__double2loint(c), l));
+                best_c = readlane_f64(c, l);
                 best_j = (uint32_t)__builtin_amdgcn_readlane((int)en.x, l);
             }
             // 7. push: parent and cost of the new node (:244-250)

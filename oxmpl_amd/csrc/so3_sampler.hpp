@@ -3,14 +3,10 @@
 // part of an SE(3) sample); arithmetic: so3_device.hpp.
 #pragma once
 #include "rrt_device.hpp"
+#include "lane_sampler.hpp"
 #include "so3_device.hpp"
 
 namespace oxhip {
-
-__device__ __forceinline__ double so3_readlane(double v, int l) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
 
 // sample_uniform by one lane after the other, word by word (random_range redraws included)
 __device__ __forceinline__ void so3_sample_serial(RngWindow& rng, const DevParams& p, double q[4]) {
@@ -36,13 +32,7 @@ __device__ __forceinline__ void so3_sample_uniform_wave(RngWindow& rng, const De
     if (p.dbg_flags & OXHIP_DEBUG_SO3_SERIAL_SAMPLER) { so3_sample_serial(rng, p, q); return; }
     for (;;) {
         const uint64_t pos = rng.pos;
-        if ((pos >> 3) - rng.base_blk >= 64 || pos + 256 > (rng.base_blk + 64) * 8) {   // the window must hold the round's 256 words
-            rng.base_blk = uni64(pos >> 3);
-            uint32_t o[16];
-            chacha12_block(rng.seed, rng.base_blk + lane, rng.stream, o);
-#pragma unroll
-            for (int w = 0; w < 16; ++w) rng.buf[w][lane] = o[w];
-        }
+        rng_window_hold(rng, 256, lane);   // the window must hold the round's 256 words
         const uint32_t rel0 = (uint32_t)(pos - rng.base_blk * 8) + 4u * lane;
         double v[4];
         bool redraw = false;
@@ -60,7 +50,7 @@ __device__ __forceinline__ void so3_sample_uniform_wave(RngWindow& rng, const De
         if (rm & upto) { so3_sample_serial(rng, p, q); return; }   // (rng.pos is still the round's start)
         if (am == 0) { rng.pos = uni64(pos + 256); continue; }
 #pragma unroll
-        for (int k = 0; k < 4; ++k) q[k] = so3_readlane(qa[k], (int)L);
+        for (int k = 0; k < 4; ++k) q[k] = readlane_f64(qa[k], (int)L);
         rng.pos = uni64(pos + 4ull * (L + 1u));
         return;
     }
