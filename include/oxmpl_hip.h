@@ -134,14 +134,16 @@ typedef enum oxhip_goal_sampler {
 
 /* oxhip_rrt_config.debug_flags (tests only; every switch leaves every result bit-identical).  rrt_cells.hip honours
  * OXHIP_DEBUG_ALL_WHOLE_TREE and OXHIP_DEBUG_ONE_LANE_ROUNDS; it has no pair pass, no end-state audit and no memo expiry
- * (its memo lasts while the tree has not grown), so it ignores PAIR_TO_WHOLE_TREE, AUDIT and SHORT_MEMO. */
+ * (its memo lasts while the tree has not grown), so it ignores PAIR_TO_WHOLE_TREE and AUDIT, and SHORT_MEMO in a growing
+ * launch; in a frozen launch, where no insert could ever expire the memo, SHORT_MEMO keeps no memo at all. */
 typedef enum oxhip_debug_flag {
     OXHIP_DEBUG_PAIR_TO_WHOLE_TREE = 1,   /* rrt_lanes.hip: two-lane near-ties take the whole-tree path like three-way ones */
     OXHIP_DEBUG_AUDIT = 2,                /* rrt_lanes.hip, stamped build: count accepted motions whose end state is invalid (stamps[50]) */
     OXHIP_DEBUG_ALL_WHOLE_TREE = 4,       /* rrt_lanes.hip, rrt_cells.hip: no screen verdict is trusted -- every query that is not answered from the memoized
                                              whole-tree answer takes the whole-tree path (with goal_bias > 0 the memo is then hit constantly) */
     OXHIP_DEBUG_ONE_LANE_ROUNDS = 8,      /* rrt_lanes.hip, rrt_cells.hip: a round commits one lane; the others are re-resolved against the grown tree */
-    OXHIP_DEBUG_SHORT_MEMO = 16,          /* rrt_lanes.hip: the memoized answer expires after 8 inserts instead of (ring - 64) */
+    OXHIP_DEBUG_SHORT_MEMO = 16,          /* rrt_lanes.hip: the memoized answer expires after 8 inserts instead of (ring - 64); rrt_cells.hip, frozen launches:
+                                             no answer is memoized (every repeat of an ambiguous query is settled afresh) */
     OXHIP_DEBUG_STAR_TWO_PASS = 32,       /* rrt_star_wire.hip: neighbour lists by a second search instead of the counting pass's chunks */
     OXHIP_DEBUG_STAR_ONE_SEGMENT = 64,    /* rrt_star_wire.hip: one edge-check segment, no overlap with the wiring stream */
     OXHIP_DEBUG_SE2_NO_SEGMENT_GRID = 128,/* rrt_connect_se2.hip / rrt_connect.hip: every interpolated state is tested against every segment / sphere (no grid lookup) */
@@ -350,7 +352,9 @@ int32_t oxhip_rrt_batch_last_timing(oxhip_rrt_batch* b, double* kernel_ms, uint3
  * committed-node ring passed a multiple of its size), [58] two-lane passes.  rrt_cells.hip (problem 0, summed over the
  * parts of a split launch, unless noted): [4] whole-tree events, [5] rounds, [6] lanes offered, [7] iterations (an unsplit
  * launch adds the running total, a part its own count), [8] shell searches, [9] trips, [10] regrids, [11] memo hits,
- * [12] conflict cuts, [15] literal-loop ties; batch-wide: [45] and [54] whole-tree events, [55] memo hits, [56] conflict
+ * [12] conflict cuts, [15] literal-loop ties; batch-wide: [14] ambiguous queries settled among the band nodes (counted in
+ * [54] too), [50] / [51] / [52] sum, bitwise complement of the minimum, and maximum of the lifetimes of all waves, in cycles,
+ * [53] lanes offered minus iterations run (0 in a frozen launch), [45] and [54] ambiguous-query events (band or whole tree), [55] memo hits, [56] conflict
  * cuts, [59] forced cuts (OXHIP_DEBUG_ONE_LANE_ROUNDS), [60] shell searches (past the first ring of cells), [61] regrids
  * inside a growing launch (not the prepare pass's builds). */
 #define OXHIP_STAMP_WORDS 64

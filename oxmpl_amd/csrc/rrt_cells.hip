@@ -430,6 +430,109 @@ __device__ __forceinline__ int cells_verdict(const Top2& t, double lb, double A)
     return 0;
 }
 
+// THE BAND RESOLVER (frozen launches): an ambiguous query -- the margin clause d1 + A < d2 - A failed -- settled among the
+// nodes the walk saw, by the whole wave.  s1 is the walk's smallest screen value, B = sqrt(s1) (1 + 2^-20) + 2A the bound the
+// walk pruned cells with.  Every filed node's screen distance is within A of its true distance, so a node with screen distance
+// > B is farther than sqrt(s1) + A >= the true distance of the screen's best node: it is neither the reference's nearest node
+// nor ties with it.  The nodes within B (the BAND) lie in the 3^D block's cells whose box comes within B of the query, and, if
+// B < lb (1 - 2^-20) (lb: the nearest open face of the block), in no cell outside it.  The reference's answer (rrt.rs:187-196:
+// sqrt, strict '<', ascending index) is therefore the lexicographic minimum of (sqrt(dist2), index) over the band, evaluated in
+// binary64 in the reference's order.  Lane = cell of the block (chains followed) with the walk's own binary32 arithmetic; the
+// band's node indices and screen values are listed in LDS (the tail list is free between walks); lane k then evaluates
+// candidate k.  Nodes flagged in skip[] are not filed in any cell, so they are not seen here, just as the whole-tree scan passes
+// them over.  Declines (false: the whole-tree path takes the query) when the block cannot rule out the cells beyond it, when
+// the band holds more than 64 nodes, or when the chosen node's binary64 distance disagrees with its screen value by more than A
+// (a corrupted record).  Every argument is wave-uniform.
+template <int DIM>
+__device__ __forceinline__ bool cells_band_resolve(const CellGrid& grid, const CellBlock* blk, const cdouble4* xyz, CellsWaveLds<DIM>* sh, uint32_t lane,
+                                                   const double (&q1)[DIM], float s1, double A, uint32_t& idx_out, double& g_out) {
+    if (!(s1 < __builtin_inff())) return false;
+    float tq[3] = {0.0f, 0.0f, 0.0f};
+    uint32_t cq[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) {   // (as the walk places the query)
+        tq[k] = (float)((q1[k] - grid.lo[k]) * grid.inv_h);
+        const float fl = floorf(tq[k]);
+        cq[k] = fl > 0.0f ? (fl < (float)grid.G[k] ? (uint32_t)fl : grid.G[k] - 1u) : 0u;
+    }
+    const double B = sqrt((double)s1) * (1.0 + 0x1p-20) + 2.0 * A;
+    if (!(B < block_lb<DIM>(grid, tq, cq, 1u) * (1.0 - 0x1p-20))) return false;
+    const float thr2 = f32_up(B * B * (1.0 + 0x1p-20));
+    // lane o < 3^D: the cell at (o % 3 - 1, o / 3 % 3 - 1, o / 9 - 1) from the query's, if the grid has it and its box is within B
+    constexpr uint32_t NC = DIM == 3 ? 27u : 9u;
+    const int d[3] = {(int)(lane % 3u) - 1, (int)((lane / 3u) % 3u) - 1, DIM == 3 ? (int)(lane / 9u) - 1 : 0};
+    uint32_t cc[3] = {0u, 0u, 0u};
+    bool on = lane < NC;
+    float gap2 = 0.0f;
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) {
+        const int c = (int)cq[k] + d[k];
+        on = on && c >= 0 && c < (int)grid.G[k];
+        cc[k] = (uint32_t)c;
+        const float gk = (d[k] < 0 ? fmaxf(tq[k] - (float)cq[k], 0.0f) : fmaxf((float)(cq[k] + 1u) - tq[k], 0.0f)) * (1.0f - 0x1p-20f);
+        gap2 = d[k] != 0 ? gap2 + gk * gk : gap2;
+    }
+    on = on && !(gap2 > thr2);
+    float off[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) off[k] = ((float)cc[k] + 0x1p-17f) - tq[k];
+    cuint4 v[4];
+    block_load(blk, on ? (cc[2] * grid.G[1] + cc[1]) * grid.G[0] + cc[0] : 0u, v);
+    const uint32_t cnt = on ? v[0][0] : 0u;
+    uint32_t base = 0, total = 0;
+    bool go = on;
+    while (true) {
+        const uint32_t left = (go && cnt > base) ? cnt - base : 0u;
+        const uint32_t nv = left < kBlkEntries ? left : kBlkEntries;
+#pragma unroll
+        for (int e = 0; e < (int)kBlkEntries; ++e) {
+            const uint32_t lo = v[(2 + 2 * e) / 4][(2 + 2 * e) % 4], hi = v[(3 + 2 * e) / 4][(3 + 2 * e) % 4];
+            const float ex = __builtin_fmaf((float)(lo & 0xFFFFu), 0x1p-16f, off[0]);
+            const float ey = __builtin_fmaf((float)(lo >> 16), 0x1p-16f, off[1]);
+            float sv = ex * ex;
+            sv = __builtin_fmaf(ey, ey, sv);
+            if (DIM >= 3) {
+                const float ez = __builtin_fmaf((float)(hi & 0xFFFFu), 0x1p-16f, off[2]);
+                sv = __builtin_fmaf(ez, ez, sv);
+            }
+            const bool in_band = (uint32_t)e < nv && !(sv > thr2);
+            const uint64_t bm = __ballot(in_band);
+            const uint32_t pos = total + (uint32_t)__popcll(bm & below_mask(lane));
+            if (in_band && pos < 64u) {
+                sh->tail_pair[pos] = hi >> 16;
+                sh->tail_s1[pos] = sv;
+            }
+            total += (uint32_t)__popcll(bm);
+        }
+        base += kBlkEntries;
+        const uint32_t next = v[0][1];
+        go = go && base < cnt && next != 0;
+        if (__ballot(go) == 0) break;
+        block_load(blk, go ? next : 0u, v);
+    }
+    if (total == 0 || total > 64u) return false;
+    const bool mine = lane < total;
+    const uint32_t ik = sh->tail_pair[mine ? lane : 0u];
+    const float sk = sh->tail_s1[mine ? lane : 0u];
+    const cdouble4 c4 = xyz[ik];
+    double c[DIM];
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) c[k] = c4[k];
+    const double g = dist2<DIM>(c, q1, DIM);
+    Exact e{__builtin_inf(), kNoNode};
+    if (mine) { e.dist = sqrt(g); e.idx = ik; }
+    e = exact_wave_reduce(e);
+    const uint64_t wm = __ballot(mine && ik == e.idx);
+    if (wm == 0) return false;   // (every distance a NaN: never expected)
+    const int wl = __ffsll((unsigned long long)wm) - 1;
+    const double gw = readlane_f64(g, wl);
+    const double sw = sqrt((double)lbits_f32((uint32_t)__builtin_amdgcn_readlane((int)lf32_bits(sk), wl)));
+    if (!(fabs(sqrt(gw) * grid.inv_h - sw) <= A + sw * 0x1p-19 + 1e-30)) return false;
+    idx_out = uni(e.idx);
+    g_out = unid(gw);
+    return true;
+}
+
 // First round of part `part` when a frozen launch of `rounds` rounds is cut into `split` parts.  A part that finds its own
 // start (split <= kSelfSkipMax) pays for the rounds in front of it -- about 1 / kSkipCostInv of a round's work each -- so the
 // later parts get fewer rounds: equal finishing times need begin_p ~ (1 - (1 - c)^p) / (1 - (1 - c)^split) of the rounds.
@@ -563,7 +666,7 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
     uint32_t mabs_bits = uni(meta.mabs_bits);
     uint32_t jr = 0, js = 0;
     int32_t stop = 1;  // OXHIP_STOP_ITERATIONS
-    uint64_t n_rounds = 0, n_lanes = 0, n_amb = 0, n_expand = 0, n_cut_conflict = 0, n_tie = 0, n_memo = 0, n_forced = 0, n_regrid = 0, n_steps = 0, n_tail = 0, n_tail_pairs = 0;
+    uint64_t n_rounds = 0, n_lanes = 0, n_amb = 0, n_expand = 0, n_cut_conflict = 0, n_tie = 0, n_memo = 0, n_forced = 0, n_regrid = 0, n_steps = 0, n_tail = 0, n_tail_pairs = 0, n_band = 0;
     uint64_t t_ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_pm = 0, t_c[4] = {0, 0, 0, 0}, t_cm = 0;
     uint64_t h_lanes[8] = {0, 0, 0, 0, 0, 0, 0, 0}, h_cells[8] = {0, 0, 0, 0, 0, 0, 0, 0}, h_trips[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const uint64_t t_begin = STAMP ? (uint64_t)clock64() : 0;
@@ -908,6 +1011,8 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
         }
         if (STAMP) n_memo += (uint64_t)__popcll(__ballot(from_memo));
         const bool amb = act && !clear;
+        // (a frozen round settles its ambiguous lanes after its commit: what the band resolver needs of the walk, by lane)
+        if (FROZEN && __ballot(amb) != 0) sh->tail_s2[lane] = (verdict == 2 && grid.level != 0) ? t2.s1 : __builtin_inff();
         const uint32_t hb = hi32(g) + 1;
         double qn[D], mid[D];
         steer<DIM>(p, false, g, q_near, q, qn);
@@ -1014,9 +1119,11 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
         uint32_t cut = m;
         int32_t stop_after = -1;
         const uint64_t ambm = __ballot(amb);
-        if (ambm != 0) cut = (uint32_t)(__ffsll((unsigned long long)ambm) - 1);
+        // (a frozen launch's queries are independent: an ambiguous lane does not cut the round -- it is left out of the commit's
+        //  sums and settled in place right after it)
+        if (!FROZEN && ambm != 0) cut = (uint32_t)(__ffsll((unsigned long long)ambm) - 1);
         const uint32_t amb_at = cut;   // lanes [0, amb_at) hold a proven nearest node of the tree as it was when the round began
-        uint64_t okm = __ballot(ok);
+        uint64_t okm = __ballot(ok && !(FROZEN && amb));
         uint64_t hitm = 0;
         if (ins) {
             // A node accepted earlier in the round that is (nearly) as close to a later query as that query's nearest node changes
@@ -1209,7 +1316,7 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
                 const uint64_t gd = iter_digest<D>(nearest, qn, DIM, ok);
                 const int src = mine ? (int)(cut - 1u - lane) : 0;
                 const uint64_t w = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(pw >> 32), src, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)pw, src, 64);
-                const uint64_t sum = wave_sum_u64(mine ? gd * w : 0ull);
+                const uint64_t sum = wave_sum_u64((mine && !(FROZEN && amb)) ? gd * w : 0ull);
                 const uint64_t pc = cut >= 64u ? pw64
                                                : uni64(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pw >> 32), (int)cut) << 32) |
                                                        (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pw, (int)cut));
@@ -1229,16 +1336,27 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
         if (STAMP) { const uint64_t nw = (uint64_t)clock64(); t_c[3] += nw - t_cm; t_cm = nw; }
         OXHIP_CPHASE(5);   // commit
         if (stop_after >= 0) { stop = stop_after; break; }
-        if (cut == m || ambm == 0 || (uint32_t)(__ffsll((unsigned long long)ambm) - 1) != cut) continue;
+        if (FROZEN ? (ambm & first_n_mask(cut)) == 0 : (cut == m || ambm == 0 || (uint32_t)(__ffsll((unsigned long long)ambm) - 1) != cut)) continue;
 
         // ---- the lane at `cut` is ambiguous: that one query over the WHOLE binary64 tree (the path of rrt_lanes.hip).  First
         //      by squared distances, the wave striding over the nodes: if exactly one node is within a rounding of the
         //      minimum, it is the reference's nearest node (sqrt is monotone).  Only a genuine near-tie -- two d2 that may
         //      share a correctly rounded root -- takes the reference's literal loop (post-sqrt compare, lowest index).
+        //      A FROZEN round has committed all its lanes but the ambiguous ones: each of those is settled here, in ascending
+        //      lane order -- among the band nodes when the resolver takes it, over the whole tree otherwise -- and its term
+        //      g_j P^(cut-1-j) joins the round's checksum sum, its verdict the accepted count (both are sums: the order of the
+        //      additions does not matter, and the next round multiplies only after this one is complete).
         if (!FROZEN && n >= p.max_nodes) { stop = 2; break; }
-        {
+        uint64_t todo = FROZEN ? (ambm & first_n_mask(cut)) : 1ull;
+        const uint32_t jr0 = FROZEN ? jr - cut : jr;   // the query of the round's lane 0 (a growing round: of the lane at the cut)
+        bool goal_stop = false;
+        // (tests, OXHIP_DEBUG_SHORT_MEMO: a frozen launch keeps no answer, so every repeat of a query is settled afresh)
+        const bool keep_memo = !(FROZEN && (p.dbg_flags & OXHIP_DEBUG_SHORT_MEMO) != 0);
+        do {
+            const uint32_t ja = FROZEN ? (uint32_t)(__ffsll((unsigned long long)todo) - 1) : 0u;
+            todo &= todo - 1;
             if (STAMP) ++n_amb;
-            const uint32_t slot1 = jr & 63u;
+            const uint32_t slot1 = (jr0 + ja) & 63u;
             double q1[D];
 #pragma unroll
             for (int k = 0; k < D; ++k) q1[k] = unid(sh->q[k][slot1]);
@@ -1247,8 +1365,18 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
             for (int k = 0; k < D; ++k) same_q = same_q && __double_as_longlong(q1[k]) == __double_as_longlong(memo_q[k]);
             double gmin = memo_g;
             uint32_t memo_hit_idx = memo_idx;
-            bool tie = false;
-            if (!same_q) {
+            bool tie = false, banded = false;
+            if (FROZEN && !same_q && (p.dbg_flags & OXHIP_DEBUG_ALL_WHOLE_TREE) == 0) {
+                const float s1j = lbits_f32(uni(lf32_bits(sh->tail_s2[ja])));
+                banded = cells_band_resolve<DIM>(grid, blk, xyz, sh, lane, q1, s1j, A, memo_hit_idx, gmin);
+                if (STAMP && banded) ++n_band;
+                if (banded && keep_memo) {   // (as exact as a whole-tree answer: it serves the later identical queries too)
+                    memo_n = n; memo_g = gmin; memo_idx = memo_hit_idx;
+#pragma unroll
+                    for (int k = 0; k < D; ++k) memo_q[k] = q1[k];
+                }
+            }
+            if (!same_q && !banded) {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // this wave's stores to the tree have landed (same CU)
                 Scan ps{__builtin_inf(), kNoNode, 0xFFFFFFFFu};  // .slot is used as the node index here
                 constexpr int WT = OXHIP_CELLS_WT_UNROLL;   // chunks of 256 nodes in flight (4 nodes per lane each)
@@ -1290,12 +1418,12 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
                 const uint64_t nearm = __ballot(ps.slot != kNoNode && hi32(ps.b1) <= hbw);
                 tie = __popcll(nearm) != 1 || __ballot(ps.h2 <= hbw) != 0;
                 memo_hit_idx = tie ? kNoNode : (uint32_t)__builtin_amdgcn_readlane((int)ps.slot, __ffsll((unsigned long long)(nearm | (1ull << 63))) - 1);
-                if (!tie) {
+                if (!tie && keep_memo) {
                     memo_n = n; memo_g = gmin; memo_idx = memo_hit_idx;
 #pragma unroll
                     for (int k = 0; k < D; ++k) memo_q[k] = q1[k];
                 }
-            } else if (STAMP) ++n_memo;
+            } else if (STAMP && same_q) ++n_memo;
             uint32_t nearest1;
             double qn1[D], q_near1[D];
             bool dup1;
@@ -1338,9 +1466,16 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
                 if (__ballot(sphere_maybe_hit<DIM>(oc, ofilt, mid1)) != 0 || extras)
                     ok1 = motion_lanes<DIM>(p, lane, q_near1, qn1, oc, othr, ofilt, ns64);
             }
-            st.checksum = uni64(chk_push(st.checksum, iter_digest<D>(nearest1, qn1, DIM, ok1)));
-            st.iterations++;
-            draws_done = uni64(sh->pos_after[slot1]);
+            if (FROZEN) {   // (the round's commit has counted the iteration and the draws)
+                const int ex = (int)(cut - 1u - ja);
+                const uint64_t pe = uni64(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pw >> 32), ex) << 32) |
+                                          (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pw, ex));
+                st.checksum = uni64(st.checksum + iter_digest<D>(nearest1, qn1, DIM, ok1) * pe);
+            } else {
+                st.checksum = uni64(chk_push(st.checksum, iter_digest<D>(nearest1, qn1, DIM, ok1)));
+                st.iterations++;
+                draws_done = uni64(sh->pos_after[slot1]);
+            }
             bool hit1 = false;
             if (ok1) {
                 st.accepted++;
@@ -1374,9 +1509,10 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
                     }
                 }
             }
-            jr += 1;
-            if (hit1 && p.stop_at_goal) { stop = 0; break; }
-        }
+            if (!FROZEN) jr += 1;
+            goal_stop = hit1 && p.stop_at_goal;
+        } while (FROZEN && todo != 0);
+        if (goal_stop) { stop = 0; break; }
     }
 #undef OXHIP_CPHASE
     if (!FROZEN) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");   // (a frozen launch has stored nothing)
@@ -1426,6 +1562,15 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
         atomicAdd((unsigned long long*)&p.dbg[60], (unsigned long long)n_expand);
         atomicAdd((unsigned long long*)&p.dbg[61], (unsigned long long)n_regrid);
         atomicAdd((unsigned long long*)&p.dbg[45], (unsigned long long)n_amb);
+        atomicAdd((unsigned long long*)&p.dbg[14], (unsigned long long)n_band);
+        {   // every wave of the launch: its lifetime (sum, minimum -- kept as the maximum of the complement, the words start at 0 --
+            // and maximum) and the lanes it offered beyond the iterations it ran
+            const uint64_t life = (uint64_t)clock64() - t_begin;
+            atomicAdd((unsigned long long*)&p.dbg[50], (unsigned long long)life);
+            atomicMax((unsigned long long*)&p.dbg[51], (unsigned long long)~life);
+            atomicMax((unsigned long long*)&p.dbg[52], (unsigned long long)life);
+            atomicAdd((unsigned long long*)&p.dbg[53], (unsigned long long)(n_lanes - (st.iterations - (split > 1 ? 0ull : st0.iterations))));
+        }
         if (prob == 0) {   // problem 0, summed over the parts of a split launch (and over the launches since enable_stamps)
             const uint64_t vals[8] = {n_amb, n_rounds, n_lanes, st.iterations, n_expand, n_steps, n_regrid, n_memo};
             const int idx[8] = {4, 5, 6, 7, 8, 9, 10, 11};

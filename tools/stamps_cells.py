@@ -23,7 +23,11 @@ def show(tag, g, iters):
         print("   %-32s %8d cycles per round" % (nm, int(s[32 + i]) // rounds))
     print("   whole-tree events %d (ties %d), memo hits %d, shell searches %d, chain steps %d (%.1f per round), regrids %d, conflict cuts %d"
           % (int(s[4]), int(s[15]), int(s[11]), int(s[8]), int(s[9]), int(s[9]) / rounds, int(s[10]), int(s[12])))
-    print("   batch-wide: whole-tree events %d, shell searches %d" % (int(s[54]), int(s[60])))
+    print("   batch-wide: whole-tree events %d (settled among the band nodes: %d), shell searches %d, lanes offered minus iterations run %d"
+          % (int(s[54]), int(s[14]), int(s[60]), int(s[53])))
+    waves = P * (split if "steady" in tag else 1)
+    print("   all %d waves of the launch (this build spills and is slower: the spread is indicative only): lifetime min %d, mean %d, max %d cycles"
+          % (waves, 2 ** 64 - 1 - int(s[51]), int(s[50]) // waves, int(s[52])))
     ci = (40, 41, 42, 43, 44, 46, 47, 48)
     print("   neighbour trips by number (trips: lanes asking / cells asked for, per trip): " +
           ", ".join("%d: %.1f / %.1f" % (int(s[24 + i]), int(s[16 + i]) / max(1, int(s[24 + i])), int(s[ci[i]]) / max(1, int(s[24 + i]))) for i in range(8)))
