@@ -121,6 +121,357 @@ static hipError_t grow(DevBuf<T>& buf, size_t count) {   // keeps a buffer that 
     return buf.alloc(count ? count : 1);
 }
 
+// ------------------------------------------------------------------ the spaces
+// One row per oxhip_space: what create(), the set_* calls, setup, solve and the path entry points need to know about a space,
+// as data.  A refusal text that is null means "accepted".  Adding a space = adding a row (and its launchers).
+struct SpaceRow {
+    uint32_t dim;               const char* bad_dim;       // the cfg.dim the space requires (0 = any), and the refusal
+    uint32_t planners;          const char* bad_planner;   // bit p: built for oxhip_planner p
+    const char* one_kernel;     // non-null: the space has one kernel, cfg.kernel must be OXHIP_KERNEL_AUTO / _STREAM (the refusal)
+    uint32_t sphere_width;      // doubles per centre in set_spheres (0 = cfg.dim)
+    const char *no_spheres, *no_boxes, *no_segments, *no_body;   // the set_* calls the space refuses
+    bool radii_uploaded;        // set_spheres uploads sph_r: obstacles are compared with the radius itself
+    bool goal_is_radius;        // goal_thr = the radius, compared with the space's distance (else sqrt_le_threshold(radius) against d2)
+    bool midpoint_filter;       // refresh_filter runs before a solve (the space's kernels read its thresholds / grids)
+    const char* no_simplify;    // simplify_paths / path_valid_matrix
+    int32_t (*solve)(oxhip_rrt_batch* b);   // one launch of dp.budget iterations on b->stream
+    void (*is_valid)(oxhip_rrt_batch* b, const double* states, uint32_t n, uint8_t* out);
+    void (*check_motion)(oxhip_rrt_batch* b, const double* from, const double* to, uint32_t n, uint8_t* out);
+};
+static int32_t solve_real_vector(oxhip_rrt_batch* b);   // R^n: the planner / kernel-kind dispatch, below
+static constexpr uint32_t kRrt = 1u << OXHIP_PLANNER_RRT, kConnect = 1u << OXHIP_PLANNER_RRT_CONNECT, kStar = 1u << OXHIP_PLANNER_RRT_STAR;
+static const char* const kNoSegments = "segments describe the SE(2) checker";
+static const char* const kNoBody = "a body describes the SE(3) checker";
+static const char* const kNoSimplifySe = "simplify_paths is not built for SE(2) / SE(3) batches (their motion checks live inside their planners' kernels)";
+static const SpaceRow kSpaces[OXHIP_SPACE_SE3 + 1] = {
+    /* OXHIP_SPACE_REAL_VECTOR */ {
+        0, nullptr, kRrt | kConnect | kStar, nullptr, nullptr,
+        0, nullptr, nullptr, kNoSegments, kNoBody,
+        false, false, true, nullptr,
+        solve_real_vector,
+        [](oxhip_rrt_batch* b, const double* s, uint32_t n, uint8_t* out) { launch_is_valid(b->dp, s, n, out, b->stream); },
+        [](oxhip_rrt_batch* b, const double* f, const double* t, uint32_t n, uint8_t* out) { launch_check_motion(b->dp, f, t, n, out, b->stream); }},
+    /* OXHIP_SPACE_SE2 */ {
+        3, "SE(2) states are (x, y, theta): dim must be 3", kConnect, "SE(2) is built for RRTConnect only", nullptr,
+        0, "SE(2) batches take oxhip_rrt_batch_set_segments", "SE(2) batches take oxhip_rrt_batch_set_segments", nullptr, kNoBody,
+        false, true, true, kNoSimplifySe,
+        [](oxhip_rrt_batch* b) -> int32_t { launch_rrt_connect_se2(b->dp, b->stream); return OXHIP_OK; },
+        [](oxhip_rrt_batch* b, const double* s, uint32_t n, uint8_t* out) { launch_se2_is_valid(b->dp, s, n, out, b->stream); },
+        [](oxhip_rrt_batch* b, const double* f, const double* t, uint32_t n, uint8_t* out) { launch_se2_check_motion(b->dp, f, t, n, out, b->stream); }},
+    /* OXHIP_SPACE_SO3 */ {   // cones: distance(centre, q) > radius in the SO(3) metric; rrt_so3.hip tests every cone
+        4, "SO(3) states are quaternions (x, y, z, w): dim must be 4", kRrt, "SO(3) is built for RRT only",
+        "SO(3) RRT runs on rrt_so3.hip: kernel must be OXHIP_KERNEL_AUTO or OXHIP_KERNEL_STREAM",
+        0, nullptr, "SO(3) batches take cones (oxhip_rrt_batch_set_spheres)", kNoSegments, kNoBody,
+        true, true, false, nullptr,
+        [](oxhip_rrt_batch* b) -> int32_t { launch_rrt_so3(b->dp, b->stream); return OXHIP_OK; },
+        [](oxhip_rrt_batch* b, const double* s, uint32_t n, uint8_t* out) { launch_so3_is_valid(b->dp, s, n, out, b->stream); },
+        [](oxhip_rrt_batch* b, const double* f, const double* t, uint32_t n, uint8_t* out) { launch_so3_check_motion(b->dp, f, t, n, out, b->stream); }},
+    /* OXHIP_SPACE_SE3 */ {   // world spheres with 3-wide centres, r_b + r_j against the distance; rrt_connect_se3.hip tests every sphere
+        7, "SE(3) states are (x, y, z, qx, qy, qz, qw): dim must be 7", kConnect, "SE(3) is built for RRTConnect only",
+        "SE(3) RRTConnect runs on rrt_connect_se3.hip: kernel must be OXHIP_KERNEL_AUTO or OXHIP_KERNEL_STREAM",
+        3, nullptr, "SE(3) batches take sphere obstacles (oxhip_rrt_batch_set_spheres)", kNoSegments, nullptr,
+        true, true, false, kNoSimplifySe,
+        [](oxhip_rrt_batch* b) -> int32_t { launch_rrt_connect_se3(b->dp, b->se3, b->stream); return OXHIP_OK; },
+        [](oxhip_rrt_batch* b, const double* s, uint32_t n, uint8_t* out) { launch_se3_is_valid(b->dp, b->se3, s, n, out, b->stream); },
+        [](oxhip_rrt_batch* b, const double* f, const double* t, uint32_t n, uint8_t* out) { launch_se3_check_motion(b->dp, b->se3, f, t, n, out, b->stream); }},
+};
+static const SpaceRow& space_of(const oxhip_rrt_batch* b) { return kSpaces[b->cfg.space]; }   // (create() refused other kinds)
+
+// ------------------------------------------------------------------ the entry points' shared openings
+// The batch exists, setup() ran and `problem` (if one is given) is in range: what most entry points check first.  Pure host code.
+static int32_t setup_done(const oxhip_rrt_batch* b, int64_t problem = -1) {
+    if (!b) return fail(OXHIP_ERR_BAD_ARG, "null batch");
+    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");  // rrt.rs:160-163
+    if (problem >= (int64_t)b->cfg.n_problems) return fail(OXHIP_ERR_BAD_ARG, "problem index out of range");
+    return OXHIP_OK;
+}
+// ... and the batch's device is current.  (An entry point that reports another check in between calls the two halves itself.)
+static int32_t ready(const oxhip_rrt_batch* b, int64_t problem = -1) {
+    OX_TRY(setup_done(b, problem));
+    return select_device(b->cfg.device);
+}
+
+// ------------------------------------------------------------------ create(), step by step
+struct Resolved {                 // what the space's constructor makes of a config
+    double fraction, res;         // the clamped lvs_fraction; res = longest valid segment length * 0.1
+    double lo[OXHIP_MAX_DIM], hi[OXHIP_MAX_DIM];   // per coordinate, theta clamped to [-PI, PI]; 0 for a rotation's coordinates
+    double so3_centre[4], so3_max_angle;           // SO(3) / SE(3): the rotation's bounds
+};
+
+// Every check create() makes before it chooses a device, in a fixed order (tests/golden/rrt_create_refusals.json pins order and
+// texts).  Calls no HIP function.
+static int32_t validate_config(const oxhip_rrt_config* cfg, Resolved& r) {
+    if (cfg->struct_size != sizeof(oxhip_rrt_config)) return fail(OXHIP_ERR_BAD_ARG, "struct_size mismatch");
+    if (cfg->dim == 0 || cfg->dim > OXHIP_MAX_DIM) return fail(OXHIP_ERR_BAD_ARG, "dim must be in 1..8");
+    if (cfg->n_problems == 0 || cfg->max_nodes == 0) return fail(OXHIP_ERR_BAD_ARG, "n_problems and max_nodes must be > 0");
+    if (cfg->max_nodes > (1u << 30)) return fail(OXHIP_ERR_BAD_ARG, "max_nodes too large");
+    if (!(cfg->goal_bias >= 0.0 && cfg->goal_bias <= 1.0))
+        return fail(OXHIP_ERR_BAD_ARG, "goal_bias outside [0,1] (rand Bernoulli::new would fail)");
+    if (!(cfg->max_distance > 0.0) || !std::isfinite(cfg->max_distance))
+        return fail(OXHIP_ERR_BAD_ARG, "max_distance must be finite and > 0");
+    if (cfg->kernel > OXHIP_KERNEL_CELLS) return fail(OXHIP_ERR_BAD_ARG, "unknown kernel kind");
+    if (cfg->kernel == OXHIP_KERNEL_RETIRED_3 || cfg->kernel == OXHIP_KERNEL_RETIRED_4)
+        return fail(OXHIP_ERR_BAD_ARG, "kernel kinds 3 (box-pruned scan) and 4 (lane-group resolver) were retired in ABI version 2");
+    if (cfg->planner > OXHIP_PLANNER_RRT_STAR) return fail(OXHIP_ERR_BAD_ARG, "unknown planner kind");
+    if (cfg->frozen_split > 64) return fail(OXHIP_ERR_BAD_ARG, "frozen_split must be 0 (automatic) or 1 .. 64");
+    if (cfg->kernel == OXHIP_KERNEL_CELLS && cfg->planner == OXHIP_PLANNER_RRT_CONNECT)
+        return fail(OXHIP_ERR_BAD_ARG, "the cell-grid kernel runs RRT, and the geometry of the decoupled RRT*");
+    if (cfg->planner == OXHIP_PLANNER_RRT_CONNECT && cfg->kernel >= OXHIP_KERNEL_RESIDENT)
+        return fail(OXHIP_ERR_BAD_ARG, "RRTConnect runs on the stream kernel only");
+    // RRT*: KERNEL_STREAM = rrt_star.hip (one workgroup per problem, everything in one kernel); KERNEL_LANES / KERNEL_CELLS = the
+    // decoupled design (geometry by rrt_lanes.hip / rrt_cells.hip, then the wiring kernels of rrt_star_wire.hip); KERNEL_AUTO = the
+    // decoupled design where it exists, its geometry by rrt_cells.hip in R^2 / R^3
+    if (cfg->planner == OXHIP_PLANNER_RRT_STAR && cfg->kernel != OXHIP_KERNEL_AUTO && cfg->kernel != OXHIP_KERNEL_STREAM &&
+        cfg->kernel != OXHIP_KERNEL_LANES && cfg->kernel != OXHIP_KERNEL_CELLS)
+        return fail(OXHIP_ERR_BAD_ARG, "RRT* runs on the stream kernel or on the lane-per-query / cell-grid kernel + wiring kernels");
+    if (cfg->planner == OXHIP_PLANNER_RRT_STAR && std::isnan(cfg->search_radius))
+        return fail(OXHIP_ERR_BAD_ARG, "search_radius is NaN");
+    if (cfg->goal_sampler > OXHIP_GOAL_SAMPLE_UNIFORM_DISC) return fail(OXHIP_ERR_BAD_ARG, "unknown goal sampler");
+    if (cfg->goal_sampler == OXHIP_GOAL_SAMPLE_UNIFORM_DISC && (cfg->dim != 2 || cfg->space != OXHIP_SPACE_REAL_VECTOR))
+        return fail(OXHIP_ERR_BAD_ARG, "the disc sampler (rrt_rvss_tests.rs:55-66) is defined for RealVectorStateSpace(2)");
+    if (cfg->goal_sampler == OXHIP_GOAL_SAMPLE_UNIFORM_DISC && (cfg->planner == OXHIP_PLANNER_RRT_CONNECT || cfg->kernel == OXHIP_KERNEL_RESIDENT))
+        return fail(OXHIP_ERR_BAD_ARG, "the disc sampler is built for RRT / RRT* on the stream, lane-per-query and cell-grid kernels");
+    if (cfg->space > OXHIP_SPACE_SE3) return fail(OXHIP_ERR_BAD_ARG, "unknown space kind");
+    const SpaceRow& row = kSpaces[cfg->space];
+    if (row.dim != 0 && cfg->dim != row.dim) return fail(OXHIP_ERR_BAD_ARG, row.bad_dim);
+    if (((row.planners >> cfg->planner) & 1u) == 0) return fail(OXHIP_ERR_BAD_ARG, row.bad_planner);
+    if (row.one_kernel && cfg->kernel != OXHIP_KERNEL_AUTO && cfg->kernel != OXHIP_KERNEL_STREAM) return fail(OXHIP_ERR_BAD_ARG, row.one_kernel);
+    // the bounds as the space's constructor reads them
+    r = Resolved{};
+    r.fraction = cfg->lvs_fraction;
+    uint32_t n_box = 0;             // leading (lo, hi) pairs that bound a coordinate as given
+    const double* rot = nullptr;    // (cx, cy, cz, cw, max_angle) of a rotation
+    if (cfg->space == OXHIP_SPACE_SE3) {
+        if (cfg->goal_sampler != OXHIP_GOAL_SAMPLE_CENTRE) return fail(OXHIP_ERR_BAD_ARG, "SE(3): the goal sampler must be OXHIP_GOAL_SAMPLE_CENTRE");
+        // (x, y, z) as RealVectorStateSpace::new(3, ..); rotation bounds as SO3StateSpace::new
+        OX_TRY(se_space_resolution(3, cfg->bounds, r.fraction, r.res));
+        OX_TRY(so3_rotation_bounds(cfg->bounds + 6, r.so3_max_angle));
+        n_box = 3; rot = cfg->bounds + 6;
+    } else if (cfg->space == OXHIP_SPACE_SO3) {
+        OX_TRY(so3_space_resolution(cfg->dim, cfg->bounds, r.fraction, r.res, r.so3_max_angle));   // centre, max_angle, fraction
+        rot = cfg->bounds;
+    } else if (cfg->space == OXHIP_SPACE_SE2) {
+        // SO2StateSpace::new (so2_state_space.rs:57-72): lo >= hi is InvalidBound; bounds clamped to [-PI, PI]
+        const double pi = 3.14159265358979323846;
+        const double th_lo = cfg->bounds[4], th_hi = cfg->bounds[5];
+        if (!(th_lo < th_hi)) return fail(OXHIP_ERR_ZERO_VOLUME, "theta: lower bound >= upper bound");
+        OX_TRY(se_space_resolution(2, cfg->bounds, r.fraction, r.res));
+        n_box = 2;
+        r.lo[2] = th_lo > -pi ? th_lo : -pi;
+        r.hi[2] = th_hi < pi ? th_hi : pi;
+    } else {
+        OX_TRY(space_resolution(cfg->dim, cfg->bounds, r.fraction, r.res));
+        n_box = cfg->dim;
+    }
+    if (cfg->space != OXHIP_SPACE_SO3 && cfg->max_distance / r.res > 1e6) return fail(OXHIP_ERR_BAD_ARG, "more than 1e6 validity checks per edge");
+    for (uint32_t k = 0; k < n_box; ++k) { r.lo[k] = cfg->bounds[2 * k]; r.hi[k] = cfg->bounds[2 * k + 1]; }
+    for (uint32_t k = 0; rot && k < 4; ++k) r.so3_centre[k] = rot[k];
+    return OXHIP_OK;
+}
+
+// The batch's copy of the config and the DevParams fields that follow from cfg and Resolved alone.
+static void fill_params(oxhip_rrt_batch* b, const oxhip_rrt_config* cfg, const Resolved& r) {
+    b->cfg = *cfg;
+    b->cfg.lvs_fraction = r.fraction;
+    const uint32_t cap = ((cfg->max_nodes + 1023u) / 1024u) * 1024u;
+    DevParams& dp = b->dp;
+    dp.dim = cfg->dim; dp.n_problems = cfg->n_problems; dp.cap = cap; dp.max_nodes = cfg->max_nodes;
+    for (uint32_t k = 0; k < cfg->dim; ++k) {
+        dp.lo[k] = r.lo[k];
+        dp.hi[k] = r.hi[k];
+        dp.scale[k] = dp.hi[k] - dp.lo[k];
+    }
+    for (uint32_t k = 0; k < 4; ++k) dp.so3_centre[k] = r.so3_centre[k];
+    dp.so3_max_angle = r.so3_max_angle;
+    dp.space = cfg->space;
+    dp.max_distance = cfg->max_distance;
+    dp.res = r.res;
+    if (cfg->planner == OXHIP_PLANNER_RRT_CONNECT) {   // rrt_connect.hip, rrt_connect_se2.hip: the step count of an Advanced extend's motion, when it is safely known
+        const double q = cfg->max_distance / r.res, c = std::ceil(q);
+        const double gap = std::fmin(q - (c - 1.0), c - q);
+        if (std::isfinite(q) && c >= 1.0 && c < 4294967295.0 && gap > 1e-6) {
+            dp.adv_steps = (uint32_t)c;
+            dp.adv_slack = 0.5 * gap * r.res;
+        }
+    }
+    dp.p_int = bernoulli_p_int(cfg->goal_bias);
+    dp.seed = cfg->seed;
+    dp.dbg_flags = cfg->debug_flags;   // oxhip_debug_flag bits: test-only, results identical (the library reads no environment variable)
+    dp.goal_sampler = cfg->goal_sampler;
+    dp.first_problem_id = cfg->first_problem_id;
+    dp.stop_at_goal = cfg->stop_at_goal ? 1 : 0;
+    dp.t_steer = sqrt_le_threshold(cfg->max_distance);
+    dp.thr_search = sqrt_lt_threshold(cfg->search_radius);
+}
+
+// RRT*'s buffers, for the decoupled design (b->star_wired) or the one-kernel design; KERNEL_AUTO falls back from the first to
+// the second when the first's memory is not to be had.  `e` collects the first failure, as in alloc_common.
+static int32_t alloc_star(oxhip_rrt_batch* b, hipError_t& e) {
+    const oxhip_rrt_config* cfg = &b->cfg;
+    DevParams& dp = b->dp;
+    const uint32_t P = cfg->n_problems, dim = cfg->dim, cap = dp.cap;
+    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    const bool geo_cells = cfg->kernel != OXHIP_KERNEL_LANES && cells_supported(dim, cap);
+    const bool geo_lanes = cfg->kernel != OXHIP_KERNEL_CELLS && lanes_supported(dim, cap);
+    const bool can_wire = star_wire_supported(dim) && (geo_cells || geo_lanes);
+    b->star_wired = cfg->kernel == OXHIP_KERNEL_LANES || cfg->kernel == OXHIP_KERNEL_CELLS || (cfg->kernel == OXHIP_KERNEL_AUTO && can_wire);
+    if (b->star_wired && !can_wire) return fail(OXHIP_ERR_BAD_ARG, "decoupled RRT*: neither geometry kernel supports this (dim, max_nodes)");
+    b->star_geo_cells = b->star_wired && geo_cells;
+    chk(b->cost.alloc((size_t)P * cap));
+    chk(b->wire_chk.alloc(P));
+    if (b->star_wired && e == hipSuccess) {
+        // neighbour lists: a pool segment per problem; a round wires the longest prefix of a problem's pending nodes whose
+        // lists fit (mean list length at radius 1 in configs[1]'s world: ~40), so the size bounds memory, not the result.
+        // Footprint per problem: share x 16 B of pool + (share / 32 + cap) x 144 B of chunk store + 4 x cap x 4..8 B; the
+        // default share is 64 x cap, cut so that pool + chunks of the whole batch stay below 24 GB.
+        uint64_t share = 64ull * cap;
+        const uint64_t budget_entries = (24ull << 30) / (sizeof(StarEntry) + sizeof(StarChunk) / 32) / P;
+        if (share > budget_entries) share = budget_entries;
+        if (cfg->star_pool_share != 0 && cfg->star_pool_share < share) share = cfg->star_pool_share;
+        if (share < cap) share = cap;   // a single list is at most cap entries long: every round wires at least one node
+        dp.pool_share = (uint32_t)share;
+        hipError_t ew = hipSuccess;
+        auto chkw = [&](hipError_t r) { if (ew == hipSuccess) ew = r; };
+        chkw(oxhip_stream_acquire(cfg->device, &b->stream2));
+        for (auto& ev : b->ev_seg) chkw(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        chkw(hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming));
+        chkw(b->pool.alloc((size_t)P * share + 64));   // (+ padding: masked lanes of the wiring kernel read one entry past an empty list)
+        dp.chunk_share = (uint32_t)(share / 32 + cap);   // enough for any set of lists that fits the pool segment (one partial chunk per node)
+        chkw(b->chunks.alloc((size_t)P * dp.chunk_share));
+        chkw(b->chunk_cursor.alloc(P));
+        chkw(b->wired.alloc(P));
+        chkw(b->nbr_take.alloc(P));
+        chkw(b->nbr_total.alloc(P));
+        chkw(b->nbr_cnt.alloc((size_t)P * cap));
+        chkw(b->nbr_off.alloc((size_t)P * cap));
+        chkw(b->d_near.alloc((size_t)P * cap));
+        if (ew != hipSuccess && cfg->kernel == OXHIP_KERNEL_AUTO) {
+            // KERNEL_AUTO promised "whatever runs": the one-kernel design (rrt_star.hip) needs 1/60 of this memory
+            (void)hipGetLastError();
+            b->pool.release(); b->chunks.release(); b->chunk_cursor.release(); b->wired.release(); b->nbr_take.release();
+            b->nbr_total.release(); b->nbr_cnt.release(); b->nbr_off.release(); b->d_near.release();
+            dp.pool_share = dp.chunk_share = 0;
+            b->star_wired = false;
+            b->star_geo_cells = false;
+        } else {
+            chk(ew);
+        }
+    }
+    if (!b->star_wired) {
+        chk(b->nb_idx.alloc((size_t)P * cap));
+        chk(b->nb_dist.alloc((size_t)P * cap));
+    }
+    return OXHIP_OK;
+}
+
+// The stream, the timing events and the buffers every batch has (the planner's own among them, RRT*'s by alloc_star at the
+// place its allocations always had), then the DevParams pointers to them.
+static int32_t alloc_common(oxhip_rrt_batch* b) {
+    const oxhip_rrt_config* cfg = &b->cfg;
+    DevParams& dp = b->dp;
+    const uint32_t P = cfg->n_problems, dim = cfg->dim, cap = dp.cap;
+    hipError_t e = hipSuccess;
+    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+    chk(oxhip_stream_acquire(cfg->device, &b->stream));
+    chk(hipEventCreate(&b->ev0));
+    chk(hipEventCreate(&b->ev1));
+    chk(b->tree.alloc((size_t)P * dim * cap));
+    chk(b->parent.alloc((size_t)P * cap));
+    chk(b->skip.alloc((size_t)P * cap));
+    if (cfg->planner == OXHIP_PLANNER_RRT_CONNECT) {
+        chk(b->tree_b.alloc((size_t)P * dim * cap));
+        chk(b->parent_b.alloc((size_t)P * cap));
+    }
+    if (cfg->planner == OXHIP_PLANNER_RRT_STAR) OX_TRY(alloc_star(b, e));
+    chk(b->state.alloc(P));
+    chk(b->goal_c.alloc((size_t)P * dim));
+    chk(b->goal_thr.alloc(P));
+    chk(b->goal_r.alloc(P));
+    if (!space_of(b).no_body && e == hipSuccess) {   // the default body: one sphere of radius 0 at the origin (a point)
+        if (upload(b->se3_body, std::vector<double>(4 * (size_t)kSe3MaxBody, 0.0), b->stream) != OXHIP_OK) e = hipErrorOutOfMemory;
+        b->se3.body = b->se3_body.p;
+        b->se3.n_body = 1;
+    }
+    if (e != hipSuccess) return alloc_failed(e);
+    dp.tree = b->tree.p; dp.parent = b->parent.p; dp.skip = b->skip.p; dp.state = b->state.p;
+    dp.tree_b = b->tree_b.p; dp.parent_b = b->parent_b.p;
+    dp.cost = b->cost.p; dp.nb_idx = b->nb_idx.p; dp.nb_dist = b->nb_dist.p;
+    dp.wire_chk = b->wire_chk.p; dp.wired = b->wired.p; dp.nbr_cnt = b->nbr_cnt.p; dp.nbr_off = b->nbr_off.p;
+    dp.nbr_take = b->nbr_take.p; dp.nbr_total = b->nbr_total.p; dp.d_near = b->d_near.p; dp.pool = b->pool.p;
+    dp.chunks = b->chunks.p; dp.chunk_cursor = b->chunk_cursor.p;
+    dp.goal_c = b->goal_c.p; dp.goal_thr = b->goal_thr.p; dp.goal_r = b->goal_r.p;
+    return OXHIP_OK;
+}
+
+// rrt_cells.hip's arena (the comment at oxhip_rrt_batch::cell_arena) and the DevParams fields that describe it.
+static int32_t alloc_cells(oxhip_rrt_batch* b) {
+    DevParams& dp = b->dp;
+    const uint32_t P = b->cfg.n_problems, dim = b->cfg.dim, cap = dp.cap;
+    dp.cell_level_max = cells_level_max(dim, cap);
+    // head blocks for the finest grid this capacity reaches + the overflow blocks (n nodes overflow into at most n / 7)
+    dp.cell_blocks = cells_head_blocks(dim, cap) + cap / 7u + 64u;
+    // frozen launches: a problem's iterations are independent, so they are divided over enough waves to fill the chip
+    // (256 CUs x 12 waves of the frozen specialisation's register budget)
+    uint32_t split = b->cfg.frozen_split;
+    if (split == 0) { split = (3072u + P - 1u) / P; if (split > 8u) split = 8u; if (split < 1u) split = 1u; }
+    dp.cells_split = split;
+    dp.sph_grid_G = sphere_grid_side(dim);
+    const size_t grid_cells = dim == 2 ? (size_t)dp.sph_grid_G * dp.sph_grid_G : (size_t)dp.sph_grid_G * dp.sph_grid_G * dp.sph_grid_G;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t at = off; off = (off + bytes + 255u) & ~(size_t)255u; return at; };
+    const size_t o_meta = carve((size_t)P * sizeof(CellMeta)), o_acc = carve((size_t)P * sizeof(CellAcc));   // (zeroed together)
+    const size_t zero_bytes = off;
+    const size_t o_pos = carve((size_t)P * 64 * sizeof(uint64_t)), o_grid = carve(grid_cells * sizeof(uint64_t));
+    const size_t o_grid2 = carve(b->star_wired ? grid_cells * sizeof(uint64_t) : 0);
+    const size_t o_flat = carve((size_t)P * 4096 * 4 * sizeof(float)), o_xyz = carve((size_t)P * cap * 4 * sizeof(double));
+    const size_t o_blk = carve((size_t)P * dp.cell_blocks * sizeof(CellBlock));
+    hipError_t e = b->cell_arena.alloc(off);
+    if (e == hipSuccess) e = hipMemset(b->cell_arena.p, 0, zero_bytes);
+    if (e != hipSuccess) return alloc_failed(e);
+    uint8_t* base = b->cell_arena.p;
+    b->cell_meta_p = reinterpret_cast<CellMeta*>(base + o_meta);
+    b->sph_grid_p = reinterpret_cast<uint64_t*>(base + o_grid);
+    if (b->star_wired) b->star_grid_p = reinterpret_cast<uint64_t*>(base + o_grid2);
+    dp.cell_blk = reinterpret_cast<CellBlock*>(base + o_blk); dp.cell_flat = reinterpret_cast<float*>(base + o_flat);
+    dp.cell_xyz = reinterpret_cast<double*>(base + o_xyz); dp.cell_meta = b->cell_meta_p;
+    dp.cell_acc = reinterpret_cast<CellAcc*>(base + o_acc); dp.cell_part_pos = reinterpret_cast<uint64_t*>(base + o_pos);
+    dp.sph_grid = b->sph_grid_p;
+    return OXHIP_OK;
+}
+
+// R^n's streaming kernels (rrt_stream.hip; RRT*: star_shadow's) screen their scans over an fl32 shadow of the tree, which they
+// maintain themselves.
+static int32_t alloc_shadow(oxhip_rrt_batch* b) {
+    const size_t P = b->cfg.n_problems;
+    hipError_t e = b->tree32.alloc(P * b->cfg.dim * b->dp.cap);
+    if (e == hipSuccess) e = b->shadow_state.alloc(P * 2);
+    if (e == hipSuccess) e = hipMemset(b->shadow_state.p, 0, P * 2 * sizeof(uint32_t));
+    if (e != hipSuccess) return alloc_failed(e);
+    b->dp.tree32 = b->tree32.p;
+    b->dp.shadow_state = b->shadow_state.p;
+    return OXHIP_OK;
+}
+
+// ------------------------------------------------------------------ the stand-alone primitives' shared body
+// The body of the element-wise primitives: rows of w_a / w_b / w_out doubles for a / b / out, one double per row of t; b and t
+// travel only when the op reads them.  launch(a, b, t, out, stream) on device pointers.
+template <typename Launch>
+static int32_t op_batch(int32_t device, const double* a, const double* b, const double* t, uint32_t n, double* out,
+                        size_t w_a, size_t w_b, size_t w_out, bool b_uploaded, bool t_uploaded, Launch launch) {
+    if (n == 0) return OXHIP_OK;
+    OX_TRY(select_device(device));
+    TmpStream ts;
+    OX_TRY(ts.acquire(device));
+    DevBuf<double> da, db, dt, dout;
+    OX_TRY(to_device(da, a, w_a * n, ts.s));
+    if (b_uploaded) OX_TRY(to_device(db, b, w_b * n, ts.s));
+    if (t_uploaded) OX_TRY(to_device(dt, t, n, ts.s));
+    HIP_TRY(dout.alloc(w_out * n));
+    launch(da.p, db.p, dt.p, dout.p, ts.s);
+    HIP_TRY(hipGetLastError());
+    return to_host(out, dout, w_out * n, ts.s);
+}
+
 extern "C" {
 
 int32_t oxhip_abi_version(void) { return OXHIP_ABI_VERSION; }
@@ -157,295 +508,36 @@ int32_t oxhip_device_count(int32_t* count) {
 int32_t oxhip_rrt_batch_create(const oxhip_rrt_config* cfg, oxhip_rrt_batch** out) {
     if (!cfg || !out) return fail(OXHIP_ERR_BAD_ARG, "null argument");
     *out = nullptr;
-    if (cfg->struct_size != sizeof(oxhip_rrt_config)) return fail(OXHIP_ERR_BAD_ARG, "struct_size mismatch");
-    if (cfg->dim == 0 || cfg->dim > OXHIP_MAX_DIM) return fail(OXHIP_ERR_BAD_ARG, "dim must be in 1..8");
-    if (cfg->n_problems == 0 || cfg->max_nodes == 0) return fail(OXHIP_ERR_BAD_ARG, "n_problems and max_nodes must be > 0");
-    if (cfg->max_nodes > (1u << 30)) return fail(OXHIP_ERR_BAD_ARG, "max_nodes too large");
-    if (!(cfg->goal_bias >= 0.0 && cfg->goal_bias <= 1.0))
-        return fail(OXHIP_ERR_BAD_ARG, "goal_bias outside [0,1] (rand Bernoulli::new would fail)");
-    if (!(cfg->max_distance > 0.0) || !std::isfinite(cfg->max_distance))
-        return fail(OXHIP_ERR_BAD_ARG, "max_distance must be finite and > 0");
-    if (cfg->kernel > OXHIP_KERNEL_CELLS) return fail(OXHIP_ERR_BAD_ARG, "unknown kernel kind");
-    if (cfg->kernel == OXHIP_KERNEL_RETIRED_3 || cfg->kernel == OXHIP_KERNEL_RETIRED_4)
-        return fail(OXHIP_ERR_BAD_ARG, "kernel kinds 3 (box-pruned scan) and 4 (lane-group resolver) were retired in ABI version 2");
-    if (cfg->planner > OXHIP_PLANNER_RRT_STAR) return fail(OXHIP_ERR_BAD_ARG, "unknown planner kind");
-    if (cfg->frozen_split > 64) return fail(OXHIP_ERR_BAD_ARG, "frozen_split must be 0 (automatic) or 1 .. 64");
-    if (cfg->kernel == OXHIP_KERNEL_CELLS && cfg->planner == OXHIP_PLANNER_RRT_CONNECT)
-        return fail(OXHIP_ERR_BAD_ARG, "the cell-grid kernel runs RRT, and the geometry of the decoupled RRT*");
-    if (cfg->planner == OXHIP_PLANNER_RRT_CONNECT && cfg->kernel >= OXHIP_KERNEL_RESIDENT)
-        return fail(OXHIP_ERR_BAD_ARG, "RRTConnect runs on the stream kernel only");
-    // RRT*: KERNEL_STREAM = rrt_star.hip (one workgroup per problem, everything in one kernel); KERNEL_LANES / KERNEL_CELLS = the
-    // decoupled design (geometry by rrt_lanes.hip / rrt_cells.hip, then the wiring kernels of rrt_star_wire.hip); KERNEL_AUTO = the
-    // decoupled design where it exists, its geometry by rrt_cells.hip in R^2 / R^3
-    if (cfg->planner == OXHIP_PLANNER_RRT_STAR && cfg->kernel != OXHIP_KERNEL_AUTO && cfg->kernel != OXHIP_KERNEL_STREAM &&
-        cfg->kernel != OXHIP_KERNEL_LANES && cfg->kernel != OXHIP_KERNEL_CELLS)
-        return fail(OXHIP_ERR_BAD_ARG, "RRT* runs on the stream kernel or on the lane-per-query / cell-grid kernel + wiring kernels");
-    if (cfg->planner == OXHIP_PLANNER_RRT_STAR && std::isnan(cfg->search_radius))
-        return fail(OXHIP_ERR_BAD_ARG, "search_radius is NaN");
-    if (cfg->goal_sampler > OXHIP_GOAL_SAMPLE_UNIFORM_DISC) return fail(OXHIP_ERR_BAD_ARG, "unknown goal sampler");
-    if (cfg->goal_sampler == OXHIP_GOAL_SAMPLE_UNIFORM_DISC && (cfg->dim != 2 || cfg->space != OXHIP_SPACE_REAL_VECTOR))
-        return fail(OXHIP_ERR_BAD_ARG, "the disc sampler (rrt_rvss_tests.rs:55-66) is defined for RealVectorStateSpace(2)");
-    if (cfg->goal_sampler == OXHIP_GOAL_SAMPLE_UNIFORM_DISC && (cfg->planner == OXHIP_PLANNER_RRT_CONNECT || cfg->kernel == OXHIP_KERNEL_RESIDENT))
-        return fail(OXHIP_ERR_BAD_ARG, "the disc sampler is built for RRT / RRT* on the stream, lane-per-query and cell-grid kernels");
-    double fraction = cfg->lvs_fraction, res = 0.0;
-    double th_lo = 0.0, th_hi = 0.0;
-    double so3_max_angle = 0.0;
-    if (cfg->space > OXHIP_SPACE_SE3) return fail(OXHIP_ERR_BAD_ARG, "unknown space kind");
-    if (cfg->space == OXHIP_SPACE_SE3) {
-        if (cfg->dim != 7) return fail(OXHIP_ERR_BAD_ARG, "SE(3) states are (x, y, z, qx, qy, qz, qw): dim must be 7");
-        if (cfg->planner != OXHIP_PLANNER_RRT_CONNECT) return fail(OXHIP_ERR_BAD_ARG, "SE(3) is built for RRTConnect only");
-        if (cfg->kernel != OXHIP_KERNEL_AUTO && cfg->kernel != OXHIP_KERNEL_STREAM)
-            return fail(OXHIP_ERR_BAD_ARG, "SE(3) RRTConnect runs on rrt_connect_se3.hip: kernel must be OXHIP_KERNEL_AUTO or OXHIP_KERNEL_STREAM");
-        if (cfg->goal_sampler != OXHIP_GOAL_SAMPLE_CENTRE) return fail(OXHIP_ERR_BAD_ARG, "SE(3): the goal sampler must be OXHIP_GOAL_SAMPLE_CENTRE");
-        // (x, y, z) as RealVectorStateSpace::new(3, ..) (validates, clamps the fraction); rotation bounds as SO3StateSpace::new;
-        // extent = extent_xyz + 0.5 * PI; lvsl = extent * fraction; res = lvsl * 0.1
-        int32_t sr = space_resolution(3, cfg->bounds, fraction, res);
-        if (sr != OXHIP_OK) return sr;
-        if ((sr = so3_rotation_bounds(cfg->bounds + 6, so3_max_angle)) != OXHIP_OK) return sr;
-        double acc = 0.0;
-        for (uint32_t k = 0; k < 3; ++k) { double w = cfg->bounds[2 * k + 1] - cfg->bounds[2 * k]; double sq = w * w; acc = acc + sq; }
-        const double extent = std::sqrt(acc) + 0.5 * 3.14159265358979323846;
-        const double lvsl = extent * fraction;
-        res = lvsl * 0.1;
-    } else
-    if (cfg->space == OXHIP_SPACE_SO3) {
-        if (cfg->dim != 4) return fail(OXHIP_ERR_BAD_ARG, "SO(3) states are quaternions (x, y, z, w): dim must be 4");
-        if (cfg->planner != OXHIP_PLANNER_RRT) return fail(OXHIP_ERR_BAD_ARG, "SO(3) is built for RRT only");
-        if (cfg->kernel != OXHIP_KERNEL_AUTO && cfg->kernel != OXHIP_KERNEL_STREAM)
-            return fail(OXHIP_ERR_BAD_ARG, "SO(3) RRT runs on rrt_so3.hip: kernel must be OXHIP_KERNEL_AUTO or OXHIP_KERNEL_STREAM");
-        int32_t sr = so3_space_resolution(cfg->dim, cfg->bounds, fraction, res, so3_max_angle);   // centre, max_angle, fraction
-        if (sr != OXHIP_OK) return sr;
-    } else if (cfg->space == OXHIP_SPACE_SE2) {
-        if (cfg->dim != 3) return fail(OXHIP_ERR_BAD_ARG, "SE(2) states are (x, y, theta): dim must be 3");
-        if (cfg->planner != OXHIP_PLANNER_RRT_CONNECT) return fail(OXHIP_ERR_BAD_ARG, "SE(2) is built for RRTConnect only");
-        // SO2StateSpace::new (so2_state_space.rs:57-72): lo >= hi is InvalidBound; bounds clamped to [-PI, PI]
-        const double pi = 3.14159265358979323846;
-        th_lo = cfg->bounds[4]; th_hi = cfg->bounds[5];
-        if (!(th_lo < th_hi)) return fail(OXHIP_ERR_ZERO_VOLUME, "theta: lower bound >= upper bound");
-        th_lo = th_lo > -pi ? th_lo : -pi;
-        th_hi = th_hi < pi ? th_hi : pi;
-        // extent = extent_xy + 0.5 * PI (so2_state_space.rs:78-80); lvsl = extent * fraction; res = lvsl * 0.1
-        int32_t sr = space_resolution(2, cfg->bounds, fraction, res);   // validates the (x, y) bounds, clamps the fraction
-        if (sr != OXHIP_OK) return sr;
-        double acc = 0.0;
-        for (uint32_t k = 0; k < 2; ++k) { double w = cfg->bounds[2 * k + 1] - cfg->bounds[2 * k]; double sq = w * w; acc = acc + sq; }
-        const double extent = std::sqrt(acc) + 0.5 * pi;
-        const double lvsl = extent * fraction;
-        res = lvsl * 0.1;
-    } else {
-        int32_t sr = space_resolution(cfg->dim, cfg->bounds, fraction, res);
-        if (sr != OXHIP_OK) return sr;
-    }
-    if (cfg->space != OXHIP_SPACE_SO3 && cfg->max_distance / res > 1e6) return fail(OXHIP_ERR_BAD_ARG, "more than 1e6 validity checks per edge");
-
-    int32_t st = select_device(cfg->device);
-    if (st != OXHIP_OK) return st;
-
-    auto* b = new oxhip_rrt_batch();
-    b->cfg = *cfg;
-    b->cfg.lvs_fraction = fraction;
-    const uint32_t P = cfg->n_problems, dim = cfg->dim;
-    const uint32_t cap = ((cfg->max_nodes + 1023u) / 1024u) * 1024u;
-    DevParams& dp = b->dp;
-    dp.dim = dim; dp.n_problems = P; dp.cap = cap; dp.max_nodes = cfg->max_nodes;
-    for (uint32_t k = 0; k < dim; ++k) {
-        dp.lo[k] = cfg->bounds[2 * k];
-        dp.hi[k] = cfg->bounds[2 * k + 1];
-        dp.scale[k] = dp.hi[k] - dp.lo[k];
-    }
-    if (cfg->space == OXHIP_SPACE_SE2) { dp.lo[2] = th_lo; dp.hi[2] = th_hi; dp.scale[2] = th_hi - th_lo; }
-    if (cfg->space == OXHIP_SPACE_SO3) {
-        for (uint32_t k = 0; k < 4; ++k) { dp.so3_centre[k] = cfg->bounds[k]; dp.lo[k] = dp.hi[k] = dp.scale[k] = 0.0; }
-        dp.so3_max_angle = so3_max_angle;
-    }
-    if (cfg->space == OXHIP_SPACE_SE3) {   // lo / hi / scale [0..3) are (x, y, z); the rotation's bounds travel as SO(3)'s do
-        for (uint32_t k = 3; k < 7; ++k) dp.lo[k] = dp.hi[k] = dp.scale[k] = 0.0;
-        for (uint32_t k = 0; k < 4; ++k) dp.so3_centre[k] = cfg->bounds[6 + k];
-        dp.so3_max_angle = so3_max_angle;
-    }
-    dp.space = cfg->space;
-    dp.max_distance = cfg->max_distance;
-    dp.res = res;
-    if (cfg->planner == OXHIP_PLANNER_RRT_CONNECT) {   // rrt_connect.hip, rrt_connect_se2.hip: the step count of an Advanced extend's motion, when it is safely known
-        const double r = cfg->max_distance / res, c = std::ceil(r);
-        const double gap = std::fmin(r - (c - 1.0), c - r);
-        if (std::isfinite(r) && c >= 1.0 && c < 4294967295.0 && gap > 1e-6) {
-            dp.adv_steps = (uint32_t)c;
-            dp.adv_slack = 0.5 * gap * res;
-        }
-    }
-    dp.p_int = bernoulli_p_int(cfg->goal_bias);
-    dp.seed = cfg->seed;
-    dp.dbg_flags = cfg->debug_flags;   // oxhip_debug_flag bits: test-only, results identical (the library reads no environment variable)
-    dp.goal_sampler = cfg->goal_sampler;
-    dp.first_problem_id = cfg->first_problem_id;
-    dp.stop_at_goal = cfg->stop_at_goal ? 1 : 0;
-    dp.t_steer = sqrt_le_threshold(cfg->max_distance);
-    dp.thr_search = sqrt_lt_threshold(cfg->search_radius);
-
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    chk(oxhip_stream_acquire(cfg->device, &b->stream));
-    chk(hipEventCreate(&b->ev0));
-    chk(hipEventCreate(&b->ev1));
-    chk(b->tree.alloc((size_t)P * dim * cap));
-    chk(b->parent.alloc((size_t)P * cap));
-    chk(b->skip.alloc((size_t)P * cap));
-    if (cfg->planner == OXHIP_PLANNER_RRT_CONNECT) {
-        chk(b->tree_b.alloc((size_t)P * dim * cap));
-        chk(b->parent_b.alloc((size_t)P * cap));
-    }
-    if (cfg->planner == OXHIP_PLANNER_RRT_STAR) {
-        const bool geo_cells = cfg->kernel != OXHIP_KERNEL_LANES && cells_supported(dim, cap);
-        const bool geo_lanes = cfg->kernel != OXHIP_KERNEL_CELLS && lanes_supported(dim, cap);
-        const bool can_wire = star_wire_supported(dim) && (geo_cells || geo_lanes);
-        b->star_wired = cfg->kernel == OXHIP_KERNEL_LANES || cfg->kernel == OXHIP_KERNEL_CELLS || (cfg->kernel == OXHIP_KERNEL_AUTO && can_wire);
-        if (b->star_wired && !can_wire) {
-            oxhip_rrt_batch_destroy(b);
-            return fail(OXHIP_ERR_BAD_ARG, "decoupled RRT*: neither geometry kernel supports this (dim, max_nodes)");
-        }
-        b->star_geo_cells = b->star_wired && geo_cells;
-        chk(b->cost.alloc((size_t)P * cap));
-        chk(b->wire_chk.alloc(P));
-        if (b->star_wired && e == hipSuccess) {
-            // neighbour lists: a pool segment per problem; a round wires the longest prefix of a problem's pending nodes whose
-            // lists fit (mean list length at radius 1 in configs[1]'s world: ~40), so the size bounds memory, not the result.
-            // Footprint per problem: share x 16 B of pool + (share / 32 + cap) x 144 B of chunk store + 4 x cap x 4..8 B; the
-            // default share is 64 x cap, cut so that pool + chunks of the whole batch stay below 24 GB.
-            uint64_t share = 64ull * cap;
-            const uint64_t budget_entries = (24ull << 30) / (sizeof(StarEntry) + sizeof(StarChunk) / 32) / P;
-            if (share > budget_entries) share = budget_entries;
-            if (cfg->star_pool_share != 0 && cfg->star_pool_share < share) share = cfg->star_pool_share;
-            if (share < cap) share = cap;   // a single list is at most cap entries long: every round wires at least one node
-            dp.pool_share = (uint32_t)share;
-            hipError_t ew = hipSuccess;
-            auto chkw = [&](hipError_t r) { if (ew == hipSuccess) ew = r; };
-            chkw(oxhip_stream_acquire(cfg->device, &b->stream2));
-            for (auto& ev : b->ev_seg) chkw(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            chkw(hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming));
-            chkw(b->pool.alloc((size_t)P * share + 64));   // (+ padding: masked lanes of the wiring kernel read one entry past an empty list)
-            dp.chunk_share = (uint32_t)(share / 32 + cap);   // enough for any set of lists that fits the pool segment (one partial chunk per node)
-            chkw(b->chunks.alloc((size_t)P * dp.chunk_share));
-            chkw(b->chunk_cursor.alloc(P));
-            chkw(b->wired.alloc(P));
-            chkw(b->nbr_take.alloc(P));
-            chkw(b->nbr_total.alloc(P));
-            chkw(b->nbr_cnt.alloc((size_t)P * cap));
-            chkw(b->nbr_off.alloc((size_t)P * cap));
-            chkw(b->d_near.alloc((size_t)P * cap));
-            if (ew != hipSuccess && cfg->kernel == OXHIP_KERNEL_AUTO) {
-                // KERNEL_AUTO promised "whatever runs": the one-kernel design (rrt_star.hip) needs 1/60 of this memory
-                (void)hipGetLastError();
-                b->pool.release(); b->chunks.release(); b->chunk_cursor.release(); b->wired.release(); b->nbr_take.release();
-                b->nbr_total.release(); b->nbr_cnt.release(); b->nbr_off.release(); b->d_near.release();
-                dp.pool_share = dp.chunk_share = 0;
-                b->star_wired = false;
-                b->star_geo_cells = false;
-            } else {
-                chk(ew);
-            }
-        }
-        if (!b->star_wired) {
-            chk(b->nb_idx.alloc((size_t)P * cap));
-            chk(b->nb_dist.alloc((size_t)P * cap));
-        }
-    }
-    chk(b->state.alloc(P));
-    chk(b->goal_c.alloc((size_t)P * dim));
-    chk(b->goal_thr.alloc(P));
-    chk(b->goal_r.alloc(P));
-    if (cfg->space == OXHIP_SPACE_SE3 && e == hipSuccess) {   // the default body: one sphere of radius 0 at the origin (a point)
-        if (upload(b->se3_body, std::vector<double>(4 * (size_t)kSe3MaxBody, 0.0), b->stream) != OXHIP_OK) e = hipErrorOutOfMemory;
-        b->se3.body = b->se3_body.p;
-        b->se3.n_body = 1;
-    }
-    if (e != hipSuccess) {
-        std::string msg = std::string("device allocation failed: ") + hipGetErrorString(e);
-        oxhip_rrt_batch_destroy(b);
-        return fail(OXHIP_ERR_HIP, msg);
-    }
-    dp.tree = b->tree.p; dp.parent = b->parent.p; dp.skip = b->skip.p; dp.state = b->state.p;
-    dp.tree_b = b->tree_b.p; dp.parent_b = b->parent_b.p;
-    dp.cost = b->cost.p; dp.nb_idx = b->nb_idx.p; dp.nb_dist = b->nb_dist.p;
-    dp.wire_chk = b->wire_chk.p; dp.wired = b->wired.p; dp.nbr_cnt = b->nbr_cnt.p; dp.nbr_off = b->nbr_off.p;
-    dp.nbr_take = b->nbr_take.p; dp.nbr_total = b->nbr_total.p; dp.d_near = b->d_near.p; dp.pool = b->pool.p;
-    dp.chunks = b->chunks.p; dp.chunk_cursor = b->chunk_cursor.p;
-    dp.goal_c = b->goal_c.p; dp.goal_thr = b->goal_thr.p; dp.goal_r = b->goal_r.p;
-
+    Resolved r;
+    OX_TRY(validate_config(cfg, r));
+    OX_TRY(select_device(cfg->device));
+    // from here on every early return destroys the batch, and with it whatever it took so far
+    std::unique_ptr<oxhip_rrt_batch, decltype(&oxhip_rrt_batch_destroy)> b(new oxhip_rrt_batch(), oxhip_rrt_batch_destroy);
+    fill_params(b.get(), cfg, r);
+    OX_TRY(alloc_common(b.get()));
+    const uint32_t dim = cfg->dim, cap = b->dp.cap;
     uint32_t kind = cfg->kernel;
-    if (cfg->space == OXHIP_SPACE_SO3) kind = OXHIP_KERNEL_STREAM;   // rrt_so3.hip (its one kernel, reported as the streaming kind)
+    if (space_of(b.get()).one_kernel) kind = OXHIP_KERNEL_STREAM;   // (e.g. rrt_so3.hip: the space's one kernel, reported as the streaming kind)
     if (cfg->planner != OXHIP_PLANNER_RRT) kind = b->star_wired ? (b->star_geo_cells ? OXHIP_KERNEL_CELLS : OXHIP_KERNEL_LANES) : OXHIP_KERNEL_STREAM;
-    if (kind == OXHIP_KERNEL_AUTO)
-    {
+    if (kind == OXHIP_KERNEL_AUTO) {
         // rrt_cells.hip (one wave per problem, R^2 / R^3, trees up to 64,512 nodes) wherever it exists: since its rounds
         // repair overtaken queries in place it grows ONE tree to 10,000 nodes in 4.3 ms -- faster than rrt_lanes.hip, which gives
         // the problem a whole CU (5.6 ms) -- and 256 of them in 4.9 ms (6.2 ms), profiles/r3_single/.  rrt_lanes.hip serves
         // R^4 .. R^6 (and trees that fit its register rows), rrt_stream.hip everything else.
         kind = cells_supported(dim, cap) ? OXHIP_KERNEL_CELLS : lanes_supported(dim, cap) ? OXHIP_KERNEL_LANES : OXHIP_KERNEL_STREAM;
     }
-    if (kind == OXHIP_KERNEL_CELLS) {
-        if (!cells_supported(dim, cap)) {
-            oxhip_rrt_batch_destroy(b);
-            return fail(OXHIP_ERR_BAD_ARG, "cell-grid kernel: R^2 / R^3 trees of at most 64,512 nodes");
-        }
-        dp.cell_level_max = cells_level_max(dim, cap);
-        // head blocks for the finest grid this capacity reaches + the overflow blocks (n nodes overflow into at most n / 7)
-        dp.cell_blocks = cells_head_blocks(dim, cap) + cap / 7u + 64u;
-        // frozen launches: a problem's iterations are independent, so they are divided over enough waves to fill the chip
-        // (256 CUs x 12 waves of the frozen specialisation's register budget)
-        uint32_t split = cfg->frozen_split;
-        if (split == 0) { split = (3072u + P - 1u) / P; if (split > 8u) split = 8u; if (split < 1u) split = 1u; }
-        dp.cells_split = split;
-        dp.sph_grid_G = sphere_grid_side(dim);
-        const size_t grid_cells = dim == 2 ? (size_t)dp.sph_grid_G * dp.sph_grid_G : (size_t)dp.sph_grid_G * dp.sph_grid_G * dp.sph_grid_G;
-        size_t off = 0;
-        auto carve = [&](size_t bytes) { const size_t at = off; off = (off + bytes + 255u) & ~(size_t)255u; return at; };
-        const size_t o_meta = carve((size_t)P * sizeof(CellMeta)), o_acc = carve((size_t)P * sizeof(CellAcc));   // (zeroed together)
-        const size_t zero_bytes = off;
-        const size_t o_pos = carve((size_t)P * 64 * sizeof(uint64_t)), o_grid = carve(grid_cells * sizeof(uint64_t));
-        const size_t o_grid2 = carve(b->star_wired ? grid_cells * sizeof(uint64_t) : 0);
-        const size_t o_flat = carve((size_t)P * 4096 * 4 * sizeof(float)), o_xyz = carve((size_t)P * cap * 4 * sizeof(double));
-        const size_t o_blk = carve((size_t)P * dp.cell_blocks * sizeof(CellBlock));
-        hipError_t e2 = b->cell_arena.alloc(off);
-        if (e2 == hipSuccess) e2 = hipMemset(b->cell_arena.p, 0, zero_bytes);
-        if (e2 != hipSuccess) {
-            std::string msg = std::string("device allocation failed: ") + hipGetErrorString(e2);
-            oxhip_rrt_batch_destroy(b);
-            return fail(OXHIP_ERR_HIP, msg);
-        }
-        uint8_t* base = b->cell_arena.p;
-        b->cell_meta_p = reinterpret_cast<CellMeta*>(base + o_meta);
-        b->sph_grid_p = reinterpret_cast<uint64_t*>(base + o_grid);
-        if (b->star_wired) b->star_grid_p = reinterpret_cast<uint64_t*>(base + o_grid2);
-        dp.cell_blk = reinterpret_cast<CellBlock*>(base + o_blk); dp.cell_flat = reinterpret_cast<float*>(base + o_flat);
-        dp.cell_xyz = reinterpret_cast<double*>(base + o_xyz); dp.cell_meta = b->cell_meta_p;
-        dp.cell_acc = reinterpret_cast<CellAcc*>(base + o_acc); dp.cell_part_pos = reinterpret_cast<uint64_t*>(base + o_pos);
-        dp.sph_grid = b->sph_grid_p;
-    }
-    if (kind == OXHIP_KERNEL_LANES && !lanes_supported(dim, cap)) {
-        oxhip_rrt_batch_destroy(b);
+    if (kind == OXHIP_KERNEL_CELLS && !cells_supported(dim, cap))
+        return fail(OXHIP_ERR_BAD_ARG, "cell-grid kernel: R^2 / R^3 trees of at most 64,512 nodes");
+    if (kind == OXHIP_KERNEL_LANES && !lanes_supported(dim, cap))
         return fail(OXHIP_ERR_BAD_ARG, "resident (lane-per-query) kernel does not support this (dim, max_nodes)");
-    }
-    if (kind == OXHIP_KERNEL_RESIDENT && !resident_supported(dim, cap)) {
-        oxhip_rrt_batch_destroy(b);
+    if (kind == OXHIP_KERNEL_RESIDENT && !resident_supported(dim, cap))
         return fail(OXHIP_ERR_BAD_ARG, "resident kernel does not support this (dim, max_nodes)");
-    }
-    b->kernel_kind = kind;
-    b->last_kind = kind;
-    if ((cfg->planner == OXHIP_PLANNER_RRT && kind == OXHIP_KERNEL_STREAM && cfg->space != OXHIP_SPACE_SO3) || cfg->planner == OXHIP_PLANNER_RRT_STAR) {   // (RRT*: star_shadow's)
-        // the streaming kernels screen their scans over an fl32 shadow of the tree, which they maintain themselves
-        hipError_t e2 = b->tree32.alloc((size_t)P * dim * cap);
-        if (e2 == hipSuccess) e2 = b->shadow_state.alloc((size_t)P * 2);
-        if (e2 == hipSuccess) e2 = hipMemset(b->shadow_state.p, 0, (size_t)P * 2 * sizeof(uint32_t));
-        if (e2 != hipSuccess) {
-            std::string msg = std::string("device allocation failed: ") + hipGetErrorString(e2);
-            oxhip_rrt_batch_destroy(b);
-            return fail(OXHIP_ERR_HIP, msg);
-        }
-        dp.tree32 = b->tree32.p;
-        dp.shadow_state = b->shadow_state.p;
-    }
-    *out = b;
+    b->kernel_kind = b->last_kind = kind;
+    if (kind == OXHIP_KERNEL_CELLS) OX_TRY(alloc_cells(b.get()));
+    // (a space with a kernel of its own keeps no shadow; RRT* does on every kind)
+    if ((cfg->planner == OXHIP_PLANNER_RRT && kind == OXHIP_KERNEL_STREAM && !space_of(b.get()).one_kernel) || cfg->planner == OXHIP_PLANNER_RRT_STAR)
+        OX_TRY(alloc_shadow(b.get()));
+    *out = b.release();
     return OXHIP_OK;
 }
 
@@ -466,10 +558,10 @@ int32_t oxhip_rrt_batch_destroy(oxhip_rrt_batch* b) {
 
 int32_t oxhip_rrt_batch_set_spheres(oxhip_rrt_batch* b, const double* centres, const double* radii, uint32_t n) {
     if (!b || (n && (!centres || !radii))) return fail(OXHIP_ERR_BAD_ARG, "null argument");
-    if (b->cfg.space == OXHIP_SPACE_SE2) return fail(OXHIP_ERR_BAD_ARG, "SE(2) batches take oxhip_rrt_batch_set_segments");
-    int32_t st = select_device(b->cfg.device);
-    if (st != OXHIP_OK) return st;
-    const uint32_t dim = b->cfg.space == OXHIP_SPACE_SE3 ? 3u : b->cfg.dim;   // SE(3): world spheres, 3-wide centres
+    const SpaceRow& row = space_of(b);
+    if (row.no_spheres) return fail(OXHIP_ERR_BAD_ARG, row.no_spheres);
+    OX_TRY(select_device(b->cfg.device));
+    const uint32_t dim = row.sphere_width ? row.sphere_width : b->cfg.dim;
     std::vector<double> c((size_t)dim * n), thr(n);
     for (uint32_t j = 0; j < n; ++j) {
         for (uint32_t k = 0; k < dim; ++k) {
@@ -479,11 +571,11 @@ int32_t oxhip_rrt_batch_set_spheres(oxhip_rrt_batch* b, const double* centres, c
         }
         thr[j] = sqrt_le_threshold(radii[j]);
     }
-    if ((st = upload(b->sph_c, c, b->stream)) != OXHIP_OK) return st;
-    if ((st = upload(b->sph_thr, thr, b->stream)) != OXHIP_OK) return st;
+    OX_TRY(upload(b->sph_c, c, b->stream));
+    OX_TRY(upload(b->sph_thr, thr, b->stream));
     b->dp.n_spheres = n; b->dp.sph_c = b->sph_c.p; b->dp.sph_thr = b->sph_thr.p;
-    if (b->cfg.space == OXHIP_SPACE_SO3 || b->cfg.space == OXHIP_SPACE_SE3) {   // cones: distance(centre, q) > radius in the SO(3) metric, compared with the radius itself; SE(3): r_b + r_j
-        if ((st = upload(b->sph_r, std::vector<double>(radii, radii + n), b->stream)) != OXHIP_OK) return st;
+    if (row.radii_uploaded) {
+        OX_TRY(upload(b->sph_r, std::vector<double>(radii, radii + n), b->stream));
         b->dp.sph_r = b->sph_r.p;
     }
     b->sph_centres.assign(centres, centres + (size_t)n * dim);
@@ -494,11 +586,8 @@ int32_t oxhip_rrt_batch_set_spheres(oxhip_rrt_batch* b, const double* centres, c
 
 int32_t oxhip_rrt_batch_set_boxes(oxhip_rrt_batch* b, const double* lo, const double* hi, uint32_t n) {
     if (!b || (n && (!lo || !hi))) return fail(OXHIP_ERR_BAD_ARG, "null argument");
-    if (b->cfg.space == OXHIP_SPACE_SE2) return fail(OXHIP_ERR_BAD_ARG, "SE(2) batches take oxhip_rrt_batch_set_segments");
-    if (b->cfg.space == OXHIP_SPACE_SO3) return fail(OXHIP_ERR_BAD_ARG, "SO(3) batches take cones (oxhip_rrt_batch_set_spheres)");
-    if (b->cfg.space == OXHIP_SPACE_SE3) return fail(OXHIP_ERR_BAD_ARG, "SE(3) batches take sphere obstacles (oxhip_rrt_batch_set_spheres)");
-    int32_t st = select_device(b->cfg.device);
-    if (st != OXHIP_OK) return st;
+    if (space_of(b).no_boxes) return fail(OXHIP_ERR_BAD_ARG, space_of(b).no_boxes);
+    OX_TRY(select_device(b->cfg.device));
     const uint32_t dim = b->cfg.dim;
     std::vector<double> l((size_t)dim * n), h((size_t)dim * n);
     for (uint32_t j = 0; j < n; ++j)
@@ -506,21 +595,20 @@ int32_t oxhip_rrt_batch_set_boxes(oxhip_rrt_batch* b, const double* lo, const do
             l[(size_t)k * n + j] = lo[(size_t)j * dim + k];
             h[(size_t)k * n + j] = hi[(size_t)j * dim + k];
         }
-    if ((st = upload(b->box_lo, l, b->stream)) != OXHIP_OK) return st;
-    if ((st = upload(b->box_hi, h, b->stream)) != OXHIP_OK) return st;
+    OX_TRY(upload(b->box_lo, l, b->stream));
+    OX_TRY(upload(b->box_hi, h, b->stream));
     b->dp.n_boxes = n; b->dp.box_lo = b->box_lo.p; b->dp.box_hi = b->box_hi.p;
     return OXHIP_OK;
 }
 
 int32_t oxhip_rrt_batch_set_segments(oxhip_rrt_batch* b, const double* segments, uint32_t n, double clearance) {
     if (!b || (n && !segments)) return fail(OXHIP_ERR_BAD_ARG, "null argument");
-    if (b->cfg.space != OXHIP_SPACE_SE2) return fail(OXHIP_ERR_BAD_ARG, "segments describe the SE(2) checker");
+    if (space_of(b).no_segments) return fail(OXHIP_ERR_BAD_ARG, space_of(b).no_segments);
     if (std::isnan(clearance)) return fail(OXHIP_ERR_BAD_ARG, "clearance is NaN");
-    int32_t st = select_device(b->cfg.device);
-    if (st != OXHIP_OK) return st;
+    OX_TRY(select_device(b->cfg.device));
     std::vector<double> v(segments, segments + (size_t)4 * n);
     for (double x : v) if (!(std::fabs(x) <= kMaxMagnitude)) return fail(OXHIP_ERR_BAD_ARG, "segment endpoint not finite / too large");
-    if ((st = upload(b->segs, v, b->stream)) != OXHIP_OK) return st;
+    OX_TRY(upload(b->segs, v, b->stream));
     b->dp.segs = b->segs.p;
     b->dp.n_segs = n;
     b->dp.seg_thr = sqrt_le_threshold(clearance);
@@ -541,7 +629,7 @@ int32_t oxhip_rrt_batch_set_segments(oxhip_rrt_batch* b, const double* segments,
 
 int32_t oxhip_rrt_batch_set_body(oxhip_rrt_batch* b, const double* centres, const double* radii, uint32_t n) {
     if (!b || !centres || !radii) return fail(OXHIP_ERR_BAD_ARG, "null argument");
-    if (b->cfg.space != OXHIP_SPACE_SE3) return fail(OXHIP_ERR_BAD_ARG, "a body describes the SE(3) checker");
+    if (space_of(b).no_body) return fail(OXHIP_ERR_BAD_ARG, space_of(b).no_body);
     if (n == 0 || n > (uint32_t)kSe3MaxBody) return fail(OXHIP_ERR_BAD_ARG, "a body has 1 .. 16 spheres");
     std::vector<double> v(4 * (size_t)kSe3MaxBody, 0.0);   // SoA [4][kSe3MaxBody]
     for (uint32_t j = 0; j < n; ++j) {
@@ -553,9 +641,8 @@ int32_t oxhip_rrt_batch_set_body(oxhip_rrt_batch* b, const double* centres, cons
         if (!(radii[j] >= 0.0 && radii[j] <= kMaxMagnitude)) return fail(OXHIP_ERR_BAD_ARG, "body sphere radius must be finite and >= 0");
         v[3 * (size_t)kSe3MaxBody + j] = radii[j];
     }
-    int32_t st = select_device(b->cfg.device);
-    if (st != OXHIP_OK) return st;
-    if ((st = upload(b->se3_body, v, b->stream)) != OXHIP_OK) return st;
+    OX_TRY(select_device(b->cfg.device));
+    OX_TRY(upload(b->se3_body, v, b->stream));
     b->se3.body = b->se3_body.p;
     b->se3.n_body = n;
     return OXHIP_OK;
@@ -565,8 +652,7 @@ int32_t oxhip_rrt_batch_setup(oxhip_rrt_batch* b, const double* starts, const do
                               const double* goal_radii) {
     if (!b || !starts || !goal_centres || !goal_radii) return fail(OXHIP_ERR_BAD_ARG, "null argument");
     drop_paths(b);
-    int32_t st = select_device(b->cfg.device);
-    if (st != OXHIP_OK) return st;
+    OX_TRY(select_device(b->cfg.device));
     const uint32_t P = b->cfg.n_problems, dim = b->cfg.dim, cap = b->dp.cap;
     for (size_t i = 0; i < (size_t)P * dim; ++i)
         if (!(std::fabs(starts[i]) <= kMaxMagnitude) || !(std::fabs(goal_centres[i]) <= kMaxMagnitude))
@@ -577,8 +663,8 @@ int32_t oxhip_rrt_batch_setup(oxhip_rrt_batch* b, const double* starts, const do
     b->starts.assign(starts, starts + (size_t)P * dim);
     b->filt_dirty = true;
     std::vector<double> thr(P);
-    // R^n: satisfied iff d2 <= T(radius); SE(2) / SO(3): the space's distance is compared with the radius itself
-    for (uint32_t p = 0; p < P; ++p) thr[p] = b->cfg.space != OXHIP_SPACE_REAL_VECTOR ? goal_radii[p] : sqrt_le_threshold(goal_radii[p]);
+    // R^n: satisfied iff d2 <= T(radius); SE(2) / SO(3) / SE(3): the space's distance is compared with the radius itself
+    for (uint32_t p = 0; p < P; ++p) thr[p] = space_of(b).goal_is_radius ? goal_radii[p] : sqrt_le_threshold(goal_radii[p]);
     std::vector<ProblemState> states(P);
     for (auto& s : states) {
         s = ProblemState{};
@@ -651,8 +737,7 @@ static int32_t refresh_filter(oxhip_rrt_batch* b) {
                 const double t = sqrt_le_threshold(b->sph_radii[j]);   // valid iff d2 > t
                 f[j] = std::isfinite(t) ? (t > 0.0 ? t * (1.0 + 1e-9) : t) : t;
             }
-            int32_t st = upload(b->conn_filt, f, b->stream);
-            if (st != OXHIP_OK) return st;
+            OX_TRY(upload(b->conn_filt, f, b->stream));
             b->dp.sph_grid_G = G;
             launch_sphere_grid(b->dp, b->conn_grid.p, b->conn_filt.p, b->stream);
             b->dp.sph_grid = b->conn_grid.p;
@@ -672,12 +757,11 @@ static int32_t refresh_filter(oxhip_rrt_batch* b) {
         else if (r < 0.0) f[j] = -1.0;                       // distance > negative radius always holds
         else f[j] = (r + h) * (r + h) * (1.0 + 1e-9);
     }
-    int32_t st = upload(b->sph_filt, f, b->stream);
-    if (st != OXHIP_OK) return st;
+    OX_TRY(upload(b->sph_filt, f, b->stream));
     b->dp.sph_filt = b->sph_filt.p;
     if (b->sph_grid_p && n > 0) launch_sphere_grid(b->dp, b->sph_grid_p, b->sph_filt.p, b->stream);   // (rrt_cells.hip looks the midpoint filter up)
     if (b->star_wired) {   // motion_seq.hpp filters motions of any length: it takes the radii as given and this absolute margin
-        if ((st = upload(b->sph_r, b->sph_radii, b->stream)) != OXHIP_OK) return st;
+        OX_TRY(upload(b->sph_r, b->sph_radii, b->stream));
         b->dp.sph_r = b->sph_r.p;
         b->dp.filt_abs = 1e-9 * maxabs;
         b->dp.star_sph_grid = nullptr;
@@ -692,7 +776,7 @@ static int32_t refresh_filter(oxhip_rrt_batch* b) {
                 sf[j] = (std::isnan(r) || std::isinf(r)) ? std::numeric_limits<double>::infinity()
                                                          : std::fmax(a, c) * (1.0 + 1e-9) * (1.0 + 1e-12);
             }
-            if ((st = upload(b->star_filt, sf, b->stream)) != OXHIP_OK) return st;
+            OX_TRY(upload(b->star_filt, sf, b->stream));
             launch_sphere_grid(b->dp, b->star_grid_p, b->star_filt.p, b->stream);
             b->dp.star_sph_grid = b->star_grid_p;
         }
@@ -701,18 +785,23 @@ static int32_t refresh_filter(oxhip_rrt_batch* b) {
     return OXHIP_OK;
 }
 
-static int32_t read_states(oxhip_rrt_batch* b, std::vector<ProblemState>& states);
+static int32_t read_states(oxhip_rrt_batch* b, std::vector<ProblemState>& states) {
+    states.resize(b->cfg.n_problems);
+    if (!b->h_states) HIP_TRY(hipHostMalloc((void**)&b->h_states, states.size() * sizeof(ProblemState), hipHostMallocDefault));
+    HIP_TRY(hipMemcpyAsync(b->h_states, b->state.p, states.size() * sizeof(ProblemState), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    std::memcpy(states.data(), b->h_states, states.size() * sizeof(ProblemState));
+    return OXHIP_OK;
+}
 
 int32_t oxhip_rrt_batch_set_tree(oxhip_rrt_batch* b, uint32_t problem, const double* states_in, const int32_t* parents_in,
                                  uint32_t n) {
     if (!b || !states_in || !parents_in) return fail(OXHIP_ERR_BAD_ARG, "null argument");
     drop_paths(b);
-    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
-    if (problem >= b->cfg.n_problems) return fail(OXHIP_ERR_BAD_ARG, "problem index out of range");
+    OX_TRY(setup_done(b, problem));
     if (n == 0 || n > b->cfg.max_nodes) return fail(OXHIP_ERR_BAD_ARG, "n_nodes must be in 1..max_nodes");
     if (b->cfg.planner != OXHIP_PLANNER_RRT) return fail(OXHIP_ERR_BAD_ARG, "set_tree is for the RRT planner");
-    int32_t st = select_device(b->cfg.device);
-    if (st != OXHIP_OK) return st;
+    OX_TRY(select_device(b->cfg.device));
     const uint32_t dim = b->cfg.dim, cap = b->dp.cap;
     if (parents_in[0] != -1) return fail(OXHIP_ERR_BAD_ARG, "parents[0] must be -1 (the root)");
     std::vector<double> soa((size_t)dim * n);
@@ -753,19 +842,10 @@ int32_t oxhip_rrt_batch_set_tree(oxhip_rrt_batch* b, uint32_t problem, const dou
     if (b->cell_meta_p) HIP_TRY(hipMemsetAsync(b->cell_meta_p + problem, 0, sizeof(CellMeta), b->stream));   // ... and its cell grid
     b->dp.cells_meta_ok = 0;
     std::vector<ProblemState> states;
-    if ((st = read_states(b, states)) != OXHIP_OK) return st;
+    OX_TRY(read_states(b, states));
     states[problem].n_nodes = n;
     HIP_TRY(hipMemcpyAsync(b->state.p + problem, &states[problem], sizeof(ProblemState), hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
-    return OXHIP_OK;
-}
-
-static int32_t read_states(oxhip_rrt_batch* b, std::vector<ProblemState>& states) {
-    states.resize(b->cfg.n_problems);
-    if (!b->h_states) HIP_TRY(hipHostMalloc((void**)&b->h_states, states.size() * sizeof(ProblemState), hipHostMallocDefault));
-    HIP_TRY(hipMemcpyAsync(b->h_states, b->state.p, states.size() * sizeof(ProblemState), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    std::memcpy(states.data(), b->h_states, states.size() * sizeof(ProblemState));
     return OXHIP_OK;
 }
 
@@ -776,8 +856,7 @@ static int32_t wire_new_nodes(oxhip_rrt_batch* b) {
     std::vector<ProblemState> states;
     std::vector<uint32_t> wired(P), take(P), total(P), chunks_used(P);
     for (;;) {
-        int32_t st = read_states(b, states);
-        if (st != OXHIP_OK) return st;
+        OX_TRY(read_states(b, states));
         HIP_TRY(hipMemcpyAsync(wired.data(), b->wired.p, (size_t)P * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
         HIP_TRY(hipStreamSynchronize(b->stream));
         uint32_t max_pending = 0;
@@ -833,15 +912,31 @@ static int32_t wire_new_nodes(oxhip_rrt_batch* b) {
     }
 }
 
+// R^n's launch: by planner and by the kernel kind create() resolved (KERNEL_AUTO among them), for frozen and growing launches alike
+static int32_t solve_real_vector(oxhip_rrt_batch* b) {
+    const uint32_t kind = b->kernel_kind;
+    if (b->cfg.planner == OXHIP_PLANNER_RRT_CONNECT) launch_rrt_connect(b->dp, b->stream);
+    else if (b->cfg.planner == OXHIP_PLANNER_RRT_STAR && b->star_wired) {
+        // geometry: exactly RRT's loop on the same stream (rrt_star_wire.hip's header); then wire the new nodes
+        if (b->star_geo_cells) { launch_rrt_cells(b->dp, b->stream); b->dp.cells_meta_ok = 1; } else launch_rrt_lanes(b->dp, b->stream);
+        HIP_TRY(hipGetLastError());
+        OX_TRY(wire_new_nodes(b));
+    }
+    else if (b->cfg.planner == OXHIP_PLANNER_RRT_STAR) launch_rrt_star(b->dp, b->stream);
+    else if (kind == OXHIP_KERNEL_CELLS) { launch_rrt_cells(b->dp, b->stream); b->dp.cells_meta_ok = 1; }
+    else if (kind == OXHIP_KERNEL_LANES) launch_rrt_lanes(b->dp, b->stream);
+    else if (kind == OXHIP_KERNEL_RESIDENT) launch_rrt_resident(b->dp, b->stream);
+    else launch_rrt_stream(b->dp, b->stream);
+    return OXHIP_OK;
+}
+
 int32_t oxhip_rrt_batch_solve(oxhip_rrt_batch* b, uint64_t max_iterations, double timeout_s, uint32_t freeze,
                               int32_t* status_out) {
     if (!b) return fail(OXHIP_ERR_BAD_ARG, "null batch");
     drop_paths(b);
-    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");  // rrt.rs:160-163
-    int32_t st = select_device(b->cfg.device);
-    if (st != OXHIP_OK) return st;
+    OX_TRY(ready(b));
     if (b->cfg.planner != OXHIP_PLANNER_RRT && freeze) return fail(OXHIP_ERR_BAD_ARG, "freeze is for the RRT planner");
-    if (b->cfg.space != OXHIP_SPACE_SO3 && b->cfg.space != OXHIP_SPACE_SE3 && (st = refresh_filter(b)) != OXHIP_OK) return st;   // (rrt_so3.hip tests every cone, rrt_connect_se3.hip every sphere)
+    if (space_of(b).midpoint_filter) OX_TRY(refresh_filter(b));
     if (std::isnan(timeout_s) || timeout_s < 0.0)   // Duration cannot be negative; from_secs_f32 (oxmpl-py rrt.rs:112) panics on both
         return fail(OXHIP_ERR_BAD_ARG, "timeout_s is NaN or negative (0 or +inf = no wall-clock limit)");
     const bool has_timeout = timeout_s > 0.0 && std::isfinite(timeout_s);
@@ -861,29 +956,12 @@ int32_t oxhip_rrt_batch_solve(oxhip_rrt_batch* b, uint64_t max_iterations, doubl
         uint64_t step = remaining < chunk ? remaining : chunk;
         b->dp.budget = step;
         b->dp.freeze = freeze ? 1 : 0;
-        // KERNEL_AUTO = the lane-per-query kernel wherever it exists (R^2 .. R^6, trees that fit its register rows), for frozen
-        // and growing launches alike; the stream kernel for everything else
-        uint32_t kind = b->kernel_kind;
-        b->last_kind = kind;
+        b->last_kind = b->kernel_kind;
         HIP_TRY(hipEventRecord(b->ev0, b->stream));
-        if (b->cfg.space == OXHIP_SPACE_SE2) launch_rrt_connect_se2(b->dp, b->stream);
-        else if (b->cfg.space == OXHIP_SPACE_SO3) launch_rrt_so3(b->dp, b->stream);
-        else if (b->cfg.space == OXHIP_SPACE_SE3) launch_rrt_connect_se3(b->dp, b->se3, b->stream);
-        else if (b->cfg.planner == OXHIP_PLANNER_RRT_CONNECT) launch_rrt_connect(b->dp, b->stream);
-        else if (b->cfg.planner == OXHIP_PLANNER_RRT_STAR && b->star_wired) {
-            // geometry: exactly RRT's loop on the same stream (rrt_star_wire.hip's header); then wire the new nodes
-            if (b->star_geo_cells) { launch_rrt_cells(b->dp, b->stream); b->dp.cells_meta_ok = 1; } else launch_rrt_lanes(b->dp, b->stream);
-            HIP_TRY(hipGetLastError());
-            if ((st = wire_new_nodes(b)) != OXHIP_OK) return st;
-        }
-        else if (b->cfg.planner == OXHIP_PLANNER_RRT_STAR) launch_rrt_star(b->dp, b->stream);
-        else if (kind == OXHIP_KERNEL_CELLS) { launch_rrt_cells(b->dp, b->stream); b->dp.cells_meta_ok = 1; }
-        else if (kind == OXHIP_KERNEL_LANES) launch_rrt_lanes(b->dp, b->stream);
-        else if (kind == OXHIP_KERNEL_RESIDENT) launch_rrt_resident(b->dp, b->stream);
-        else launch_rrt_stream(b->dp, b->stream);
+        OX_TRY(space_of(b).solve(b));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(b->ev1, b->stream));
-        if ((st = read_states(b, states)) != OXHIP_OK) return st;   // (the launch's one synchronisation: the stop reasons come with it)
+        OX_TRY(read_states(b, states));   // (the launch's one synchronisation: the stop reasons come with it)
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, b->ev0, b->ev1));
         b->last_kernel_ms += ms;
@@ -898,7 +976,7 @@ int32_t oxhip_rrt_batch_solve(oxhip_rrt_batch* b, uint64_t max_iterations, doubl
             break;
         }
     }
-    if (states.empty() && (st = read_states(b, states)) != OXHIP_OK) return st;   // (no launch: max_iterations = 0)
+    if (states.empty()) OX_TRY(read_states(b, states));   // (no launch: max_iterations = 0)
     for (auto& s : states)
         if (s.stop_reason == OXHIP_STOP_INTERNAL) return fail(OXHIP_ERR_HIP, "resident kernel: scanner/resolver hand-off stalled");
     if (timed_out) {
@@ -917,12 +995,9 @@ int32_t oxhip_rrt_batch_solve(oxhip_rrt_batch* b, uint64_t max_iterations, doubl
 
 int32_t oxhip_rrt_batch_get_counts(oxhip_rrt_batch* b, uint64_t* iterations, uint32_t* nodes, uint64_t* accepted,
                                    uint64_t* checksum, int32_t* goal_node, int32_t* stop_reason) {
-    if (!b) return fail(OXHIP_ERR_BAD_ARG, "null batch");
-    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
-    int32_t st = select_device(b->cfg.device);
-    if (st != OXHIP_OK) return st;
+    OX_TRY(ready(b));
     std::vector<ProblemState> states;
-    if ((st = read_states(b, states)) != OXHIP_OK) return st;
+    OX_TRY(read_states(b, states));
     if (b->cfg.planner == OXHIP_PLANNER_RRT_STAR) {   // reported checksum = H (iterations) + W (wiring), DESIGN.md section 10
         std::vector<uint64_t> w(b->cfg.n_problems);
         HIP_TRY(hipMemcpyAsync(w.data(), b->wire_chk.p, w.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
@@ -956,21 +1031,21 @@ static int32_t fetch_tree(oxhip_rrt_batch* b, uint32_t problem, uint32_t n, std:
     return OXHIP_OK;
 }
 
-int32_t oxhip_rrt_batch_get_tree(oxhip_rrt_batch* b, uint32_t problem, double* states_out, int32_t* parents_out,
-                                 uint32_t cap_nodes, uint32_t* n_nodes) {
+// One problem's start tree or (RRTConnect) goal tree, as [n][dim] rows and parent indices.
+static int32_t copy_tree(oxhip_rrt_batch* b, uint32_t problem, bool goal_tree, double* states_out, int32_t* parents_out,
+                         uint32_t cap_nodes, uint32_t* n_nodes) {
     if (!b || !n_nodes) return fail(OXHIP_ERR_BAD_ARG, "null argument");
-    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
-    if (problem >= b->cfg.n_problems) return fail(OXHIP_ERR_BAD_ARG, "problem index out of range");
-    int32_t st = select_device(b->cfg.device);
-    if (st != OXHIP_OK) return st;
+    OX_TRY(setup_done(b));
+    if (goal_tree && b->cfg.planner != OXHIP_PLANNER_RRT_CONNECT) return fail(OXHIP_ERR_BAD_ARG, "not an RRTConnect batch");
+    OX_TRY(ready(b, problem));
     std::vector<ProblemState> states;
-    if ((st = read_states(b, states)) != OXHIP_OK) return st;
-    const uint32_t n = states[problem].n_nodes, dim = b->cfg.dim;
+    OX_TRY(read_states(b, states));
+    const uint32_t n = goal_tree ? states[problem].n_nodes_b : states[problem].n_nodes, dim = b->cfg.dim;
     *n_nodes = n;
     if (n > cap_nodes || (!states_out && !parents_out)) return n > cap_nodes ? fail(OXHIP_ERR_CAPACITY, "tree buffer too small") : OXHIP_OK;
     std::vector<double> soa;
     std::vector<int32_t> par;
-    if ((st = fetch_tree(b, problem, n, soa, par)) != OXHIP_OK) return st;
+    OX_TRY(fetch_tree(b, problem, n, soa, par, goal_tree));
     if (states_out)
         for (uint32_t i = 0; i < n; ++i)
             for (uint32_t k = 0; k < dim; ++k) states_out[(size_t)i * dim + k] = soa[(size_t)k * n + i];
@@ -978,22 +1053,24 @@ int32_t oxhip_rrt_batch_get_tree(oxhip_rrt_batch* b, uint32_t problem, double* s
     return OXHIP_OK;
 }
 
+int32_t oxhip_rrt_batch_get_tree(oxhip_rrt_batch* b, uint32_t problem, double* states_out, int32_t* parents_out,
+                                 uint32_t cap_nodes, uint32_t* n_nodes) {
+    return copy_tree(b, problem, false, states_out, parents_out, cap_nodes, n_nodes);
+}
+
 int32_t oxhip_rrt_batch_get_path(oxhip_rrt_batch* b, uint32_t problem, double* states_out, uint32_t cap_states,
                                  uint32_t* len) {
     if (!b || !len) return fail(OXHIP_ERR_BAD_ARG, "null argument");
-    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
-    if (problem >= b->cfg.n_problems) return fail(OXHIP_ERR_BAD_ARG, "problem index out of range");
-    int32_t st = select_device(b->cfg.device);
-    if (st != OXHIP_OK) return st;
+    OX_TRY(ready(b, problem));
     std::vector<ProblemState> states;
-    if ((st = read_states(b, states)) != OXHIP_OK) return st;
+    OX_TRY(read_states(b, states));
     *len = 0;
     const int32_t goal = states[problem].goal_node;
     if (goal < 0) return OXHIP_OK;
     const uint32_t n = states[problem].n_nodes, dim = b->cfg.dim;
     std::vector<double> soa;
     std::vector<int32_t> par;
-    if ((st = fetch_tree(b, problem, n, soa, par)) != OXHIP_OK) return st;
+    OX_TRY(fetch_tree(b, problem, n, soa, par));
     // reconstruct_path (rrt.rs:118-128): follow parents from the goal node, reverse
     std::vector<uint32_t> chain;
     for (int64_t i = goal; i >= 0; i = par[(size_t)i]) {
@@ -1007,7 +1084,7 @@ int32_t oxhip_rrt_batch_get_path(oxhip_rrt_batch* b, uint32_t problem, double* s
     std::vector<uint32_t> chain_b;
     const uint32_t nb = states[problem].n_nodes_b;
     if (b->cfg.planner == OXHIP_PLANNER_RRT_CONNECT && states[problem].goal_node_b >= 0) {
-        if ((st = fetch_tree(b, problem, nb, soa_b, par_b, true)) != OXHIP_OK) return st;
+        OX_TRY(fetch_tree(b, problem, nb, soa_b, par_b, true));
         for (int64_t i = par_b[(size_t)states[problem].goal_node_b]; i >= 0; i = par_b[(size_t)i]) {
             chain_b.push_back((uint32_t)i);
             if (chain_b.size() > nb) return fail(OXHIP_ERR_HIP, "goal-tree parent chain is cyclic (corrupt tree)");
@@ -1026,13 +1103,11 @@ int32_t oxhip_rrt_batch_get_path(oxhip_rrt_batch* b, uint32_t problem, double* s
 }
 
 int32_t oxhip_rrt_batch_get_goal_counts(oxhip_rrt_batch* b, uint32_t* nodes, int32_t* end_node) {
-    if (!b) return fail(OXHIP_ERR_BAD_ARG, "null batch");
-    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
+    OX_TRY(setup_done(b));
     if (b->cfg.planner != OXHIP_PLANNER_RRT_CONNECT) return fail(OXHIP_ERR_BAD_ARG, "not an RRTConnect batch");
-    int32_t st = select_device(b->cfg.device);
-    if (st != OXHIP_OK) return st;
+    OX_TRY(select_device(b->cfg.device));
     std::vector<ProblemState> states;
-    if ((st = read_states(b, states)) != OXHIP_OK) return st;
+    OX_TRY(read_states(b, states));
     for (uint32_t p = 0; p < b->cfg.n_problems; ++p) {
         if (nodes) nodes[p] = states[p].n_nodes_b;
         if (end_node) end_node[p] = states[p].goal_node_b;
@@ -1042,36 +1117,16 @@ int32_t oxhip_rrt_batch_get_goal_counts(oxhip_rrt_batch* b, uint32_t* nodes, int
 
 int32_t oxhip_rrt_batch_get_goal_tree(oxhip_rrt_batch* b, uint32_t problem, double* states_out, int32_t* parents_out,
                                       uint32_t cap_nodes, uint32_t* n_nodes) {
-    if (!b || !n_nodes) return fail(OXHIP_ERR_BAD_ARG, "null argument");
-    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
-    if (b->cfg.planner != OXHIP_PLANNER_RRT_CONNECT) return fail(OXHIP_ERR_BAD_ARG, "not an RRTConnect batch");
-    if (problem >= b->cfg.n_problems) return fail(OXHIP_ERR_BAD_ARG, "problem index out of range");
-    int32_t st = select_device(b->cfg.device);
-    if (st != OXHIP_OK) return st;
-    std::vector<ProblemState> states;
-    if ((st = read_states(b, states)) != OXHIP_OK) return st;
-    const uint32_t n = states[problem].n_nodes_b, dim = b->cfg.dim;
-    *n_nodes = n;
-    if (n > cap_nodes || (!states_out && !parents_out)) return n > cap_nodes ? fail(OXHIP_ERR_CAPACITY, "tree buffer too small") : OXHIP_OK;
-    std::vector<double> soa;
-    std::vector<int32_t> par;
-    if ((st = fetch_tree(b, problem, n, soa, par, true)) != OXHIP_OK) return st;
-    if (states_out)
-        for (uint32_t i = 0; i < n; ++i)
-            for (uint32_t k = 0; k < dim; ++k) states_out[(size_t)i * dim + k] = soa[(size_t)k * n + i];
-    if (parents_out) std::memcpy(parents_out, par.data(), (size_t)n * sizeof(int32_t));
-    return OXHIP_OK;
+    return copy_tree(b, problem, true, states_out, parents_out, cap_nodes, n_nodes);
 }
 
 int32_t oxhip_rrt_batch_get_costs(oxhip_rrt_batch* b, uint32_t problem, double* costs, uint32_t cap_nodes, uint32_t* n_nodes) {
     if (!b || !n_nodes) return fail(OXHIP_ERR_BAD_ARG, "null argument");
-    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
+    OX_TRY(setup_done(b));
     if (b->cfg.planner != OXHIP_PLANNER_RRT_STAR) return fail(OXHIP_ERR_BAD_ARG, "not an RRT* batch");
-    if (problem >= b->cfg.n_problems) return fail(OXHIP_ERR_BAD_ARG, "problem index out of range");
-    int32_t st = select_device(b->cfg.device);
-    if (st != OXHIP_OK) return st;
+    OX_TRY(ready(b, problem));
     std::vector<ProblemState> states;
-    if ((st = read_states(b, states)) != OXHIP_OK) return st;
+    OX_TRY(read_states(b, states));
     const uint32_t n = states[problem].n_nodes;
     *n_nodes = n;
     if (!costs) return OXHIP_OK;
@@ -1084,9 +1139,7 @@ int32_t oxhip_rrt_batch_get_costs(oxhip_rrt_batch* b, uint32_t problem, double* 
 // ------------------------------------------------------------------ the whole batch's paths (path_simplify.hip)
 
 int32_t oxhip_rrt_batch_extract_paths(oxhip_rrt_batch* b) {
-    if (!b) return fail(OXHIP_ERR_BAD_ARG, "null batch");
-    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
-    OX_TRY(select_device(b->cfg.device));
+    OX_TRY(ready(b));
     drop_paths(b);
     const uint32_t P = b->cfg.n_problems, dim = b->cfg.dim;
     HIP_TRY(grow(b->path_len, P));
@@ -1126,7 +1179,7 @@ int32_t oxhip_rrt_batch_extract_paths(oxhip_rrt_batch* b) {
 
 int32_t oxhip_rrt_batch_get_paths(oxhip_rrt_batch* b, uint64_t* offsets_out, double* states_out, uint64_t cap_states, uint64_t* total_out) {
     if (!b || !total_out) return fail(OXHIP_ERR_BAD_ARG, "null argument");
-    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
+    OX_TRY(setup_done(b));
     if (!b->paths_ok) return fail(OXHIP_ERR_BAD_ARG, "no extracted paths: call oxhip_rrt_batch_extract_paths after the last setup / solve / set_tree");
     OX_TRY(select_device(b->cfg.device));
     const uint32_t P = b->cfg.n_problems;
@@ -1146,7 +1199,7 @@ static constexpr uint64_t kPairWordsMax = (1ull << 30) / sizeof(uint64_t);
 // the batch's parameters as the pair kernel reads them (R^n: the radii and the absolute margin of motion_seq.hpp's midpoint filter)
 static int32_t pair_params(oxhip_rrt_batch* b, double& filt_base) {
     filt_base = 0.0;
-    if (b->cfg.space != OXHIP_SPACE_REAL_VECTOR) return OXHIP_OK;
+    if (!space_of(b).midpoint_filter) return OXHIP_OK;
     if (b->dp.n_spheres != 0) {
         OX_TRY(upload(b->sph_r, b->sph_radii, b->stream));
         b->dp.sph_r = b->sph_r.p;
@@ -1159,16 +1212,14 @@ static int32_t pair_params(oxhip_rrt_batch* b, double& filt_base) {
 }
 
 static int32_t simplify_supported(const oxhip_rrt_batch* b) {
-    if (b->cfg.space == OXHIP_SPACE_SE2 || b->cfg.space == OXHIP_SPACE_SE3)
-        return fail(OXHIP_ERR_BAD_ARG, "simplify_paths is not built for SE(2) / SE(3) batches (their motion checks live inside their planners' kernels)");
-    if (b->cfg.space == OXHIP_SPACE_REAL_VECTOR && b->cfg.dim < 2)
+    if (space_of(b).no_simplify) return fail(OXHIP_ERR_BAD_ARG, space_of(b).no_simplify);
+    if (b->cfg.dim < 2)   // (R^1: every other space is wider)
         return fail(OXHIP_ERR_BAD_ARG, "simplify_paths is not built for dim 1 (R^2 .. R^8 and SO(3))");
     return OXHIP_OK;
 }
 
 int32_t oxhip_rrt_batch_simplify_paths(oxhip_rrt_batch* b, uint32_t max_span, uint32_t chunk_problems) {
-    if (!b) return fail(OXHIP_ERR_BAD_ARG, "null batch");
-    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
+    OX_TRY(setup_done(b));
     OX_TRY(simplify_supported(b));
     OX_TRY(select_device(b->cfg.device));
     b->simp_ok = false;
@@ -1230,7 +1281,7 @@ int32_t oxhip_rrt_batch_simplify_paths(oxhip_rrt_batch* b, uint32_t max_span, ui
 int32_t oxhip_rrt_batch_get_simplified_paths(oxhip_rrt_batch* b, uint64_t* offsets_out, double* states_out, uint32_t* indices_out,
                                              uint64_t cap_states, uint64_t* total_out) {
     if (!b || !total_out) return fail(OXHIP_ERR_BAD_ARG, "null argument");
-    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
+    OX_TRY(setup_done(b));
     if (!b->simp_ok || !b->paths_ok)
         return fail(OXHIP_ERR_BAD_ARG, "no simplified paths: call oxhip_rrt_batch_simplify_paths after the last setup / solve / set_tree");
     OX_TRY(select_device(b->cfg.device));
@@ -1265,8 +1316,7 @@ int32_t oxhip_rrt_batch_get_simplified_paths(oxhip_rrt_batch* b, uint64_t* offse
 }
 
 int32_t oxhip_rrt_batch_get_simplify_results(oxhip_rrt_batch* b, double* raw_cost, double* simplified_cost, uint64_t* checks) {
-    if (!b) return fail(OXHIP_ERR_BAD_ARG, "null batch");
-    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
+    OX_TRY(setup_done(b));
     if (!b->simp_ok || !b->paths_ok)
         return fail(OXHIP_ERR_BAD_ARG, "no simplified paths: call oxhip_rrt_batch_simplify_paths after the last setup / solve / set_tree");
     OX_TRY(select_device(b->cfg.device));
@@ -1281,8 +1331,7 @@ int32_t oxhip_rrt_batch_get_simplify_results(oxhip_rrt_batch* b, double* raw_cos
 int32_t oxhip_rrt_batch_path_valid_matrix(oxhip_rrt_batch* b, uint32_t problem, uint32_t max_span, uint8_t* out, uint64_t cap_bytes,
                                           uint32_t* len_out) {
     if (!b || !len_out) return fail(OXHIP_ERR_BAD_ARG, "null argument");
-    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
-    if (problem >= b->cfg.n_problems) return fail(OXHIP_ERR_BAD_ARG, "problem index out of range");
+    OX_TRY(setup_done(b, problem));
     OX_TRY(simplify_supported(b));
     if (!b->paths_ok) return fail(OXHIP_ERR_BAD_ARG, "no extracted paths: call oxhip_rrt_batch_extract_paths after the last setup / solve / set_tree");
     OX_TRY(select_device(b->cfg.device));
@@ -1333,8 +1382,7 @@ int32_t oxhip_rrt_batch_last_timing(oxhip_rrt_batch* b, double* kernel_ms, uint3
 
 int32_t oxhip_rrt_batch_enable_stamps(oxhip_rrt_batch* b, uint32_t enable) {
     if (!b) return fail(OXHIP_ERR_BAD_ARG, "null batch");
-    int32_t st = select_device(b->cfg.device);
-    if (st != OXHIP_OK) return st;
+    OX_TRY(select_device(b->cfg.device));
     if (enable) {
         HIP_TRY(b->dbg.alloc(OXHIP_STAMP_WORDS));
         HIP_TRY(hipMemsetAsync(b->dbg.p, 0, OXHIP_STAMP_WORDS * sizeof(uint64_t), b->stream));
@@ -1349,8 +1397,7 @@ int32_t oxhip_rrt_batch_enable_stamps(oxhip_rrt_batch* b, uint32_t enable) {
 int32_t oxhip_rrt_batch_get_stamps(oxhip_rrt_batch* b, uint64_t* out, uint32_t cap_words) {
     if (!b || !out) return fail(OXHIP_ERR_BAD_ARG, "null argument");
     if (!b->dp.dbg) return fail(OXHIP_ERR_BAD_ARG, "stamps are not enabled");
-    int32_t st = select_device(b->cfg.device);
-    if (st != OXHIP_OK) return st;
+    OX_TRY(select_device(b->cfg.device));
     const uint32_t n = cap_words < OXHIP_STAMP_WORDS ? cap_words : OXHIP_STAMP_WORDS;
     if (n) HIP_TRY(hipMemcpyAsync(out, b->dbg.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
@@ -1373,8 +1420,7 @@ int32_t oxhip_nn_argmin_batch(int32_t device, uint32_t dim, const double* nodes,
         total += n_nodes[q];
     }
     TmpStream ts;
-    HIP_TRY(oxhip_stream_acquire(device, &ts.s));
-    ts.device = device;
+    OX_TRY(ts.acquire(device));
     DevBuf<double> d_nodes, d_q, d_dist;
     DevBuf<uint64_t> d_off;
     DevBuf<uint32_t> d_n, d_idx;
@@ -1394,37 +1440,16 @@ int32_t oxhip_nn_argmin_batch(int32_t device, uint32_t dim, const double* nodes,
 int32_t oxhip_distance_batch(int32_t device, uint32_t dim, const double* a, const double* b, uint32_t n, double* out) {
     if (!a || !b || !out) return fail(OXHIP_ERR_BAD_ARG, "null argument");
     if (dim == 0 || dim > OXHIP_MAX_DIM) return fail(OXHIP_ERR_BAD_ARG, "dim must be in 1..8");
-    if (n == 0) return OXHIP_OK;
-    OX_TRY(select_device(device));
-    TmpStream ts;
-    HIP_TRY(oxhip_stream_acquire(device, &ts.s));
-    ts.device = device;
-    DevBuf<double> da, db, dout;
-    OX_TRY(to_device(da, a, (size_t)n * dim, ts.s));
-    OX_TRY(to_device(db, b, (size_t)n * dim, ts.s));
-    HIP_TRY(dout.alloc(n));
-    launch_distance(dim, da.p, db.p, n, dout.p, ts.s);
-    HIP_TRY(hipGetLastError());
-    return to_host(out, dout, n, ts.s);
+    return op_batch(device, a, b, nullptr, n, out, dim, dim, 1, true, false,
+                    [=](const double* da, const double* db, const double*, double* dout, hipStream_t s) { launch_distance(dim, da, db, n, dout, s); });
 }
 
 int32_t oxhip_interpolate_batch(int32_t device, uint32_t dim, const double* from, const double* to, const double* t,
                                 uint32_t n, double* out) {
     if (!from || !to || !t || !out) return fail(OXHIP_ERR_BAD_ARG, "null argument");
     if (dim == 0 || dim > OXHIP_MAX_DIM) return fail(OXHIP_ERR_BAD_ARG, "dim must be in 1..8");
-    if (n == 0) return OXHIP_OK;
-    OX_TRY(select_device(device));
-    TmpStream ts;
-    HIP_TRY(oxhip_stream_acquire(device, &ts.s));
-    ts.device = device;
-    DevBuf<double> da, db, dt, dout;
-    OX_TRY(to_device(da, from, (size_t)n * dim, ts.s));
-    OX_TRY(to_device(db, to, (size_t)n * dim, ts.s));
-    OX_TRY(to_device(dt, t, n, ts.s));
-    HIP_TRY(dout.alloc((size_t)n * dim));
-    launch_interpolate(dim, da.p, db.p, dt.p, n, dout.p, ts.s);
-    HIP_TRY(hipGetLastError());
-    return to_host(out, dout, (size_t)n * dim, ts.s);
+    return op_batch(device, from, to, t, n, out, dim, dim, dim, true, true,
+                    [=](const double* da, const double* db, const double* dt, double* dout, hipStream_t s) { launch_interpolate(dim, da, db, dt, n, dout, s); });
 }
 
 int32_t oxhip_rrt_batch_is_valid(oxhip_rrt_batch* b, const double* states, uint32_t n, uint8_t* out) {
@@ -1435,10 +1460,7 @@ int32_t oxhip_rrt_batch_is_valid(oxhip_rrt_batch* b, const double* states, uint3
     DevBuf<uint8_t> dout;
     OX_TRY(to_device(ds, states, (size_t)n * b->cfg.dim, b->stream));
     HIP_TRY(dout.alloc(n));
-    if (b->cfg.space == OXHIP_SPACE_SE2) launch_se2_is_valid(b->dp, ds.p, n, dout.p, b->stream);
-    else if (b->cfg.space == OXHIP_SPACE_SO3) launch_so3_is_valid(b->dp, ds.p, n, dout.p, b->stream);
-    else if (b->cfg.space == OXHIP_SPACE_SE3) launch_se3_is_valid(b->dp, b->se3, ds.p, n, dout.p, b->stream);
-    else launch_is_valid(b->dp, ds.p, n, dout.p, b->stream);
+    space_of(b).is_valid(b, ds.p, n, dout.p);
     HIP_TRY(hipGetLastError());
     return to_host(out, dout, n, b->stream);
 }
@@ -1452,10 +1474,7 @@ int32_t oxhip_rrt_batch_check_motion(oxhip_rrt_batch* b, const double* from, con
     OX_TRY(to_device(da, from, (size_t)n * b->cfg.dim, b->stream));
     OX_TRY(to_device(db, to, (size_t)n * b->cfg.dim, b->stream));
     HIP_TRY(dout.alloc(n));
-    if (b->cfg.space == OXHIP_SPACE_SE2) launch_se2_check_motion(b->dp, da.p, db.p, n, dout.p, b->stream);
-    else if (b->cfg.space == OXHIP_SPACE_SO3) launch_so3_check_motion(b->dp, da.p, db.p, n, dout.p, b->stream);
-    else if (b->cfg.space == OXHIP_SPACE_SE3) launch_se3_check_motion(b->dp, b->se3, da.p, db.p, n, dout.p, b->stream);
-    else launch_check_motion(b->dp, da.p, db.p, n, dout.p, b->stream);
+    space_of(b).check_motion(b, da.p, db.p, n, dout.p);
     HIP_TRY(hipGetLastError());
     return to_host(out, dout, n, b->stream);
 }
@@ -1465,76 +1484,29 @@ int32_t oxhip_f64_op_batch(int32_t device, uint32_t op, const double* a, const d
     if (!a || !out || op > 6) return fail(OXHIP_ERR_BAD_ARG, "bad argument");
     if ((op == 1 || op == 3 || op == 4) && !b) return fail(OXHIP_ERR_BAD_ARG, "operand b required");
     if (op == 3 && !c) return fail(OXHIP_ERR_BAD_ARG, "operand c required");
-    if (n == 0) return OXHIP_OK;
-    OX_TRY(select_device(device));
-    TmpStream ts;
-    HIP_TRY(oxhip_stream_acquire(device, &ts.s));
-    ts.device = device;
-    DevBuf<double> da, db, dc, dout;
-    OX_TRY(to_device(da, a, n, ts.s));
-    if (b) OX_TRY(to_device(db, b, n, ts.s));
-    if (c) OX_TRY(to_device(dc, c, n, ts.s));
-    HIP_TRY(dout.alloc(n));
-    launch_f64_op(op, da.p, db.p, dc.p, n, dout.p, ts.s);
-    HIP_TRY(hipGetLastError());
-    return to_host(out, dout, n, ts.s);
+    return op_batch(device, a, b, c, n, out, 1, 1, 1, b != nullptr, c != nullptr,
+                    [=](const double* da, const double* db, const double* dt, double* dout, hipStream_t s) { launch_f64_op(op, da, db, dt, n, dout, s); });
 }
 
 int32_t oxhip_se2_op_batch(int32_t device, uint32_t op, const double* a, const double* b, const double* t, uint32_t n,
                            double* out) {
     if (!a || !b || !out || op > 1 || (op == 1 && !t)) return fail(OXHIP_ERR_BAD_ARG, "bad argument");
-    if (n == 0) return OXHIP_OK;
-    OX_TRY(select_device(device));
-    TmpStream ts;
-    HIP_TRY(oxhip_stream_acquire(device, &ts.s));
-    ts.device = device;
-    DevBuf<double> da, db, dt, dout;
-    OX_TRY(to_device(da, a, (size_t)3 * n, ts.s));
-    OX_TRY(to_device(db, b, (size_t)3 * n, ts.s));
-    if (t) OX_TRY(to_device(dt, t, n, ts.s));
-    HIP_TRY(dout.alloc((size_t)3 * n));
-    launch_se2_op(op, da.p, db.p, dt.p, n, dout.p, ts.s);
-    HIP_TRY(hipGetLastError());
-    return to_host(out, dout, (size_t)3 * n, ts.s);
+    return op_batch(device, a, b, t, n, out, 3, 3, 3, true, t != nullptr,
+                    [=](const double* da, const double* db, const double* dt, double* dout, hipStream_t s) { launch_se2_op(op, da, db, dt, n, dout, s); });
 }
 
 int32_t oxhip_so3_op_batch(int32_t device, uint32_t op, const double* a, const double* b, const double* t, uint32_t n,
                            double* out) {
     if (!a || !out || op > 2 || (op <= 1 && !b) || (op == 1 && !t)) return fail(OXHIP_ERR_BAD_ARG, "bad argument");
-    if (n == 0) return OXHIP_OK;
-    OX_TRY(select_device(device));
-    TmpStream ts;
-    HIP_TRY(oxhip_stream_acquire(device, &ts.s));
-    ts.device = device;
-    const size_t w = op == 2 ? 1 : 4;          // doubles per row of a (and b)
-    const size_t w_out = op == 1 ? 4 : 1;      // ... of out
-    DevBuf<double> da, db, dt, dout;
-    OX_TRY(to_device(da, a, w * n, ts.s));
-    if (op <= 1) OX_TRY(to_device(db, b, (size_t)4 * n, ts.s));
-    if (op == 1) OX_TRY(to_device(dt, t, n, ts.s));
-    HIP_TRY(dout.alloc(w_out * n));
-    launch_so3_op(op, da.p, db.p, dt.p, n, dout.p, ts.s);
-    HIP_TRY(hipGetLastError());
-    return to_host(out, dout, w_out * n, ts.s);
+    return op_batch(device, a, b, t, n, out, op == 2 ? 1 : 4, 4, op == 1 ? 4 : 1, op <= 1, op == 1,
+                    [=](const double* da, const double* db, const double* dt, double* dout, hipStream_t s) { launch_so3_op(op, da, db, dt, n, dout, s); });
 }
 
 int32_t oxhip_se3_op_batch(int32_t device, uint32_t op, const double* a, const double* b, const double* t, uint32_t n,
                            double* out) {
     if (!a || !b || !out || op > 2 || (op == 1 && !t)) return fail(OXHIP_ERR_BAD_ARG, "bad argument");
-    if (n == 0) return OXHIP_OK;
-    OX_TRY(select_device(device));
-    TmpStream ts;
-    HIP_TRY(oxhip_stream_acquire(device, &ts.s));
-    ts.device = device;
-    const size_t w_out = op == 0 ? 1 : (op == 1 ? 7 : 3);   // doubles per row of out
-    DevBuf<double> da, db, dt, dout;
-    OX_TRY(to_device(da, a, (size_t)7 * n, ts.s));
-    OX_TRY(to_device(db, b, (size_t)7 * n, ts.s));
-    if (op == 1) OX_TRY(to_device(dt, t, n, ts.s));
-    HIP_TRY(dout.alloc(w_out * n));
-    launch_se3_op(op, da.p, db.p, dt.p, n, dout.p, ts.s);
-    HIP_TRY(hipGetLastError());
-    return to_host(out, dout, w_out * n, ts.s);
+    return op_batch(device, a, b, t, n, out, 7, 7, op == 0 ? 1 : (op == 1 ? 7 : 3), true, op == 1,
+                    [=](const double* da, const double* db, const double* dt, double* dout, hipStream_t s) { launch_se3_op(op, da, db, dt, n, dout, s); });
 }
 
 int32_t oxhip_rng_u64_batch(int32_t device, uint64_t seed, uint64_t stream, uint32_t n, uint64_t* out) {
@@ -1542,8 +1514,7 @@ int32_t oxhip_rng_u64_batch(int32_t device, uint64_t seed, uint64_t stream, uint
     if (n == 0) return OXHIP_OK;
     OX_TRY(select_device(device));
     TmpStream ts;
-    HIP_TRY(oxhip_stream_acquire(device, &ts.s));
-    ts.device = device;
+    OX_TRY(ts.acquire(device));
     DevBuf<uint64_t> dout;
     HIP_TRY(dout.alloc(n));
     launch_rng_u64(seed, stream, n, dout.p, ts.s);

@@ -1,5 +1,10 @@
 // oxhip_host.hpp -- host-side helpers shared by the C-ABI translation units (oxhip_api.hip: RRT /
 // RRTConnect batches and primitives; oxhip_prm_api.hip: PRM).  Not installed.
+//
+// What oxhip_api.hip builds from them: the table of spaces (kSpaces, one row per oxhip_space) and create() in its steps --
+// validate_config (pure host code: space_resolution, se_space_resolution and so3_space_resolution below), fill_params,
+// alloc_common (alloc_star at its place), the kernel kind, alloc_cells, alloc_shadow -- and the entry points' shared openings
+// (setup_done / ready) and bodies (copy_tree, op_batch with a TmpStream).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -7,6 +12,7 @@
 
 #include <cmath>
 #include <limits>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -92,6 +98,9 @@ struct DevBuf {
     }
 };
 
+// what create() answers when one of its device allocations failed
+inline int32_t alloc_failed(hipError_t e) { return fail(OXHIP_ERR_HIP, std::string("device allocation failed: ") + hipGetErrorString(e)); }
+
 // Streams are recycled.  On this stack hipStreamCreate takes 1.5 ms and hipStreamDestroy 1.7 ms (rocprofv3 --hip-trace of
 // tools/bench_single.py, profiles/r3_single/hip_api_stats.csv) -- more than every other call of a one-problem Planner::solve together,
 // kernel included -- so a destroyed planner's stream (drained) goes to a small per-device pool and the next create takes it from
@@ -99,10 +108,16 @@ struct DevBuf {
 hipError_t oxhip_stream_acquire(int device, hipStream_t* out);   // non-blocking streams; `device` is the current device
 void oxhip_stream_release(int device, hipStream_t s);            // synchronises s first
 
-struct TmpStream {
+struct TmpStream {   // a pooled stream for one call of a stand-alone primitive
     hipStream_t s = nullptr;
     int device = 0;
     ~TmpStream() { if (s) oxhip_stream_release(device, s); }
+    int32_t acquire(int dev) {   // `dev` is the current device
+        hipError_t e = oxhip_stream_acquire(dev, &s);
+        if (e != hipSuccess) return fail(OXHIP_ERR_HIP, std::string("oxhip_stream_acquire(device, &ts.s): ") + hipGetErrorString(e));
+        device = dev;
+        return OXHIP_OK;
+    }
 };
 template <typename T>
 int32_t to_device(DevBuf<T>& buf, const T* host, size_t n, hipStream_t s) {
@@ -151,6 +166,19 @@ inline int32_t space_resolution(uint32_t dim, const double* bounds, double& frac
     double lvsl = extent * fraction;  // rvss.rs:251-253
     res = lvsl * 0.1;                 // rrt.rs:97
     if (!(res > 0.0)) return fail(OXHIP_ERR_BAD_ARG, "longest valid segment length is 0: check_motion would never terminate");
+    return OXHIP_OK;
+}
+
+// SE(2) / SE(3): the first n bounds pairs are (x, y[, z]), validated as RealVectorStateSpace::new(n, ..) (which also clamps the
+// fraction); extent = extent_xy[z] + 0.5 * PI (so2_state_space.rs:78-80; the rotation's extent likewise), lvsl = extent * fraction,
+// res = lvsl * 0.1.  Sequential sum of squared widths, one sqrt, one add, two multiplies.
+inline int32_t se_space_resolution(uint32_t n, const double* bounds, double& fraction, double& res) {
+    OX_TRY(space_resolution(n, bounds, fraction, res));
+    double acc = 0.0;
+    for (uint32_t k = 0; k < n; ++k) { double w = bounds[2 * k + 1] - bounds[2 * k]; double sq = w * w; acc = acc + sq; }
+    const double extent = std::sqrt(acc) + 0.5 * 3.14159265358979323846;
+    const double lvsl = extent * fraction;
+    res = lvsl * 0.1;
     return OXHIP_OK;
 }
 

@@ -267,7 +267,7 @@ int32_t oxhip_prm_create(const oxhip_prm_config* cfg, oxhip_prm** out) {
     }
     OX_TRY(select_device(cfg->device));
 
-    auto* h = new oxhip_prm();
+    std::unique_ptr<oxhip_prm, decltype(&oxhip_prm_destroy)> h(new oxhip_prm(), oxhip_prm_destroy);   // (an early return destroys it)
     h->cfg = *cfg;
     h->cfg.lvs_fraction = fraction;
     const uint32_t dim = cfg->dim;
@@ -304,17 +304,13 @@ int32_t oxhip_prm_create(const oxhip_prm_config* cfg, oxhip_prm** out) {
     chk(h->flags.alloc(cap));
     chk(h->start_valid.alloc(1));
     chk(h->offsets.alloc((size_t)cap + 1));
-    if (e != hipSuccess) {
-        std::string msg = std::string("device allocation failed: ") + hipGetErrorString(e);
-        oxhip_prm_destroy(h);
-        return fail(OXHIP_ERR_HIP, msg);
-    }
+    if (e != hipSuccess) return alloc_failed(e);
     h->args.ms = h->ms.p;
     h->args.ms32 = h->ms32.p;
     h->args.cap = cap;
     h->args.stream = cfg->stream;
     h->args.state = h->state.p;
-    *out = h;
+    *out = h.release();
     return OXHIP_OK;
 }
 
