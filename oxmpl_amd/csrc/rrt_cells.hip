@@ -44,15 +44,13 @@ static_assert(kBruteMax <= kFlatCap, "the flat list holds the small trees");
 constexpr int kCellsWaves = 4;                       // waves (= problems, or parts of problems) per workgroup
 constexpr uint32_t kSelfSkipMax = 4;                 // up to this many parts, a part skips ahead to its start itself
 constexpr uint32_t kMaxSplit = 64;                   // parts a frozen launch of one problem is cut into, at most (cell_part_pos's row length)
+constexpr int kWholeTreeUnroll = 4;                  // the whole-tree path's chunks of 256 nodes in flight (whole_tree_nearest)
 constexpr int kMaxShell = 6;                         // the cooperative search gives up beyond this ring (-> whole-tree path)
 #ifndef OXHIP_CELLS_NB
 #define OXHIP_CELLS_NB 4                             // neighbour cells in flight per trip
 #endif
 #ifndef OXHIP_ABLATE
 #define OXHIP_ABLATE 0   // (timing experiments only: 1 no sphere pre-filter, 2 no neighbour cells, 4 no motion check, 8 first trip without faces)
-#endif
-#ifndef OXHIP_CELLS_WT_UNROLL
-#define OXHIP_CELLS_WT_UNROLL 4
 #endif
 #ifndef OXHIP_CELLS_NB_FROZEN
 #define OXHIP_CELLS_NB_FROZEN 3                      // ... of a frozen launch (three waves per SIMD hide the latency; 16 registers per cell in flight)
@@ -169,8 +167,7 @@ __device__ __forceinline__ void cells_insert_finish(CellBlock* blk, uint32_t& po
         const int j = __ffsll((unsigned long long)over) - 1;
         over &= over - 1;
         const uint32_t cj = (uint32_t)__builtin_amdgcn_readlane((int)cell, j), sj = (uint32_t)__builtin_amdgcn_readlane((int)slot, j);
-        const uint64_t ej = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(entry >> 32), j) << 32) |
-                            (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)entry, j);
+        const uint64_t ej = readlane_u64(entry, j);
         uint32_t b = cj;
         for (uint32_t t = 0; t < sj / kBlkEntries; ++t) {
             // (this wave's earlier link stores have landed: a wait, not a cache flush -- only this wave ever touches the problem's blocks)
@@ -637,18 +634,7 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
     }
     const uint32_t budget = j_hi - j_lo;
 
-    // P^lane for the batched checksum (H <- H P^m + sum_j g_j P^(m-1-j)); P^64 for a full batch
-    uint64_t pw = 1;
-    {
-        uint64_t base = kFnvPrime;
-#pragma unroll
-        for (int b = 0; b < 6; ++b) {
-            if ((lane >> b) & 1u) pw *= base;
-            base *= base;
-        }
-    }
-    const uint64_t pw64 = uni64(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pw >> 32), 63) << 32 |
-                                 (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pw, 63)) * kFnvPrime);
+    const uint64_t pw = chk_lane_power(lane), pw64 = readlane_u64(pw, 63) * kFnvPrime;   // the batched checksum's P^lane, P^64
 
     RngWindow rng;
     rng.init(sh->rng_buf, p.seed, p.first_problem_id + prob, pos_start);
@@ -676,7 +662,6 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
     double memo_g = 0.0, memo_q[D];
 #pragma unroll
     for (int k = 0; k < D; ++k) memo_q[k] = 0.0;
-    typedef double ldouble4 __attribute__((ext_vector_type(4)));
 
     while (true) {
         if (jr >= budget) { stop = 1; break; }
@@ -712,9 +697,7 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
         const double A = sqrt((double)D) * (grid.delta_node + (double)(gmax + 8u) * 0x1p-23) * 1.01 + 1e-30;
         int verdict;   // 0 proven, 2 ambiguous (whole-tree path)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // this wave's own earlier stores (tree, cell blocks) have landed: the loads below may read them
-        bool from_memo = act && memo_n == n;
-#pragma unroll
-        for (int k = 0; k < D; ++k) from_memo = from_memo && __double_as_longlong(q[k]) == __double_as_longlong(memo_q[k]);
+        const bool from_memo = act && memo_matches<D>(memo_n, memo_q, n, q);
         if (grid.level == 0) {
             // every node, by index: a coalesced load gives each lane one node of the next 64, then node after node is
             // broadcast from its lane (v_readlane -> scalar operands): no memory latency per node
@@ -1049,71 +1032,17 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
                 const uint64_t m = p.sph_grid[D == 3 ? (ci[2] * p.sph_grid_G + ci[1]) * p.sph_grid_G + ci[0] : ci[1] * p.sph_grid_G + ci[0]];
                 cand = inside ? m : ~0ull;
             }
-            uint32_t maybe_lo = (uint32_t)cand, maybe_hi = (uint32_t)(cand >> 32);
-            {
-                uint64_t rem = ((uint64_t)maybe_hi << 32) | maybe_lo;
-                if (ns64 < 64) rem &= (1ull << ns64) - 1ull;
-                uint64_t keep = 0;
-                while (__ballot(rem != 0) != 0) {
-                    const bool has = rem != 0;
-                    const uint32_t o = has ? (uint32_t)(__ffsll((unsigned long long)rem) - 1) : 0u;
-                    double c[D];
-#pragma unroll
-                    for (int k = 0; k < D; ++k) c[k] = shared.obs[k][o];
-                    if (has && sphere_maybe_hit<DIM>(c, shared.obs[D + 1][o], mid)) keep |= 1ull << o;
-                    rem &= rem - 1;
-                }
-                maybe_lo = (uint32_t)keep;
-                maybe_hi = (uint32_t)(keep >> 32);
-            }
-            const uint64_t maybe = ((uint64_t)maybe_hi << 32) | maybe_lo;
+            if (ns64 < 64) cand &= (1ull << ns64) - 1ull;
+            const uint64_t maybe = spheres_maybe_hit<D>(shared.obs, cand, mid);   // (the binary64 filter)
             OXHIP_CPHASE(2);   // sphere filter
             const bool need = !(OXHIP_ABLATE & 4) && act && !amb && (maybe != 0 || extras);
-            if (__ballot(need) != 0) {
-                // ... and every lane steps through its own motion against just those (is_valid is pure: testing all states
-                // equals the reference's first-invalid early exit)
-                const double dist = sqrt(dist2<DIM>(q_near, qn, DIM));
-                const uint32_t nsteps = num_steps_u32(dist, p.res);
-                const uint32_t steps_l = need ? (nsteps <= 1 ? 1u : nsteps) : 0u;
-                const uint32_t smax = wave_max_u32(steps_l);
-                const double dn = (double)nsteps;
-                for (uint32_t s = 1; s <= smax && s != 0; ++s) {
-                    const bool on = s <= steps_l;
-                    double x[D];
-                    {
-                        const double t = (double)s / dn;
-                        double xi[D];
-                        lerp<DIM>(q_near, qn, t, xi, DIM);
-#pragma unroll
-                        for (int k = 0; k < D; ++k) x[k] = nsteps <= 1 ? qn[k] : xi[k];   // num_steps <= 1: is_valid(to) only
-                    }
-                    uint64_t rem = on ? maybe : 0ull;
-                    while (__ballot(rem != 0) != 0) {
-                        const bool has = rem != 0;
-                        const uint32_t o = has ? (uint32_t)(__ffsll((unsigned long long)rem) - 1) : 0u;
-                        double c[D];
-#pragma unroll
-                        for (int k = 0; k < D; ++k) c[k] = shared.obs[k][o];
-                        bad = bad || (has && !(dist2<D>(c, x, DIM) > shared.obs[D][o]));
-                        rem &= rem - 1;
-                    }
-                    for (uint32_t jx = ns64; jx < nobs; ++jx) bad = bad || (on && obstacle_hit<DIM>(p, DIM, x, jx));
-                }
-            }
+            bad = motion_own_lane<D>(p, shared.obs, need, maybe, q_near, qn, ns64, nobs, [](uint32_t) {});
         }
         OXHIP_CPHASE(3);   // motion check
         bool ok = act && !bad;
         constexpr bool ins = !FROZEN;
         float nf_a[D], nf_cc;
-        {
-            double sq = 0.0;
-#pragma unroll
-            for (int k = 0; k < D; ++k) {
-                nf_a[k] = (float)(qn[k] - c0[k]);
-                sq += (double)nf_a[k] * (double)nf_a[k];
-            }
-            nf_cc = (float)sq;
-        }
+        node_f32<D>(qn, c0, nf_a, nf_cc);
 
         // ---- the prefix this round may commit
         uint32_t cut = m;
@@ -1174,8 +1103,7 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
                 if (dirtym == 0) break;
                 const uint32_t c = (uint32_t)(__ffsll((unsigned long long)dirtym) - 1);
                 if (STAMP) ++n_cut_conflict;
-                const uint64_t candm = uni64(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((confl & newm) >> 32), (int)c) << 32) |
-                                             (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(confl & newm), (int)c));
+                const uint64_t candm = readlane_u64(confl & newm, (int)c);
                 double qc[D];
 #pragma unroll
                 for (int k = 0; k < D; ++k) qc[k] = unid(sh->q[k][(jr + c) & 63u]);
@@ -1198,27 +1126,15 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
                     steer<DIM>(p, false, g1, q_near1, qc, qn1);
                     bool ok1 = true;
                     if (nobs > 0) {
-                        double mid1[D];
-                        lerp<DIM>(q_near1, qn1, 0.5, mid1, DIM);
                         double oc[D];
 #pragma unroll
                         for (int k = 0; k < D; ++k) oc[k] = shared.obs[k][lane];
-                        const double othr = shared.obs[D][lane], ofilt = shared.obs[D + 1][lane];
-                        if (__ballot(sphere_maybe_hit<DIM>(oc, ofilt, mid1)) != 0 || extras)
-                            ok1 = motion_lanes<DIM>(p, lane, q_near1, qn1, oc, othr, ofilt, ns64);
+                        ok1 = motion_wave<D>(p, lane, q_near1, qn1, oc, shared.obs[D][lane], shared.obs[D + 1][lane], ns64, extras);
                     }
                     const bool dup1 = g1 == 0.0;
                     const bool hit1 = ok1 && dist2<D>(qn1, goal_c, DIM) <= goal_thr;
                     float na1[D], ncc1;
-                    {
-                        double sq = 0.0;
-#pragma unroll
-                        for (int k = 0; k < D; ++k) {
-                            na1[k] = (float)(qn1[k] - c0[k]);
-                            sq += (double)na1[k] * (double)na1[k];
-                        }
-                        ncc1 = (float)sq;
-                    }
+                    node_f32<D>(qn1, c0, na1, ncc1);
                     if (lane == c) {
                         nearest = nearest1;
                         g = g1;
@@ -1312,16 +1228,7 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
             }
             if (STAMP) { const uint64_t nw = (uint64_t)clock64(); t_c[2] += nw - t_cm; t_cm = nw; }
             // checksum: H <- H P^cut + sum_{j < cut} g_j P^(cut-1-j)
-            {
-                const uint64_t gd = iter_digest<D>(nearest, qn, DIM, ok);
-                const int src = mine ? (int)(cut - 1u - lane) : 0;
-                const uint64_t w = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(pw >> 32), src, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)pw, src, 64);
-                const uint64_t sum = wave_sum_u64((mine && !(FROZEN && amb)) ? gd * w : 0ull);
-                const uint64_t pc = cut >= 64u ? pw64
-                                               : uni64(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pw >> 32), (int)cut) << 32) |
-                                                       (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pw, (int)cut));
-                st.checksum = st.checksum * pc + sum;
-            }
+            st.checksum = chk_push_round<D>(st.checksum, pw, pw64, lane, cut, !(FROZEN && amb), nearest, qn, ok);
             if (ins && grid.level != 0) {
                 if (STAMP) { const uint64_t nw = (uint64_t)clock64(); t_c[0] += nw - t_cm; t_cm = nw; }
                 cells_insert_finish(blk, grid.pool_next, ins_cell, ins_entry, ins_link, ins_slot, lane);
@@ -1329,8 +1236,7 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
             }
             st.iterations += cut;
             st.accepted += (uint64_t)__popcll(okm & cutm);
-            draws_done = uni64((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pos_after_l, (int)(cut - 1u)) |
-                               ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pos_after_l >> 32), (int)(cut - 1u)) << 32));
+            draws_done = readlane_u64(pos_after_l, (int)(cut - 1u));
             jr += cut;
         }
         if (STAMP) { const uint64_t nw = (uint64_t)clock64(); t_c[3] += nw - t_cm; t_cm = nw; }
@@ -1338,10 +1244,9 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
         if (stop_after >= 0) { stop = stop_after; break; }
         if (FROZEN ? (ambm & first_n_mask(cut)) == 0 : (cut == m || ambm == 0 || (uint32_t)(__ffsll((unsigned long long)ambm) - 1) != cut)) continue;
 
-        // ---- the lane at `cut` is ambiguous: that one query over the WHOLE binary64 tree (the path of rrt_lanes.hip).  First
-        //      by squared distances, the wave striding over the nodes: if exactly one node is within a rounding of the
-        //      minimum, it is the reference's nearest node (sqrt is monotone).  Only a genuine near-tie -- two d2 that may
-        //      share a correctly rounded root -- takes the reference's literal loop (post-sqrt compare, lowest index).
+        // ---- the lane at `cut` is ambiguous: that one query over the WHOLE binary64 tree (the path rrt_lanes.hip takes too:
+        //      lane_query_common.hpp).  First by squared distances (whole_tree_nearest); only a genuine near-tie takes the
+        //      reference's literal loop.
         //      A FROZEN round has committed all its lanes but the ambiguous ones: each of those is settled here, in ascending
         //      lane order -- among the band nodes when the resolver takes it, over the whole tree otherwise -- and its term
         //      g_j P^(cut-1-j) joins the round's checksum sum, its verdict the accepted count (both are sums: the order of the
@@ -1360,9 +1265,7 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
             double q1[D];
 #pragma unroll
             for (int k = 0; k < D; ++k) q1[k] = unid(sh->q[k][slot1]);
-            bool same_q = memo_n == n;
-#pragma unroll
-            for (int k = 0; k < D; ++k) same_q = same_q && __double_as_longlong(q1[k]) == __double_as_longlong(memo_q[k]);
+            const bool same_q = memo_matches<D>(memo_n, memo_q, n, q1);
             double gmin = memo_g;
             uint32_t memo_hit_idx = memo_idx;
             bool tie = false, banded = false;
@@ -1370,59 +1273,12 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
                 const float s1j = lbits_f32(uni(lf32_bits(sh->tail_s2[ja])));
                 banded = cells_band_resolve<DIM>(grid, blk, xyz, sh, lane, q1, s1j, A, memo_hit_idx, gmin);
                 if (STAMP && banded) ++n_band;
-                if (banded && keep_memo) {   // (as exact as a whole-tree answer: it serves the later identical queries too)
-                    memo_n = n; memo_g = gmin; memo_idx = memo_hit_idx;
-#pragma unroll
-                    for (int k = 0; k < D; ++k) memo_q[k] = q1[k];
-                }
+                // (as exact as a whole-tree answer: it serves the later identical queries too)
+                if (banded && keep_memo) memo_keep<D>(memo_n, memo_q, memo_g, memo_idx, n, q1, gmin, memo_hit_idx);
             }
             if (!same_q && !banded) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // this wave's stores to the tree have landed (same CU)
-                Scan ps{__builtin_inf(), kNoNode, 0xFFFFFFFFu};  // .slot is used as the node index here
-                constexpr int WT = OXHIP_CELLS_WT_UNROLL;   // chunks of 256 nodes in flight (4 nodes per lane each)
-                for (uint32_t i0 = 4u * lane; i0 < n; i0 += 256u * (uint32_t)WT) {
-                    uint32_t sk4[WT], il[WT];
-                    double d16[WT][4];
-#pragma unroll
-                    for (int t = 0; t < WT; ++t) {
-                        const uint32_t ib = i0 + 256u * (uint32_t)t;
-                        il[t] = ib < n ? ib : 0u;   // (rows are padded to cap >= n rounded up to 1024)
-                        sk4[t] = *reinterpret_cast<const uint32_t*>(skip + il[t]);
-                    }
-#pragma unroll
-                    for (int k = 0; k < D; ++k) {
-                        ldouble4 ck[WT];
-#pragma unroll
-                        for (int t = 0; t < WT; ++t) ck[t] = *reinterpret_cast<const ldouble4*>(tree + (size_t)k * cap + il[t]);
-#pragma unroll
-                        for (int t = 0; t < WT; ++t) {
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                const double df = ck[t][r] - q1[k];
-                                const double sq = df * df;
-                                d16[t][r] = k == 0 ? sq : d16[t][r] + sq;   // the reference's summation order
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int t = 0; t < WT; ++t) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const uint32_t i = i0 + 256u * (uint32_t)t + (uint32_t)r;
-                            if (i < n && ((sk4[t] >> (8 * r)) & 0xFFu) == 0) scan_push(ps, d16[t][r], i);   // ascending within the lane: ties keep the lower index
-                        }
-                    }
-                }
-                gmin = wave_min_f64(ps.b1);
-                const uint32_t hbw = hi32(gmin) + 1;
-                const uint64_t nearm = __ballot(ps.slot != kNoNode && hi32(ps.b1) <= hbw);
-                tie = __popcll(nearm) != 1 || __ballot(ps.h2 <= hbw) != 0;
-                memo_hit_idx = tie ? kNoNode : (uint32_t)__builtin_amdgcn_readlane((int)ps.slot, __ffsll((unsigned long long)(nearm | (1ull << 63))) - 1);
-                if (!tie && keep_memo) {
-                    memo_n = n; memo_g = gmin; memo_idx = memo_hit_idx;
-#pragma unroll
-                    for (int k = 0; k < D; ++k) memo_q[k] = q1[k];
-                }
+                tie = whole_tree_nearest<D, kWholeTreeUnroll>(tree, skip, cap, n, lane, q1, gmin, memo_hit_idx);
+                if (!tie && keep_memo) memo_keep<D>(memo_n, memo_q, memo_g, memo_idx, n, q1, gmin, memo_hit_idx);
             } else if (STAMP && same_q) ++n_memo;
             uint32_t nearest1;
             double qn1[D], q_near1[D];
@@ -1435,41 +1291,19 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
                 steer<DIM>(p, false, gmin, q_near1, q1, qn1);
             } else {
                 if (STAMP) ++n_tie;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                Exact e{__builtin_inf(), kNoNode};
-                for (uint32_t i = lane; i < n; i += 64) {
-                    double c[D];
-#pragma unroll
-                    for (int k = 0; k < D; ++k)
-                        c[k] = __hip_atomic_load(&tree[(size_t)k * cap + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const double d = sqrt(dist2<D>(c, q1, DIM));
-                    if (d < e.dist) { e.dist = d; e.idx = i; }
-                }
-                e = exact_wave_reduce(e);
-                nearest1 = uni(e.idx);
-#pragma unroll
-                for (int k = 0; k < D; ++k)
-                    q_near1[k] = unid(__hip_atomic_load(&tree[(size_t)k * cap + nearest1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                const double dist1 = unid(e.dist);
+                const double dist1 = literal_nearest<D>(tree, cap, n, lane, q1, nearest1, q_near1);
                 dup1 = dist1 == 0.0;
                 steer<DIM>(p, true, dist1, q_near1, q1, qn1);
             }
             bool ok1 = true;
             if (nobs > 0) {
-                double mid1[D];
-                lerp<DIM>(q_near1, qn1, 0.5, mid1, DIM);
                 double oc[D];
 #pragma unroll
                 for (int k = 0; k < D; ++k) oc[k] = shared.obs[k][lane];
-                const double othr = shared.obs[D][lane], ofilt = shared.obs[D + 1][lane];
-                if (__ballot(sphere_maybe_hit<DIM>(oc, ofilt, mid1)) != 0 || extras)
-                    ok1 = motion_lanes<DIM>(p, lane, q_near1, qn1, oc, othr, ofilt, ns64);
+                ok1 = motion_wave<D>(p, lane, q_near1, qn1, oc, shared.obs[D][lane], shared.obs[D + 1][lane], ns64, extras);
             }
             if (FROZEN) {   // (the round's commit has counted the iteration and the draws)
-                const int ex = (int)(cut - 1u - ja);
-                const uint64_t pe = uni64(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pw >> 32), ex) << 32) |
-                                          (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pw, ex));
+                const uint64_t pe = readlane_u64(pw, (int)(cut - 1u - ja));
                 st.checksum = uni64(st.checksum + iter_digest<D>(nearest1, qn1, DIM, ok1) * pe);
             } else {
                 st.checksum = uni64(chk_push(st.checksum, iter_digest<D>(nearest1, qn1, DIM, ok1)));

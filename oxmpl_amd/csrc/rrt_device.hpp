@@ -174,6 +174,10 @@ __device__ __forceinline__ double readlane_f64(double v, int l) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
     return __hiloint2double(hi, lo);
 }
+__device__ __forceinline__ uint64_t readlane_u64(uint64_t v, int l) {
+    return uni64(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l) << 32) |
+                 (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l));
+}
 __device__ __forceinline__ uint64_t below_mask(uint32_t lane) { return (1ull << lane) - 1ull; }   // the lanes below `lane`
 
 // ------------------------------------------------------------------ ChaCha12 (rand_chacha)

@@ -888,58 +888,14 @@ __global__ __launch_bounds__(kLanesThreads) void rrt_lanes_kernel(DevParams p) {
                 if (o0 < 32) maybe_lo |= bits << o0; else maybe_hi |= bits << (o0 - 32);
             }
             }
-            // the binary64 filter for the spheres the pre-filter left (per lane: usually none or one)
-            {
-                uint64_t rem = ((uint64_t)maybe_hi << 32) | maybe_lo;
-                uint64_t keep = 0;
-                while (__ballot(rem != 0) != 0) {
-                    const bool has = rem != 0;
-                    const uint32_t o = has ? (uint32_t)(__ffsll((unsigned long long)rem) - 1) : 0u;
-                    double c[D];
-#pragma unroll
-                    for (int k = 0; k < D; ++k) c[k] = sh.obs[k][o];
-                    if (has && sphere_maybe_hit<DIM>(c, sh.obs[D + 1][o], mid)) keep |= 1ull << o;
-                    rem &= rem - 1;
-                }
-                maybe_lo = (uint32_t)keep;
-                maybe_hi = (uint32_t)(keep >> 32);
-            }
-            const uint64_t maybe = ((uint64_t)maybe_hi << 32) | maybe_lo;
+            // the binary64 filter for the spheres the pre-filter left
+            const uint64_t maybe = spheres_maybe_hit<D>(sh.obs, ((uint64_t)maybe_hi << 32) | maybe_lo, mid);
             OXHIP_PHASE(3);   // sphere filter
             if (STAMP) maybe_dbg = maybe;
             const bool need = act && !amb && (maybe != 0 || extras);
-            if (__ballot(need) != 0) {
-                // ... and every lane steps through its own motion against just those (is_valid is pure: testing all states
-                // equals the reference's first-invalid early exit)
-                const double dist = sqrt(dist2<DIM>(q_near, qn, DIM));
-                const uint32_t nsteps = num_steps_u32(dist, p.res);
-                const uint32_t steps_l = need ? (nsteps <= 1 ? 1u : nsteps) : 0u;
-                const uint32_t smax = wave_max_u32(steps_l);
-                const double dn = (double)nsteps;
-                for (uint32_t s = 1; s <= smax && s != 0; ++s) {
-                    const bool on = s <= steps_l;
-                    double x[D];
-                    {
-                        const double t = (double)s / dn;
-                        double xi[D];
-                        lerp<DIM>(q_near, qn, t, xi, DIM);
-#pragma unroll
-                        for (int k = 0; k < D; ++k) x[k] = nsteps <= 1 ? qn[k] : xi[k];   // num_steps <= 1: is_valid(to) only
-                    }
-                    uint64_t rem = on ? maybe : 0ull;
-                    while (__ballot(rem != 0) != 0) {
-                        const bool has = rem != 0;
-                        const uint32_t o = has ? (uint32_t)(__ffsll((unsigned long long)rem) - 1) : 0u;
-                        double c[D];
-#pragma unroll
-                        for (int k = 0; k < D; ++k) c[k] = sh.obs[k][o];
-                        bad = bad || (has && !(dist2<D>(c, x, DIM) > sh.obs[D][o]));
-                        rem &= rem - 1;
-                    }
-                    for (uint32_t jx = ns64; jx < nobs; ++jx) bad = bad || (on && obstacle_hit<DIM>(p, DIM, x, jx));
-                    if ((s & 63u) == 0 && lane == 0) lds_bump(&sh.heartbeat);
-                }
-            }
+            bad = motion_own_lane<D>(p, sh.obs, need, maybe, q_near, qn, ns64, nobs, [&](uint32_t s) {
+                if ((s & 63u) == 0 && lane == 0) lds_bump(&sh.heartbeat);
+            });
         }
         OXHIP_PHASE(4);   // motion check
         if (STAMP && p.dbg && (p.dbg_flags & OXHIP_DEBUG_AUDIT) != 0) {   // audit (diagnostic instantiation with OXHIP_DEBUG_AUDIT): an accepted motion whose end state lies inside one of the first 64 spheres

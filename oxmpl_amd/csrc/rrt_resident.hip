@@ -12,6 +12,7 @@
 #include "oxhip_internal.hpp"
 #include "rrt_device.hpp"
 #include "rrt_resident_common.hpp"
+#include "lane_query_common.hpp"
 #include "lane_sampler.hpp"
 
 namespace oxhip {
@@ -272,31 +273,11 @@ __global__ __launch_bounds__(kPipeThreads) void rrt_resident_kernel(DevParams p)
             // rare (~1e-6 of queries): the reference's own loop -- post-sqrt compare with lowest-index ties --
             // over the persistent copy of the tree in global memory
             if (STAMP) ++n_amb;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            Exact e{__builtin_inf(), kNoNode};
-            for (uint32_t i = lane; i < n; i += 64) {
-                double c[D];
-#pragma unroll
-                for (int k = 0; k < D; ++k)
-                    c[k] = __hip_atomic_load(&tree[(size_t)k * cap + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const double d = sqrt(dist2<D>(c, q, DIM));
-                if (d < e.dist) { e.dist = d; e.idx = i; }
-            }
-            e = exact_wave_reduce(e);
-            nearest = uni(e.idx);
-#pragma unroll
-            for (int k = 0; k < D; ++k)
-                q_near[k] = unid(__hip_atomic_load(&tree[(size_t)k * cap + nearest], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            dist_or_g = unid(e.dist);
+            dist_or_g = literal_nearest<D>(tree, cap, n, lane, q, nearest, q_near);
             dup = dist_or_g == 0.0;
         }
         steer<DIM>(p, amb, dist_or_g, q_near, q, q_new);
-        if (nobs == 0) return true;
-        double mid[D];
-        lerp<DIM>(q_near, q_new, 0.5, mid, DIM);
-        if (__ballot(sphere_maybe_hit<DIM>(oc, ofilt, mid)) == 0 && !extras) return true;
-        return motion_lanes<DIM>(p, lane, q_near, q_new, oc, othr, ofilt, ns64);
+        return nobs == 0 || motion_wave<D>(p, lane, q_near, q_new, oc, othr, ofilt, ns64, extras);
     };
 
     while (jr < budget) {
@@ -433,8 +414,7 @@ __global__ __launch_bounds__(kPipeThreads) void rrt_resident_kernel(DevParams p)
                 // bookkeeping (wave-uniform, on the scalar unit where the compiler can)
                 st.checksum = uni64(chk_push(st.checksum, iter_digest<D>(nearest, q_new, DIM, ok)));
                 st.iterations++;
-                draws_done = uni64((uint64_t)__builtin_amdgcn_readlane((int)(uint32_t)pos_after_r, l0) |
-                                   ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pos_after_r >> 32), l0) << 32));
+                draws_done = readlane_u64(pos_after_r, l0);
                 bool hit = false;
                 if (ok) {
                     st.accepted++;

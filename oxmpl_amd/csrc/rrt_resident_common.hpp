@@ -1,5 +1,5 @@
-// rrt_resident_common.hpp -- pieces shared by the register-resident kernels (rrt_resident.hip,
-// rrt_pruned.hip): DPP reductions, the scan state, the scanner/resolver LDS ring, the tree layout,
+// rrt_resident_common.hpp -- pieces shared by the register-resident kernel (rrt_resident.hip) and the
+// lane-per-query kernels: DPP reductions, the scan state, the scanner/resolver LDS ring, the tree layout,
 // steer / motion check / conservative filter.
 #pragma once
 
