@@ -394,6 +394,19 @@ class PRM {
     // The planner's own problem definition is left as it is.  Every problem must share the planner's space.
     std::vector<Result<base::Path, base::PlanningError>> solve_batch(const std::vector<std::shared_ptr<base::ProblemDefinition>>& problems,
                                                                      std::chrono::duration<double> timeout_) {
+        return solve_batch_with(problems, timeout_, false);
+    }
+
+    // The same batch answered with shortest paths on the roadmap in the space's distance (oxhip_prm_solve_batch_shortest): the
+    // statuses are solve_batch's, the paths are no longer than its fewest-hop ones.
+    std::vector<Result<base::Path, base::PlanningError>> solve_batch_shortest(const std::vector<std::shared_ptr<base::ProblemDefinition>>& problems,
+                                                                              std::chrono::duration<double> timeout_) {
+        return solve_batch_with(problems, timeout_, true);
+    }
+
+  private:
+    std::vector<Result<base::Path, base::PlanningError>> solve_batch_with(const std::vector<std::shared_ptr<base::ProblemDefinition>>& problems,
+                                                                          std::chrono::duration<double> timeout_, bool shortest) {
         std::vector<Result<base::Path, base::PlanningError>> out;
         out.reserve(problems.size());
         const std::size_t q = problems.size();
@@ -415,7 +428,9 @@ class PRM {
             radii.push_back(pd->goal->radius());
         }
         std::vector<int32_t> status(q ? q : 1);
-        int32_t st = oxhip_prm_solve_batch(prm_, (uint32_t)q, starts.data(), centres.data(), radii.data(), timeout_.count(), 0, status.data());
+        int32_t st = shortest ? oxhip_prm_solve_batch_shortest(prm_, (uint32_t)q, starts.data(), centres.data(), radii.data(), timeout_.count(), 0, 0,
+                                                               status.data())
+                              : oxhip_prm_solve_batch(prm_, (uint32_t)q, starts.data(), centres.data(), radii.data(), timeout_.count(), 0, status.data());
         std::vector<uint64_t> off(q + 1);
         uint64_t total = 0;
         if (st == OXHIP_OK) st = oxhip_prm_batch_get_paths(prm_, off.data(), nullptr, nullptr, 0, &total);
@@ -434,6 +449,7 @@ class PRM {
         return out;
     }
 
+  public:
     // PRM::get_roadmap (prm.rs:82-84): milestone count and, per node, its `edges`
     uint32_t num_milestones() const {
         uint32_t n = 0;

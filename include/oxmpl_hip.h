@@ -516,6 +516,42 @@ int32_t oxhip_prm_batch_get_query_sets(oxhip_prm* prm, uint32_t query, uint32_t*
  * extraction, device-to-host copies}; the number of rounds */
 int32_t oxhip_prm_batch_last_timing(oxhip_prm* prm, double* phase_ms /*[4]*/, uint32_t* rounds);
 
+/* ---- the same batch answered with shortest paths (prm_shortest.hip) ----
+ * The semantics are this build's own (the reference searches breadth-first only).  Per query, start validity, the start
+ * connections S and the goal milestones G are exactly oxhip_prm_solve_batch's (the same flag kernels), and so are the statuses:
+ * OXHIP_ERR_INVALID_START_STATE; OXHIP_ERR_NO_SOLUTION_FOUND when S or G is empty or no milestone of G has a finite label;
+ * OXHIP_OK; OXHIP_ERR_TIMEOUT.  w(u, v) is the space's own distance between the milestones (the bits of oxhip_distance_batch /
+ * oxhip_so3_op_batch op 0), init[m] = distance(start, m) for m in S and +inf elsewhere, and the labels c are the least solution of
+ *     c[v] = min(init[v], min over neighbours u of fl(c[u] + w(u, v)))        (one rounded binary64 add per edge)
+ * -- what Dijkstra computes.  An edge u -> v is tight iff fl(c[u] + w(u, v)) == c[v]; the sources are the m in S with
+ * c[m] == init[m] (hops 0, parent = the start); hops[v] is v's breadth-first depth from the sources over tight edges and
+ * parent[v] its lowest-index tight predecessor with hops[v] - 1.  The answer is the goal milestone of least (c, hops, index),
+ * the path [start, chain ...] has hops + 2 states, and the left-to-right sum of its edge distances is c[goal] bit for bit.
+ * weights: 0 = distance (above); 1 = every w and every init[m], m in S, is 1.0 (fewest hops under this tie rule); 2 = all of
+ * them 0.0 (test only: every edge is tight); anything else is OXHIP_ERR_BAD_ARG.  Call-level statuses, argument checks,
+ * chunk_queries (0 = automatic: 21 bytes per query and milestone, at most 1 GiB a round; results never depend on it) and the
+ * timeout's suffix rule are oxhip_prm_solve_batch's.  The call becomes "the last batch": oxhip_prm_batch_get_results, _get_paths
+ * and _get_query_sets serve it unchanged, and oxhip_prm_batch_last_timing reports phase_ms[4] = {flag kernel + initial labels,
+ * label rounds + tight levels, path extraction, device-to-host copies} (the edge weights, computed once per roadmap -- 8 bytes
+ * per CSR entry, kept until setup() -- are in none of them: see oxhip_prm_batch_get_search_stats).  It neither reads nor
+ * writes the handle's own problem definition or the last single solve's query sets. */
+int32_t oxhip_prm_solve_batch_shortest(oxhip_prm* prm, uint32_t n_queries, const double* starts /*[Q][dim]*/,
+                                       const double* goal_centres /*[Q][dim]*/, const double* goal_radii /*[Q]*/, double timeout_s,
+                                       uint32_t chunk_queries, uint32_t weights, int32_t* status_out /*[Q] or NULL*/);
+/* c[goal] per query of the last batch, +inf where its status is not OXHIP_OK.  OXHIP_ERR_BAD_ARG when the last batch was an
+ * oxhip_prm_solve_batch; OXHIP_ERR_UNSAMPLED_STATE_SPACE before any batch or after setup(), like the other getters. */
+int32_t oxhip_prm_batch_get_costs(oxhip_prm* prm, double* cost /*[Q]*/);
+/* test hook: all n labels of query `query` of the last shortest-path batch (flags, labels and levels run again for it, as
+ * oxhip_prm_batch_get_query_sets re-runs the flags): cost = c (+inf: not reached), hops (0xFFFFFFFF where c is +inf), parent
+ * (0x7FFFFFFF for a source, 0xFFFFFFFF where c is +inf).  Any pointer may be NULL; cap < n is OXHIP_ERR_CAPACITY. */
+int32_t oxhip_prm_batch_get_labels(oxhip_prm* prm, uint32_t query, double* cost /*[n]*/, uint32_t* hops /*[n]*/,
+                                   uint32_t* parent /*[n]*/, uint32_t cap);
+/* diagnostics of the last shortest-path batch: per query the label rounds run and the edge relaxations evaluated; HIP-event
+ * times (ms) summed over the rounds, phase_ms[6] = {edge weights (0 unless this batch computed them), flag kernel + initial
+ * labels, label rounds, tight levels, path extraction, device-to-host copies}.  Any pointer may be NULL. */
+int32_t oxhip_prm_batch_get_search_stats(oxhip_prm* prm, uint32_t* label_rounds /*[Q]*/, uint64_t* relaxations /*[Q]*/,
+                                         double* phase_ms /*[6]*/);
+
 #ifdef __cplusplus
 }
 #endif

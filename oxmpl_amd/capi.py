@@ -49,6 +49,7 @@ EXPORTS = [
     "oxhip_prm_solve", "oxhip_prm_get_query_sets", "oxhip_prm_last_timing", "oxhip_prm_knn_exact_rows",
     "oxhip_prm_solve_batch", "oxhip_prm_batch_get_results", "oxhip_prm_batch_get_paths", "oxhip_prm_batch_get_query_sets",
     "oxhip_prm_batch_last_timing",
+    "oxhip_prm_solve_batch_shortest", "oxhip_prm_batch_get_costs", "oxhip_prm_batch_get_labels", "oxhip_prm_batch_get_search_stats",
     "oxhip_rrt_batch_extract_paths", "oxhip_rrt_batch_get_paths", "oxhip_rrt_batch_simplify_paths",
     "oxhip_rrt_batch_get_simplified_paths", "oxhip_rrt_batch_get_simplify_results", "oxhip_rrt_batch_path_valid_matrix",
     "oxhip_rrt_batch_paths_last_timing",
@@ -163,6 +164,10 @@ def lib():
         L.oxhip_prm_batch_get_paths.argtypes = [C.c_void_p, _u64p, _u32p, _dp, C.c_uint64, _u64p]
         L.oxhip_prm_batch_get_query_sets.argtypes = [C.c_void_p, C.c_uint32, _u32p, C.c_uint32, _u32p, _u32p, C.c_uint32, _u32p]
         L.oxhip_prm_batch_last_timing.argtypes = [C.c_void_p, _dp, _u32p]
+        L.oxhip_prm_solve_batch_shortest.argtypes = [C.c_void_p, C.c_uint32, _dp, _dp, _dp, C.c_double, C.c_uint32, C.c_uint32, _i32p]
+        L.oxhip_prm_batch_get_costs.argtypes = [C.c_void_p, _dp]
+        L.oxhip_prm_batch_get_labels.argtypes = [C.c_void_p, C.c_uint32, _dp, _u32p, _u32p, C.c_uint32]
+        L.oxhip_prm_batch_get_search_stats.argtypes = [C.c_void_p, _u32p, _u64p, _dp]
         L.oxhip_rrt_batch_extract_paths.argtypes = [C.c_void_p]
         L.oxhip_rrt_batch_get_paths.argtypes = [C.c_void_p, _u64p, _dp, C.c_uint64, _u64p]
         L.oxhip_rrt_batch_simplify_paths.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
@@ -669,3 +674,39 @@ class PRMRoadmap:
         r = C.c_uint32()
         _check(lib().oxhip_prm_batch_last_timing(self._h, _p(ms), C.byref(r)))
         return dict(phase_ms=[float(v) for v in ms], rounds=r.value)
+
+    # ---- the same batch answered with shortest paths
+
+    def solve_batch_shortest(self, starts, goal_centres, goal_radii, timeout_s=0.0, chunk_queries=0, weights=0):
+        """Q queries in one call, each answered with a shortest path on the roadmap: weights 0 = the space's distance, 1 = unit
+        (fewest hops), 2 = zero (test only).  Statuses and query sets are solve_batch's; batch_results / batch_paths /
+        batch_query_sets / batch_last_timing serve this batch as they serve solve_batch's."""
+        r = _f64(goal_radii).reshape(-1)
+        s, g = _f64(starts, (r.size, self.dim)), _f64(goal_centres, (r.size, self.dim))
+        status = np.zeros(max(r.size, 1), dtype=np.int32)
+        _check(lib().oxhip_prm_solve_batch_shortest(self._h, r.size, _p(s), _p(g), _p(r), timeout_s, chunk_queries, weights,
+                                                    _p(status, _i32p)))
+        self._batch_q = r.size
+        return status[:r.size]
+
+    def batch_costs(self):
+        """the label of the goal milestone reached, per query of the last shortest-path batch (+inf unless OK)"""
+        q = getattr(self, "_batch_q", 0)
+        cost = np.zeros(max(q, 1), dtype=np.float64)
+        _check(lib().oxhip_prm_batch_get_costs(self._h, _p(cost)))
+        return cost[:q]
+
+    def batch_labels(self, query):
+        """(cost [n], hops [n], parent [n]) of every milestone for query `query` of the last shortest-path batch"""
+        n = self.sizes()[0]
+        cost = np.zeros(max(n, 1), dtype=np.float64)
+        hops, parent = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+        _check(lib().oxhip_prm_batch_get_labels(self._h, query, _p(cost), _p(hops, _u32p), _p(parent, _u32p), n))
+        return cost[:n], hops[:n], parent[:n]
+
+    def batch_search_stats(self):
+        """dict(label_rounds [Q], relaxations [Q], phase_ms=[weights, flags, labels, levels, paths, copies]) of the last shortest-path batch"""
+        q = getattr(self, "_batch_q", 0)
+        rounds, relax, ms = np.zeros(max(q, 1), dtype=np.uint32), np.zeros(max(q, 1), dtype=np.uint64), np.zeros(6, dtype=np.float64)
+        _check(lib().oxhip_prm_batch_get_search_stats(self._h, _p(rounds, _u32p), _p(relax, _u64p), _p(ms)))
+        return dict(label_rounds=rounds[:q], relaxations=relax[:q], phase_ms=[float(v) for v in ms])

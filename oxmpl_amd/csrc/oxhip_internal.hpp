@@ -191,6 +191,23 @@ void launch_prm_batch_search(const PrmBatchArgs& b, uint32_t group, hipStream_t 
 // row_off[c]: first row of query c's path within nodes / rows (this round's rows)
 void launch_prm_batch_paths(const PrmBatchArgs& b, const uint64_t* row_off, uint32_t* nodes, double* rows, hipStream_t s);
 
+// prm_shortest.hip: the same batch answered with shortest paths.  The query sets come from the flag
+// launchers above and the rows from launch_prm_batch_paths; a round's rows of `label` and `stamp` lie beside those of PrmBatchArgs.
+struct PrmShortestArgs {
+    const double* w;             // [n_edge_entries] w[e] = distance(ms[u], ms[nbrs[e]]); read in mode 0 only
+    uint64_t* label;             // [n_chunk][stride] bit pattern of the label c (a non-negative binary64, +inf = none)
+    uint32_t* stamp;             // [n_chunk][stride] the label round that last put the node on a worklist; then its hops
+    double* cost;                // [n_chunk] c[goal], +inf unless OXHIP_OK
+    uint32_t* rounds;            // [n_chunk] label rounds run
+    unsigned long long* relaxed; // [n_chunk] edge relaxations evaluated
+    uint32_t mode, pad;          // 0: distance weights, 1: every weight 1.0, 2: every weight 0.0
+};
+void launch_prm_shortest_weights(bool so3, uint32_t dim, const double* ms, const uint32_t* offsets, const uint32_t* nbrs, uint32_t n,
+                                 uint32_t n_entries, double* w, hipStream_t s);
+void launch_prm_shortest_init(bool so3, const PrmBatchArgs& b, const PrmShortestArgs& a, hipStream_t s);
+void launch_prm_shortest_labels(const PrmBatchArgs& b, const PrmShortestArgs& a, uint32_t group, hipStream_t s);
+void launch_prm_shortest_levels(const PrmBatchArgs& b, const PrmShortestArgs& a, uint32_t group, hipStream_t s);
+
 // path_simplify.hip: the solution paths of an RRT / RRTConnect / RRT* batch, extracted and shortcut on the device (DESIGN.md
 // section 18).  Problem p's raw path is rows off[p] .. off[p] + len[p] of `rows`.
 struct PathArgs {

@@ -80,6 +80,19 @@ struct oxhip_prm {
     DevBuf<uint32_t> bd_start_valid, bd_parent, bd_queue, bd_res, bd_nodes;
     DevBuf<uint64_t> bd_off;
     hipEvent_t bev[7] = {};
+    // oxhip_prm_solve_batch_shortest: the edge weights live until the roadmap changes; the rest is the last batch's
+    int32_t batch_mode = -1;   // weights mode of the last batch, -1: it was the breadth-first oxhip_prm_solve_batch
+    bool w_valid = false;      // w_edges holds the distances of the roadmap's CSR entries
+    DevBuf<double> w_edges;
+    double short_ms[6] = {};   // edge weights (when this batch computed them), flags + initial labels, label rounds, tight levels, paths, copies
+    std::vector<double> b_cost;
+    std::vector<uint32_t> b_rounds;
+    std::vector<uint64_t> b_relaxed;
+    DevBuf<uint64_t> bd_label;
+    DevBuf<uint32_t> bd_stamp, bd_rounds;
+    DevBuf<double> bd_cost;
+    DevBuf<unsigned long long> bd_relaxed;
+    hipEvent_t sev[2] = {};
 };
 
 namespace {
@@ -120,6 +133,7 @@ void clear_roadmap(oxhip_prm* h) {
     h->start_conn.clear();
     h->goal_idx.clear();
     h->batch_valid = false;   // the batch's results are about the roadmap that just went
+    h->w_valid = false;       // and so are the edge weights
 }
 
 // Draw samples until `target` milestones exist or `max_samples` were drawn.  Rounds of the parallel sampler
@@ -298,6 +312,7 @@ int32_t oxhip_prm_create(const oxhip_prm_config* cfg, oxhip_prm** out) {
     chk(oxhip_stream_acquire(cfg->device, &h->stream));
     for (auto& ev : h->ev) chk(hipEventCreate(&ev));
     for (auto& ev : h->bev) chk(hipEventCreate(&ev));
+    for (auto& ev : h->sev) chk(hipEventCreate(&ev));
     chk(h->ms.alloc((size_t)dim * cap));
     if (!so3) chk(h->ms32.alloc((size_t)dim * cap));   // (the SO(3) pair search screens nothing)
     chk(h->state.alloc(1));
@@ -320,6 +335,7 @@ int32_t oxhip_prm_destroy(oxhip_prm* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (auto& ev : h->ev) if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : h->bev) if (ev) (void)hipEventDestroy(ev);
+    for (auto& ev : h->sev) if (ev) (void)hipEventDestroy(ev);
     if (h->stream) oxhip_stream_release(h->cfg.device, h->stream);
     delete h;
     return OXHIP_OK;
@@ -557,6 +573,7 @@ int32_t oxhip_prm_construct_roadmap(oxhip_prm* h) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->t_ms[3] = elapsed_ms(h->ev[4], h->ev[5]);
     h->n_keys = n_keys;
+    h->w_valid = false;     // the edge weights of the roadmap before this one
     h->host_copy = false;   // fetched by the first get_roadmap / solve
     h->n = n;
     h->n_samples = st.n_samples;
@@ -717,12 +734,42 @@ void launch_batch_flags(oxhip_prm* h, const PrmBatchArgs& b) {
     else launch_prm_batch_flags(h->dp, b, h->thr_conn, h->stream);
 }
 
-}  // namespace
+PrmShortestArgs shortest_args(oxhip_prm* h, int32_t mode) {
+    PrmShortestArgs a{};
+    a.w = h->w_edges.p; a.label = h->bd_label.p; a.stamp = h->bd_stamp.p; a.cost = h->bd_cost.p; a.rounds = h->bd_rounds.p;
+    a.relaxed = h->bd_relaxed.p; a.mode = (uint32_t)mode;
+    return a;
+}
 
-extern "C" {
+// the distances of the roadmap's CSR entries, once per roadmap (distance weights only)
+int32_t ensure_edge_weights(oxhip_prm* h) {
+    if (h->w_valid) return OXHIP_OK;
+    if (h->w_edges.n < h->n_keys) HIP_TRY(h->w_edges.alloc(h->n_keys));
+    HIP_TRY(hipEventRecord(h->sev[0], h->stream));
+    launch_prm_shortest_weights(h->so3, h->cfg.dim, h->ms.p, h->offsets.p, h->nbrs.p, h->n, h->n_keys, h->w_edges.p, h->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->sev[1], h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->short_ms[0] = elapsed_ms(h->sev[0], h->sev[1]);
+    h->w_valid = true;
+    return OXHIP_OK;
+}
 
-int32_t oxhip_prm_solve_batch(oxhip_prm* h, uint32_t n_queries, const double* starts, const double* goal_centres, const double* goal_radii,
-                              double timeout_s, uint32_t chunk_queries, int32_t* status_out) {
+// bytes of a round's workspace per query and milestone: flag 1, parent 4, queue 4; label 8 and stamp 4 for the shortest-path search
+uint64_t batch_bytes_per_node(int32_t mode) { return mode < 0 ? 9ull : 21ull; }
+
+int32_t ensure_shortest_workspace(oxhip_prm* h, uint32_t chunk, uint32_t stride) {
+    if (h->bd_label.n < (size_t)chunk * stride) {
+        HIP_TRY(h->bd_label.alloc((size_t)chunk * stride));
+        HIP_TRY(h->bd_stamp.alloc((size_t)chunk * stride));
+    }
+    if (h->bd_cost.n < chunk) { HIP_TRY(h->bd_cost.alloc(chunk)); HIP_TRY(h->bd_rounds.alloc(chunk)); HIP_TRY(h->bd_relaxed.alloc(chunk)); }
+    return OXHIP_OK;
+}
+
+// mode < 0: the breadth-first search of prm.rs (oxhip_prm_solve_batch); 0, 1, 2: shortest paths with that weights mode
+int32_t solve_batch_common(oxhip_prm* h, uint32_t n_queries, const double* starts, const double* goal_centres, const double* goal_radii,
+                           double timeout_s, uint32_t chunk_queries, int32_t mode, int32_t* status_out) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
     if (n_queries && (!starts || !goal_centres || !goal_radii)) return fail(OXHIP_ERR_BAD_ARG, "null argument");
     if (!h->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");      // prm.rs:229-236
@@ -736,7 +783,12 @@ int32_t oxhip_prm_solve_batch(oxhip_prm* h, uint32_t n_queries, const double* st
     const bool has_timeout = timeout_s > 0.0 && std::isfinite(timeout_s);
     h->batch_valid = false;
     h->batch_rounds = 0;
+    h->batch_mode = mode;
     for (double& t : h->batch_ms) t = 0.0;
+    for (double& t : h->short_ms) t = 0.0;
+    h->b_cost.assign(mode < 0 ? 0 : n_queries, std::numeric_limits<double>::infinity());
+    h->b_rounds.assign(mode < 0 ? 0 : n_queries, 0u);
+    h->b_relaxed.assign(mode < 0 ? 0 : n_queries, 0ull);
     h->b_starts.assign(starts, starts + (size_t)Q * dim);
     h->b_goals.assign(goal_centres, goal_centres + (size_t)Q * dim);
     h->b_thr.resize(Q);
@@ -756,10 +808,16 @@ int32_t oxhip_prm_solve_batch(oxhip_prm* h, uint32_t n_queries, const double* st
     h->b_nodes.clear();
     h->b_rows.clear();
     if (Q) {
-        // 9 bytes per query and milestone: the round is sized to keep the workspace within 1 GiB
+        // 9 bytes per query and milestone (21 for shortest paths): the round is sized to keep the workspace within 1 GiB
         const uint32_t stride = (n + 63u) & ~63u;
-        uint32_t chunk = chunk_queries ? chunk_queries : (uint32_t)std::max<uint64_t>(1, (1ull << 30) / (9ull * stride));
+        uint32_t chunk = chunk_queries ? chunk_queries : (uint32_t)std::max<uint64_t>(1, (1ull << 30) / (batch_bytes_per_node(mode) * stride));
         chunk = std::min(std::min(chunk, Q), 65535u);
+        if (mode >= 0) OX_TRY(ensure_shortest_workspace(h, chunk, stride));
+        if (mode == 0) OX_TRY(ensure_edge_weights(h));
+        const PrmShortestArgs sa = shortest_args(h, mode);
+        std::vector<double> cost(mode < 0 ? 0 : chunk);
+        std::vector<uint32_t> lrounds(mode < 0 ? 0 : chunk);
+        std::vector<unsigned long long> relaxed(mode < 0 ? 0 : chunk);
         if (h->bd_starts.n < (size_t)Q * dim) { HIP_TRY(h->bd_starts.alloc((size_t)Q * dim)); HIP_TRY(h->bd_goals.alloc((size_t)Q * dim)); }
         if (h->bd_thr.n < Q) { HIP_TRY(h->bd_thr.alloc(Q)); HIP_TRY(h->bd_filt.alloc(Q)); }
         if (h->bd_flags.n < (size_t)chunk * stride) {
@@ -786,16 +844,40 @@ int32_t oxhip_prm_solve_batch(oxhip_prm* h, uint32_t n_queries, const double* st
             HIP_TRY(hipMemsetAsync(h->bd_parent.p, 0xFF, (size_t)c * stride * sizeof(uint32_t), h->stream));
             HIP_TRY(hipEventRecord(h->bev[0], h->stream));
             launch_batch_flags(h, b);
+            if (mode >= 0) launch_prm_shortest_init(h->so3, b, sa, h->stream);
             HIP_TRY(hipEventRecord(h->bev[1], h->stream));
-            launch_prm_batch_search(b, group, h->stream);
+            if (mode < 0) {
+                launch_prm_batch_search(b, group, h->stream);
+            } else {
+                launch_prm_shortest_labels(b, sa, group, h->stream);
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipEventRecord(h->sev[0], h->stream));
+                launch_prm_shortest_levels(b, sa, group, h->stream);
+            }
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipEventRecord(h->bev[2], h->stream));
             HIP_TRY(hipMemcpyAsync(res.data(), h->bd_res.p, 5 * (size_t)chunk * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+            if (mode >= 0) {
+                HIP_TRY(hipMemcpyAsync(cost.data(), h->bd_cost.p, (size_t)c * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+                HIP_TRY(hipMemcpyAsync(lrounds.data(), h->bd_rounds.p, (size_t)c * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+                HIP_TRY(hipMemcpyAsync(relaxed.data(), h->bd_relaxed.p, (size_t)c * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+            }
             HIP_TRY(hipEventRecord(h->bev[3], h->stream));
             HIP_TRY(hipStreamSynchronize(h->stream));
             h->batch_ms[0] += elapsed_ms(h->bev[0], h->bev[1]);
             h->batch_ms[1] += elapsed_ms(h->bev[1], h->bev[2]);
             h->batch_ms[3] += elapsed_ms(h->bev[2], h->bev[3]);
+            if (mode >= 0) {
+                h->short_ms[2] += elapsed_ms(h->bev[1], h->sev[0]);
+                h->short_ms[3] += elapsed_ms(h->sev[0], h->bev[2]);
+                for (uint32_t i = 0; i < c; ++i) {
+                    if ((int32_t)res[i] == OXHIP_ERR_HIP)   // (no query status is OXHIP_ERR_HIP otherwise)
+                        return fail(OXHIP_ERR_HIP, "shortest-path search: a label round or level cap was hit, which cannot happen");
+                    h->b_cost[q0 + i] = cost[i];
+                    h->b_rounds[q0 + i] = lrounds[i];
+                    h->b_relaxed[q0 + i] = relaxed[i];
+                }
+            }
             uint64_t rows = 0;
             const uint64_t row0 = h->b_off[q0];
             for (uint32_t i = 0; i < c; ++i) {
@@ -830,8 +912,81 @@ int32_t oxhip_prm_solve_batch(oxhip_prm* h, uint32_t n_queries, const double* st
         }
         for (uint32_t q = answered + 1; q <= Q; ++q) h->b_off[q] = h->b_off[answered];   // (the rounds not begun add no rows)
     }
+    if (mode >= 0) { h->short_ms[1] = h->batch_ms[0]; h->short_ms[4] = h->batch_ms[2]; h->short_ms[5] = h->batch_ms[3]; }
     h->batch_valid = true;
     if (status_out) for (uint32_t q = 0; q < Q; ++q) status_out[q] = h->b_status[q];
+    return OXHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t oxhip_prm_solve_batch(oxhip_prm* h, uint32_t n_queries, const double* starts, const double* goal_centres, const double* goal_radii,
+                              double timeout_s, uint32_t chunk_queries, int32_t* status_out) {
+    return solve_batch_common(h, n_queries, starts, goal_centres, goal_radii, timeout_s, chunk_queries, -1, status_out);
+}
+
+int32_t oxhip_prm_solve_batch_shortest(oxhip_prm* h, uint32_t n_queries, const double* starts, const double* goal_centres,
+                                       const double* goal_radii, double timeout_s, uint32_t chunk_queries, uint32_t weights, int32_t* status_out) {
+    if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
+    if (weights > 2u) return fail(OXHIP_ERR_BAD_ARG, "weights must be 0 (distance), 1 (unit) or 2 (zero)");
+    return solve_batch_common(h, n_queries, starts, goal_centres, goal_radii, timeout_s, chunk_queries, (int32_t)weights, status_out);
+}
+
+int32_t oxhip_prm_batch_get_costs(oxhip_prm* h, double* cost) {
+    if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
+    if (!h->batch_valid) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "no batch was solved on this roadmap");
+    if (h->batch_mode < 0) return fail(OXHIP_ERR_BAD_ARG, "the last batch was not a shortest-path batch");
+    if (cost && !h->b_cost.empty()) std::memcpy(cost, h->b_cost.data(), h->b_cost.size() * sizeof(double));
+    return OXHIP_OK;
+}
+
+int32_t oxhip_prm_batch_get_labels(oxhip_prm* h, uint32_t query, double* cost, uint32_t* hops, uint32_t* parent, uint32_t cap) {
+    if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
+    if (!h->batch_valid) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "no batch was solved on this roadmap");
+    if (h->batch_mode < 0) return fail(OXHIP_ERR_BAD_ARG, "the last batch was not a shortest-path batch");
+    if (query >= h->b_status.size()) return fail(OXHIP_ERR_BAD_ARG, "query index beyond the last batch");
+    const uint32_t n = h->n;
+    if ((cost || hops || parent) && cap < n) return fail(OXHIP_ERR_CAPACITY, "label buffers too small");
+    if (!cost && !hops && !parent) return OXHIP_OK;
+    if (h->b_status[query] == OXHIP_ERR_INVALID_START_STATE || h->b_status[query] == OXHIP_ERR_TIMEOUT) {   // no search ran
+        for (uint32_t i = 0; i < n; ++i) {
+            if (cost) cost[i] = std::numeric_limits<double>::infinity();
+            if (hops) hops[i] = 0xFFFFFFFFu;
+            if (parent) parent[i] = 0xFFFFFFFFu;
+        }
+        return OXHIP_OK;
+    }
+    // the labels are not kept per query: flags, initial labels, label rounds and levels run again for this one (same kernels, and
+    // a fixed point that does not depend on the order of arrival: same bits) into workspace row 0
+    OX_TRY(select_device(h->cfg.device));
+    const PrmBatchArgs b = batch_args(h, query, 1, (uint32_t)(h->bd_res.n / 5));
+    const PrmShortestArgs sa = shortest_args(h, h->batch_mode);
+    const uint32_t group = prm_batch_group(n, h->n_keys);
+    launch_batch_flags(h, b);
+    launch_prm_shortest_init(h->so3, b, sa, h->stream);
+    launch_prm_shortest_labels(b, sa, group, h->stream);
+    launch_prm_shortest_levels(b, sa, group, h->stream);
+    HIP_TRY(hipGetLastError());
+    int32_t status = 0;
+    HIP_TRY(hipMemcpyAsync(&status, h->bd_res.p, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (cost) HIP_TRY(hipMemcpyAsync(cost, h->bd_label.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (hops) HIP_TRY(hipMemcpyAsync(hops, h->bd_stamp.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (parent) HIP_TRY(hipMemcpyAsync(parent, h->bd_parent.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (status == OXHIP_ERR_HIP) return fail(OXHIP_ERR_HIP, "shortest-path search: a label round or level cap was hit, which cannot happen");
+    return OXHIP_OK;
+}
+
+int32_t oxhip_prm_batch_get_search_stats(oxhip_prm* h, uint32_t* label_rounds, uint64_t* relaxations, double* phase_ms) {
+    if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
+    if (!h->batch_valid) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "no batch was solved on this roadmap");
+    if (h->batch_mode < 0) return fail(OXHIP_ERR_BAD_ARG, "the last batch was not a shortest-path batch");
+    const size_t Q = h->b_rounds.size();
+    if (label_rounds && Q) std::memcpy(label_rounds, h->b_rounds.data(), Q * sizeof(uint32_t));
+    if (relaxations && Q) std::memcpy(relaxations, h->b_relaxed.data(), Q * sizeof(uint64_t));
+    if (phase_ms) for (int i = 0; i < 6; ++i) phase_ms[i] = h->short_ms[i];
     return OXHIP_OK;
 }
 

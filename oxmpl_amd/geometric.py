@@ -284,12 +284,14 @@ class PRM:
             raise Exception(_MESSAGES.get(int(st), capi.status_string(int(st))))
         return Path([self._state(row) for row in path])
 
-    def solve_batch(self, problem_definitions, timeout_secs):
+    def solve_batch(self, problem_definitions, timeout_secs, shortest=False):
         """Many problem definitions on the roadmap already built, in one device call (oxhip_prm_solve_batch: start
         connections, goal test, breadth-first search and path extraction on the GPU).  Returns a list with, per problem, what
         set_problem_definition + solve would give: a Path, or an Exception instance carrying the reference's message for that
         status -- returned, not raised, so one start in collision does not hide a thousand answers.  The planner's own problem
-        definition is left as it is.  All problems must share the planner's space."""
+        definition is left as it is.  All problems must share the planner's space.  shortest=True answers every problem with
+        a shortest path on the roadmap in the space's distance (oxhip_prm_solve_batch_shortest) instead of the reference's
+        fewest-hop path; the statuses are the same."""
         if self._prm is None:
             raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
         pds = list(problem_definitions)
@@ -299,8 +301,9 @@ class PRM:
             if type(pd.space) is not type(self._pd.space) or len(pd.start_state.values) != len(self._pd.start_state.values):
                 raise ValueError("every problem of a batch must share the planner's state space")
         try:
-            status = self._prm.solve_batch([pd.start_state.values for pd in pds], [pd.goal.target.values for pd in pds],
-                                           [float(pd.goal.radius) for pd in pds], float(timeout_secs))
+            run = self._prm.solve_batch_shortest if shortest else self._prm.solve_batch
+            status = run([pd.start_state.values for pd in pds], [pd.goal.target.values for pd in pds],
+                         [float(pd.goal.radius) for pd in pds], float(timeout_secs))
         except capi.OxhipError as e:
             if e.status in _MESSAGES:
                 raise Exception(_MESSAGES[e.status]) from None

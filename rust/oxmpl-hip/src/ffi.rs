@@ -247,6 +247,20 @@ extern "C" {
         n_goal: *mut u32,
     ) -> i32;
     pub fn oxhip_prm_batch_last_timing(p: *mut OxhipPrm, phase_ms: *mut f64, rounds: *mut u32) -> i32;
+    pub fn oxhip_prm_solve_batch_shortest(
+        p: *mut OxhipPrm,
+        n_queries: u32,
+        starts: *const f64,
+        goal_centres: *const f64,
+        goal_radii: *const f64,
+        timeout_s: f64,
+        chunk_queries: u32,
+        weights: u32,
+        status_out: *mut i32,
+    ) -> i32;
+    pub fn oxhip_prm_batch_get_costs(p: *mut OxhipPrm, cost: *mut f64) -> i32;
+    pub fn oxhip_prm_batch_get_labels(p: *mut OxhipPrm, query: u32, cost: *mut f64, hops: *mut u32, parent: *mut u32, cap: u32) -> i32;
+    pub fn oxhip_prm_batch_get_search_stats(p: *mut OxhipPrm, label_rounds: *mut u32, relaxations: *mut u64, phase_ms: *mut f64) -> i32;
 }
 
 #[cfg(test)]

@@ -481,6 +481,16 @@ impl<D: DeviceValidityChecker, G: DeviceGoal> HipPRM<D, G> {
     /// `set_problem_definition` + `solve` would return, the breadth-first search included on the GPU.  The planner's own
     /// problem definition is left as it is.
     pub fn solve_batch(&mut self, problems: &[Arc<Pd<G>>], timeout: Duration) -> Vec<Result<Path<RealVectorState>, PlanningError>> {
+        self.solve_batch_with(problems, timeout, false)
+    }
+
+    /// The same batch answered with shortest paths on the roadmap in the space's distance (`oxhip_prm_solve_batch_shortest`):
+    /// the statuses are `solve_batch`'s, the paths are no longer than its fewest-hop ones.
+    pub fn solve_batch_shortest(&mut self, problems: &[Arc<Pd<G>>], timeout: Duration) -> Vec<Result<Path<RealVectorState>, PlanningError>> {
+        self.solve_batch_with(problems, timeout, true)
+    }
+
+    fn solve_batch_with(&mut self, problems: &[Arc<Pd<G>>], timeout: Duration, shortest: bool) -> Vec<Result<Path<RealVectorState>, PlanningError>> {
         let dim = match (&self.problem_def, self.prm.is_null()) {
             (Some(pd), false) => pd.space.dimension,
             _ => return problems.iter().map(|_| Err(PlanningError::PlannerUninitialised)).collect(), // prm.rs:229-236
@@ -496,7 +506,11 @@ impl<D: DeviceValidityChecker, G: DeviceGoal> HipPRM<D, G> {
         }
         let mut status = vec![0i32; q.max(1)];
         let st = unsafe {
-            ffi::oxhip_prm_solve_batch(self.prm, q as u32, starts.as_ptr(), centres.as_ptr(), radii.as_ptr(), timeout.as_secs_f64(), 0, status.as_mut_ptr())
+            if shortest {
+                ffi::oxhip_prm_solve_batch_shortest(self.prm, q as u32, starts.as_ptr(), centres.as_ptr(), radii.as_ptr(), timeout.as_secs_f64(), 0, 0, status.as_mut_ptr())
+            } else {
+                ffi::oxhip_prm_solve_batch(self.prm, q as u32, starts.as_ptr(), centres.as_ptr(), radii.as_ptr(), timeout.as_secs_f64(), 0, status.as_mut_ptr())
+            }
         };
         if st != ffi::OXHIP_OK {
             return problems.iter().map(|_| Err(to_planning_error(st))).collect();

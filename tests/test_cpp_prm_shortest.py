@@ -1,0 +1,36 @@
+"""The C++ host mirror's PRM::solve_batch_shortest (include/oxmpl/oxmpl.hpp) compiled against the C ABI.  CPU: it must build, link
+and refuse to plan without a GPU (exit 77).  GPU: the outcomes are solve_batch's and no path is longer than its (exit 0)."""
+import os
+import subprocess
+
+import pytest
+
+from oxmpl_amd import capi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _build(tmp_path, name="test_prm_shortest_rvss"):
+    capi.build_library()
+    exe = str(tmp_path / name)
+    libdir = os.path.join(ROOT, "oxmpl_amd", "lib")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", name + ".cpp"), "-o", exe,
+                           "-L", libdir, "-loxmpl_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
+    return exe
+
+
+def test_cpp_prm_shortest_builds_and_refuses_without_gpu(tmp_path):
+    exe = _build(tmp_path)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode in (0, 77), r.stdout + r.stderr
+    if r.returncode == 77:
+        assert "refused as designed" in r.stdout
+
+
+@pytest.mark.gpu
+def test_cpp_prm_shortest_against_the_breadth_first_batch(tmp_path):
+    exe = _build(tmp_path)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "PRM shortest batch test passed!" in r.stdout
