@@ -10,7 +10,7 @@ import sys
 import numpy as np
 import pytest
 
-from helpers import unhex, hexf, bits, params_spheres, params_boxes
+from helpers import unhex, hexf, bits
 from prm_helpers import STATUS_NAME
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -23,29 +23,16 @@ import make_golden_so3 as g3  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 from oxmpl_amd import capi  # noqa: E402
+from prm_shortest_helpers import Batch, RoadmapChecker, make_gpu_prm, DISTANCE, UNIT, ZERO  # noqa: E402
 
 SEED = 20261019
-START_ROW = 0xFFFFFFFF
 FIXTURE = [0.0, 0.0, 0.0, 1.0, math.pi]
 SCENES = ("wall", "r6", "fixture")
-DISTANCE, UNIT, ZERO = 0, 1, 2
 
 
 def _golden(name):
     with open(os.path.join(HERE, "golden", name)) as f:
         return json.load(f)
-
-
-def make_gpu_prm(P, **kw):
-    args = dict(max_milestones=P["max_milestones"], lvs_fraction=P["fraction"], seed=P["seed"], stream=P["stream"],
-                max_samples=0 if P["max_samples"] >= 10 ** 9 else P["max_samples"])
-    args.update(kw)
-    g = capi.PRMRoadmap(P["dim"], P["bounds"], P["radius"], **args)
-    if P["spheres"]:
-        g.set_spheres(*params_spheres(P))
-    if P["boxes"]:
-        g.set_boxes(*params_boxes(P))
-    return g
 
 
 def make_so3_prm(sc, **kw):
@@ -58,59 +45,7 @@ def make_so3_prm(sc, **kw):
     return g
 
 
-class Batch:
-    """one batch -- shortest paths with `weights`, or the breadth-first one (weights=None) -- and everything its getters return"""
-
-    def __init__(self, g, starts, goals, radii, weights=DISTANCE, **kw):
-        self.starts = np.asarray(starts, dtype=np.float64).reshape(len(radii), g.dim)
-        if weights is None:
-            self.status = g.solve_batch(starts, goals, radii, **kw).copy()
-        else:
-            self.status = g.solve_batch_shortest(starts, goals, radii, weights=weights, **kw).copy()
-        r = g.batch_results()
-        assert np.array_equal(self.status, r["status"])
-        self.len, self.goal, self.ns, self.ng = r["path_len"], r["goal_node"], r["n_start"], r["n_goal"]
-        self.off, self.nodes, self.rows = g.batch_paths()
-        self.timing = g.batch_last_timing()
-        self.cost = None if weights is None else g.batch_costs().copy()
-        q = len(radii)
-        assert len(self.status) == q and len(self.off) == q + 1 and int(self.off[0]) == 0
-        assert np.array_equal(np.diff(self.off.astype(np.int64)), self.len.astype(np.int64))
-        assert len(self.nodes) == int(self.off[-1]) and self.rows.shape == (int(self.off[-1]), g.dim)
-        ok = self.status == capi.OK
-        assert np.all(self.len[~ok] == 0) and np.all(self.goal[~ok] == -1) and np.all(self.len[ok] >= 2)
-        bad = (self.status == capi.ERR_INVALID_START_STATE) | (self.status == capi.ERR_TIMEOUT)
-        assert np.all(self.ns[bad] == 0) and np.all(self.ng[bad] == 0)
-        assert set(np.unique(self.status)) <= {capi.OK, capi.ERR_NO_SOLUTION_FOUND, capi.ERR_INVALID_START_STATE, capi.ERR_TIMEOUT}
-        if self.cost is not None:
-            assert np.all(np.isinf(self.cost[~ok])) and np.all(np.isfinite(self.cost[ok]))
-
-    def path(self, q):
-        return self.rows[int(self.off[q]):int(self.off[q + 1])]
-
-    def path_nodes(self, q):
-        return [int(v) for v in self.nodes[int(self.off[q]):int(self.off[q + 1])]]
-
-    def check_rows_are_milestones(self, milestones):
-        for q in np.nonzero(self.status == capi.OK)[0]:
-            nd, rows = self.path_nodes(q), self.path(q)
-            assert nd[0] == START_ROW and np.array_equal(bits(rows[0]), bits(self.starts[q]))
-            assert np.array_equal(bits(rows[1:]), bits(milestones[nd[1:]]))
-            assert nd[-1] == int(self.goal[q])
-
-    def same_as(self, other, upto=None):
-        n = len(self.status) if upto is None else upto
-        rows = int(other.off[n])
-        pairs = [(self.status[:n], other.status[:n]), (self.len[:n], other.len[:n]), (self.goal[:n], other.goal[:n]), (self.ns[:n], other.ns[:n]),
-                 (self.ng[:n], other.ng[:n]), (self.off[:n + 1], other.off[:n + 1]), (self.nodes[:rows], other.nodes[:rows]),
-                 (bits(self.rows[:rows]), bits(other.rows[:rows]))]
-        if self.cost is not None and other.cost is not None:
-            pairs.append((bits(self.cost[:n]), bits(other.cost[:n])))
-        for a, b in pairs:
-            assert np.array_equal(a, b)
-
-
-class Scene:
+class Scene(RoadmapChecker):
     """a golden scene's roadmap on the device, its copy for the checker, and the scene's 32 recorded queries"""
 
     def __init__(self, name):
@@ -127,17 +62,6 @@ class Scene:
         self.g.construct_roadmap()
         self.load_roadmap()
 
-    def load_roadmap(self):
-        self.states, offsets, nbrs = self.g.roadmap()
-        self.n = len(offsets) - 1
-        self.edges = [[int(v) for v in nbrs[int(offsets[i]):int(offsets[i + 1])]] for i in range(self.n)]
-        self.W = {}
-
-    def weights(self, mode):
-        if mode not in self.W:
-            self.W[mode] = gsp.edge_weights(self.edges, self.states, self.dist, mode)
-        return self.W[mode]
-
     def random_queries(self, n, seed):
         rng = np.random.default_rng([SEED, seed])
         if self.so3:
@@ -148,25 +72,6 @@ class Scene:
         r_lo, r_hi = (0.3, 0.8) if dim == 2 else (2.0, 3.5)
         return (rng.uniform(0.0, 10.0, size=(n, dim)).tolist(), rng.uniform(0.0, 10.0, size=(n, dim)).tolist(),
                 [float(v) for v in rng.uniform(r_lo, r_hi, size=n)])
-
-    def checker(self, B, q, mode):
-        """the checker's answer to query q of batch B, from the device's own roadmap and query sets"""
-        sc, gi = self.g.batch_query_sets(q)
-        init = gsp.init_labels(self.n, [int(v) for v in sc], [float(v) for v in B.starts[q]], self.states, self.dist, mode)
-        return gsp.shortest_query(self.edges, self.weights(mode), init, [int(v) for v in gi])
-
-    def check_against_checker(self, B, mode, queries=None):
-        """statuses, costs and node lists of the batch against the checker; -> number solved"""
-        solved = 0
-        for q in (range(len(B.status)) if queries is None else queries):
-            if B.status[q] == capi.ERR_INVALID_START_STATE:
-                continue
-            res = self.checker(B, q, mode)
-            assert STATUS_NAME[int(B.status[q])] == res["status"], q
-            assert bits(np.float64(B.cost[q])) == bits(np.float64(res["cost"])), q
-            assert B.path_nodes(q)[1:] == res["nodes"] and int(B.goal[q]) == res["goal"], q
-            solved += res["status"] == "solved"
-        return solved
 
 
 _scenes = {}
