@@ -4,13 +4,16 @@
 // What oxhip_api.hip builds from them: the table of spaces (kSpaces, one row per oxhip_space) and create() in its steps --
 // validate_config (pure host code: space_resolution, se_space_resolution and so3_space_resolution below), fill_params,
 // alloc_common (alloc_star at its place), the kernel kind, alloc_cells, alloc_shadow -- and the entry points' shared openings
-// (setup_done / ready) and bodies (copy_tree, op_batch with a TmpStream).
+// (setup_done / ready) and bodies (copy_tree, op_batch with a TmpStream).  oxhip_prm_api.hip takes the same resolution helpers for
+// validate_prm_config, DevBuf::reserve for its workspaces and prm_bfs_path, the graph search of Planner::solve.  No device code.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <chrono>
 #include <cmath>
+#include <deque>
 #include <limits>
 #include <memory>
 #include <string>
@@ -96,6 +99,7 @@ struct DevBuf {
         if (count == 0) return hipSuccess;
         return hipMalloc((void**)&p, count * sizeof(T));
     }
+    hipError_t reserve(size_t count) { return n < count ? alloc(count) : hipSuccess; }   // grow to at least `count`; contents not preserved
 };
 
 // what create() answers when one of its device allocations failed
@@ -200,14 +204,45 @@ inline int32_t so3_rotation_bounds(const double* bounds, double& max_angle) {
 inline int32_t so3_space_resolution(uint32_t dim, const double* bounds, double& fraction, double& res, double& max_angle) {
     if (dim != 4) return fail(OXHIP_ERR_BAD_ARG, "SO(3) states are quaternions (x, y, z, w): dim must be 4");
     const double pi = 3.14159265358979323846;
-    int32_t rb = so3_rotation_bounds(bounds, max_angle);
-    if (rb != OXHIP_OK) return rb;
+    OX_TRY(so3_rotation_bounds(bounds, max_angle));
     if (fraction > 0.0 && fraction <= 1.0) {} else if (fraction <= 0.0) fraction = 0.0; else fraction = 1.0;
     const double lvsl = 0.5 * pi * fraction;
     res = lvsl * 0.1;
     if (!(res > 0.0)) return fail(OXHIP_ERR_BAD_ARG, "longest valid segment length is 0: check_motion would never terminate");
     if (0.5 * pi / res > 1e6) return fail(OXHIP_ERR_BAD_ARG, "more than 1e6 validity checks per edge");
     return OXHIP_OK;
+}
+
+// PRM's Planner::solve from the query sets on (prm.rs:266-304) and reconstruct_path (prm.rs:189-208), on the CSR roadmap (every
+// row ascending): pure host code.  flags[i] & 2 marks a goal milestone; start_conn are the start connections, enqueued twice, as
+// the reference does.  The clock starts here and is read at every pop (prm.rs:285-287); timeout_s = +inf: no limit, and no clock read.
+// found: out_chain = goal milestone ... root connection (the path's states in reverse).
+enum class PrmBfs { found, unreachable, timed_out, empty_set };
+inline PrmBfs prm_bfs_path(const std::vector<uint32_t>& offsets, const std::vector<uint32_t>& nbrs, const std::vector<uint8_t>& flags,
+                           const std::vector<uint32_t>& start_conn, double timeout_s, std::vector<uint32_t>& out_chain) {
+    const auto t0 = std::chrono::steady_clock::now();
+    out_chain.clear();
+    bool any_goal = false;
+    for (uint8_t f : flags) any_goal = any_goal || (f & 2);
+    if (start_conn.empty() || !any_goal) return PrmBfs::empty_set;   // prm.rs:266-268
+    std::deque<uint32_t> queue(start_conn.begin(), start_conn.end());
+    std::vector<int64_t> parent(flags.size(), -2);   // parent_map: -2 absent, -1 = Some(None)
+    std::vector<uint8_t> visited(flags.size(), 0);
+    for (uint32_t s : start_conn) { queue.push_back(s); parent[s] = -1; visited[s] = 1; }
+    while (!queue.empty()) {
+        const uint32_t cur = queue.front();
+        queue.pop_front();
+        if (std::isfinite(timeout_s) && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > timeout_s) return PrmBfs::timed_out;
+        if (flags[cur] & 2) {   // goal_indices.contains(&current_idx)
+            for (int64_t c = cur; c >= 0; c = parent[(size_t)c]) out_chain.push_back((uint32_t)c);
+            return PrmBfs::found;
+        }
+        for (uint32_t e = offsets[cur]; e < offsets[cur + 1]; ++e) {
+            const uint32_t nb = nbrs[e];
+            if (!visited[nb]) { visited[nb] = 1; parent[nb] = (int64_t)cur; queue.push_back(nb); }
+        }
+    }
+    return PrmBfs::unreachable;   // prm.rs:304
 }
 
 }  // namespace oxhip

@@ -1,13 +1,13 @@
 // oxhip_prm_api.hip -- the PRM part of the C ABI (include/oxmpl_hip.h, oxhip_prm_*).
 //
-// Host side of oxmpl's PRM (oxmpl/src/geometric/planners/prm.rs): owns the device roadmap, drives
-// the construction phases of prm_kernels.hip, and runs the breadth-first query (prm.rs:270-307) and
-// reconstruct_path (prm.rs:189-208) on the CSR roadmap it copies back once per construction.  Start
-// validity, start connections and goal milestones (prm.rs:243-264) are computed on the device.
-// oxhip_prm_solve_batch (the end of this file; prm_batch.hip) answers many queries in one call with the search
-// and the path extraction on the device as well; it needs no host copy of the roadmap.
-// There is no CPU fallback: without a HIP device every computing entry point fails.
-// space = OXHIP_SPACE_SO3 runs the same phases with the kernels of prm_so3.hip.
+// Host side of oxmpl's PRM (oxmpl/src/geometric/planners/prm.rs): owns the device roadmap and drives the kernels of prm_kernels.hip
+// (space = OXHIP_SPACE_SO3: prm_so3.hip).  No CPU fallback: without a HIP device every computing entry point fails.
+// Each entry point is a sequence of named steps ("PRM host side"): create = validate_prm_config, select_device,
+// fill_prm_params, alloc_prm; construct_roadmap = the reference's loop over sample_until, knn_row_radii, find_pairs, knn_select,
+// reserve_keys, check_edges, then build_csr; solve = query_sets, prm_bfs_path (oxhip_host.hpp, on the CSR roadmap copied back once per
+// construction), the path; solve_batch[_shortest] (DESIGN.md sections 17, 19) = stage_batch, reserve_batch_workspace, then per round
+// run_round, scatter_round, extract_round_paths.  The space is named by the dispatchers below the handle, the per-space part of
+// the sampler, the steps of create, the two obstacle setters and the prm_shortest launches that take it as an argument.
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -109,15 +109,44 @@ int32_t write_state(oxhip_prm* h, const PrmState& st) {
     return OXHIP_OK;
 }
 
+// ---- the one place that names the space: which launcher, and whether a radius travels as given or as its squared threshold
+void launch_pairs(oxhip_prm* h, uint32_t j0, uint32_t j1) {   // the k-nearest variant searches its per-row radii (knn_row_radii)
+    if (h->so3) launch_prm_so3_pairs(h->args, j0, j1, h->so3_lo, h->so3_hi, h->cfg.connection_radius, h->stream);
+    else if (h->cfg.knn_k) launch_prm_pairs(h->dp, h->args, j0, j1, std::numeric_limits<double>::infinity(), h->stream, h->knn_thr.p, h->knn_thr32.p);
+    else launch_prm_pairs(h->dp, h->args, j0, j1, h->thr_conn, h->stream);
+}
+void launch_edges(oxhip_prm* h, const PrmArgs& a, uint32_t n_cand) {
+    if (h->so3) launch_prm_so3_edges(h->dp, a, n_cand, h->stream);
+    else launch_prm_edges(h->dp, a, n_cand, h->stream);
+}
+void launch_query(oxhip_prm* h) {
+    if (h->so3) return launch_prm_so3_query(h->dp, h->args, h->n, h->query, h->cfg.connection_radius, h->flags.p, h->start_valid.p, h->stream);
+    DevParams qdp = h->dp;   // the start may lie anywhere: widen the filter's absolute margin for this launch
+    for (uint32_t k = 0; k < h->cfg.dim; ++k) qdp.filt_abs = std::fmax(qdp.filt_abs, 1e-9 * std::fabs(h->query.start[k]));
+    launch_prm_query(qdp, h->args, h->n, h->query, h->thr_conn, h->flags.p, h->start_valid.p, h->stream);
+}
+void launch_batch_flags(oxhip_prm* h, const PrmBatchArgs& b) {
+    if (h->so3) launch_prm_batch_so3_flags(h->dp, b, h->cfg.connection_radius, h->stream);
+    else launch_prm_batch_flags(h->dp, b, h->thr_conn, h->stream);
+}
+// what a goal's radius is compared with: SO(3) compares the distance with the radius itself, R^n d2 with its squared threshold
+double goal_threshold(const oxhip_prm* h, double radius) { return h->so3 ? radius : sqrt_le_threshold(radius); }
+
+// `count` coordinates of starts and of goal centres: what oxhip_prm_set_problem accepts
+int32_t check_query_points(const double* starts, const double* goal_centres, size_t count) {
+    for (size_t k = 0; k < count; ++k)
+        if (!(std::fabs(starts[k]) <= kMaxMagnitude) || !(std::fabs(goal_centres[k]) <= kMaxMagnitude))
+            return fail(OXHIP_ERR_BAD_ARG, "start / goal centre not finite or beyond 1e150");
+    return OXHIP_OK;
+}
+
 int32_t set_query(oxhip_prm* h, const double* start, const double* goal_centre, double goal_radius) {
     const uint32_t dim = h->cfg.dim;
-    for (uint32_t k = 0; k < dim; ++k)
-        if (!(std::fabs(start[k]) <= kMaxMagnitude) || !(std::fabs(goal_centre[k]) <= kMaxMagnitude))
-            return fail(OXHIP_ERR_BAD_ARG, "start / goal centre not finite or beyond 1e150");
+    OX_TRY(check_query_points(start, goal_centre, dim));
     h->query = PrmQuery{};
     std::memcpy(h->query.start, start, dim * sizeof(double));
     std::memcpy(h->query.goal_c, goal_centre, dim * sizeof(double));
-    h->query.goal_thr = h->so3 ? goal_radius : sqrt_le_threshold(goal_radius);   // SO(3): the distance is compared with the radius itself
+    h->query.goal_thr = goal_threshold(h, goal_radius);
     return OXHIP_OK;
 }
 
@@ -136,81 +165,63 @@ void clear_roadmap(oxhip_prm* h) {
     h->w_valid = false;       // and so are the edge weights
 }
 
-// Draw samples until `target` milestones exist or `max_samples` were drawn.  Rounds of the parallel sampler
-// sized by the observed validity rate; a round in which rand's range sampler would have rejected a draw is
-// replayed by the sequential kernel (exact for any bounds, and about as likely as a 2^-52 event).
-int32_t sample_until(oxhip_prm* h, PrmState& st, uint32_t target, uint64_t max_samples) {
-    constexpr uint64_t kRoundMax = 1ull << 22;
-    const uint32_t dim = h->cfg.dim;
-    h->args.n_target = target;
-    while (st.n_milestones < target && st.n_samples < max_samples) {
-        const uint32_t need = target - st.n_milestones;
-        uint64_t want = (uint64_t)((double)need / h->valid_rate * 1.02) + 256;
-        want = std::min(want, std::min(max_samples - st.n_samples, kRoundMax));
-        const uint32_t m = (uint32_t)want, nw = (m + 63) / 64;
-        if (h->spec_tmp.n < (size_t)m * dim) HIP_TRY(h->spec_tmp.alloc((size_t)m * dim));
-        if (h->spec_vbits.n < nw) { HIP_TRY(h->spec_vbits.alloc(nw)); HIP_TRY(h->spec_off.alloc(nw)); }
-        if (h->spec_flag.n == 0) HIP_TRY(h->spec_flag.alloc(1));
-        HIP_TRY(hipMemsetAsync(h->spec_flag.p, 0, sizeof(uint32_t), h->stream));
-        PrmSpec sp{};
-        sp.pos0 = st.draws; sp.m = m;
-        sp.tmp = h->spec_tmp.p; sp.vbits = h->spec_vbits.p; sp.wave_off = h->spec_off.p;
-        sp.redraw_flag = h->spec_flag.p; sp.result = h->state.p;   // the scan kernel advances the device state
-        launch_prm_sample_spec(h->dp, h->args, sp, st.n_milestones, h->stream);
-        HIP_TRY(hipGetLastError());
-        PrmState after{};
-        uint32_t flag = 0;
-        HIP_TRY(hipMemcpyAsync(&after, h->state.p, sizeof(PrmState), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(&flag, h->spec_flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        if (flag == 0) {
-            const double drawn = (double)(after.n_samples - st.n_samples), got = (double)(after.n_milestones - st.n_milestones);
-            h->valid_rate = std::max(1.0 / 64.0, std::min(1.0, (got + 1.0) / (drawn + 1.0)));
-            st = after;
-        } else {
-            // a draw was rejected somewhere in the round: put the state back and replay this window in order
-            OX_TRY(write_state(h, st));
-            h->args.max_samples = st.n_samples + m;
-            launch_prm_sample(h->dp, h->args, h->stream);
-            HIP_TRY(hipGetLastError());
-            OX_TRY(read_state(h, st));
-        }
-    }
-    return OXHIP_OK;
-}
-
-// The SO(3) sampler (prm_so3.hip): rounds of m rejection attempts, attempt a at stream word pos0 + 4 a, sized by the observed
-// rate of milestones per attempt.  random_range(-1.0..1.0) cannot draw again (its largest value is 1 - 2^-51), so a flagged round
-// would mean the word positions are wrong: it is refused, never shifted.
-int32_t sample_until_so3(oxhip_prm* h, PrmState& st, uint32_t target, uint64_t max_samples) {
-    constexpr uint64_t kRoundMax = 1ull << 22;
-    h->args.n_target = target;
-    h->args.max_samples = max_samples;
-    while (st.n_milestones < target && st.n_samples < max_samples) {
-        const uint32_t need = target - st.n_milestones;
-        uint64_t want = (uint64_t)((double)need / h->valid_rate * 1.02) + 256;
-        want = std::min(want, kRoundMax);
-        const uint32_t m = (uint32_t)want, nw = (m + 63) / 64;
-        if (h->spec_tmp.n < (size_t)m * 4) HIP_TRY(h->spec_tmp.alloc((size_t)m * 4));
-        if (h->spec_vbits.n < nw) {
-            HIP_TRY(h->spec_vbits.alloc(nw)); HIP_TRY(h->spec_off.alloc(nw)); HIP_TRY(h->spec_abits.alloc(nw)); HIP_TRY(h->spec_acnt.alloc(nw));
-        }
-        if (h->spec_flag.n == 0) HIP_TRY(h->spec_flag.alloc(1));
-        HIP_TRY(hipMemsetAsync(h->spec_flag.p, 0, sizeof(uint32_t), h->stream));
+// One round of the space's parallel sampler from stream word st.draws on.  R^n: m samples.  SO(3) (prm_so3.hip): m rejection
+// attempts, attempt a at stream word pos0 + 4 a.
+int32_t sample_round(oxhip_prm* h, const PrmState& st, uint32_t m) {
+    if (h->so3) {
+        HIP_TRY(h->spec_abits.reserve((m + 63) / 64)); HIP_TRY(h->spec_acnt.reserve((m + 63) / 64));
         PrmSo3Spec sp{};
         sp.pos0 = st.draws; sp.m = m;
         sp.tmp = h->spec_tmp.p; sp.vbits = h->spec_vbits.p; sp.abits = h->spec_abits.p; sp.voff = h->spec_off.p; sp.acnt = h->spec_acnt.p;
         sp.redraw_flag = h->spec_flag.p; sp.result = h->state.p;
         launch_prm_so3_sample(h->dp, h->args, sp, st.n_milestones, h->stream);
-        HIP_TRY(hipGetLastError());
+    } else {
+        PrmSpec sp{};
+        sp.pos0 = st.draws; sp.m = m;
+        sp.tmp = h->spec_tmp.p; sp.vbits = h->spec_vbits.p; sp.wave_off = h->spec_off.p;
+        sp.redraw_flag = h->spec_flag.p; sp.result = h->state.p;   // the scan kernel advances the device state
+        launch_prm_sample_spec(h->dp, h->args, sp, st.n_milestones, h->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return OXHIP_OK;
+}
+
+// A round whose flag came back set.  R^n: rand's range sampler would have rejected a draw somewhere in it (about as likely as a
+// 2^-52 event): put the state back and replay this window in order with the sequential kernel, exact for any bounds.  SO(3):
+// random_range(-1.0..1.0) cannot draw again (its largest value is 1 - 2^-51), so the word positions would be wrong: refused, never shifted.
+int32_t flagged_round(oxhip_prm* h, PrmState& st, uint32_t m) {
+    if (h->so3) return fail(OXHIP_ERR_HIP, "SO(3) sampler: random_range(-1.0..1.0) drew again, which cannot happen; round refused");
+    OX_TRY(write_state(h, st));
+    h->args.max_samples = st.n_samples + m;
+    launch_prm_sample(h->dp, h->args, h->stream);
+    HIP_TRY(hipGetLastError());
+    return read_state(h, st);
+}
+
+// Draw samples until `target` milestones exist or `max_samples` were drawn: rounds of the parallel sampler, sized by the observed
+// rate of milestones per sample (SO(3): per attempt; its kernel stops at args.max_samples itself, so its rounds are not clamped).
+int32_t sample_until(oxhip_prm* h, PrmState& st, uint32_t target, uint64_t max_samples) {
+    constexpr uint64_t kRoundMax = 1ull << 22;
+    const bool so3 = h->so3;
+    h->args.n_target = target;
+    if (so3) h->args.max_samples = max_samples;
+    while (st.n_milestones < target && st.n_samples < max_samples) {
+        const uint32_t need = target - st.n_milestones;
+        uint64_t want = std::min((uint64_t)((double)need / h->valid_rate * 1.02) + 256, kRoundMax);
+        if (!so3) want = std::min(want, max_samples - st.n_samples);
+        const uint32_t m = (uint32_t)want, nw = (m + 63) / 64;
+        HIP_TRY(h->spec_tmp.reserve((size_t)m * h->cfg.dim)); HIP_TRY(h->spec_flag.reserve(1));   // (SO(3): dim is 4)
+        HIP_TRY(h->spec_vbits.reserve(nw)); HIP_TRY(h->spec_off.reserve(nw));
+        HIP_TRY(hipMemsetAsync(h->spec_flag.p, 0, sizeof(uint32_t), h->stream));
+        OX_TRY(sample_round(h, st, m));
         PrmState after{};
         uint32_t flag = 0;
         HIP_TRY(hipMemcpyAsync(&after, h->state.p, sizeof(PrmState), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipMemcpyAsync(&flag, h->spec_flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
-        if (flag != 0) return fail(OXHIP_ERR_HIP, "SO(3) sampler: random_range(-1.0..1.0) drew again, which cannot happen; round refused");
-        const double got = (double)(after.n_milestones - st.n_milestones);
-        h->valid_rate = std::max(1e-6, std::min(1.0, (got + 1.0) / ((double)m + 1.0)));
+        if (flag != 0) { OX_TRY(flagged_round(h, st, m)); continue; }
+        const double got = (double)(after.n_milestones - st.n_milestones), drawn = so3 ? (double)m : (double)(after.n_samples - st.n_samples);
+        h->valid_rate = std::max(so3 ? 1e-6 : 1.0 / 64.0, std::min(1.0, (got + 1.0) / (drawn + 1.0)));
         st = after;
     }
     return OXHIP_OK;
@@ -252,22 +263,16 @@ double elapsed_ms(hipEvent_t a, hipEvent_t b) {
     return hipEventElapsedTime(&ms, a, b) == hipSuccess ? (double)ms : 0.0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int32_t oxhip_prm_create(const oxhip_prm_config* cfg, oxhip_prm** out) {
-    if (!cfg || !out) return fail(OXHIP_ERR_BAD_ARG, "null argument");
-    *out = nullptr;
+// ---- oxhip_prm_create in its steps
+// Every refusal that precedes the choice of a device, in the order tests/golden/prm_create_refusals.json pins: pure host code.
+// Returns the clamped fraction, res and (SO(3)) max_angle.
+int32_t validate_prm_config(const oxhip_prm_config* cfg, double& fraction, double& res, double& so3_max_angle) {
     if (cfg->struct_size != sizeof(oxhip_prm_config)) return fail(OXHIP_ERR_BAD_ARG, "struct_size mismatch");
-    if (cfg->max_milestones == 0 || cfg->max_milestones > (1u << 26))
-        return fail(OXHIP_ERR_BAD_ARG, "max_milestones must be in 1..2^26");
+    if (cfg->max_milestones == 0 || cfg->max_milestones > (1u << 26)) return fail(OXHIP_ERR_BAD_ARG, "max_milestones must be in 1..2^26");
     if (std::isnan(cfg->connection_radius)) return fail(OXHIP_ERR_BAD_ARG, "connection_radius is NaN");
-    if (cfg->space != OXHIP_SPACE_REAL_VECTOR && cfg->space != OXHIP_SPACE_SO3)
-        return fail(OXHIP_ERR_BAD_ARG, "PRM space must be OXHIP_SPACE_REAL_VECTOR (0) or OXHIP_SPACE_SO3");
-    const bool so3 = cfg->space == OXHIP_SPACE_SO3;
-    double fraction = cfg->lvs_fraction, res = 0.0, so3_max_angle = 0.0;
-    if (so3) {
+    if (cfg->space != OXHIP_SPACE_REAL_VECTOR && cfg->space != OXHIP_SPACE_SO3) return fail(OXHIP_ERR_BAD_ARG, "PRM space must be OXHIP_SPACE_REAL_VECTOR (0) or OXHIP_SPACE_SO3");
+    fraction = cfg->lvs_fraction;
+    if (cfg->space == OXHIP_SPACE_SO3) {
         OX_TRY(so3_space_resolution(cfg->dim, cfg->bounds, fraction, res, so3_max_angle));
         if (cfg->knn_k) return fail(OXHIP_ERR_BAD_ARG, "SO(3) PRM connects by radius only: knn_k must be 0");
         // no SO(3) motion is longer than PI / 2, whatever the radius
@@ -279,52 +284,233 @@ int32_t oxhip_prm_create(const oxhip_prm_config* cfg, oxhip_prm** out) {
         if (std::isfinite(cfg->connection_radius) && cfg->connection_radius / res > 1e6)
             return fail(OXHIP_ERR_BAD_ARG, "more than 1e6 validity checks per edge");
     }
-    OX_TRY(select_device(cfg->device));
+    return OXHIP_OK;
+}
 
-    std::unique_ptr<oxhip_prm, decltype(&oxhip_prm_destroy)> h(new oxhip_prm(), oxhip_prm_destroy);   // (an early return destroys it)
+// the midpoint filter's absolute margin (R^n): 1e-9 of the largest |coordinate| of the bounds and the sphere centres, at least 1e-9
+void set_filter_margin(oxhip_prm* h, const std::vector<double>& centres) {
+    h->maxabs = 1.0;
+    for (uint32_t k = 0; k < 2 * h->cfg.dim; ++k) h->maxabs = std::fmax(h->maxabs, std::fabs(h->cfg.bounds[k]));
+    for (double v : centres) h->maxabs = std::fmax(h->maxabs, std::fabs(v));
+    h->dp.filt_abs = 1e-9 * h->maxabs;
+}
+
+void fill_prm_params(oxhip_prm* h, const oxhip_prm_config* cfg, double fraction, double res, double so3_max_angle) {
     h->cfg = *cfg;
     h->cfg.lvs_fraction = fraction;
-    const uint32_t dim = cfg->dim;
-    const uint32_t cap = ((cfg->max_milestones + 1023u) / 1024u) * 1024u;
     DevParams& dp = h->dp;
-    dp.dim = dim;
-    h->so3 = so3;
-    if (so3) {   // the bounds are (cx, cy, cz, cw, max_angle); lo / hi / scale stay zero
+    dp.dim = cfg->dim; dp.res = res; dp.seed = cfg->seed;
+    h->so3 = cfg->space == OXHIP_SPACE_SO3;
+    if (h->so3) {   // the bounds are (cx, cy, cz, cw, max_angle); lo / hi / scale stay zero, and no coordinate enters the filter margin
         for (uint32_t k = 0; k < 4; ++k) dp.so3_centre[k] = cfg->bounds[k];
         dp.so3_max_angle = so3_max_angle;
         dp.space = OXHIP_SPACE_SO3;
         so3_radius_bands(cfg->connection_radius, h->so3_lo, h->so3_hi);
+        dp.filt_abs = 1e-9 * h->maxabs;
     } else {
-        for (uint32_t k = 0; k < dim; ++k) {
+        for (uint32_t k = 0; k < cfg->dim; ++k) {
             dp.lo[k] = cfg->bounds[2 * k];
             dp.hi[k] = cfg->bounds[2 * k + 1];
             dp.scale[k] = dp.hi[k] - dp.lo[k];
         }
+        set_filter_margin(h, {});
     }
-    dp.res = res;
-    dp.seed = cfg->seed;
-    if (!so3) for (uint32_t k = 0; k < 2 * dim; ++k) h->maxabs = std::fmax(h->maxabs, std::fabs(cfg->bounds[k]));
-    dp.filt_abs = 1e-9 * h->maxabs;
     h->thr_conn = sqrt_lt_threshold(cfg->connection_radius);
+}
 
+// the stream, the events and the buffers that live as long as the handle; the first error wins
+int32_t alloc_prm(oxhip_prm* h) {
+    const uint32_t dim = h->cfg.dim, cap = ((h->cfg.max_milestones + 1023u) / 1024u) * 1024u;
     hipError_t e = hipSuccess;
     auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    chk(oxhip_stream_acquire(cfg->device, &h->stream));
+    chk(oxhip_stream_acquire(h->cfg.device, &h->stream));
     for (auto& ev : h->ev) chk(hipEventCreate(&ev));
     for (auto& ev : h->bev) chk(hipEventCreate(&ev));
     for (auto& ev : h->sev) chk(hipEventCreate(&ev));
     chk(h->ms.alloc((size_t)dim * cap));
-    if (!so3) chk(h->ms32.alloc((size_t)dim * cap));   // (the SO(3) pair search screens nothing)
+    if (!h->so3) chk(h->ms32.alloc((size_t)dim * cap));   // (the SO(3) pair search screens nothing)
     chk(h->state.alloc(1));
     chk(h->flags.alloc(cap));
     chk(h->start_valid.alloc(1));
     chk(h->offsets.alloc((size_t)cap + 1));
     if (e != hipSuccess) return alloc_failed(e);
-    h->args.ms = h->ms.p;
-    h->args.ms32 = h->ms32.p;
-    h->args.cap = cap;
-    h->args.stream = cfg->stream;
-    h->args.state = h->state.p;
+    h->args.ms = h->ms.p; h->args.ms32 = h->ms32.p; h->args.state = h->state.p;
+    h->args.cap = cap; h->args.stream = h->cfg.stream;
+    return OXHIP_OK;
+}
+
+// ---- oxhip_prm_construct_roadmap in its steps: each serves the milestones [n_done, n_now) of one round
+// k-nearest variant: row j searches a radius expected to hold ~6 k earlier milestones -- the milestones are uniform over the valid
+// part of the box (fraction n / n_samples of its volume V): count(r) ~ j c_D r^D / (V f) -- so that its k nearest are almost surely
+// among the hits; a row that falls short gets the exact search afterwards (knn_select)
+int32_t knn_row_radii(oxhip_prm* h, const PrmState& st, uint32_t n_done, uint32_t n_now) {
+    const uint32_t dim = h->cfg.dim;
+    double vol = 1.0;
+    for (uint32_t k2 = 0; k2 < dim; ++k2) vol *= h->cfg.bounds[2 * k2 + 1] - h->cfg.bounds[2 * k2];
+    const double frac = st.n_samples ? std::fmin(1.0, (double)n_now / (double)st.n_samples) : 1.0;
+    const double c_d = std::pow(3.14159265358979323846, 0.5 * dim) / std::tgamma(0.5 * dim + 1.0);
+    const double want = 6.0 * h->cfg.knn_k;
+    std::vector<double> thr(h->args.cap, std::numeric_limits<double>::infinity());
+    std::vector<float> thr32(h->args.cap, std::numeric_limits<float>::infinity());
+    for (uint32_t j = n_done; j < n_now; ++j) {
+        if ((double)j <= want) continue;   // few earlier milestones: all of them are candidates
+        const double rd = want * vol * frac / (c_d * (double)j);
+        const double r = std::pow(rd, 1.0 / dim);
+        thr[j] = r * r;
+        thr32[j] = prm_screen_threshold(h->dp, thr[j]);
+    }
+    HIP_TRY(h->knn_thr.reserve(h->args.cap)); HIP_TRY(h->knn_thr32.reserve(h->args.cap));
+    HIP_TRY(hipMemcpyAsync(h->knn_thr.p, thr.data(), thr.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->knn_thr32.p, thr32.data(), thr32.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return OXHIP_OK;
+}
+
+// pairs (j in [n_done, n_now), i < j) within the connection radius, into h->cand; st.n_cand counts them
+int32_t find_pairs(oxhip_prm* h, PrmState& st, uint32_t n_done, uint32_t n_now) {
+    if (h->cand.n == 0) HIP_TRY(h->cand.alloc(std::min<size_t>(std::max<size_t>(1u << 20, (size_t)64 * h->cfg.max_milestones), (size_t)1 << 28)));
+    for (;;) {
+        h->args.cand = h->cand.p;
+        h->args.cand_cap = (uint32_t)h->cand.n;
+        st.n_cand = 0;
+        OX_TRY(write_state(h, st));
+        HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+        launch_pairs(h, n_done, n_now);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(h->ev[3], h->stream));
+        PrmState s2{};
+        OX_TRY(read_state(h, s2));
+        h->t_ms[1] += elapsed_ms(h->ev[2], h->ev[3]);
+        st.n_cand = s2.n_cand;
+        if (st.n_cand <= h->args.cand_cap) break;
+        // candidate buffer too small: the kernel kept counting, so the exact need is known; run again
+        if (st.n_cand > 0x7FFFFFFFull) return fail(OXHIP_ERR_CAPACITY, "more than 2^31 in-radius pairs in one round");
+        HIP_TRY(h->cand.alloc((size_t)st.n_cand));
+    }
+    h->n_candidates += st.n_cand;
+    return OXHIP_OK;
+}
+
+// k-nearest variant: each row's k nearest among its candidates (sorted by (j, i)), the exact search for rows that fell short.
+// The selected pairs replace the candidates as what the edge step reads: `pairs` and st.n_cand.
+int32_t knn_select(oxhip_prm* h, PrmState& st, uint32_t n_done, uint32_t n_now, uint2*& pairs) {
+    const uint32_t nc = (uint32_t)st.n_cand, rows = n_now - n_done, knn_k = h->cfg.knn_k;
+    HIP_TRY(h->knn_keys.reserve(nc + 1)); HIP_TRY(h->knn_sorted.reserve(nc + 1)); HIP_TRY(h->knn_dist.reserve(nc + 1));
+    HIP_TRY(h->knn_sel.reserve((size_t)rows * knn_k)); HIP_TRY(h->knn_failed.reserve(rows)); HIP_TRY(h->knn_counters.reserve(2));
+    size_t tb = 0;
+    if (nc) {
+        HIP_TRY(prm_sort_keys(nullptr, tb, h->knn_keys.p, h->knn_sorted.p, nc, h->args.cap, h->stream));
+        HIP_TRY(h->sort_tmp.reserve(tb));
+    }
+    HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+    HIP_TRY(hipMemsetAsync(h->knn_counters.p, 0, 2 * sizeof(uint32_t), h->stream));
+    launch_prm_knn_keys(h->args, nc, h->knn_keys.p, h->stream);
+    if (nc) HIP_TRY(prm_sort_keys(h->sort_tmp.p, tb, h->knn_keys.p, h->knn_sorted.p, nc, h->args.cap, h->stream));
+    launch_prm_knn_select(h->dp, h->args, h->knn_sorted.p, h->knn_dist.p, nc, n_done, n_now, knn_k, h->knn_sel.p, h->knn_counters.p,
+                          h->knn_failed.p, h->stream);
+    HIP_TRY(hipGetLastError());
+    uint32_t cnt[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(cnt, h->knn_counters.p, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (cnt[1]) {
+        launch_prm_knn_brute(h->dp, h->args, h->knn_failed.p, cnt[1], knn_k, h->knn_sel.p, h->knn_counters.p, h->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(cnt, h->knn_counters.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        h->knn_failed_rows += cnt[1];
+    }
+    HIP_TRY(hipEventRecord(h->ev[3], h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->t_ms[1] += elapsed_ms(h->ev[2], h->ev[3]);
+    st.n_cand = cnt[0];
+    pairs = h->knn_sel.p;
+    return OXHIP_OK;
+}
+
+// room for the keys this round can add, at most 2 per pair: growth keeps the keys of the rounds before
+int32_t reserve_keys(oxhip_prm* h, const PrmState& st) {
+    const uint64_t need = (uint64_t)st.n_keys + 2ull * st.n_cand;
+    if (need > 0xFFFFFFFFull) return fail(OXHIP_ERR_CAPACITY, "more than 2^32 directed edges");
+    if (need <= h->keys.n) return OXHIP_OK;
+    DevBuf<uint64_t> bigger;
+    HIP_TRY(bigger.alloc(std::max<size_t>((size_t)need, h->keys.n * 2)));
+    if (st.n_keys) HIP_TRY(hipMemcpyAsync(bigger.p, h->keys.p, (size_t)st.n_keys * sizeof(uint64_t), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    std::swap(bigger.p, h->keys.p); std::swap(bigger.n, h->keys.n);
+    h->args.keys = h->keys.p;
+    return OXHIP_OK;
+}
+
+// check_motion per pair of `pairs`; the kernel appends the keys of the edges and st comes back with their count
+int32_t check_edges(oxhip_prm* h, PrmState& st, uint2* pairs) {
+    PrmArgs a = h->args;
+    a.cand = pairs;
+    HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+    launch_edges(h, a, (uint32_t)st.n_cand);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[3], h->stream));
+    OX_TRY(read_state(h, st));
+    h->t_ms[2] += elapsed_ms(h->ev[2], h->ev[3]);
+    return OXHIP_OK;
+}
+
+// sort the directed keys -> every node's neighbours in ascending order (the reference's `edges`), as CSR
+int32_t build_csr(oxhip_prm* h, uint32_t n, uint32_t n_keys) {
+    size_t tmp_bytes = 0;
+    if (n_keys) {
+        // (re)size the sort's buffers before the timed region: hipMalloc is a blocking call
+        HIP_TRY(h->keys_sorted.reserve(n_keys)); HIP_TRY(h->nbrs.reserve(n_keys));
+        HIP_TRY(prm_sort_keys(nullptr, tmp_bytes, h->keys.p, h->keys_sorted.p, n_keys, h->args.cap, h->stream));
+        HIP_TRY(h->sort_tmp.reserve(tmp_bytes));
+    }
+    HIP_TRY(hipEventRecord(h->ev[4], h->stream));
+    if (n_keys) {
+        HIP_TRY(prm_sort_keys(h->sort_tmp.p, tmp_bytes, h->keys.p, h->keys_sorted.p, n_keys, h->args.cap, h->stream));
+        launch_prm_csr(h->keys_sorted.p, n_keys, n, h->args.cap, h->offsets.p, h->nbrs.p, h->stream);
+        HIP_TRY(hipGetLastError());
+    } else {
+        HIP_TRY(hipMemsetAsync(h->offsets.p, 0, ((size_t)n + 1) * sizeof(uint32_t), h->stream));
+    }
+    HIP_TRY(hipEventRecord(h->ev[5], h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->t_ms[3] = elapsed_ms(h->ev[4], h->ev[5]);
+    return OXHIP_OK;
+}
+
+// start validity, start connections and goal milestones of h->query (prm.rs:243-264), on the device
+int32_t query_sets(oxhip_prm* h, std::vector<uint8_t>& flags) {
+    const uint32_t n = h->n;
+    uint32_t start_valid = 0;
+    HIP_TRY(hipEventRecord(h->ev[0], h->stream));
+    launch_query(h);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[1], h->stream));
+    flags.assign(n, 0);
+    HIP_TRY(hipMemcpyAsync(flags.data(), h->flags.p, n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(&start_valid, h->start_valid.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->t_ms[4] = elapsed_ms(h->ev[0], h->ev[1]);
+    if (!start_valid) return fail(OXHIP_ERR_INVALID_START_STATE, "start state is in collision");  // prm.rs:243-246
+    for (uint32_t i = 0; i < n; ++i) {
+        if (flags[i] & 1) h->start_conn.push_back(i);   // prm.rs:249-256
+        if (flags[i] & 2) h->goal_idx.push_back(i);     // prm.rs:259-264
+    }
+    return OXHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t oxhip_prm_create(const oxhip_prm_config* cfg, oxhip_prm** out) {
+    if (!cfg || !out) return fail(OXHIP_ERR_BAD_ARG, "null argument");
+    *out = nullptr;
+    double fraction = 0.0, res = 0.0, so3_max_angle = 0.0;
+    OX_TRY(validate_prm_config(cfg, fraction, res, so3_max_angle));
+    OX_TRY(select_device(cfg->device));
+    std::unique_ptr<oxhip_prm, decltype(&oxhip_prm_destroy)> h(new oxhip_prm(), oxhip_prm_destroy);   // (an early return destroys it)
+    fill_prm_params(h.get(), cfg, fraction, res, so3_max_angle);
+    OX_TRY(alloc_prm(h.get()));
     *out = h.release();
     return OXHIP_OK;
 }
@@ -358,11 +544,7 @@ int32_t oxhip_prm_set_spheres(oxhip_prm* h, const double* centres, const double*
     OX_TRY(upload(h->sph_thr, thr, h->stream));
     OX_TRY(upload(h->sph_r, std::vector<double>(radii, radii + n), h->stream));
     h->dp.n_spheres = n; h->dp.sph_c = h->sph_c.p; h->dp.sph_thr = h->sph_thr.p; h->dp.sph_r = h->sph_r.p;
-    if (h->so3) return OXHIP_OK;   // cones: distance(centre, q) > radius, compared with sph_r itself
-    h->maxabs = 1.0;
-    for (uint32_t k = 0; k < 2 * dim; ++k) h->maxabs = std::fmax(h->maxabs, std::fabs(h->cfg.bounds[k]));
-    for (double v : c) h->maxabs = std::fmax(h->maxabs, std::fabs(v));
-    h->dp.filt_abs = 1e-9 * h->maxabs;
+    if (!h->so3) set_filter_margin(h, c);   // (cones: distance(centre, q) > radius, compared with sph_r itself; no filter)
     return OXHIP_OK;
 }
 
@@ -409,7 +591,7 @@ int32_t oxhip_prm_construct_roadmap(oxhip_prm* h) {
     OX_TRY(select_device(h->cfg.device));
     const auto t0 = std::chrono::steady_clock::now();
     const bool has_timeout = h->cfg.timeout > 0.0 && std::isfinite(h->cfg.timeout);
-    const uint32_t n_max = h->cfg.max_milestones;
+    const uint32_t n_max = h->cfg.max_milestones, knn_k = h->cfg.knn_k;
     // 0 = "unlimited", which still has to end when (almost) no sample is valid: 4096 draws per requested milestone
     const uint64_t max_samples = h->cfg.max_samples ? h->cfg.max_samples : 4096ull * n_max + (1ull << 22);
     for (double& t : h->t_ms) t = 0.0;
@@ -423,127 +605,20 @@ int32_t oxhip_prm_construct_roadmap(oxhip_prm* h) {
     uint32_t target = has_timeout ? std::min<uint32_t>(n_max, 4096u) : n_max;
     uint32_t n_done = 0;  // milestones whose pairs are already connected
     for (;;) {
-        // ---- 1. sample until `target` milestones
         HIP_TRY(hipEventRecord(h->ev[0], h->stream));
-        OX_TRY(h->so3 ? sample_until_so3(h, st, target, max_samples) : sample_until(h, st, target, max_samples));
+        OX_TRY(sample_until(h, st, target, max_samples));
         HIP_TRY(hipEventRecord(h->ev[1], h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
         h->t_ms[0] += elapsed_ms(h->ev[0], h->ev[1]);
         const uint32_t n_now = st.n_milestones;
-        // ---- 2. pairs (j in [n_done, n_now), i < j) within the connection radius
-        const bool any_pair = h->so3 ? h->cfg.connection_radius > 0.0 : (h->thr_conn >= 0.0 || h->cfg.knn_k);
-        if (n_now > n_done && n_now >= 2 && any_pair) {
-            if (h->cand.n == 0) {
-                HIP_TRY(h->cand.alloc(std::min<size_t>(std::max<size_t>(1u << 20, (size_t)64 * n_max), (size_t)1 << 28)));
-                h->args.cand = h->cand.p;
-                h->args.cand_cap = (uint32_t)h->cand.n;
-            }
-            const uint32_t knn_k = h->cfg.knn_k;
-            if (knn_k) {
-                // k-nearest variant: row j searches a radius expected to hold ~6 k earlier milestones -- the milestones are uniform
-                // over the valid part of the box (fraction n / n_samples of its volume V): count(r) ~ j c_D r^D / (V f) -- so that its
-                // k nearest are almost surely among the hits; a row that falls short gets the exact search afterwards
-                const uint32_t dim = h->cfg.dim;
-                double vol = 1.0;
-                for (uint32_t k2 = 0; k2 < dim; ++k2) vol *= h->cfg.bounds[2 * k2 + 1] - h->cfg.bounds[2 * k2];
-                const double frac = st.n_samples ? std::fmin(1.0, (double)n_now / (double)st.n_samples) : 1.0;
-                const double c_d = std::pow(3.14159265358979323846, 0.5 * dim) / std::tgamma(0.5 * dim + 1.0);
-                const double want = 6.0 * knn_k;
-                std::vector<double> thr(h->args.cap, std::numeric_limits<double>::infinity());
-                std::vector<float> thr32(h->args.cap, std::numeric_limits<float>::infinity());
-                for (uint32_t j = n_done; j < n_now; ++j) {
-                    if ((double)j <= want) continue;   // few earlier milestones: all of them are candidates
-                    const double rd = want * vol * frac / (c_d * (double)j);
-                    const double r = std::pow(rd, 1.0 / dim);
-                    thr[j] = r * r;
-                    thr32[j] = prm_screen_threshold(h->dp, thr[j]);
-                }
-                if (h->knn_thr.n < h->args.cap) { HIP_TRY(h->knn_thr.alloc(h->args.cap)); HIP_TRY(h->knn_thr32.alloc(h->args.cap)); }
-                HIP_TRY(hipMemcpyAsync(h->knn_thr.p, thr.data(), thr.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-                HIP_TRY(hipMemcpyAsync(h->knn_thr32.p, thr32.data(), thr32.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-                HIP_TRY(hipStreamSynchronize(h->stream));
-            }
-            for (;;) {
-                st.n_cand = 0;
-                OX_TRY(write_state(h, st));
-                HIP_TRY(hipEventRecord(h->ev[2], h->stream));
-                if (h->so3) launch_prm_so3_pairs(h->args, n_done, n_now, h->so3_lo, h->so3_hi, h->cfg.connection_radius, h->stream);
-                else if (knn_k) launch_prm_pairs(h->dp, h->args, n_done, n_now, std::numeric_limits<double>::infinity(), h->stream, h->knn_thr.p, h->knn_thr32.p);
-                else launch_prm_pairs(h->dp, h->args, n_done, n_now, h->thr_conn, h->stream);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipEventRecord(h->ev[3], h->stream));
-                PrmState s2{};
-                OX_TRY(read_state(h, s2));
-                h->t_ms[1] += elapsed_ms(h->ev[2], h->ev[3]);
-                st.n_cand = s2.n_cand;
-                if (st.n_cand <= h->args.cand_cap) break;
-                // candidate buffer too small: the kernel kept counting, so the exact need is known; run again
-                if (st.n_cand > 0x7FFFFFFFull) return fail(OXHIP_ERR_CAPACITY, "more than 2^31 in-radius pairs in one round");
-                HIP_TRY(h->cand.alloc((size_t)st.n_cand));
-                h->args.cand = h->cand.p;
-                h->args.cand_cap = (uint32_t)st.n_cand;
-            }
-            h->n_candidates += st.n_cand;
-            uint2* const cand_all = h->args.cand;
-            if (knn_k) {
-                // ---- 2b. each row's k nearest among its candidates (sorted by (j, i)); the exact search for rows that fell short
-                const uint32_t nc = (uint32_t)st.n_cand, rows = n_now - n_done;
-                if (h->knn_keys.n < nc + 1) {
-                    HIP_TRY(h->knn_keys.alloc(nc + 1)); HIP_TRY(h->knn_sorted.alloc(nc + 1)); HIP_TRY(h->knn_dist.alloc(nc + 1));
-                }
-                if (h->knn_sel.n < (size_t)rows * knn_k) HIP_TRY(h->knn_sel.alloc((size_t)rows * knn_k));
-                if (h->knn_failed.n < rows) HIP_TRY(h->knn_failed.alloc(rows));
-                if (h->knn_counters.n < 2) HIP_TRY(h->knn_counters.alloc(2));
-                size_t tb = 0;
-                if (nc) {
-                    HIP_TRY(prm_sort_keys(nullptr, tb, h->knn_keys.p, h->knn_sorted.p, nc, h->args.cap, h->stream));
-                    if (h->sort_tmp.n < tb) HIP_TRY(h->sort_tmp.alloc(tb));
-                }
-                HIP_TRY(hipEventRecord(h->ev[2], h->stream));
-                HIP_TRY(hipMemsetAsync(h->knn_counters.p, 0, 2 * sizeof(uint32_t), h->stream));
-                launch_prm_knn_keys(h->args, nc, h->knn_keys.p, h->stream);
-                if (nc) HIP_TRY(prm_sort_keys(h->sort_tmp.p, tb, h->knn_keys.p, h->knn_sorted.p, nc, h->args.cap, h->stream));
-                launch_prm_knn_select(h->dp, h->args, h->knn_sorted.p, h->knn_dist.p, nc, n_done, n_now, knn_k, h->knn_sel.p, h->knn_counters.p,
-                                      h->knn_failed.p, h->stream);
-                HIP_TRY(hipGetLastError());
-                uint32_t cnt[2] = {0, 0};
-                HIP_TRY(hipMemcpyAsync(cnt, h->knn_counters.p, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
-                HIP_TRY(hipStreamSynchronize(h->stream));
-                if (cnt[1]) {
-                    launch_prm_knn_brute(h->dp, h->args, h->knn_failed.p, cnt[1], knn_k, h->knn_sel.p, h->knn_counters.p, h->stream);
-                    HIP_TRY(hipGetLastError());
-                    HIP_TRY(hipMemcpyAsync(cnt, h->knn_counters.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-                    HIP_TRY(hipStreamSynchronize(h->stream));
-                    h->knn_failed_rows += cnt[1];
-                }
-                HIP_TRY(hipEventRecord(h->ev[3], h->stream));
-                HIP_TRY(hipStreamSynchronize(h->stream));
-                h->t_ms[1] += elapsed_ms(h->ev[2], h->ev[3]);
-                st.n_cand = cnt[0];
-                h->args.cand = h->knn_sel.p;   // the edge kernel checks the selected pairs
-            }
-            // ---- 3. check_motion per candidate; keys grow by at most 2 per candidate
-            const uint64_t need = (uint64_t)st.n_keys + 2ull * st.n_cand;
-            if (need > 0xFFFFFFFFull) return fail(OXHIP_ERR_CAPACITY, "more than 2^32 directed edges");
-            if (need > h->keys.n) {
-                DevBuf<uint64_t> bigger;
-                HIP_TRY(bigger.alloc(std::max<size_t>((size_t)need, h->keys.n * 2)));
-                if (st.n_keys)
-                    HIP_TRY(hipMemcpyAsync(bigger.p, h->keys.p, (size_t)st.n_keys * sizeof(uint64_t), hipMemcpyDeviceToDevice,
-                                           h->stream));
-                HIP_TRY(hipStreamSynchronize(h->stream));
-                std::swap(bigger.p, h->keys.p);
-                std::swap(bigger.n, h->keys.n);
-                h->args.keys = h->keys.p;
-            }
-            HIP_TRY(hipEventRecord(h->ev[2], h->stream));
-            if (h->so3) launch_prm_so3_edges(h->dp, h->args, (uint32_t)st.n_cand, h->stream);
-            else launch_prm_edges(h->dp, h->args, (uint32_t)st.n_cand, h->stream);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(h->ev[3], h->stream));
-            OX_TRY(read_state(h, st));
-            h->t_ms[2] += elapsed_ms(h->ev[2], h->ev[3]);
-            h->args.cand = cand_all;
+        // thr_conn >= 0 <=> connection_radius > 0 (sqrt_lt_threshold; NaN was refused), in either space: a radius <= 0 takes no pair
+        if (n_now > n_done && n_now >= 2 && (h->thr_conn >= 0.0 || knn_k)) {
+            if (knn_k) OX_TRY(knn_row_radii(h, st, n_done, n_now));
+            OX_TRY(find_pairs(h, st, n_done, n_now));
+            uint2* pairs = h->cand.p;
+            if (knn_k) OX_TRY(knn_select(h, st, n_done, n_now, pairs));
+            OX_TRY(reserve_keys(h, st));
+            OX_TRY(check_edges(h, st, pairs));
         }
         n_done = n_now;
         if (n_now < target) break;                       // max_samples exhausted
@@ -552,30 +627,11 @@ int32_t oxhip_prm_construct_roadmap(oxhip_prm* h) {
             break;                                       // prm.rs:118-120
         target = target > n_max / 2 ? n_max : target * 2;
     }
-    // ---- 4. sort the directed keys -> every node's neighbours in ascending order (the reference's `edges`)
-    const uint32_t n = st.n_milestones, n_keys = st.n_keys;
-    size_t tmp_bytes = 0;
-    if (n_keys) {
-        // (re)size the sort's buffers before the timed region: hipMalloc is a blocking call
-        if (h->keys_sorted.n < n_keys) { HIP_TRY(h->keys_sorted.alloc(n_keys)); HIP_TRY(h->nbrs.alloc(n_keys)); }
-        HIP_TRY(prm_sort_keys(nullptr, tmp_bytes, h->keys.p, h->keys_sorted.p, n_keys, h->args.cap, h->stream));
-        if (h->sort_tmp.n < tmp_bytes) HIP_TRY(h->sort_tmp.alloc(tmp_bytes));
-    }
-    HIP_TRY(hipEventRecord(h->ev[4], h->stream));
-    if (n_keys) {
-        HIP_TRY(prm_sort_keys(h->sort_tmp.p, tmp_bytes, h->keys.p, h->keys_sorted.p, n_keys, h->args.cap, h->stream));
-        launch_prm_csr(h->keys_sorted.p, n_keys, n, h->args.cap, h->offsets.p, h->nbrs.p, h->stream);
-        HIP_TRY(hipGetLastError());
-    } else {
-        HIP_TRY(hipMemsetAsync(h->offsets.p, 0, ((size_t)n + 1) * sizeof(uint32_t), h->stream));
-    }
-    HIP_TRY(hipEventRecord(h->ev[5], h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    h->t_ms[3] = elapsed_ms(h->ev[4], h->ev[5]);
-    h->n_keys = n_keys;
+    OX_TRY(build_csr(h, st.n_milestones, st.n_keys));
+    h->n_keys = st.n_keys;
     h->w_valid = false;     // the edge weights of the roadmap before this one
     h->host_copy = false;   // fetched by the first get_roadmap / solve
-    h->n = n;
+    h->n = st.n_milestones;
     h->n_samples = st.n_samples;
     h->redraw_batches = st.redraw_batches;
     return OXHIP_OK;
@@ -623,61 +679,18 @@ int32_t oxhip_prm_solve(oxhip_prm* h, double timeout_s, double* path, uint32_t c
     if (h->n == 0) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "construct_roadmap() left no milestones");  // prm.rs:239-241
     OX_TRY(select_device(h->cfg.device));
     OX_TRY(fetch_roadmap(h));
-    const uint32_t n = h->n, dim = h->cfg.dim;
-    DevParams qdp = h->dp;   // the start may lie anywhere: widen the filter's absolute margin for this launch
-    for (uint32_t k = 0; k < dim; ++k) qdp.filt_abs = std::fmax(qdp.filt_abs, 1e-9 * std::fabs(h->query.start[k]));
-    HIP_TRY(hipEventRecord(h->ev[0], h->stream));
-    if (h->so3) launch_prm_so3_query(h->dp, h->args, n, h->query, h->cfg.connection_radius, h->flags.p, h->start_valid.p, h->stream);
-    else launch_prm_query(qdp, h->args, n, h->query, h->thr_conn, h->flags.p, h->start_valid.p, h->stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-    std::vector<uint8_t> flags(n);
-    uint32_t start_valid = 0;
-    HIP_TRY(hipMemcpyAsync(flags.data(), h->flags.p, n, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(&start_valid, h->start_valid.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    h->t_ms[4] = elapsed_ms(h->ev[0], h->ev[1]);
-    if (!start_valid) return fail(OXHIP_ERR_INVALID_START_STATE, "start state is in collision");  // prm.rs:243-246
+    std::vector<uint8_t> flags;
+    OX_TRY(query_sets(h, flags));
     const auto t0 = std::chrono::steady_clock::now();
-    for (uint32_t i = 0; i < n; ++i) {
-        if (flags[i] & 1) h->start_conn.push_back(i);   // prm.rs:249-256
-        if (flags[i] & 2) h->goal_idx.push_back(i);     // prm.rs:259-264
-    }
-    if (h->start_conn.empty() || h->goal_idx.empty())
-        return fail(OXHIP_ERR_NO_SOLUTION_FOUND, "start or goal does not connect to the roadmap");  // prm.rs:266-268
-    // breadth-first search, prm.rs:270-301 (start connections are enqueued twice, as there)
-    std::deque<uint32_t> queue(h->start_conn.begin(), h->start_conn.end());
-    std::vector<int64_t> parent(n, -2);   // parent_map: -2 absent, -1 = Some(None)
-    std::vector<uint8_t> visited(n, 0);
-    for (uint32_t s : h->start_conn) {
-        queue.push_back(s);
-        parent[s] = -1;
-        visited[s] = 1;
-    }
     const bool has_timeout = timeout_s > 0.0 && std::isfinite(timeout_s);
-    int64_t goal_reached = -1;
-    while (!queue.empty()) {
-        const uint32_t cur = queue.front();
-        queue.pop_front();
-        if (has_timeout && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > timeout_s) {
-            h->t_ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            return fail(OXHIP_ERR_TIMEOUT, "graph search timed out");  // prm.rs:285-287
-        }
-        if (flags[cur] & 2) { goal_reached = cur; break; }             // goal_indices.contains(&current_idx)
-        for (uint32_t e = h->h_offsets[cur]; e < h->h_offsets[cur + 1]; ++e) {
-            const uint32_t nb = h->h_nbrs[e];
-            if (!visited[nb]) {
-                visited[nb] = 1;
-                parent[nb] = (int64_t)cur;
-                queue.push_back(nb);
-            }
-        }
-    }
+    std::vector<uint32_t> chain;   // goal milestone ... root connection
+    const PrmBfs found = prm_bfs_path(h->h_offsets, h->h_nbrs, flags, h->start_conn, has_timeout ? timeout_s : std::numeric_limits<double>::infinity(), chain);
+    if (found == PrmBfs::empty_set) return fail(OXHIP_ERR_NO_SOLUTION_FOUND, "start or goal does not connect to the roadmap");  // prm.rs:266-268
     h->t_ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (goal_reached < 0) return fail(OXHIP_ERR_NO_SOLUTION_FOUND, "goal is not reachable on the roadmap");  // prm.rs:304
-    // reconstruct_path (prm.rs:189-208): [start] ++ (root connection ... goal milestone)
-    std::vector<uint32_t> chain;
-    for (int64_t c = goal_reached; c >= 0; c = parent[(size_t)c]) chain.push_back((uint32_t)c);
+    if (found == PrmBfs::timed_out) return fail(OXHIP_ERR_TIMEOUT, "graph search timed out");  // prm.rs:285-287
+    if (found == PrmBfs::unreachable) return fail(OXHIP_ERR_NO_SOLUTION_FOUND, "goal is not reachable on the roadmap");  // prm.rs:304
+    // [start] ++ (root connection ... goal milestone)
+    const uint32_t dim = h->cfg.dim;
     *len = (uint32_t)chain.size() + 1;
     if (!path) return OXHIP_OK;
     if (*len > cap_states) return fail(OXHIP_ERR_CAPACITY, "path buffer too small");
@@ -729,11 +742,6 @@ PrmBatchArgs batch_args(oxhip_prm* h, uint32_t q0, uint32_t n_chunk, uint32_t re
     return b;
 }
 
-void launch_batch_flags(oxhip_prm* h, const PrmBatchArgs& b) {
-    if (h->so3) launch_prm_batch_so3_flags(h->dp, b, h->cfg.connection_radius, h->stream);
-    else launch_prm_batch_flags(h->dp, b, h->thr_conn, h->stream);
-}
-
 PrmShortestArgs shortest_args(oxhip_prm* h, int32_t mode) {
     PrmShortestArgs a{};
     a.w = h->w_edges.p; a.label = h->bd_label.p; a.stamp = h->bd_stamp.p; a.cost = h->bd_cost.p; a.rounds = h->bd_rounds.p;
@@ -744,7 +752,7 @@ PrmShortestArgs shortest_args(oxhip_prm* h, int32_t mode) {
 // the distances of the roadmap's CSR entries, once per roadmap (distance weights only)
 int32_t ensure_edge_weights(oxhip_prm* h) {
     if (h->w_valid) return OXHIP_OK;
-    if (h->w_edges.n < h->n_keys) HIP_TRY(h->w_edges.alloc(h->n_keys));
+    HIP_TRY(h->w_edges.reserve(h->n_keys));
     HIP_TRY(hipEventRecord(h->sev[0], h->stream));
     launch_prm_shortest_weights(h->so3, h->cfg.dim, h->ms.p, h->offsets.p, h->nbrs.p, h->n, h->n_keys, h->w_edges.p, h->stream);
     HIP_TRY(hipGetLastError());
@@ -758,163 +766,189 @@ int32_t ensure_edge_weights(oxhip_prm* h) {
 // bytes of a round's workspace per query and milestone: flag 1, parent 4, queue 4; label 8 and stamp 4 for the shortest-path search
 uint64_t batch_bytes_per_node(int32_t mode) { return mode < 0 ? 9ull : 21ull; }
 
-int32_t ensure_shortest_workspace(oxhip_prm* h, uint32_t chunk, uint32_t stride) {
-    if (h->bd_label.n < (size_t)chunk * stride) {
-        HIP_TRY(h->bd_label.alloc((size_t)chunk * stride));
-        HIP_TRY(h->bd_stamp.alloc((size_t)chunk * stride));
-    }
-    if (h->bd_cost.n < chunk) { HIP_TRY(h->bd_cost.alloc(chunk)); HIP_TRY(h->bd_rounds.alloc(chunk)); HIP_TRY(h->bd_relaxed.alloc(chunk)); }
-    return OXHIP_OK;
-}
+// one batch while it runs: its shape, and where a round's results land on the host before scatter_round files them per query
+struct BatchRun {
+    uint32_t Q = 0, chunk = 0, stride = 0, group = 0;
+    int32_t mode = -1;   // < 0: the breadth-first search of prm.rs (oxhip_prm_solve_batch); 0, 1, 2: shortest paths with that weights mode
+    PrmShortestArgs sa{};
+    std::vector<uint32_t> res;   // [5][chunk] status, path_len, goal_node, n_start, n_goal
+    std::vector<uint64_t> off;   // [chunk] first row of each query's path among the round's rows
+};
 
-// mode < 0: the breadth-first search of prm.rs (oxhip_prm_solve_batch); 0, 1, 2: shortest paths with that weights mode
-int32_t solve_batch_common(oxhip_prm* h, uint32_t n_queries, const double* starts, const double* goal_centres, const double* goal_radii,
-                           double timeout_s, uint32_t chunk_queries, int32_t mode, int32_t* status_out) {
+// the checks, the host side of the batch (every query starts out OXHIP_ERR_TIMEOUT) and the upload of the queries
+int32_t stage_batch(oxhip_prm* h, uint32_t Q, const double* starts, const double* goal_centres, const double* goal_radii, int32_t mode) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
-    if (n_queries && (!starts || !goal_centres || !goal_radii)) return fail(OXHIP_ERR_BAD_ARG, "null argument");
+    if (Q && (!starts || !goal_centres || !goal_radii)) return fail(OXHIP_ERR_BAD_ARG, "null argument");
     if (!h->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");      // prm.rs:229-236
     if (h->n == 0) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "construct_roadmap() left no milestones");  // prm.rs:239-241
-    const uint32_t Q = n_queries, n = h->n, dim = h->cfg.dim;
-    for (size_t k = 0; k < (size_t)Q * dim; ++k)   // as oxhip_prm_set_problem validates one
-        if (!(std::fabs(starts[k]) <= kMaxMagnitude) || !(std::fabs(goal_centres[k]) <= kMaxMagnitude))
-            return fail(OXHIP_ERR_BAD_ARG, "start / goal centre not finite or beyond 1e150");
+    const uint32_t dim = h->cfg.dim;
+    OX_TRY(check_query_points(starts, goal_centres, (size_t)Q * dim));
     OX_TRY(select_device(h->cfg.device));
-    const auto t0 = std::chrono::steady_clock::now();
-    const bool has_timeout = timeout_s > 0.0 && std::isfinite(timeout_s);
     h->batch_valid = false;
     h->batch_rounds = 0;
     h->batch_mode = mode;
     for (double& t : h->batch_ms) t = 0.0;
     for (double& t : h->short_ms) t = 0.0;
-    h->b_cost.assign(mode < 0 ? 0 : n_queries, std::numeric_limits<double>::infinity());
-    h->b_rounds.assign(mode < 0 ? 0 : n_queries, 0u);
-    h->b_relaxed.assign(mode < 0 ? 0 : n_queries, 0ull);
+    h->b_cost.assign(mode < 0 ? 0 : Q, std::numeric_limits<double>::infinity());
+    h->b_rounds.assign(mode < 0 ? 0 : Q, 0u);
+    h->b_relaxed.assign(mode < 0 ? 0 : Q, 0ull);
     h->b_starts.assign(starts, starts + (size_t)Q * dim);
     h->b_goals.assign(goal_centres, goal_centres + (size_t)Q * dim);
-    h->b_thr.resize(Q);
-    h->b_filt.resize(Q);
+    h->b_thr.resize(Q); h->b_filt.resize(Q);
     for (uint32_t q = 0; q < Q; ++q) {
-        h->b_thr[q] = h->so3 ? goal_radii[q] : sqrt_le_threshold(goal_radii[q]);
+        h->b_thr[q] = goal_threshold(h, goal_radii[q]);
         double f = h->dp.filt_abs;   // the start may lie anywhere: the filter's absolute margin with this start in play
         for (uint32_t k = 0; k < dim; ++k) f = std::fmax(f, 1e-9 * std::fabs(starts[(size_t)q * dim + k]));
         h->b_filt[q] = f;
     }
     h->b_status.assign(Q, OXHIP_ERR_TIMEOUT);
     h->b_goal_node.assign(Q, -1);
-    h->b_len.assign(Q, 0);
-    h->b_nstart.assign(Q, 0);
-    h->b_ngoal.assign(Q, 0);
+    h->b_len.assign(Q, 0); h->b_nstart.assign(Q, 0); h->b_ngoal.assign(Q, 0);
     h->b_off.assign((size_t)Q + 1, 0);
-    h->b_nodes.clear();
-    h->b_rows.clear();
-    if (Q) {
-        // 9 bytes per query and milestone (21 for shortest paths): the round is sized to keep the workspace within 1 GiB
-        const uint32_t stride = (n + 63u) & ~63u;
-        uint32_t chunk = chunk_queries ? chunk_queries : (uint32_t)std::max<uint64_t>(1, (1ull << 30) / (batch_bytes_per_node(mode) * stride));
-        chunk = std::min(std::min(chunk, Q), 65535u);
-        if (mode >= 0) OX_TRY(ensure_shortest_workspace(h, chunk, stride));
-        if (mode == 0) OX_TRY(ensure_edge_weights(h));
-        const PrmShortestArgs sa = shortest_args(h, mode);
-        std::vector<double> cost(mode < 0 ? 0 : chunk);
-        std::vector<uint32_t> lrounds(mode < 0 ? 0 : chunk);
-        std::vector<unsigned long long> relaxed(mode < 0 ? 0 : chunk);
-        if (h->bd_starts.n < (size_t)Q * dim) { HIP_TRY(h->bd_starts.alloc((size_t)Q * dim)); HIP_TRY(h->bd_goals.alloc((size_t)Q * dim)); }
-        if (h->bd_thr.n < Q) { HIP_TRY(h->bd_thr.alloc(Q)); HIP_TRY(h->bd_filt.alloc(Q)); }
-        if (h->bd_flags.n < (size_t)chunk * stride) {
-            HIP_TRY(h->bd_flags.alloc((size_t)chunk * stride));
-            HIP_TRY(h->bd_parent.alloc((size_t)chunk * stride));
-            HIP_TRY(h->bd_queue.alloc((size_t)chunk * stride));
-        }
-        if (h->bd_start_valid.n < chunk) {
-            HIP_TRY(h->bd_start_valid.alloc(chunk)); HIP_TRY(h->bd_res.alloc(5 * (size_t)chunk)); HIP_TRY(h->bd_off.alloc(chunk));
-        }
-        HIP_TRY(hipMemcpyAsync(h->bd_starts.p, h->b_starts.data(), (size_t)Q * dim * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->bd_goals.p, h->b_goals.data(), (size_t)Q * dim * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->bd_thr.p, h->b_thr.data(), (size_t)Q * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->bd_filt.p, h->b_filt.data(), (size_t)Q * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        const uint32_t group = prm_batch_group(n, h->n_keys);
-        std::vector<uint32_t> res(5 * (size_t)chunk);
-        std::vector<uint64_t> off(chunk);
+    h->b_nodes.clear(); h->b_rows.clear();
+    if (!Q) return OXHIP_OK;
+    HIP_TRY(h->bd_starts.reserve((size_t)Q * dim)); HIP_TRY(h->bd_goals.reserve((size_t)Q * dim));
+    HIP_TRY(h->bd_thr.reserve(Q)); HIP_TRY(h->bd_filt.reserve(Q));
+    HIP_TRY(hipMemcpyAsync(h->bd_starts.p, h->b_starts.data(), (size_t)Q * dim * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->bd_goals.p, h->b_goals.data(), (size_t)Q * dim * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->bd_thr.p, h->b_thr.data(), (size_t)Q * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->bd_filt.p, h->b_filt.data(), (size_t)Q * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    return OXHIP_OK;
+}
+
+// The size of a round -- 9 bytes per query and milestone (21 for shortest paths), sized to keep the workspace within 1 GiB -- and
+// every buffer a round of that size needs; distance weights: the roadmap's edge weights, once per roadmap
+int32_t reserve_batch_workspace(oxhip_prm* h, BatchRun& br, uint32_t chunk_queries) {
+    br.stride = (h->n + 63u) & ~63u;
+    uint32_t chunk = chunk_queries ? chunk_queries : (uint32_t)std::max<uint64_t>(1, (1ull << 30) / (batch_bytes_per_node(br.mode) * br.stride));
+    br.chunk = chunk = std::min(std::min(chunk, br.Q), 65535u);
+    const size_t cells = (size_t)chunk * br.stride;
+    if (br.mode >= 0) {
+        HIP_TRY(h->bd_label.reserve(cells)); HIP_TRY(h->bd_stamp.reserve(cells));
+        HIP_TRY(h->bd_cost.reserve(chunk)); HIP_TRY(h->bd_rounds.reserve(chunk)); HIP_TRY(h->bd_relaxed.reserve(chunk));
+    }
+    if (br.mode == 0) OX_TRY(ensure_edge_weights(h));
+    br.sa = shortest_args(h, br.mode);
+    HIP_TRY(h->bd_flags.reserve(cells)); HIP_TRY(h->bd_parent.reserve(cells)); HIP_TRY(h->bd_queue.reserve(cells));
+    HIP_TRY(h->bd_start_valid.reserve(chunk)); HIP_TRY(h->bd_off.reserve(chunk));
+    HIP_TRY(h->bd_res.reserve(5 * (size_t)chunk));   // (the getters take bd_res.n / 5 as a round's row count: never below this one)
+    br.group = prm_batch_group(h->n, h->n_keys);
+    br.res.resize(5 * (size_t)chunk); br.off.resize(chunk);
+    return OXHIP_OK;
+}
+
+// flags, initial labels, label rounds and tight levels of the queries of `b`; `timed`: a batch's round, which records its events between
+int32_t launch_shortest(oxhip_prm* h, const PrmBatchArgs& b, const PrmShortestArgs& sa, uint32_t group, bool timed) {
+    launch_batch_flags(h, b);
+    launch_prm_shortest_init(h->so3, b, sa, h->stream);
+    if (timed) HIP_TRY(hipEventRecord(h->bev[1], h->stream));
+    launch_prm_shortest_labels(b, sa, group, h->stream);
+    HIP_TRY(hipGetLastError());
+    if (timed) HIP_TRY(hipEventRecord(h->sev[0], h->stream));
+    launch_prm_shortest_levels(b, sa, group, h->stream);
+    HIP_TRY(hipGetLastError());
+    return OXHIP_OK;
+}
+
+// one round on the device: the query sets, the search, and its results copied into `br` (the search's own figures: to their queries)
+int32_t run_round(oxhip_prm* h, BatchRun& br, const PrmBatchArgs& b) {
+    const uint32_t c = b.n_chunk, q0 = b.q0;
+    HIP_TRY(hipMemsetAsync(h->bd_parent.p, 0xFF, (size_t)c * br.stride * sizeof(uint32_t), h->stream));
+    HIP_TRY(hipEventRecord(h->bev[0], h->stream));
+    if (br.mode < 0) {
+        launch_batch_flags(h, b);
+        HIP_TRY(hipEventRecord(h->bev[1], h->stream));
+        launch_prm_batch_search(b, br.group, h->stream);
+        HIP_TRY(hipGetLastError());
+    } else {
+        OX_TRY(launch_shortest(h, b, br.sa, br.group, true));
+    }
+    HIP_TRY(hipEventRecord(h->bev[2], h->stream));
+    HIP_TRY(hipMemcpyAsync(br.res.data(), h->bd_res.p, 5 * (size_t)br.chunk * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (br.mode >= 0) {
+        HIP_TRY(hipMemcpyAsync(h->b_cost.data() + q0, h->bd_cost.p, (size_t)c * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->b_rounds.data() + q0, h->bd_rounds.p, (size_t)c * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->b_relaxed.data() + q0, h->bd_relaxed.p, (size_t)c * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipEventRecord(h->bev[3], h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->batch_ms[0] += elapsed_ms(h->bev[0], h->bev[1]);
+    h->batch_ms[1] += elapsed_ms(h->bev[1], h->bev[2]);
+    h->batch_ms[3] += elapsed_ms(h->bev[2], h->bev[3]);
+    if (br.mode < 0) return OXHIP_OK;
+    h->short_ms[2] += elapsed_ms(h->bev[1], h->sev[0]);
+    h->short_ms[3] += elapsed_ms(h->sev[0], h->bev[2]);
+    for (uint32_t i = 0; i < c; ++i)
+        if ((int32_t)br.res[i] == OXHIP_ERR_HIP)   // (no query status is OXHIP_ERR_HIP otherwise)
+            return fail(OXHIP_ERR_HIP, "shortest-path search: a label round or level cap was hit, which cannot happen");
+    return OXHIP_OK;
+}
+
+// the round's results into the per-query vectors; returns the rows of the round's paths (br.off: where each begins among them)
+uint64_t scatter_round(oxhip_prm* h, BatchRun& br, uint32_t q0, uint32_t c) {
+    const size_t chunk = br.chunk;
+    uint64_t rows = 0;
+    const uint64_t row0 = h->b_off[q0];
+    for (uint32_t i = 0; i < c; ++i) {
+        h->b_status[q0 + i] = (int32_t)br.res[i];
+        h->b_len[q0 + i] = br.res[chunk + i];
+        h->b_goal_node[q0 + i] = (int32_t)br.res[2 * chunk + i];
+        h->b_nstart[q0 + i] = br.res[3 * chunk + i];
+        h->b_ngoal[q0 + i] = br.res[4 * chunk + i];
+        br.off[i] = rows;
+        rows += br.res[chunk + i];
+        h->b_off[q0 + i + 1] = row0 + rows;
+    }
+    return rows;
+}
+
+// the `rows` path rows of the round, extracted on the device and appended to b_nodes / b_rows
+int32_t extract_round_paths(oxhip_prm* h, const BatchRun& br, const PrmBatchArgs& b, uint64_t rows) {
+    const uint32_t dim = h->cfg.dim;
+    const uint64_t row0 = h->b_off[b.q0];
+    HIP_TRY(h->bd_nodes.reserve((size_t)rows)); HIP_TRY(h->bd_rows.reserve((size_t)rows * dim));
+    h->b_nodes.resize((size_t)(row0 + rows)); h->b_rows.resize((size_t)(row0 + rows) * dim);
+    HIP_TRY(hipMemcpyAsync(h->bd_off.p, br.off.data(), (size_t)b.n_chunk * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipEventRecord(h->bev[4], h->stream));
+    launch_prm_batch_paths(b, h->bd_off.p, h->bd_nodes.p, h->bd_rows.p, h->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->bev[5], h->stream));
+    HIP_TRY(hipMemcpyAsync(h->b_nodes.data() + row0, h->bd_nodes.p, (size_t)rows * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->b_rows.data() + (size_t)row0 * dim, h->bd_rows.p, (size_t)rows * dim * sizeof(double), hipMemcpyDeviceToHost,
+                           h->stream));
+    HIP_TRY(hipEventRecord(h->bev[6], h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->batch_ms[2] += elapsed_ms(h->bev[4], h->bev[5]);
+    h->batch_ms[3] += elapsed_ms(h->bev[5], h->bev[6]);
+    return OXHIP_OK;
+}
+
+int32_t solve_batch_common(oxhip_prm* h, uint32_t n_queries, const double* starts, const double* goal_centres, const double* goal_radii,
+                           double timeout_s, uint32_t chunk_queries, int32_t mode, int32_t* status_out) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool has_timeout = timeout_s > 0.0 && std::isfinite(timeout_s);
+    OX_TRY(stage_batch(h, n_queries, starts, goal_centres, goal_radii, mode));
+    BatchRun br;
+    br.Q = n_queries; br.mode = mode;
+    if (br.Q) {
+        OX_TRY(reserve_batch_workspace(h, br, chunk_queries));
         uint32_t answered = 0;
-        for (uint32_t q0 = 0; q0 < Q; q0 += chunk) {
+        for (uint32_t q0 = 0; q0 < br.Q; q0 += br.chunk) {
             // the clock is read between rounds: the queries of the rounds not begun keep OXHIP_ERR_TIMEOUT
             if (q0 && has_timeout && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > timeout_s) break;
-            const uint32_t c = std::min(chunk, Q - q0);
-            const PrmBatchArgs b = batch_args(h, q0, c, chunk);
-            HIP_TRY(hipMemsetAsync(h->bd_parent.p, 0xFF, (size_t)c * stride * sizeof(uint32_t), h->stream));
-            HIP_TRY(hipEventRecord(h->bev[0], h->stream));
-            launch_batch_flags(h, b);
-            if (mode >= 0) launch_prm_shortest_init(h->so3, b, sa, h->stream);
-            HIP_TRY(hipEventRecord(h->bev[1], h->stream));
-            if (mode < 0) {
-                launch_prm_batch_search(b, group, h->stream);
-            } else {
-                launch_prm_shortest_labels(b, sa, group, h->stream);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipEventRecord(h->sev[0], h->stream));
-                launch_prm_shortest_levels(b, sa, group, h->stream);
-            }
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(h->bev[2], h->stream));
-            HIP_TRY(hipMemcpyAsync(res.data(), h->bd_res.p, 5 * (size_t)chunk * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-            if (mode >= 0) {
-                HIP_TRY(hipMemcpyAsync(cost.data(), h->bd_cost.p, (size_t)c * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-                HIP_TRY(hipMemcpyAsync(lrounds.data(), h->bd_rounds.p, (size_t)c * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-                HIP_TRY(hipMemcpyAsync(relaxed.data(), h->bd_relaxed.p, (size_t)c * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-            }
-            HIP_TRY(hipEventRecord(h->bev[3], h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            h->batch_ms[0] += elapsed_ms(h->bev[0], h->bev[1]);
-            h->batch_ms[1] += elapsed_ms(h->bev[1], h->bev[2]);
-            h->batch_ms[3] += elapsed_ms(h->bev[2], h->bev[3]);
-            if (mode >= 0) {
-                h->short_ms[2] += elapsed_ms(h->bev[1], h->sev[0]);
-                h->short_ms[3] += elapsed_ms(h->sev[0], h->bev[2]);
-                for (uint32_t i = 0; i < c; ++i) {
-                    if ((int32_t)res[i] == OXHIP_ERR_HIP)   // (no query status is OXHIP_ERR_HIP otherwise)
-                        return fail(OXHIP_ERR_HIP, "shortest-path search: a label round or level cap was hit, which cannot happen");
-                    h->b_cost[q0 + i] = cost[i];
-                    h->b_rounds[q0 + i] = lrounds[i];
-                    h->b_relaxed[q0 + i] = relaxed[i];
-                }
-            }
-            uint64_t rows = 0;
-            const uint64_t row0 = h->b_off[q0];
-            for (uint32_t i = 0; i < c; ++i) {
-                h->b_status[q0 + i] = (int32_t)res[i];
-                h->b_len[q0 + i] = res[chunk + i];
-                h->b_goal_node[q0 + i] = (int32_t)res[2 * (size_t)chunk + i];
-                h->b_nstart[q0 + i] = res[3 * (size_t)chunk + i];
-                h->b_ngoal[q0 + i] = res[4 * (size_t)chunk + i];
-                off[i] = rows;
-                rows += res[chunk + i];
-                h->b_off[q0 + i + 1] = row0 + rows;
-            }
-            if (rows) {
-                if (h->bd_nodes.n < rows) { HIP_TRY(h->bd_nodes.alloc((size_t)rows)); HIP_TRY(h->bd_rows.alloc((size_t)rows * dim)); }
-                h->b_nodes.resize((size_t)(row0 + rows));
-                h->b_rows.resize((size_t)(row0 + rows) * dim);
-                HIP_TRY(hipMemcpyAsync(h->bd_off.p, off.data(), (size_t)c * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
-                HIP_TRY(hipEventRecord(h->bev[4], h->stream));
-                launch_prm_batch_paths(b, h->bd_off.p, h->bd_nodes.p, h->bd_rows.p, h->stream);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipEventRecord(h->bev[5], h->stream));
-                HIP_TRY(hipMemcpyAsync(h->b_nodes.data() + row0, h->bd_nodes.p, (size_t)rows * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-                HIP_TRY(hipMemcpyAsync(h->b_rows.data() + (size_t)row0 * dim, h->bd_rows.p, (size_t)rows * dim * sizeof(double), hipMemcpyDeviceToHost,
-                                       h->stream));
-                HIP_TRY(hipEventRecord(h->bev[6], h->stream));
-                HIP_TRY(hipStreamSynchronize(h->stream));
-                h->batch_ms[2] += elapsed_ms(h->bev[4], h->bev[5]);
-                h->batch_ms[3] += elapsed_ms(h->bev[5], h->bev[6]);
-            }
+            const uint32_t c = std::min(br.chunk, br.Q - q0);
+            const PrmBatchArgs b = batch_args(h, q0, c, br.chunk);
+            OX_TRY(run_round(h, br, b));
+            const uint64_t rows = scatter_round(h, br, q0, c);
+            if (rows) OX_TRY(extract_round_paths(h, br, b, rows));
             ++h->batch_rounds;
             answered = q0 + c;
         }
-        for (uint32_t q = answered + 1; q <= Q; ++q) h->b_off[q] = h->b_off[answered];   // (the rounds not begun add no rows)
+        for (uint32_t q = answered + 1; q <= br.Q; ++q) h->b_off[q] = h->b_off[answered];   // (the rounds not begun add no rows)
     }
     if (mode >= 0) { h->short_ms[1] = h->batch_ms[0]; h->short_ms[4] = h->batch_ms[2]; h->short_ms[5] = h->batch_ms[3]; }
     h->batch_valid = true;
-    if (status_out) for (uint32_t q = 0; q < Q; ++q) status_out[q] = h->b_status[q];
+    if (status_out) for (uint32_t q = 0; q < br.Q; ++q) status_out[q] = h->b_status[q];
     return OXHIP_OK;
 }
 
@@ -964,11 +998,7 @@ int32_t oxhip_prm_batch_get_labels(oxhip_prm* h, uint32_t query, double* cost, u
     const PrmBatchArgs b = batch_args(h, query, 1, (uint32_t)(h->bd_res.n / 5));
     const PrmShortestArgs sa = shortest_args(h, h->batch_mode);
     const uint32_t group = prm_batch_group(n, h->n_keys);
-    launch_batch_flags(h, b);
-    launch_prm_shortest_init(h->so3, b, sa, h->stream);
-    launch_prm_shortest_labels(b, sa, group, h->stream);
-    launch_prm_shortest_levels(b, sa, group, h->stream);
-    HIP_TRY(hipGetLastError());
+    OX_TRY(launch_shortest(h, b, sa, group, false));
     int32_t status = 0;
     HIP_TRY(hipMemcpyAsync(&status, h->bd_res.p, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     if (cost) HIP_TRY(hipMemcpyAsync(cost, h->bd_label.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
