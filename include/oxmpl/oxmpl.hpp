@@ -474,6 +474,50 @@ class PRM {
         }
         return rm;
     }
+    // Replaces the roadmap with `rm` (oxhip_prm_set_roadmap): the library checks on the GPU that the edge lists are ascending
+    // and symmetric.  A refused roadmap returns false and leaves the planner's own as it was and the planner usable
+    // (last_status() stays OXHIP_OK); last_set_roadmap_status() holds OXHIP_ERR_BAD_ARG / _CAPACITY and
+    // oxhip_last_error_string() the rule and the row.
+    bool set_roadmap(const Roadmap& rm) {
+        if (!prm_ || !pd_ || rm.states.size() != rm.edges.size()) return false;
+        const std::size_t dim = pd_->space->dimension, n = rm.states.size();
+        std::vector<double> flat;
+        std::vector<uint64_t> off(n + 1, 0);
+        std::vector<uint32_t> nb;
+        for (std::size_t i = 0; i < n; ++i) {
+            if (rm.states[i].values.size() != dim) return false;
+            flat.insert(flat.end(), rm.states[i].values.begin(), rm.states[i].values.end());
+            nb.insert(nb.end(), rm.edges[i].begin(), rm.edges[i].end());
+            off[i + 1] = nb.size();
+        }
+        if (flat.empty()) flat.push_back(0.0);
+        set_roadmap_status_ = oxhip_prm_set_roadmap(prm_, flat.data(), (uint32_t)n, off.data(), nb.empty() ? nullptr : nb.data());
+        if (set_roadmap_status_ != OXHIP_OK && set_roadmap_status_ != OXHIP_ERR_BAD_ARG && set_roadmap_status_ != OXHIP_ERR_CAPACITY)
+            last_status_ = set_roadmap_status_;   // (a refusal leaves the planner as it was; anything else is the planner's error)
+        return set_roadmap_status_ == OXHIP_OK;
+    }
+    int32_t last_set_roadmap_status() const { return set_roadmap_status_; }
+    // Re-checks every milestone and edge against the obstacles of `checker` as they are now (oxhip_prm_revalidate); an
+    // invalid milestone keeps its index and loses its edges.  valid[i] per milestone, and the edge entries removed.
+    struct Revalidation { std::vector<uint8_t> valid; uint64_t removed_entries = 0; };
+    Result<Revalidation, base::PlanningError> revalidate(const std::shared_ptr<base::StateValidityChecker>& checker) {
+        if (!prm_ || !pd_ || !checker) return base::PlanningError::PlannerUninitialised;
+        std::vector<double> c, r, lo, hi;
+        for (auto& s : checker->spheres()) { c.insert(c.end(), s.centre.begin(), s.centre.end()); r.push_back(s.radius); }
+        for (auto& b : checker->boxes()) { lo.insert(lo.end(), b.lo.begin(), b.lo.end()); hi.insert(hi.end(), b.hi.begin(), b.hi.end()); }
+        int32_t st = oxhip_prm_set_spheres(prm_, c.data(), r.data(), (uint32_t)r.size());
+        if (st == OXHIP_OK) st = oxhip_prm_set_boxes(prm_, lo.data(), hi.data(), (uint32_t)(lo.size() / pd_->space->dimension));
+        if (st != OXHIP_OK) return to_error(st);
+        return revalidate();
+    }
+    Result<Revalidation, base::PlanningError> revalidate() {
+        if (!prm_) return base::PlanningError::PlannerUninitialised;
+        Revalidation out;
+        out.valid.assign(num_milestones(), 0);
+        const int32_t st = oxhip_prm_revalidate(prm_, out.valid.empty() ? nullptr : out.valid.data(), nullptr, &out.removed_entries);
+        if (st != OXHIP_OK) return to_error(st);
+        return out;
+    }
     int32_t last_status() const { return last_status_; }
 
   private:
@@ -493,6 +537,7 @@ class PRM {
     oxhip_prm* prm_ = nullptr;
     std::shared_ptr<base::ProblemDefinition> pd_;
     int32_t last_status_ = OXHIP_ERR_PLANNER_UNINITIALISED;
+    int32_t set_roadmap_status_ = OXHIP_OK;
 };
 
 }  // namespace geometric

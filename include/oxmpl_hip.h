@@ -552,6 +552,36 @@ int32_t oxhip_prm_batch_get_labels(oxhip_prm* prm, uint32_t query, double* cost 
 int32_t oxhip_prm_batch_get_search_stats(oxhip_prm* prm, uint32_t* label_rounds /*[Q]*/, uint64_t* relaxations /*[Q]*/,
                                          double* phase_ms /*[6]*/);
 
+/* ---- planting a roadmap from the host, re-checking a roadmap on the device (prm_revalidate.hip) ----
+ * oxhip_prm_set_roadmap replaces the handle's roadmap with the caller's, in exactly the layout oxhip_prm_get_roadmap writes
+ * (states AoS [n][dim]; node i's neighbours = neighbours[offsets[i] .. offsets[i+1])), for R^n (radius and k-nearest handles)
+ * and SO(3).  OXHIP_ERR_BAD_ARG for a null argument (neighbours may be NULL when offsets[n] == 0),
+ * OXHIP_ERR_PLANNER_UNINITIALISED without setup(), OXHIP_ERR_CAPACITY when n > max_milestones or offsets[n] > 0xFFFFFFFF.
+ * n == 0 is OXHIP_OK and leaves an empty roadmap (construct_roadmap builds again).  Every coordinate must be finite and within
+ * 1e150 (what set_problem asks of a start); a state need not lie inside the bounds and is not normalised.  The structure is
+ * checked on the device: offsets[0] == 0 and offsets non-decreasing; every neighbour < n; no self-loop; every row strictly
+ * ascending; symmetric (v in row u implies u in row v).  A violation is OXHIP_ERR_BAD_ARG, and oxhip_last_error_string() names
+ * the first violated rule in that order (offsets_start, offsets_order, neighbour_range, self_loop, unsorted, asymmetric) and the
+ * lowest offending row.  A refused call leaves the handle exactly as it was.  Success sets n_samples = 0 and drops what
+ * belonged to the old roadmap, as setup() does: the last solve's query sets, the last batch's results, the edge weights.
+ * construct_roadmap afterwards is the no-op it is for any existing roadmap; setup() clears a planted roadmap like any other. */
+int32_t oxhip_prm_set_roadmap(oxhip_prm* prm, const double* states /*[n][dim]*/, uint32_t n, const uint64_t* offsets /*[n+1]*/,
+                              const uint32_t* neighbours);
+/* Re-checks the roadmap as it stands against the handle's CURRENT spheres / boxes / cones (the semantics are this build's own;
+ * the reference has no such call).  valid[i] = is_valid(milestone i), the bits of oxhip_rrt_batch_is_valid on an RRT batch of
+ * the same space, bounds, fraction and obstacles.  An undirected edge {i < j} is kept iff valid[i], valid[j] and
+ * check_motion(from = milestone j, to = milestone i) -- construction's own direction (prm.rs:134).  Milestone indices are
+ * stable: an invalid milestone stays in place as a row with no entries (check_motion tests its `to` state, so it can never
+ * become a start connection, and no search reaches it).  Rows stay ascending.  milestone_valid [n] receives valid,
+ * *n_invalid_milestones its zeros, *n_removed_entries = entries before - entries after; any of the three may be NULL.  Drops
+ * the same derived state as oxhip_prm_set_roadmap (the batch getters answer as after setup()).
+ * OXHIP_ERR_PLANNER_UNINITIALISED without setup(), OXHIP_ERR_UNSAMPLED_STATE_SPACE on an empty roadmap. */
+int32_t oxhip_prm_revalidate(oxhip_prm* prm, uint8_t* milestone_valid /*[n] or NULL*/, uint32_t* n_invalid_milestones,
+                             uint64_t* n_removed_entries);
+/* HIP-event times (ms) of the last oxhip_prm_revalidate: phase_ms[4] = {milestone validity, pair emission, edge checks,
+ * compaction (scan + move)} */
+int32_t oxhip_prm_revalidate_last_timing(oxhip_prm* prm, double* phase_ms /*[4]*/);
+
 #ifdef __cplusplus
 }
 #endif

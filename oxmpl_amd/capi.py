@@ -50,6 +50,7 @@ EXPORTS = [
     "oxhip_prm_solve_batch", "oxhip_prm_batch_get_results", "oxhip_prm_batch_get_paths", "oxhip_prm_batch_get_query_sets",
     "oxhip_prm_batch_last_timing",
     "oxhip_prm_solve_batch_shortest", "oxhip_prm_batch_get_costs", "oxhip_prm_batch_get_labels", "oxhip_prm_batch_get_search_stats",
+    "oxhip_prm_set_roadmap", "oxhip_prm_revalidate", "oxhip_prm_revalidate_last_timing",
     "oxhip_rrt_batch_extract_paths", "oxhip_rrt_batch_get_paths", "oxhip_rrt_batch_simplify_paths",
     "oxhip_rrt_batch_get_simplified_paths", "oxhip_rrt_batch_get_simplify_results", "oxhip_rrt_batch_path_valid_matrix",
     "oxhip_rrt_batch_paths_last_timing",
@@ -168,6 +169,9 @@ def lib():
         L.oxhip_prm_batch_get_costs.argtypes = [C.c_void_p, _dp]
         L.oxhip_prm_batch_get_labels.argtypes = [C.c_void_p, C.c_uint32, _dp, _u32p, _u32p, C.c_uint32]
         L.oxhip_prm_batch_get_search_stats.argtypes = [C.c_void_p, _u32p, _u64p, _dp]
+        L.oxhip_prm_set_roadmap.argtypes = [C.c_void_p, _dp, C.c_uint32, _u64p, _u32p]
+        L.oxhip_prm_revalidate.argtypes = [C.c_void_p, _u8p, _u32p, _u64p]
+        L.oxhip_prm_revalidate_last_timing.argtypes = [C.c_void_p, _dp]
         L.oxhip_rrt_batch_extract_paths.argtypes = [C.c_void_p]
         L.oxhip_rrt_batch_get_paths.argtypes = [C.c_void_p, _u64p, _dp, C.c_uint64, _u64p]
         L.oxhip_rrt_batch_simplify_paths.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
@@ -710,3 +714,36 @@ class PRMRoadmap:
         rounds, relax, ms = np.zeros(max(q, 1), dtype=np.uint32), np.zeros(max(q, 1), dtype=np.uint64), np.zeros(6, dtype=np.float64)
         _check(lib().oxhip_prm_batch_get_search_stats(self._h, _p(rounds, _u32p), _p(relax, _u64p), _p(ms)))
         return dict(label_rounds=rounds[:q], relaxations=relax[:q], phase_ms=[float(v) for v in ms])
+
+    # ---- a roadmap planted from the host; the roadmap re-checked against the current obstacles
+
+    def set_roadmap(self, states, offsets, neighbours):
+        """Replaces the roadmap with (states [n][dim], offsets [n+1], neighbours [E]), the layout roadmap() returns.  The
+        structure is checked on the device; a violation raises OxhipError(ERR_BAD_ARG) naming the rule and the lowest
+        offending row, and leaves the handle as it was."""
+        off = np.ascontiguousarray(np.asarray(offsets).reshape(-1), dtype=np.uint64)
+        n = off.size - 1
+        if n < 0:
+            raise OxhipError(ERR_BAD_ARG, "offsets must hold n + 1 entries")
+        s = _f64(states).reshape(-1)
+        if s.size != n * self.dim:
+            raise OxhipError(ERR_BAD_ARG, "states must be [n][dim] for offsets of n + 1 entries")
+        if s.size == 0:
+            s = np.zeros(1, dtype=np.float64)
+        nb = np.ascontiguousarray(np.asarray(neighbours).reshape(-1), dtype=np.uint32)
+        _check(lib().oxhip_prm_set_roadmap(self._h, _p(s), n, _p(off, _u64p), _p(nb, _u32p) if nb.size else None))
+
+    def revalidate(self):
+        """Re-checks every milestone and every edge against the obstacles as they are now.  Returns (valid_mask [n] bool,
+        n_removed_entries); an invalid milestone keeps its index and loses its entries."""
+        n = self.sizes()[0]
+        valid = np.zeros(max(n, 1), dtype=np.uint8)
+        removed = C.c_uint64()
+        _check(lib().oxhip_prm_revalidate(self._h, _p(valid, _u8p), None, C.byref(removed)))   # (the invalid count is the mask's zeros)
+        return valid[:n].astype(bool), removed.value
+
+    def revalidate_last_timing(self):
+        """dict(phase_ms=[milestone validity, pair emission, edge checks, compaction]) of the last revalidate"""
+        ms = np.zeros(4, dtype=np.float64)
+        _check(lib().oxhip_prm_revalidate_last_timing(self._h, _p(ms)))
+        return dict(phase_ms=[float(v) for v in ms])

@@ -163,6 +163,34 @@ void launch_prm_so3_edges(const DevParams& p, const PrmArgs& a, uint32_t n_cand,
 void launch_prm_so3_query(const DevParams& p, const PrmArgs& a, uint32_t n, const PrmQuery& q, double r, uint8_t* flags,
                           uint32_t* start_valid, hipStream_t s);
 
+// prm_revalidate.hip: a roadmap planted from the host, and a roadmap re-checked against the current obstacles
+enum PrmPlantRule : uint32_t {   // one result word per rule: the lowest offending row, 0xFFFFFFFF = none; reported in this order
+    kPlantOffsetsStart = 0, kPlantOffsetsOrder, kPlantRange, kPlantSelfLoop, kPlantUnsorted, kPlantAsymmetric, kPlantRules
+};
+enum PrmRevalCounter : uint32_t { kRevalInvalid = 0, kRevalPairs, kRevalCounters };
+void launch_prm_shadow(const double* ms, float* ms32, uint64_t count, hipStream_t s);   // (prm_kernels.hip) ms32[i] = fl32(ms[i]), i < count
+// off32 = the caller's 64-bit offsets; the rules kPlantOffsetsStart / kPlantOffsetsOrder
+void launch_prm_plant_offsets(const uint64_t* off64, uint32_t n, uint32_t* off32, uint32_t* viol, hipStream_t s);
+// the per-entry rules; only for offsets that passed the two above
+void launch_prm_plant_entries(const uint32_t* offsets, const uint32_t* nbrs, uint32_t n, uint32_t n_entries, uint32_t* viol, hipStream_t s);
+void launch_prm_reval_valid(bool so3, const DevParams& p, const double* ms, uint32_t n, uint8_t* valid, uint32_t* counters, hipStream_t s);
+// the entries u -> v with v < u and both ends valid, counters[kRevalPairs] of them: pairs[] = (entry, u, v), or -- cand != nullptr --
+// cand[] = (u, v) in construction's candidate layout instead
+void launch_prm_reval_emit(const uint32_t* offsets, const uint32_t* nbrs, const uint8_t* valid, uint32_t n, uint32_t n_entries, uint4* pairs,
+                           uint2* cand, uint32_t pair_cap, uint32_t* counters, hipStream_t s);
+// R^n: keep[entry] = keep[mirror entry] = 1 for every pair whose motion u -> v is valid (keep starts at 0)
+void launch_prm_reval_check(const DevParams& p, const double* ms, const uint32_t* offsets, const uint32_t* nbrs, uint32_t n, uint32_t n_entries,
+                            const uint4* pairs, uint32_t n_pairs, uint8_t* keep, hipStream_t s);
+// SO(3): keep[entry of v in row u] = 1 for every directed key (u << shift) | v that launch_prm_so3_edges emitted; state->n_keys of
+// them, at most key_cap (one thread each)
+void launch_prm_reval_keys(const uint64_t* keys, const PrmState* state, uint32_t key_cap, uint32_t shift, const uint32_t* offsets,
+                           const uint32_t* nbrs, uint32_t n, uint8_t* keep, hipStream_t s);
+// pos = exclusive scan of keep (rocPRIM); tmp == nullptr queries tmp_bytes
+hipError_t prm_reval_scan(void* tmp, size_t& tmp_bytes, const uint8_t* keep, uint32_t* pos, uint32_t n_entries, hipStream_t s);
+// offsets in place, the kept neighbours into nbrs_out in their old order (n_entries > 0)
+void launch_prm_reval_compact(uint32_t* offsets, const uint32_t* nbrs, const uint8_t* keep, const uint32_t* pos, uint32_t n, uint32_t n_entries,
+                              uint32_t* nbrs_out, hipStream_t s);
+
 // prm_batch.hip: a batch of queries on the constructed roadmap, breadth-first search and path extraction on the device
 // (DESIGN.md section 17).  One round answers the queries [q0, q0 + n_chunk) of the batch; row c of a per-round array is query q0 + c.
 struct PrmBatchArgs {

@@ -93,6 +93,14 @@ struct oxhip_prm {
     DevBuf<double> bd_cost;
     DevBuf<unsigned long long> bd_relaxed;
     hipEvent_t sev[2] = {};
+    // oxhip_prm_revalidate: its workspace and the phase times of the last call
+    DevBuf<uint8_t> rv_valid, rv_keep, rv_tmp;
+    DevBuf<uint32_t> rv_pos, rv_nbrs, rv_counters;
+    DevBuf<uint4> rv_pairs;
+    DevBuf<uint2> rv_cand;       // SO(3): the pairs as construction's edge kernel reads them, the keys it emits and their count
+    DevBuf<uint64_t> rv_keys;
+    DevBuf<PrmState> rv_state;
+    double reval_ms[4] = {};   // milestone validity, pair emission, edge checks, compaction
 };
 
 namespace {
@@ -150,12 +158,9 @@ int32_t set_query(oxhip_prm* h, const double* start, const double* goal_centre, 
     return OXHIP_OK;
 }
 
-void clear_roadmap(oxhip_prm* h) {
-    h->n = 0;
-    h->n_keys = 0;
+// what belongs to the roadmap as it was: gone whenever the roadmap is cleared, replaced (set_roadmap) or pruned (revalidate)
+void drop_derived(oxhip_prm* h) {
     h->host_copy = false;
-    h->n_samples = 0;
-    h->redraw_batches = 0;
     h->h_offsets.clear();
     h->h_nbrs.clear();
     h->h_states.clear();
@@ -163,6 +168,14 @@ void clear_roadmap(oxhip_prm* h) {
     h->goal_idx.clear();
     h->batch_valid = false;   // the batch's results are about the roadmap that just went
     h->w_valid = false;       // and so are the edge weights
+}
+
+void clear_roadmap(oxhip_prm* h) {
+    h->n = 0;
+    h->n_keys = 0;
+    h->n_samples = 0;
+    h->redraw_batches = 0;
+    drop_derived(h);
 }
 
 // One round of the space's parallel sampler from stream word st.draws on.  R^n: m samples.  SO(3) (prm_so3.hip): m rejection
@@ -1076,6 +1089,151 @@ int32_t oxhip_prm_batch_last_timing(oxhip_prm* h, double* phase_ms, uint32_t* ro
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
     if (phase_ms) for (int i = 0; i < 4; ++i) phase_ms[i] = h->batch_ms[i];
     if (rounds) *rounds = h->batch_rounds;
+    return OXHIP_OK;
+}
+
+}  // extern "C"
+
+// ---- a roadmap planted from the host, and the roadmap re-checked against the current obstacles
+
+namespace {
+
+// the structure rules of a planted roadmap in the order they are reported (PrmPlantRule)
+const char* const kPlantRuleName[kPlantRules] = {
+    "offsets_start (offsets[0] must be 0)", "offsets_order (offsets must not decrease)", "neighbour_range (every neighbour < n)",
+    "self_loop (no milestone is its own neighbour)", "unsorted (every row strictly ascending)", "asymmetric (v in row u needs u in row v)"};
+
+// the first violated rule among [first, last) of the device's result words, as the refusal
+int32_t plant_verdict(oxhip_prm* h, uint32_t* d_viol, uint32_t first, uint32_t last) {
+    uint32_t viol[kPlantRules];
+    HIP_TRY(hipMemcpyAsync(viol, d_viol, sizeof viol, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (uint32_t r = first; r < last; ++r)
+        if (viol[r] != 0xFFFFFFFFu)
+            return fail(OXHIP_ERR_BAD_ARG, std::string("roadmap refused: rule ") + kPlantRuleName[r] + ", lowest offending row " + std::to_string(viol[r]));
+    return OXHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t oxhip_prm_set_roadmap(oxhip_prm* h, const double* states, uint32_t n, const uint64_t* offsets, const uint32_t* neighbours) {
+    if (!h || !states || !offsets) return fail(OXHIP_ERR_BAD_ARG, "null argument");
+    if (!neighbours && offsets[n] != 0) return fail(OXHIP_ERR_BAD_ARG, "null argument: neighbours may be null only when offsets[n] is 0");
+    if (!h->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
+    if (n > h->cfg.max_milestones) return fail(OXHIP_ERR_CAPACITY, "more milestones than max_milestones");
+    if (offsets[n] > 0xFFFFFFFFull) return fail(OXHIP_ERR_CAPACITY, "more than 2^32 - 1 directed edge entries");
+    const uint32_t dim = h->cfg.dim, n_entries = (uint32_t)offsets[n];
+    if (n == 0) {
+        if (n_entries) return fail(OXHIP_ERR_BAD_ARG, std::string("roadmap refused: rule ") + kPlantRuleName[kPlantOffsetsStart] + ", lowest offending row 0");
+        clear_roadmap(h);   // an empty roadmap: construct_roadmap builds again
+        return OXHIP_OK;
+    }
+    for (size_t k = 0; k < (size_t)n * dim; ++k)   // what set_problem asks of a start (check_query_points)
+        if (!(std::fabs(states[k]) <= kMaxMagnitude)) return fail(OXHIP_ERR_BAD_ARG, "milestone coordinate not finite or beyond 1e150");
+    OX_TRY(select_device(h->cfg.device));
+    // upload and check in staging buffers: a refused call leaves the handle as it was
+    DevBuf<double> s_ms;
+    DevBuf<uint64_t> s_off64;
+    DevBuf<uint32_t> s_off, s_nbrs, s_viol;
+    HIP_TRY(s_ms.alloc((size_t)n * dim)); HIP_TRY(s_off64.alloc((size_t)n + 1)); HIP_TRY(s_off.alloc((size_t)n + 1));
+    HIP_TRY(s_nbrs.alloc(n_entries)); HIP_TRY(s_viol.alloc(kPlantRules));
+    HIP_TRY(hipMemcpyAsync(s_ms.p, states, (size_t)n * dim * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(s_off64.p, offsets, ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+    if (n_entries) HIP_TRY(hipMemcpyAsync(s_nbrs.p, neighbours, (size_t)n_entries * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(s_viol.p, 0xFF, kPlantRules * sizeof(uint32_t), h->stream));
+    launch_prm_plant_offsets(s_off64.p, n, s_off.p, s_viol.p, h->stream);
+    HIP_TRY(hipGetLastError());
+    OX_TRY(plant_verdict(h, s_viol.p, kPlantOffsetsStart, kPlantRange));   // the entry rules read rows: only inside proven offsets
+    launch_prm_plant_entries(s_off.p, s_nbrs.p, n, n_entries, s_viol.p, h->stream);
+    HIP_TRY(hipGetLastError());
+    OX_TRY(plant_verdict(h, s_viol.p, kPlantRange, kPlantRules));
+    // accepted: the staged roadmap becomes the handle's
+    HIP_TRY(hipMemcpyAsync(h->ms.p, s_ms.p, (size_t)n * dim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->offsets.p, s_off.p, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
+    if (!h->so3) launch_prm_shadow(h->ms.p, h->ms32.p, (uint64_t)n * dim, h->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    std::swap(h->nbrs.p, s_nbrs.p); std::swap(h->nbrs.n, s_nbrs.n);
+    clear_roadmap(h);   // everything that belonged to the roadmap before; n_samples = redraw_batches = 0
+    h->n = n;
+    h->n_keys = n_entries;
+    return OXHIP_OK;
+}
+
+int32_t oxhip_prm_revalidate(oxhip_prm* h, uint8_t* milestone_valid, uint32_t* n_invalid_milestones, uint64_t* n_removed_entries) {
+    if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
+    if (!h->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
+    if (h->n == 0) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "the roadmap holds no milestones");
+    OX_TRY(select_device(h->cfg.device));
+    const uint32_t n = h->n, n_old = h->n_keys, pair_cap = n_old / 2 + 1;
+    // every buffer before the timed region: hipMalloc is a blocking call
+    size_t tmp_bytes = 0;
+    HIP_TRY(h->rv_valid.reserve(n)); HIP_TRY(h->rv_counters.reserve(kRevalCounters));
+    if (n_old) {
+        HIP_TRY(h->rv_keep.reserve(n_old)); HIP_TRY(h->rv_pos.reserve(n_old)); HIP_TRY(h->rv_nbrs.reserve(n_old));
+        if (h->so3) {   // the pairs go through construction's own edge kernel, with a candidate list, key array and counter of the re-check's own
+            HIP_TRY(h->rv_cand.reserve(pair_cap)); HIP_TRY(h->rv_keys.reserve(2 * (size_t)pair_cap)); HIP_TRY(h->rv_state.reserve(1));
+            HIP_TRY(hipMemsetAsync(h->rv_state.p, 0, sizeof(PrmState), h->stream));
+        } else {
+            HIP_TRY(h->rv_pairs.reserve(pair_cap));
+        }
+        HIP_TRY(prm_reval_scan(nullptr, tmp_bytes, h->rv_keep.p, h->rv_pos.p, n_old, h->stream));
+        HIP_TRY(h->rv_tmp.reserve(tmp_bytes));
+    }
+    uint32_t cnt[kRevalCounters] = {};
+    HIP_TRY(hipMemsetAsync(h->rv_counters.p, 0, sizeof cnt, h->stream));
+    if (n_old) HIP_TRY(hipMemsetAsync(h->rv_keep.p, 0, n_old, h->stream));
+    HIP_TRY(hipEventRecord(h->bev[0], h->stream));
+    launch_prm_reval_valid(h->so3, h->dp, h->ms.p, n, h->rv_valid.p, h->rv_counters.p, h->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->bev[1], h->stream));
+    launch_prm_reval_emit(h->offsets.p, h->nbrs.p, h->rv_valid.p, n, n_old, h->rv_pairs.p, h->so3 ? h->rv_cand.p : nullptr, pair_cap,
+                          h->rv_counters.p, h->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->bev[2], h->stream));
+    HIP_TRY(hipMemcpyAsync(cnt, h->rv_counters.p, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (cnt[kRevalPairs] > pair_cap) return fail(OXHIP_ERR_HIP, "revalidate: more lower-index entries than half the roadmap's, which a symmetric roadmap cannot have");
+    HIP_TRY(hipEventRecord(h->bev[3], h->stream));
+    if (h->so3 && cnt[kRevalPairs]) {
+        PrmArgs a = h->args;   // construction's kernel, the re-check's buffers: nothing of construction's workspace is touched
+        a.cand = h->rv_cand.p; a.keys = h->rv_keys.p; a.state = h->rv_state.p;
+        launch_edges(h, a, cnt[kRevalPairs]);   // check_motion(from = u, to = v) per pair; both directed keys of every valid one
+        HIP_TRY(hipGetLastError());
+        launch_prm_reval_keys(h->rv_keys.p, h->rv_state.p, 2 * cnt[kRevalPairs], prm_key_shift(h->args.cap), h->offsets.p, h->nbrs.p, n,
+                              h->rv_keep.p, h->stream);
+    } else if (!h->so3) {
+        launch_prm_reval_check(h->dp, h->ms.p, h->offsets.p, h->nbrs.p, n, n_old, h->rv_pairs.p, cnt[kRevalPairs], h->rv_keep.p, h->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->bev[4], h->stream));
+    uint32_t n_new = 0;
+    if (n_old) {
+        HIP_TRY(prm_reval_scan(h->rv_tmp.p, tmp_bytes, h->rv_keep.p, h->rv_pos.p, n_old, h->stream));
+        launch_prm_reval_compact(h->offsets.p, h->nbrs.p, h->rv_keep.p, h->rv_pos.p, n, n_old, h->rv_nbrs.p, h->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(h->bev[5], h->stream));
+    if (n_old) HIP_TRY(hipMemcpyAsync(&n_new, h->offsets.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (milestone_valid) HIP_TRY(hipMemcpyAsync(milestone_valid, h->rv_valid.p, n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (n_old) { std::swap(h->nbrs.p, h->rv_nbrs.p); std::swap(h->nbrs.n, h->rv_nbrs.n); }
+    h->reval_ms[0] = elapsed_ms(h->bev[0], h->bev[1]);
+    h->reval_ms[1] = elapsed_ms(h->bev[1], h->bev[2]);
+    h->reval_ms[2] = elapsed_ms(h->bev[3], h->bev[4]);
+    h->reval_ms[3] = elapsed_ms(h->bev[4], h->bev[5]);
+    h->n_keys = n_new;
+    drop_derived(h);   // the host copy (the single solve searches it), the last solve's sets, the last batch, the edge weights
+    if (n_invalid_milestones) *n_invalid_milestones = cnt[kRevalInvalid];
+    if (n_removed_entries) *n_removed_entries = (uint64_t)n_old - n_new;
+    return OXHIP_OK;
+}
+
+int32_t oxhip_prm_revalidate_last_timing(oxhip_prm* h, double* phase_ms) {
+    if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
+    if (phase_ms) for (int i = 0; i < 4; ++i) phase_ms[i] = h->reval_ms[i];
     return OXHIP_OK;
 }
 

@@ -687,6 +687,10 @@ __global__ void prm_shadow_kernel(const double* __restrict__ ms, float* __restri
     if (i < last) ms32[i] = (float)ms[i];
 }
 
+void launch_prm_shadow(const double* ms, float* ms32, uint64_t count, hipStream_t s) {   // a planted roadmap's shadow (prm_revalidate.hip)
+    if (count) hipLaunchKernelGGL(prm_shadow_kernel, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, s, ms, ms32, (uint64_t)0, count);
+}
+
 float prm_screen_threshold(const DevParams& p, double thr) {
     double m = 0.0;
     for (uint32_t k = 0; k < p.dim; ++k) m = std::fmax(m, std::fmax(std::fabs(p.lo[k]), std::fabs(p.hi[k])));

@@ -325,6 +325,75 @@ class PRM:
             states = [SO3State(*row) for row in states]
         return states, offsets, nbrs
 
+    # ---- a roadmap that outlives its planner, and one that follows its scene (oxhip_prm_set_roadmap / oxhip_prm_revalidate)
+
+    def _space_kind(self):
+        return "so3" if isinstance(self._pd.space, SO3StateSpace) else "real_vector"
+
+    def _space_dim(self):
+        return 4 if isinstance(self._pd.space, SO3StateSpace) else int(self._pd.space.dimension)
+
+    def set_roadmap(self, states, offsets, neighbours):
+        """Replaces the roadmap with the caller's, in the layout get_roadmap returns (states: rows or state objects).  The
+        library checks the structure on the GPU and raises ValueError, naming the rule and the lowest offending row, when it is
+        not a symmetric roadmap with ascending rows; the planner's roadmap is then unchanged."""
+        if self._prm is None:
+            raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
+        rows = [s.values if hasattr(s, "values") else s for s in states]
+        try:
+            self._prm.set_roadmap(rows, offsets, neighbours)
+        except capi.OxhipError as e:
+            if e.status in (capi.ERR_BAD_ARG, capi.ERR_CAPACITY):
+                raise ValueError(str(e)) from None
+            raise
+
+    def revalidate(self, validity_checker=None):
+        """Re-checks every milestone and edge of the roadmap against the obstacles as they are now -- `validity_checker`'s when
+        one is given (it replaces the planner's), else the ones already set.  Milestone indices are stable: an invalid
+        milestone keeps its place and loses its edges.  Returns (valid_mask [n] bool, removed edge entries)."""
+        if self._prm is None:
+            raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
+        if validity_checker is not None:
+            if isinstance(self._pd.space, SO3StateSpace):
+                if not isinstance(validity_checker, SO3ConeValidityChecker):
+                    raise TypeError("an SO(3) roadmap is re-checked against an SO3ConeValidityChecker")
+                self._prm.set_spheres([c for c, _ in validity_checker.cones], [r for _, r in validity_checker.cones])
+            else:
+                if not isinstance(validity_checker, SphereBoxValidityChecker):
+                    raise TypeError("describe the obstacles with oxmpl_amd.base.SphereBoxValidityChecker")
+                self._prm.set_spheres([c for c, _ in validity_checker.spheres], [r for _, r in validity_checker.spheres])
+                self._prm.set_boxes([lo for lo, _ in validity_checker.boxes], [hi for _, hi in validity_checker.boxes])
+        try:
+            return self._prm.revalidate()
+        except capi.OxhipError as e:
+            if e.status in _MESSAGES:
+                raise Exception(_MESSAGES[e.status]) from None
+            raise
+
+    def save_roadmap(self, path):
+        """The roadmap as a .npz file: states, offsets, neighbours, the space's kind and the width of a state."""
+        import numpy as np
+        if self._prm is None:
+            raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
+        states, offsets, nbrs = self._prm.roadmap()
+        with open(path, "wb") as f:
+            np.savez(f, states=states, offsets=offsets, neighbours=nbrs, space=np.array(self._space_kind()),
+                     dim=np.array(self._space_dim(), dtype=np.uint32))
+
+    def load_roadmap(self, path):
+        """Plants the roadmap of a save_roadmap file.  ValueError -- before any device call -- when the file's space or
+        dimension is not the planner's."""
+        import numpy as np
+        with np.load(path, allow_pickle=False) as z:
+            space, dim = str(z["space"]), int(z["dim"])
+            states, offsets, nbrs = z["states"], z["offsets"], z["neighbours"]
+        if space != self._space_kind() or dim != self._space_dim():
+            raise ValueError("roadmap file is for %s dim %d, the planner's space is %s dim %d"
+                             % (space, dim, self._space_kind(), self._space_dim()))
+        if states.ndim != 2 or states.shape[1] != dim or offsets.shape != (states.shape[0] + 1,):
+            raise ValueError("roadmap file is malformed: states %s, offsets %s" % (states.shape, offsets.shape))
+        self.set_roadmap(states, offsets, nbrs)
+
     @property
     def num_milestones(self):
         return 0 if self._prm is None else self._prm.sizes()[0]

@@ -261,6 +261,9 @@ extern "C" {
     pub fn oxhip_prm_batch_get_costs(p: *mut OxhipPrm, cost: *mut f64) -> i32;
     pub fn oxhip_prm_batch_get_labels(p: *mut OxhipPrm, query: u32, cost: *mut f64, hops: *mut u32, parent: *mut u32, cap: u32) -> i32;
     pub fn oxhip_prm_batch_get_search_stats(p: *mut OxhipPrm, label_rounds: *mut u32, relaxations: *mut u64, phase_ms: *mut f64) -> i32;
+    pub fn oxhip_prm_set_roadmap(p: *mut OxhipPrm, states: *const f64, n: u32, offsets: *const u64, neighbours: *const u32) -> i32;
+    pub fn oxhip_prm_revalidate(p: *mut OxhipPrm, milestone_valid: *mut u8, n_invalid_milestones: *mut u32, n_removed_entries: *mut u64) -> i32;
+    pub fn oxhip_prm_revalidate_last_timing(p: *mut OxhipPrm, phase_ms: *mut f64) -> i32;
 }
 
 #[cfg(test)]

@@ -477,6 +477,52 @@ impl<D: DeviceValidityChecker, G: DeviceGoal> HipPRM<D, G> {
             .collect()
     }
 
+    /// Replaces the roadmap with the caller's, in `get_roadmap`'s shape (`oxhip_prm_set_roadmap`).  The library checks on the GPU
+    /// that the edge lists are ascending and symmetric; `Err` carries its message (the rule and the lowest offending row) and the
+    /// planner's roadmap is then unchanged.
+    pub fn set_roadmap(&mut self, roadmap: &[(RealVectorState, Vec<usize>)]) -> Result<(), String> {
+        let dim = match (&self.problem_def, self.prm.is_null()) {
+            (Some(pd), false) => pd.space.dimension,
+            _ => return Err("setup() was not called".to_string()),
+        };
+        let n = roadmap.len();
+        let mut states = Vec::with_capacity(n * dim + 1);
+        let mut offsets = vec![0u64; n + 1];
+        let mut nbrs: Vec<u32> = Vec::new();
+        for (i, (state, edges)) in roadmap.iter().enumerate() {
+            if state.values.len() != dim {
+                return Err(format!("milestone {} has {} coordinates, the space has {}", i, state.values.len(), dim));
+            }
+            states.extend_from_slice(&state.values);
+            nbrs.extend(edges.iter().map(|&v| v.min(u32::MAX as usize) as u32));
+            offsets[i + 1] = nbrs.len() as u64;
+        }
+        if states.is_empty() {
+            states.push(0.0);
+        }
+        let nb = if nbrs.is_empty() { std::ptr::null() } else { nbrs.as_ptr() };
+        match unsafe { ffi::oxhip_prm_set_roadmap(self.prm, states.as_ptr(), n as u32, offsets.as_ptr(), nb) } {
+            ffi::OXHIP_OK => Ok(()),
+            _ => Err(last_error()),
+        }
+    }
+
+    /// Re-checks every milestone and edge of the roadmap against the handle's current obstacles (`oxhip_prm_revalidate`): an
+    /// invalid milestone keeps its index and loses its edges.  Returns (valid per milestone, edge entries removed).
+    pub fn revalidate(&mut self) -> Result<(Vec<bool>, u64), PlanningError> {
+        if self.prm.is_null() {
+            return Err(PlanningError::PlannerUninitialised);
+        }
+        let (mut n, mut entries, mut samples) = (0u32, 0u64, 0u64);
+        unsafe { ffi::oxhip_prm_get_sizes(self.prm, &mut n, &mut entries, &mut samples) };
+        let mut valid = vec![0u8; (n as usize).max(1)];
+        let (mut bad, mut removed) = (0u32, 0u64);
+        match unsafe { ffi::oxhip_prm_revalidate(self.prm, valid.as_mut_ptr(), &mut bad, &mut removed) } {
+            ffi::OXHIP_OK => Ok((valid[..n as usize].iter().map(|&v| v != 0).collect(), removed)),
+            st => Err(to_planning_error(st)),
+        }
+    }
+
     /// Many problem definitions on the roadmap already built, in one device call (`oxhip_prm_solve_batch`): per problem what
     /// `set_problem_definition` + `solve` would return, the breadth-first search included on the GPU.  The planner's own
     /// problem definition is left as it is.
