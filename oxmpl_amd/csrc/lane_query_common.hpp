@@ -3,7 +3,9 @@
 // Then the steps of a round that carry the reference's semantics, each stated once: a new node as the binary32 screens hold
 // it, every lane's own motion check, the round's checksum, and the whole-tree path of one ambiguous query -- its memo, the d2
 // scan, the literal loop and the motion check by the whole wave (rrt_resident.hip takes the last two as well).
-// rrt_cells.hip calls every one of them.  rrt_lanes.hip calls the lanes' own motion check and keeps its own text of the other
+// rrt_cells.hip calls every one of them (the motion check in its table form, motion_own_lane_short, which falls back to
+// motion_own_lane).  rrt_lanes.hip calls the lanes' own motion check -- motion_own_lane: its callback runs once per step of the
+// longest motion, which the table form's loop order does not offer -- and keeps its own text of the other
 // steps, each on a measured figure (profiles/lane_query_shared/README.md): growing trees ran slower with the d2 scan shared
 // (R^5 -5.3 %: the register allocation around the hot loop moves with the text of the rare path), with the literal loop or the
 // wave-wide motion check (R^5 -1.1 % each), with the checksum (R^5 -1.4 %), and with the binary32 node, the memo and
@@ -98,14 +100,18 @@ __device__ __forceinline__ void node_f32(const double (&qn)[D], const double (&c
 template <int D>
 __device__ __forceinline__ uint64_t spheres_maybe_hit(const double (&obs)[D + 2][64], uint64_t cand, const double (&mid)[D]) {
     uint64_t rem = cand, keep = 0;
-    while (__ballot(rem != 0) != 0) {
-        const bool has = rem != 0;
-        const uint32_t o = has ? (uint32_t)(__ffsll((unsigned long long)rem) - 1) : 0u;
-        double c[D];
+    while (__ballot(rem != 0) != 0) {   // two candidates per trip: both spheres are on their way before either is tested
+        const uint64_t rem1 = rem & (rem - 1);
+        const bool has0 = rem != 0, has1 = rem1 != 0;
+        const uint32_t o0 = has0 ? (uint32_t)(__ffsll((unsigned long long)rem) - 1) : 0u;
+        const uint32_t o1 = has1 ? (uint32_t)(__ffsll((unsigned long long)rem1) - 1) : 0u;
+        double c0[D], c1[D];
 #pragma unroll
-        for (int k = 0; k < D; ++k) c[k] = obs[k][o];
-        if (has && sphere_maybe_hit<D>(c, obs[D + 1][o], mid)) keep |= 1ull << o;
-        rem &= rem - 1;
+        for (int k = 0; k < D; ++k) { c0[k] = obs[k][o0]; c1[k] = obs[k][o1]; }
+        const double f0 = obs[D + 1][o0], f1 = obs[D + 1][o1];
+        if (has0 && sphere_maybe_hit<D>(c0, f0, mid)) keep |= 1ull << o0;
+        if (has1 && sphere_maybe_hit<D>(c1, f1, mid)) keep |= 1ull << o1;
+        rem = rem1 & (rem1 - 1);
     }
     return keep;
 }
@@ -149,6 +155,63 @@ __device__ __forceinline__ bool motion_own_lane(const DevParams& p, const double
     return bad;
 }
 
+// The step fractions of short motions, t[n - 1][s - 1] = (double)s / (double)n for 1 <= s <= n <= kStepTabMax, in LDS: the
+// quotients of the loop above by the device's own binary64 division, so their bits are the ones that loop computes.  Filled
+// by the first 64 threads of the workgroup before its barrier.
+constexpr uint32_t kStepTabMax = 8;
+struct StepFractions { double t[kStepTabMax][kStepTabMax]; };
+__device__ __forceinline__ void step_fractions_fill(StepFractions& tab, uint32_t tid) {
+    if (tid < kStepTabMax * kStepTabMax) tab.t[tid >> 3][tid & 7u] = (double)((tid & 7u) + 1u) / (double)((tid >> 3) + 1u);
+}
+// motion_own_lane with the loops interchanged where the order is free: the spheres of `maybe` outside -- a sphere is read
+// from LDS once, as many trips as the fullest lane has bits -- and the steps inside, t from the table (no division; the next
+// step's t is on its way while this step is tested).  The obstacles beyond the first 64 keep their loop over the steps.  A
+// wave in which a motion has more than kStepTabMax steps takes motion_own_lane as it is.
+template <int D>
+__device__ __forceinline__ bool motion_own_lane_short(const DevParams& p, const double (&obs)[D + 2][64], const StepFractions& tab, bool need, uint64_t maybe,
+                                                      const double (&q_near)[D], const double (&qn)[D], uint32_t ns64, uint32_t nobs) {
+    if (__ballot(need) == 0) return false;
+    const double dist = sqrt(dist2<D>(q_near, qn, D));
+    const uint32_t nsteps = num_steps_u32(dist, p.res);
+    const uint32_t steps_l = need ? (nsteps <= 1 ? 1u : nsteps) : 0u;
+    const uint32_t smax = wave_max_u32(steps_l);
+    if (smax > kStepTabMax) return motion_own_lane<D>(p, obs, need, maybe, q_near, qn, ns64, nobs, [](uint32_t) {});
+    const double* trow = tab.t[(steps_l == 0 ? 1u : steps_l) - 1u];   // (a lane without `need` reads row 0 and tests nothing)
+    auto state = [&](double t, double (&x)[D]) {
+        double xi[D];
+        lerp<D>(q_near, qn, t, xi, D);
+#pragma unroll
+        for (int k = 0; k < D; ++k) x[k] = nsteps <= 1 ? qn[k] : xi[k];   // num_steps <= 1: is_valid(to) only
+    };
+    bool bad = false;
+    uint64_t rem = need ? maybe : 0ull;
+    while (__ballot(rem != 0) != 0) {
+        const bool has = rem != 0;
+        const uint32_t o = has ? (uint32_t)(__ffsll((unsigned long long)rem) - 1) : 0u;
+        double c[D];
+#pragma unroll
+        for (int k = 0; k < D; ++k) c[k] = obs[k][o];
+        const double thr = obs[D][o];
+        double t_next = trow[0];
+        for (uint32_t s = 1; s <= smax; ++s) {
+            const double t = t_next;
+            t_next = trow[s < kStepTabMax ? s : kStepTabMax - 1u];
+            double x[D];
+            state(t, x);
+            bad |= (bool)((int)has & (int)(s <= steps_l) & (int)!(dist2<D>(c, x, D) > thr));   // (no short circuit: the steps overlap)
+        }
+        rem &= rem - 1;
+    }
+    if (ns64 < nobs) {
+        for (uint32_t s = 1; s <= smax; ++s) {
+            double x[D];
+            state(trow[s - 1u], x);
+            for (uint32_t jx = ns64; jx < nobs; ++jx) bad = bad || (s <= steps_l && obstacle_hit<D>(p, D, x, jx));
+        }
+    }
+    return bad;
+}
+
 // ---------------------------------------------------------------- the round's checksum
 // P^lane for the batched checksum (H <- H P^m + sum_j g_j P^(m-1-j)); P^64 for a full batch is chk_lane_power(..)[63] * P
 __device__ __forceinline__ uint64_t chk_lane_power(uint32_t lane) {
@@ -167,7 +230,9 @@ __device__ __forceinline__ uint64_t chk_push_round(uint64_t h, uint64_t pw, uint
     const bool mine = lane < cut;
     const uint64_t gd = iter_digest<D>(nearest, qn, D, ok);
     const int src = mine ? (int)(cut - 1u - lane) : 0;
-    const uint64_t w = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(pw >> 32), src, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)pw, src, 64);
+    // (src < 64: the permute itself, without __shfl's own lane number -- one more register held across the rounds)
+    const uint64_t w = ((uint64_t)(uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)(uint32_t)(pw >> 32)) << 32) |
+                       (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)(uint32_t)pw);
     const uint64_t sum = wave_sum_u64((mine && counted) ? gd * w : 0ull);
     const uint64_t pc = cut >= 64u ? pw64 : readlane_u64(pw, (int)cut);
     return h * pc + sum;

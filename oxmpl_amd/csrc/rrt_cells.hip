@@ -86,9 +86,18 @@ struct CellsWaveLds {
     float tail_s1[64], tail_s2[64];   // ... and what lane k found in that cell
     uint32_t tail_i1[64];
 };
+// What a launch computes once and every round reads: wave-uniform, written before the launch's barrier.  (The frozen kernel has
+// no registers to hold them across the round loop: there the compiler spills them and reloads them from scratch every round.)
+template <int DIM>
+struct CellsConsts {
+    double c0[DIM];               // the centre of the bounds
+    float sg_inv[DIM], sg_bias[DIM];   // the midpoint filter's lookup: cell = fl32(mid - c0) sg_inv + sg_bias
+};
 template <int DIM>
 struct CellsShared {
     double obs[DIM + 2][64];      // first 64 spheres: centre, validity threshold, filter threshold
+    StepFractions steps;          // s / n of the motions of up to kStepTabMax steps
+    CellsConsts<DIM> k;
     CellsWaveLds<DIM> w[kCellsWaves];
 };
 
@@ -577,6 +586,17 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
         for (int k = 0; k < D; ++k) shared.obs[k][lane] = lane < ns64 ? p.sph_c[(size_t)k * p.n_spheres + lane] : 0.0;
         shared.obs[D][lane] = lane < ns64 ? p.sph_thr[lane] : -1.0;
         shared.obs[D + 1][lane] = lane < ns64 ? p.sph_filt[lane] : -1.0;
+        step_fractions_fill(shared.steps, lane);
+        // the midpoint filter's lookup (DevParams::sph_grid): cell = (mid - lo) G / (hi - lo), from fl32(mid - c0)
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            if (lane == (uint32_t)k) {
+                const double inv = (double)p.sph_grid_G / (p.hi[k] - p.lo[k]);
+                shared.k.c0[k] = c0[k];
+                shared.k.sg_inv[k] = (float)inv;
+                shared.k.sg_bias[k] = (float)((c0[k] - p.lo[k]) * inv);
+            }
+        }
     }
     const bool live = prob < p.n_problems;
     const ProblemState st0 = p.state[live ? prob : 0u];
@@ -599,14 +619,6 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
     __syncthreads();   // the launch's only barrier: the obstacle tables are in LDS
     if (!live) return;
     if (p.stop_at_goal && st0.goal_node >= 0) return;
-    // the midpoint filter's lookup (DevParams::sph_grid): cell = (mid - lo) G / (hi - lo), from fl32(mid - c0)
-    float sg_inv[D], sg_bias[D];
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        const double inv = (double)p.sph_grid_G / (p.hi[k] - p.lo[k]);
-        sg_inv[k] = lbits_f32(uni(lf32_bits((float)inv)));
-        sg_bias[k] = lbits_f32(uni(lf32_bits((float)((c0[k] - p.lo[k]) * inv))));
-    }
 
     const size_t cap = p.cap;
     double* tree = p.tree + (size_t)prob * DIM * cap;
@@ -672,7 +684,11 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
         }
         uint32_t m = budget - jr < 64u ? budget - jr : 64u;
         if (js < jr + m) {   // draw the queries this round still lacks (rrt.rs:177-184): they depend on the stream only
-            cells_sample_block<DIM, true>(rng, p, goal_c, goal_radius, jr + m - js, lane, sh, js);
+            // (the sampler's per-lane constants -- below_mask(lane) -- from an opaque copy of the lane number: formed here, two
+            //  instructions; as loop invariants the frozen kernel would spill them and reload them from scratch every round)
+            uint32_t lane_s = lane;
+            if (FROZEN) asm volatile("" : "+v"(lane_s));
+            cells_sample_block<DIM, true>(rng, p, goal_c, goal_radius, jr + m - js, lane_s, sh, js);
             js = jr + m;
         }
         if (STAMP) { ++n_rounds; n_lanes += m; t_pm = (uint64_t)clock64(); }
@@ -701,7 +717,9 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
         if (grid.level == 0) {
             // every node, by index: a coalesced load gives each lane one node of the next 64, then node after node is
             // broadcast from its lane (v_readlane -> scalar operands): no memory latency per node
-            cfloat4 mine_nd = flat[lane < n ? lane : 0u];
+            uint32_t lane_f = lane;   // (opaque in a frozen launch, whose n never changes: the address is formed here, not held across the rounds)
+            if (FROZEN) asm volatile("" : "+v"(lane_f));
+            cfloat4 mine_nd = flat[lane_f < n ? lane_f : 0u];
             // (four independent running pairs: with one wave on the SIMD a single chain of dependent min / med3 / select
             //  instructions would wait out every instruction's latency)
             Top2 ta[4] = {{__builtin_inff(), __builtin_inff(), kNoNode}, {__builtin_inff(), __builtin_inff(), kNoNode},
@@ -1013,6 +1031,14 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
         // ---- check_motion (rrt.rs:90-116): the midpoint filter names the spheres the segment can touch at all ...
         bool bad = false;
         if (nobs > 0) {
+            // (the launch's constants from LDS, one broadcast read each, asked for before the midpoint is computed; the index is
+            //  opaque so that the reads stay inside the round)
+            uint32_t kz = 0;
+            asm volatile("" : "+v"(kz));
+            double kc0[D];
+            float ksg_inv[D], ksg_bias[D];
+#pragma unroll
+            for (int k = 0; k < D; ++k) { kc0[k] = shared.k.c0[kz + k]; ksg_inv[k] = shared.k.sg_inv[kz + k]; ksg_bias[k] = shared.k.sg_bias[kz + k]; }
             lerp<DIM>(q_near, qn, 0.5, mid, DIM);
             // ... looked up: the grid cell of the midpoint holds the spheres whose filter ball reaches the cell (a superset of
             // the spheres the midpoint test keeps; the cells are built 2^-9 wider than they are, the index below is good to
@@ -1024,7 +1050,7 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
                 uint32_t ci[3] = {0u, 0u, 0u};
 #pragma unroll
                 for (int k = 0; k < D; ++k) {
-                    const float u = __builtin_fmaf((float)(mid[k] - c0[k]), sg_inv[k], sg_bias[k]);
+                    const float u = __builtin_fmaf((float)(mid[k] - kc0[k]), ksg_inv[k], ksg_bias[k]);
                     inside = inside && u >= -0x1p-10f && u <= gs + 0x1p-10f;   // (NaN: outside)
                     const float fl = floorf(u);
                     ci[k] = fl > 0.0f ? (fl < gs ? (uint32_t)fl : p.sph_grid_G - 1u) : 0u;
@@ -1036,7 +1062,7 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
             const uint64_t maybe = spheres_maybe_hit<D>(shared.obs, cand, mid);   // (the binary64 filter)
             OXHIP_CPHASE(2);   // sphere filter
             const bool need = !(OXHIP_ABLATE & 4) && act && !amb && (maybe != 0 || extras);
-            bad = motion_own_lane<D>(p, shared.obs, need, maybe, q_near, qn, ns64, nobs, [](uint32_t) {});
+            bad = motion_own_lane_short<D>(p, shared.obs, shared.steps, need, maybe, q_near, qn, ns64, nobs);
         }
         OXHIP_CPHASE(3);   // motion check
         bool ok = act && !bad;
