@@ -139,7 +139,8 @@ hipError_t prm_sort_keys(void* tmp, size_t& tmp_bytes, uint64_t* in, uint64_t* o
                          hipStream_t s);
 void launch_prm_csr(const uint64_t* sorted, uint32_t n_keys, uint32_t n_nodes, uint32_t cap, uint32_t* offsets,
                     uint32_t* nbrs, hipStream_t s);
-void launch_prm_query(const DevParams& p, const PrmArgs& a, uint32_t n, const PrmQuery& q, double thr, uint8_t* flags,
+// near: R^n the squared-distance threshold of the connection radius, SO(3) the radius itself (seq_space.hpp: connects)
+void launch_prm_query(bool so3, const DevParams& p, const PrmArgs& a, uint32_t n, const PrmQuery& q, double near, uint8_t* flags,
                       uint32_t* start_valid, hipStream_t s);
 uint32_t prm_key_shift(uint32_t cap);   // directed keys are (u << shift) | v
 
@@ -160,8 +161,6 @@ void launch_prm_so3_sample(const DevParams& p, const PrmArgs& a, const PrmSo3Spe
 // candidates (j, i < j) with distance < r, j in [j0, j1): |dot| > hi is in, |dot| < lo is out, in between the exact distance
 void launch_prm_so3_pairs(const PrmArgs& a, uint32_t j0, uint32_t j1, double lo, double hi, double r, hipStream_t s);
 void launch_prm_so3_edges(const DevParams& p, const PrmArgs& a, uint32_t n_cand, hipStream_t s);
-void launch_prm_so3_query(const DevParams& p, const PrmArgs& a, uint32_t n, const PrmQuery& q, double r, uint8_t* flags,
-                          uint32_t* start_valid, hipStream_t s);
 
 // prm_revalidate.hip: a roadmap planted from the host, and a roadmap re-checked against the current obstacles
 enum PrmPlantRule : uint32_t {   // one result word per rule: the lowest offending row, 0xFFFFFFFF = none; reported in this order
@@ -212,8 +211,7 @@ struct PrmBatchArgs {
     uint32_t* n_goal;
     uint32_t n, stride, dim, q0, n_chunk, pad;
 };
-void launch_prm_batch_flags(const DevParams& p, const PrmBatchArgs& b, double thr, hipStream_t s);
-void launch_prm_batch_so3_flags(const DevParams& p, const PrmBatchArgs& b, double r, hipStream_t s);
+void launch_prm_batch_flags(bool so3, const DevParams& p, const PrmBatchArgs& b, double near, hipStream_t s);   // near: as launch_prm_query's
 uint32_t prm_batch_group(uint32_t n, uint64_t n_edge_entries);   // lanes per level node, from the roadmap's mean degree
 void launch_prm_batch_search(const PrmBatchArgs& b, uint32_t group, hipStream_t s);
 // row_off[c]: first row of query c's path within nodes / rows (this round's rows)

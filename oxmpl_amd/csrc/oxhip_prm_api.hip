@@ -127,15 +127,40 @@ void launch_edges(oxhip_prm* h, const PrmArgs& a, uint32_t n_cand) {
     if (h->so3) launch_prm_so3_edges(h->dp, a, n_cand, h->stream);
     else launch_prm_edges(h->dp, a, n_cand, h->stream);
 }
+// what "near the start" is compared with: SO(3) compares the distance with the radius itself, R^n d2 with its squared threshold
+double near_threshold(const oxhip_prm* h) { return h->so3 ? h->cfg.connection_radius : h->thr_conn; }
 void launch_query(oxhip_prm* h) {
-    if (h->so3) return launch_prm_so3_query(h->dp, h->args, h->n, h->query, h->cfg.connection_radius, h->flags.p, h->start_valid.p, h->stream);
     DevParams qdp = h->dp;   // the start may lie anywhere: widen the filter's absolute margin for this launch
     for (uint32_t k = 0; k < h->cfg.dim; ++k) qdp.filt_abs = std::fmax(qdp.filt_abs, 1e-9 * std::fabs(h->query.start[k]));
-    launch_prm_query(qdp, h->args, h->n, h->query, h->thr_conn, h->flags.p, h->start_valid.p, h->stream);
+    launch_prm_query(h->so3, qdp, h->args, h->n, h->query, near_threshold(h), h->flags.p, h->start_valid.p, h->stream);
 }
-void launch_batch_flags(oxhip_prm* h, const PrmBatchArgs& b) {
-    if (h->so3) launch_prm_batch_so3_flags(h->dp, b, h->cfg.connection_radius, h->stream);
-    else launch_prm_batch_flags(h->dp, b, h->thr_conn, h->stream);
+void launch_batch_flags(oxhip_prm* h, const PrmBatchArgs& b) { launch_prm_batch_flags(h->so3, h->dp, b, near_threshold(h), h->stream); }
+// a planted roadmap's fl32 shadow, which the R^n pair search screens with (the SO(3) pair search screens nothing)
+void launch_planted_shadow(oxhip_prm* h, uint32_t n) {
+    if (!h->so3) launch_prm_shadow(h->ms.p, h->ms32.p, (uint64_t)n * h->cfg.dim, h->stream);
+}
+// the re-check's pair list: R^n (entry, u, v) for its own check kernel; SO(3) construction's candidate layout, with a key array
+// and a counter of the re-check's own, for construction's edge kernel
+int32_t reserve_reval_pairs(oxhip_prm* h, uint32_t pair_cap) {
+    if (!h->so3) { HIP_TRY(h->rv_pairs.reserve(pair_cap)); return OXHIP_OK; }
+    HIP_TRY(h->rv_cand.reserve(pair_cap)); HIP_TRY(h->rv_keys.reserve(2 * (size_t)pair_cap)); HIP_TRY(h->rv_state.reserve(1));
+    HIP_TRY(hipMemsetAsync(h->rv_state.p, 0, sizeof(PrmState), h->stream));
+    return OXHIP_OK;
+}
+uint2* reval_cand(oxhip_prm* h) { return h->so3 ? h->rv_cand.p : nullptr; }   // (the emit launcher fills rv_pairs when this is null)
+// check_motion(from = u, to = v) per pair of the list; a valid one keeps its two entries
+int32_t launch_reval_edges(oxhip_prm* h, uint32_t n_pairs, uint32_t n, uint32_t n_old) {
+    if (!h->so3) {
+        launch_prm_reval_check(h->dp, h->ms.p, h->offsets.p, h->nbrs.p, n, n_old, h->rv_pairs.p, n_pairs, h->rv_keep.p, h->stream);
+    } else if (n_pairs) {
+        PrmArgs a = h->args;   // construction's kernel, the re-check's buffers: nothing of construction's workspace is touched
+        a.cand = h->rv_cand.p; a.keys = h->rv_keys.p; a.state = h->rv_state.p;
+        launch_edges(h, a, n_pairs);   // both directed keys of every valid pair
+        HIP_TRY(hipGetLastError());
+        launch_prm_reval_keys(h->rv_keys.p, h->rv_state.p, 2 * n_pairs, prm_key_shift(h->args.cap), h->offsets.p, h->nbrs.p, n, h->rv_keep.p,
+                              h->stream);
+    }
+    return OXHIP_OK;
 }
 // what a goal's radius is compared with: SO(3) compares the distance with the radius itself, R^n d2 with its squared threshold
 double goal_threshold(const oxhip_prm* h, double radius) { return h->so3 ? radius : sqrt_le_threshold(radius); }
@@ -1152,7 +1177,7 @@ int32_t oxhip_prm_set_roadmap(oxhip_prm* h, const double* states, uint32_t n, co
     // accepted: the staged roadmap becomes the handle's
     HIP_TRY(hipMemcpyAsync(h->ms.p, s_ms.p, (size_t)n * dim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->offsets.p, s_off.p, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
-    if (!h->so3) launch_prm_shadow(h->ms.p, h->ms32.p, (uint64_t)n * dim, h->stream);
+    launch_planted_shadow(h, n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->stream));
     std::swap(h->nbrs.p, s_nbrs.p); std::swap(h->nbrs.n, s_nbrs.n);
@@ -1173,12 +1198,7 @@ int32_t oxhip_prm_revalidate(oxhip_prm* h, uint8_t* milestone_valid, uint32_t* n
     HIP_TRY(h->rv_valid.reserve(n)); HIP_TRY(h->rv_counters.reserve(kRevalCounters));
     if (n_old) {
         HIP_TRY(h->rv_keep.reserve(n_old)); HIP_TRY(h->rv_pos.reserve(n_old)); HIP_TRY(h->rv_nbrs.reserve(n_old));
-        if (h->so3) {   // the pairs go through construction's own edge kernel, with a candidate list, key array and counter of the re-check's own
-            HIP_TRY(h->rv_cand.reserve(pair_cap)); HIP_TRY(h->rv_keys.reserve(2 * (size_t)pair_cap)); HIP_TRY(h->rv_state.reserve(1));
-            HIP_TRY(hipMemsetAsync(h->rv_state.p, 0, sizeof(PrmState), h->stream));
-        } else {
-            HIP_TRY(h->rv_pairs.reserve(pair_cap));
-        }
+        OX_TRY(reserve_reval_pairs(h, pair_cap));
         HIP_TRY(prm_reval_scan(nullptr, tmp_bytes, h->rv_keep.p, h->rv_pos.p, n_old, h->stream));
         HIP_TRY(h->rv_tmp.reserve(tmp_bytes));
     }
@@ -1189,7 +1209,7 @@ int32_t oxhip_prm_revalidate(oxhip_prm* h, uint8_t* milestone_valid, uint32_t* n
     launch_prm_reval_valid(h->so3, h->dp, h->ms.p, n, h->rv_valid.p, h->rv_counters.p, h->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(h->bev[1], h->stream));
-    launch_prm_reval_emit(h->offsets.p, h->nbrs.p, h->rv_valid.p, n, n_old, h->rv_pairs.p, h->so3 ? h->rv_cand.p : nullptr, pair_cap,
+    launch_prm_reval_emit(h->offsets.p, h->nbrs.p, h->rv_valid.p, n, n_old, h->rv_pairs.p, reval_cand(h), pair_cap,
                           h->rv_counters.p, h->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(h->bev[2], h->stream));
@@ -1197,16 +1217,7 @@ int32_t oxhip_prm_revalidate(oxhip_prm* h, uint8_t* milestone_valid, uint32_t* n
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (cnt[kRevalPairs] > pair_cap) return fail(OXHIP_ERR_HIP, "revalidate: more lower-index entries than half the roadmap's, which a symmetric roadmap cannot have");
     HIP_TRY(hipEventRecord(h->bev[3], h->stream));
-    if (h->so3 && cnt[kRevalPairs]) {
-        PrmArgs a = h->args;   // construction's kernel, the re-check's buffers: nothing of construction's workspace is touched
-        a.cand = h->rv_cand.p; a.keys = h->rv_keys.p; a.state = h->rv_state.p;
-        launch_edges(h, a, cnt[kRevalPairs]);   // check_motion(from = u, to = v) per pair; both directed keys of every valid one
-        HIP_TRY(hipGetLastError());
-        launch_prm_reval_keys(h->rv_keys.p, h->rv_state.p, 2 * cnt[kRevalPairs], prm_key_shift(h->args.cap), h->offsets.p, h->nbrs.p, n,
-                              h->rv_keep.p, h->stream);
-    } else if (!h->so3) {
-        launch_prm_reval_check(h->dp, h->ms.p, h->offsets.p, h->nbrs.p, n, n_old, h->rv_pairs.p, cnt[kRevalPairs], h->rv_keep.p, h->stream);
-    }
+    OX_TRY(launch_reval_edges(h, cnt[kRevalPairs], n, n_old));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(h->bev[4], h->stream));
     uint32_t n_new = 0;

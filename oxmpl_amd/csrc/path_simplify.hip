@@ -5,13 +5,13 @@
 //        rrt_connect.rs:288-304) on the device -- the parent chain from the goal node is counted, the host takes one prefix sum,
 //        and the chain is walked again writing the rows reversed behind the problem's offset (what prm_batch_paths_kernel does
 //        for a roadmap).  Rows are copied as 64-bit words: bit for bit.
-//   2. path_pairs_kernel<D> / path_pairs_so3_kernel   the hot path: one thread per pair (i, d = j - i), 2 <= d <= span, of a
-//        path's own waypoints, check_motion(from = p_i, to = p_j) by motion_valid_seq<D> / so3_motion_valid_seq, one bit per
-//        pair.  The pairs are dealt d-major: slot = (d - 2) * L + i, so the 64 lanes of a wave hold motions of equal index
-//        distance -- similar lengths, similar step counts -- and a wave's ballot is one word of the bit matrix (a problem's slots
-//        are padded to whole words; slots with i + d >= L are idle).  The motion check's midpoint filter runs over a wave-uniform
-//        sphere index (scalar loads); its absolute margin is per motion, since a path state may lie outside the bounds (the goal
-//        centre, a tree given through set_tree).
+//   2. path_pairs_kernel<D>   (D = 0: SO(3), seq_space.hpp) the hot path: one thread per pair (i, d = j - i), 2 <= d <= span, of
+//        a path's own waypoints, check_motion(from = p_i, to = p_j) by SeqSpace<D>::motion_valid (motion_valid_seq<D> /
+//        so3_motion_valid_seq), one bit per pair.  The pairs are dealt d-major: slot = (d - 2) * L + i, so the 64 lanes of a
+//        wave hold motions of equal index distance -- similar lengths, similar step counts -- and a wave's ballot is one word of
+//        the bit matrix (a problem's slots are padded to whole words; slots with i + d >= L are idle).  The motion check's
+//        midpoint filter runs over a wave-uniform sphere index (scalar loads); its absolute margin is per motion, since a path
+//        state may lie outside the bounds (the goal centre, a tree given through set_tree).
 //   3. path_dp_kernel<SO3>   one wave per problem, j serial: cost[j] = min over the window of i with valid(i, j) of
 //        fl(cost[i] + distance(p_i, p_j)), lowest i among ties (every lane scans its i ascending with strict '<', then the
 //        lexicographic (cost, i) minimum over the wave).  Distances are computed on the fly in the space's own evaluation order,
@@ -19,13 +19,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <type_traits>
-
 #include "oxhip_internal.hpp"
 #include "rrt_device.hpp"
-#include "motion_seq.hpp"
-#include "so3_device.hpp"
-#include "so3_motion_seq.hpp"
+#include "seq_space.hpp"
 
 namespace oxhip {
 
@@ -133,41 +129,18 @@ __device__ __forceinline__ PairSlot pair_slot(const PairArgs& a, uint64_t gw, ui
 }
 
 template <int D>
-__global__ __launch_bounds__(256) void path_pairs_kernel(DevParams p, PairArgs a) {
+__global__ __launch_bounds__(256) void path_pairs_kernel(typename SeqSpace<D>::Checker p, PairArgs a) {
+    using Space = SeqSpace<D>;
     const uint64_t gw = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
     if (gw >= a.n_words) return;                                 // wave-uniform
     const uint32_t lane = threadIdx.x & 63u;
     const PairSlot s = pair_slot(a, gw, lane);
     bool ok = false;
     if (s.active) {
-        double from[D], to[D];
-        double m = a.filt_base;
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-            from[k] = a.rows[s.row_i * D + k];
-            to[k] = a.rows[s.row_j * D + k];
-            m = fmax(m, 1e-9 * fmax(fabs(from[k]), fabs(to[k])));
-        }
-        ok = motion_valid_seq<D>(p, from, to, m);
-    }
-    const uint64_t word = __ballot(ok);
-    if (lane == 0) a.bits[gw] = word;
-}
-
-__global__ __launch_bounds__(256) void path_pairs_so3_kernel(So3Cones p, PairArgs a) {
-    const uint64_t gw = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (gw >= a.n_words) return;
-    const uint32_t lane = threadIdx.x & 63u;
-    const PairSlot s = pair_slot(a, gw, lane);
-    bool ok = false;
-    if (s.active) {
-        double from[4], to[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            from[k] = a.rows[s.row_i * 4 + k];
-            to[k] = a.rows[s.row_j * 4 + k];
-        }
-        ok = so3_motion_valid_seq(p.c, p.n, p.r, p.n, from, to, p.res);
+        double from[Space::W], to[Space::W];
+        Space::load(a.rows + s.row_i * Space::W, from);
+        Space::load(a.rows + s.row_j * Space::W, to);
+        ok = Space::motion_valid(p, from, to, Space::motion_margin(a.filt_base, from, to));
     }
     const uint64_t word = __ballot(ok);
     if (lane == 0) a.bits[gw] = word;
@@ -273,20 +246,10 @@ uint64_t path_pair_words(uint32_t L, uint32_t max_span) {
 void launch_path_pairs(const DevParams& p, const PairArgs& a, hipStream_t s) {
     if (a.n_words == 0) return;
     const dim3 grid((uint32_t)((a.n_words + 3u) / 4u)), block(256);
-    if (p.space == OXHIP_SPACE_SO3) {
-        const So3Cones cones{p.sph_c, p.sph_r, p.n_spheres, p.res};
-        hipLaunchKernelGGL(path_pairs_so3_kernel, grid, block, 0, s, cones, a);
-        return;
-    }
-    switch (p.dim) {
-        case 2: hipLaunchKernelGGL(path_pairs_kernel<2>, grid, block, 0, s, p, a); break;
-        case 3: hipLaunchKernelGGL(path_pairs_kernel<3>, grid, block, 0, s, p, a); break;
-        case 4: hipLaunchKernelGGL(path_pairs_kernel<4>, grid, block, 0, s, p, a); break;
-        case 5: hipLaunchKernelGGL(path_pairs_kernel<5>, grid, block, 0, s, p, a); break;
-        case 6: hipLaunchKernelGGL(path_pairs_kernel<6>, grid, block, 0, s, p, a); break;
-        case 7: hipLaunchKernelGGL(path_pairs_kernel<7>, grid, block, 0, s, p, a); break;
-        default: hipLaunchKernelGGL(path_pairs_kernel<8>, grid, block, 0, s, p, a); break;
-    }
+    space_dispatch<2>(p.space == OXHIP_SPACE_SO3, p.dim, [&](auto d) {   // (an RRT batch has at least two dimensions)
+        constexpr int D = decltype(d)::value;
+        hipLaunchKernelGGL(path_pairs_kernel<D>, grid, block, 0, s, SeqSpace<D>::checker(p), a);
+    });
 }
 
 void launch_path_dp(const DevParams& p, const PairArgs& a, const SimplifyOut& o, hipStream_t s) {

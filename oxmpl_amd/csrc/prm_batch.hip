@@ -1,9 +1,9 @@
 // prm_batch.hip -- a batch of PRM queries on one roadmap, search included, on gfx950 (wave64).  DESIGN.md section 17.
 //
 // Reference: oxmpl/src/geometric/planners/prm.rs:243-307 (solve) and :189-208 (reconstruct_path), once per query.
-//   1. prm_batch_flags_kernel / prm_batch_so3_flags_kernel   one thread per (query, milestone): start validity, start connection,
-//        goal membership -- the device functions, evaluation order and thresholds of prm_query_kernel / prm_so3_query_kernel,
-//        so the bits are theirs; the midpoint filter's absolute margin is per query (the start may lie anywhere).
+//   1. prm_batch_flags_kernel<DIM>   one thread per (query, milestone): start validity, start connection, goal membership --
+//        the lines of prm_query_kernel<DIM> over SeqSpace<DIM> (seq_space.hpp; DIM = 0: SO(3)), so the bits are its; the
+//        midpoint filter's absolute margin is per query (the start may lie anywhere).
 //   2. prm_batch_search_kernel   one 1024-thread workgroup per query: the reference's FIFO (:270-301) evaluated level by level.
 //        Level 0 is the start connections, ascending; a node's rank is its position in its level.  A level that holds goal
 //        milestones answers with the one of lowest rank.  Otherwise every unvisited neighbour of the level takes as parent the
@@ -19,13 +19,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <type_traits>
-
 #include "oxhip_internal.hpp"
 #include "rrt_device.hpp"
-#include "motion_seq.hpp"
-#include "so3_device.hpp"
-#include "so3_motion_seq.hpp"
+#include "prm_csr.hpp"
+#include "seq_space.hpp"
 
 namespace oxhip {
 
@@ -33,37 +30,24 @@ namespace oxhip {
 // 1. flags
 
 template <int DIM>
-__global__ __launch_bounds__(256) void prm_batch_flags_kernel(DevParams p, PrmBatchArgs b, double thr) {
+__global__ __launch_bounds__(256) void prm_batch_flags_kernel(typename SeqSpace<DIM>::Checker p, PrmBatchArgs b, double near) {
+    using Space = SeqSpace<DIM>;
+    constexpr int W = Space::W;
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     const uint32_t c = blockIdx.y;                 // query of the round
     const size_t q = (size_t)b.q0 + c;             // query of the batch
-    double s[DIM], g[DIM];
+    double s[W], g[W];
 #pragma unroll
-    for (int k = 0; k < DIM; ++k) { s[k] = b.starts[q * DIM + k]; g[k] = b.goals[q * DIM + k]; }
-    if (i == 0) b.start_valid[c] = state_valid_seq<DIM>(p, s) ? 1u : 0u;   // prm.rs:244
+    for (int k = 0; k < W; ++k) { s[k] = b.starts[q * W + k]; g[k] = b.goals[q * W + k]; }
+    if (i == 0) b.start_valid[c] = Space::state_valid(p, s) ? 1u : 0u;                       // prm.rs:244
     if (i >= b.n) return;
-    double m[DIM];
-#pragma unroll
-    for (int k = 0; k < DIM; ++k) m[k] = b.ms[(size_t)i * DIM + k];
+    double m[W];
+    Space::load(b.ms + (size_t)i * W, m);
+    // the flag byte as prm_query_kernel writes it (prm_kernels.hip, which says why the lines stand in the kernel); the midpoint
+    // filter's absolute margin is per query (R^n: the start may lie anywhere)
     uint8_t f = 0;
-    if (dist2<DIM>(s, m, DIM) <= thr && motion_valid_seq<DIM>(p, s, m, b.filt[q])) f |= 1;   // prm.rs:251-252
-    if (dist2<DIM>(m, g, DIM) <= b.goal_thr[q]) f |= 2;                                       // goal.is_satisfied, prm.rs:261
-    b.flags[(size_t)c * b.stride + i] = f;
-}
-
-__global__ __launch_bounds__(256) void prm_batch_so3_flags_kernel(So3Cones p, PrmBatchArgs b, double r) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t c = blockIdx.y;
-    const size_t q = (size_t)b.q0 + c;
-    const double s[4] = {b.starts[q * 4], b.starts[q * 4 + 1], b.starts[q * 4 + 2], b.starts[q * 4 + 3]};
-    const double g[4] = {b.goals[q * 4], b.goals[q * 4 + 1], b.goals[q * 4 + 2], b.goals[q * 4 + 3]};
-    const uint32_t nc = p.n;
-    if (i == 0) b.start_valid[c] = so3_cone_hit(p.c, nc, p.r, nc, s) ? 0u : 1u;   // prm.rs:244
-    if (i >= b.n) return;
-    const double m[4] = {b.ms[(size_t)i * 4], b.ms[(size_t)i * 4 + 1], b.ms[(size_t)i * 4 + 2], b.ms[(size_t)i * 4 + 3]};
-    uint8_t f = 0;
-    if (so3_distance(s, m) < r && so3_motion_valid_seq(p.c, nc, p.r, nc, s, m, p.res)) f |= 1;   // prm.rs:251-252
-    if (so3_distance(m, g) <= b.goal_thr[q]) f |= 2;                                              // prm.rs:261
+    if (Space::connects(s, m, near) && Space::motion_valid(p, s, m, b.filt[q])) f |= 1;     // prm.rs:251-252
+    if (Space::goal_measure(m, g) <= b.goal_thr[q]) f |= 2;                                  // goal.is_satisfied, prm.rs:261
     b.flags[(size_t)c * b.stride + i] = f;
 }
 
@@ -71,13 +55,8 @@ __global__ __launch_bounds__(256) void prm_batch_so3_flags_kernel(So3Cones p, Pr
 // 2. search
 
 // a claim / parent word: 0xFFFFFFFF (what the host's memset leaves) = not yet in a level, then
-constexpr uint32_t kTentative = 0x80000000u;   // | rank: claimed in the level being expanded
-constexpr uint32_t kRoot = 0x7FFFFFFFu;        // a start connection (parent_map's Some(None)); milestone indices are < 2^26
+constexpr uint32_t kTentative = 0x80000000u;   // | rank: claimed in the level being expanded, kRoot (prm_csr.hpp): a start connection
 constexpr uint32_t kNoGoal = 0xFFFFFFFFu;
-
-// Words another wave of the workgroup wrote (plain stores and atomics alike) are read and written at L2.
-__device__ __forceinline__ uint32_t ld_l2(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_l2(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 
 // 1024 threads per query: the search is a chain of dependent loads (edge list -> claim word), and with one workgroup per query
@@ -270,32 +249,12 @@ __global__ __launch_bounds__(64) void prm_batch_paths_kernel(PrmBatchArgs b, con
 // ------------------------------------------------------------------------------------------------
 // launchers
 
-template <typename F>
-static void batch_dim_dispatch(uint32_t dim, F&& f) {
-    switch (dim) {
-        case 1: f(std::integral_constant<int, 1>{}); break;
-        case 2: f(std::integral_constant<int, 2>{}); break;
-        case 3: f(std::integral_constant<int, 3>{}); break;
-        case 4: f(std::integral_constant<int, 4>{}); break;
-        case 5: f(std::integral_constant<int, 5>{}); break;
-        case 6: f(std::integral_constant<int, 6>{}); break;
-        case 7: f(std::integral_constant<int, 7>{}); break;
-        default: f(std::integral_constant<int, 8>{}); break;
-    }
-}
-
-void launch_prm_batch_flags(const DevParams& p, const PrmBatchArgs& b, double thr, hipStream_t s) {
+void launch_prm_batch_flags(bool so3, const DevParams& p, const PrmBatchArgs& b, double near, hipStream_t s) {
     const dim3 grid(b.n ? (b.n + 255) / 256 : 1, b.n_chunk);
-    batch_dim_dispatch(p.dim, [&](auto d) {
+    space_dispatch(so3, p.dim, [&](auto d) {
         constexpr int D = decltype(d)::value;
-        hipLaunchKernelGGL(prm_batch_flags_kernel<D>, grid, dim3(256), 0, s, p, b, thr);
+        hipLaunchKernelGGL(prm_batch_flags_kernel<D>, grid, dim3(256), 0, s, SeqSpace<D>::checker(p), b, near);
     });
-}
-
-void launch_prm_batch_so3_flags(const DevParams& p, const PrmBatchArgs& b, double r, hipStream_t s) {
-    const dim3 grid(b.n ? (b.n + 255) / 256 : 1, b.n_chunk);
-    const So3Cones cones{p.sph_c, p.sph_r, p.n_spheres, p.res};
-    hipLaunchKernelGGL(prm_batch_so3_flags_kernel, grid, dim3(256), 0, s, cones, b, r);
 }
 
 uint32_t prm_batch_group(uint32_t n, uint64_t n_edge_entries) {

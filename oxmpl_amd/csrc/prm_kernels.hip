@@ -29,6 +29,8 @@
 #include "oxhip_internal.hpp"
 #include "rrt_device.hpp"
 #include "motion_seq.hpp"
+#include "prm_stage.hpp"
+#include "seq_space.hpp"
 
 namespace oxhip {
 
@@ -292,11 +294,7 @@ constexpr int kPairR = OXHIP_PAIR_R;                // milestones j held in regi
 constexpr int kPairJB = kPairThreads * kPairR;      // j per workgroup
 constexpr int kPairIC = OXHIP_PAIR_IC;              // i per workgroup
 
-constexpr int kStage = 512;                         // per-wave LDS staging of hits before they go to HBM
-
-// Hits are appended to a per-wave LDS buffer with ballot / prefix-count positions (the wave is its only
-// writer, so no atomic is involved) and flushed to the candidate list with ONE global atomic per flush.
-// A single global counter bumped once per hit serialises at the L2: 291 k hits cost 3 ms that way.
+// (the hits' staging in LDS and its flush: prm_stage.hpp)
 typedef float pair_f32x2 __attribute__((ext_vector_type(2)));
 
 // host twin of screen_margins / screen_threshold (rrt_device.hpp): the largest binary32 squared distance a pair whose
@@ -310,25 +308,6 @@ static float host_screen_threshold(double m_all, int dim, double thr) {
     const double r_hi = 1.0 + 2.0 * (0x1p-19 + (double)(dim + 2) * u);
     const double d = (r * (1.0 + 1e-12) + a2) * r_hi * r_hi;
     return (float)(d * d * (1.0 + 0x1p-20));
-}
-
-struct PairStage {
-    uint2* buf;       // this wave's kStage entries in LDS
-    uint32_t cnt;     // wave-uniform
-};
-
-__device__ __forceinline__ void stage_flush(const PrmArgs& a, PairStage& st, uint32_t lane) {
-    if (st.cnt == 0) return;
-    unsigned long long base = 0;
-    if (lane == 0) base = atomicAdd(&a.state->n_cand, (unsigned long long)st.cnt);
-    base = uni64(base);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the wave's LDS writes precede its reads below
-    for (uint32_t e = lane; e < st.cnt; e += 64) {
-        const unsigned long long slot = base + e;
-        if (slot < (unsigned long long)a.cand_cap) a.cand[slot] = st.buf[e];
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // ... and those reads precede the next writes
-    st.cnt = 0;
 }
 
 // A range of i against the thread's kPairR milestones.  `ci` is wave-uniform: it is loaded through the scalar
@@ -484,17 +463,7 @@ __global__ __launch_bounds__(256) void prm_edge_kernel(DevParams p, PrmArgs a, u
         }
         ok = motion_valid_seq<DIM>(p, from, to);
     }
-    // one atomic per wave: a counter bumped once per edge serialises at the L2
-    const uint64_t bal = __ballot(ok);
-    if (bal == 0) return;
-    uint32_t base = 0;
-    if (lane == 0) base = atomicAdd(&a.state->n_keys, 2u * (uint32_t)__popcll(bal));
-    base = uni(base);
-    if (ok) {
-        const uint32_t slot = base + 2u * (uint32_t)__popcll(bal & below_mask(lane));
-        a.keys[slot] = ((uint64_t)pr.x << key_shift) | pr.y;       // i in j's list
-        a.keys[slot + 1] = ((uint64_t)pr.y << key_shift) | pr.x;   // j in i's list (prm.rs:143-145)
-    }
+    append_edge_keys(ok, pr.x, pr.y, a.keys, &a.state->n_keys, key_shift, lane);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -628,39 +597,28 @@ __global__ __launch_bounds__(256) void prm_csr_kernel(const uint64_t* sorted, ui
 // query (prm.rs:243-264): start validity, start connections, goal milestones
 
 template <int DIM>
-__global__ __launch_bounds__(256) void prm_query_kernel(DevParams p, PrmArgs a, uint32_t n, PrmQuery q, double thr,
+__global__ __launch_bounds__(256) void prm_query_kernel(typename SeqSpace<DIM>::Checker p, PrmArgs a, uint32_t n, PrmQuery q, double near,
                                                          uint8_t* flags, uint32_t* start_valid) {
+    using Space = SeqSpace<DIM>;
+    constexpr int W = Space::W;
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    double s[DIM], g[DIM];
+    double s[W], g[W];
 #pragma unroll
-    for (int k = 0; k < DIM; ++k) { s[k] = q.start[k]; g[k] = q.goal_c[k]; }
-    if (i == 0) *start_valid = state_valid_seq<DIM>(p, s) ? 1u : 0u;   // prm.rs:244
+    for (int k = 0; k < W; ++k) { s[k] = q.start[k]; g[k] = q.goal_c[k]; }
+    if (i == 0) *start_valid = Space::state_valid(p, s) ? 1u : 0u;                       // prm.rs:244
     if (i >= n) return;
-    double m[DIM];
-#pragma unroll
-    for (int k = 0; k < DIM; ++k) m[k] = a.ms[(size_t)i * DIM + k];
+    double m[W];
+    Space::load(a.ms + (size_t)i * W, m);
+    // the flag byte, the same three lines as prm_batch_flags_kernel (prm_batch.hip).  They stand in the kernel: behind a function
+    // the goal threshold is read before the motion check instead of after it, and the register allocation changes with that
     uint8_t f = 0;
-    if (dist2<DIM>(s, m, DIM) <= thr && motion_valid_seq<DIM>(p, s, m)) f |= 1;   // prm.rs:251-252
-    if (dist2<DIM>(m, g, DIM) <= q.goal_thr) f |= 2;                               // goal.is_satisfied, prm.rs:261
+    if (Space::connects(s, m, near) && Space::motion_valid(p, s, m)) f |= 1;            // prm.rs:251-252
+    if (Space::goal_measure(m, g) <= q.goal_thr) f |= 2;                                 // goal.is_satisfied, prm.rs:261
     flags[i] = f;
 }
 
 // ------------------------------------------------------------------------------------------------
 // launchers
-
-template <typename F>
-static void dim_dispatch(uint32_t dim, F&& f) {
-    switch (dim) {
-        case 1: f(std::integral_constant<int, 1>{}); break;
-        case 2: f(std::integral_constant<int, 2>{}); break;
-        case 3: f(std::integral_constant<int, 3>{}); break;
-        case 4: f(std::integral_constant<int, 4>{}); break;
-        case 5: f(std::integral_constant<int, 5>{}); break;
-        case 6: f(std::integral_constant<int, 6>{}); break;
-        case 7: f(std::integral_constant<int, 7>{}); break;
-        default: f(std::integral_constant<int, 8>{}); break;
-    }
-}
 
 void launch_prm_sample(const DevParams& p, const PrmArgs& a, hipStream_t s) {
     dim_dispatch(p.dim, [&](auto d) {
@@ -768,12 +726,12 @@ void launch_prm_csr(const uint64_t* sorted, uint32_t n_keys, uint32_t n_nodes, u
                        offsets, nbrs);
 }
 
-void launch_prm_query(const DevParams& p, const PrmArgs& a, uint32_t n, const PrmQuery& q, double thr, uint8_t* flags,
+void launch_prm_query(bool so3, const DevParams& p, const PrmArgs& a, uint32_t n, const PrmQuery& q, double near, uint8_t* flags,
                       uint32_t* start_valid, hipStream_t s) {
     const uint32_t blocks = n ? (n + 255) / 256 : 1;
-    dim_dispatch(p.dim, [&](auto d) {
+    space_dispatch(so3, p.dim, [&](auto d) {
         constexpr int D = decltype(d)::value;
-        hipLaunchKernelGGL(prm_query_kernel<D>, dim3(blocks), dim3(256), 0, s, p, a, n, q, thr, flags, start_valid);
+        hipLaunchKernelGGL(prm_query_kernel<D>, dim3(blocks), dim3(256), 0, s, SeqSpace<D>::checker(p), a, n, q, near, flags, start_valid);
     });
 }
 

@@ -6,7 +6,7 @@
 // holding the lowest offending row (atomicMin), so the refusal's message does not depend on the order of arrival.
 //
 // Re-checking (the semantics are this build's own; the reference has no such call):
-//   1. prm_reval_valid_kernel   valid[i] = is_valid(milestone i), one thread per milestone
+//   1. prm_reval_valid_kernel   valid[i] = is_valid(milestone i), one thread per milestone, over SeqSpace<DIM> (seq_space.hpp)
 //   2. prm_reval_emit_kernel    one thread per CSR entry (u -> v): v < u and both ends valid -> (entry, u, v) joins the pair list
 //                               (one atomic per wave, from a ballot, as prm_edge_kernel appends its keys)
 //   3. prm_reval_check_kernel   R^n, one thread per pair: check_motion(from = milestone u, to = milestone v), construction's own
@@ -21,57 +21,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <type_traits>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "oxhip_internal.hpp"
 #include "rrt_device.hpp"
-#include "motion_seq.hpp"
-#include "so3_motion_seq.hpp"
+#include "prm_csr.hpp"
+#include "seq_space.hpp"
 
 namespace oxhip {
-
-// the row of CSR entry e: the last u with offsets[u] <= e (rows may be empty; offsets[0] = 0 <= e < offsets[n])
-__device__ __forceinline__ uint32_t reval_row_of(const uint32_t* __restrict__ offsets, uint32_t n, uint32_t e) {
-    uint32_t lo = 0, hi = n;   // the answer lies in [lo, hi)
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (offsets[mid] <= e) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// the entry of row `row` that holds `want` (rows ascending), 0xFFFFFFFF when it holds none
-__device__ __forceinline__ uint32_t reval_find(const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ nbrs, uint32_t row,
-                                               uint32_t want) {
-    uint32_t lo = offsets[row], hi = offsets[row + 1];
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (nbrs[mid] < want) lo = mid + 1; else hi = mid;
-    }
-    return lo < offsets[row + 1] && nbrs[lo] == want ? lo : 0xFFFFFFFFu;
-}
-
-// The obstacle tables are SoA [dim][n], read by the shared device functions at a wave-uniform index: as kernel arguments their
-// per-dimension rows become scalar address pairs and scalar operands, about ten SGPRs per dimension, and from R^6 on that spills
-// SGPRs.  Here the three table pointers pass through a VGPR first, so the same loads are issued as vector loads of the same
-// addresses: the same values, the same arithmetic, no spill.  (The radii, thresholds and the box count follow for R^8's last
-// SGPRs.)
-template <typename T>
-__device__ __forceinline__ void reval_vector_pointer(const T*& ptr) {
-    asm volatile("" : "+v"(ptr));
-}
-__device__ __forceinline__ DevParams reval_params(const DevParams& p) {
-    DevParams q = p;
-    reval_vector_pointer(q.sph_c);
-    reval_vector_pointer(q.box_lo);
-    reval_vector_pointer(q.box_hi);
-    reval_vector_pointer(q.sph_r);
-    reval_vector_pointer(q.sph_thr);
-    asm volatile("" : "+v"(q.n_boxes));   // (and with it the box tables' row strides k * n_boxes)
-    return q;
-}
 
 // ------------------------------------------------------------------------------------------------
 // planting: the structure rules.  viol[rule] starts at 0xFFFFFFFF and ends as the lowest offending row.
@@ -93,40 +51,27 @@ __global__ __launch_bounds__(256) void prm_plant_entries_kernel(const uint32_t* 
     const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= n_entries) return;
     const uint32_t e = (uint32_t)t;
-    const uint32_t u = reval_row_of(offsets, n, e), v = nbrs[e];
+    const uint32_t u = row_of(offsets, n, e), v = nbrs[e];
     if (v >= n) { atomicMin(&viol[kPlantRange], u); return; }
     if (v == u) atomicMin(&viol[kPlantSelfLoop], u);
     if (e > offsets[u] && nbrs[e - 1] >= v) atomicMin(&viol[kPlantUnsorted], u);
     // (an unsorted row v can hide u from the search: the host reports the rules in this order, so that refusal comes first)
-    if (reval_find(offsets, nbrs, v, u) == 0xFFFFFFFFu) atomicMin(&viol[kPlantAsymmetric], u);
+    if (row_find(offsets, nbrs, v, u) == 0xFFFFFFFFu) atomicMin(&viol[kPlantAsymmetric], u);
 }
 
 // ------------------------------------------------------------------------------------------------
 // 1. milestone validity (the bits of oxhip_rrt_batch_is_valid: obstacle_hit / so3_cone_hit per obstacle)
 
 template <int DIM>
-__global__ __launch_bounds__(256) void prm_reval_valid_kernel(DevParams p, const double* __restrict__ ms, uint32_t n, uint8_t* __restrict__ valid,
-                                                               uint32_t* counters) {
+__global__ __launch_bounds__(256) void prm_reval_valid_kernel(typename SeqSpace<DIM>::Checker p, const double* __restrict__ ms, uint32_t n,
+                                                               uint8_t* __restrict__ valid, uint32_t* counters) {
+    using Space = SeqSpace<DIM>;
     const uint32_t i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
     bool bad = false;
     if (i < n) {
-        double s[DIM];
-#pragma unroll
-        for (int k = 0; k < DIM; ++k) s[k] = ms[(size_t)i * DIM + k];
-        bad = !state_valid_seq<DIM>(reval_params(p), s);
-        valid[i] = bad ? 0 : 1;
-    }
-    const uint64_t bal = __ballot(bad);
-    if (bal != 0 && lane == 0) atomicAdd(&counters[kRevalInvalid], (uint32_t)__popcll(bal));
-}
-
-__global__ __launch_bounds__(256) void prm_reval_so3_valid_kernel(So3Cones p, const double* __restrict__ ms, uint32_t n,
-                                                                   uint8_t* __restrict__ valid, uint32_t* counters) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
-    bool bad = false;
-    if (i < n) {
-        const double s[4] = {ms[(size_t)i * 4], ms[(size_t)i * 4 + 1], ms[(size_t)i * 4 + 2], ms[(size_t)i * 4 + 3]};
-        bad = so3_cone_hit(p.c, p.n, p.r, p.n, s);
+        double s[Space::W];
+        Space::load(ms + (size_t)i * Space::W, s);
+        bad = !Space::state_valid(Space::vgpr_pointers(p), s);
         valid[i] = bad ? 0 : 1;
     }
     const uint64_t bal = __ballot(bad);
@@ -146,7 +91,7 @@ __global__ __launch_bounds__(256) void prm_reval_emit_kernel(const uint32_t* __r
     uint32_t u = 0, v = 0;
     if (t < n_entries) {
         v = nbrs[t];
-        u = reval_row_of(offsets, n, (uint32_t)t);
+        u = row_of(offsets, n, (uint32_t)t);
         take = v < u && valid[u] != 0 && valid[v] != 0;
     }
     const uint64_t bal = __ballot(take);
@@ -172,17 +117,13 @@ __global__ __launch_bounds__(256) void prm_reval_check_kernel(DevParams p, const
     const uint32_t c = blockIdx.x * 256 + threadIdx.x;
     if (c >= n_pairs) return;
     const uint4 pr = pairs[c];
+    using Space = SeqSpace<DIM>;
     double from[DIM], to[DIM];
-    // a planted milestone may lie outside the bounds: the midpoint filter's absolute margin with this motion's ends in play
-    // (the filter only ever drops spheres that cannot be hit, so the verdict is construction's whatever the margin)
-    double filt = p.filt_abs;
-#pragma unroll
-    for (int k = 0; k < DIM; ++k) {
-        from[k] = ms[(size_t)pr.y * DIM + k];
-        to[k] = ms[(size_t)pr.z * DIM + k];
-        filt = fmax(filt, 1e-9 * fmax(fabs(from[k]), fabs(to[k])));
-    }
-    if (motion_valid_seq<DIM>(reval_params(p), from, to, filt)) keep[pr.x] = 1;
+    Space::load(ms + (size_t)pr.y * DIM, from);
+    Space::load(ms + (size_t)pr.z * DIM, to);
+    // a planted milestone may lie outside the bounds: the filter's margin with this motion's ends in play (the verdict is construction's)
+    const double filt = Space::motion_margin(p.filt_abs, from, to);
+    if (Space::motion_valid(Space::vgpr_pointers(p), from, to, filt)) keep[pr.x] = 1;
 }
 
 // SO(3): the pairs go through construction's own prm_so3_edge_kernel (prm_so3.hip), which appends both directed keys
@@ -196,7 +137,7 @@ __global__ __launch_bounds__(256) void prm_reval_keys_kernel(const uint64_t* __r
     const uint64_t key = keys[k];
     const uint32_t u = (uint32_t)(key >> shift), v = (uint32_t)(key & ((1ull << shift) - 1ull));
     if (u >= n) return;
-    const uint32_t e = reval_find(offsets, nbrs, u, v);
+    const uint32_t e = row_find(offsets, nbrs, u, v);
     if (e != 0xFFFFFFFFu) keep[e] = 1;
 }
 
@@ -206,9 +147,9 @@ __global__ __launch_bounds__(256) void prm_reval_mirror_kernel(const uint32_t* _
                                                                 uint32_t n_entries, uint8_t* keep) {
     const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= n_entries) return;
-    const uint32_t v = nbrs[t], u = reval_row_of(offsets, n, (uint32_t)t);
+    const uint32_t v = nbrs[t], u = row_of(offsets, n, (uint32_t)t);
     if (v <= u) return;
-    const uint32_t lower = reval_find(offsets, nbrs, v, u);
+    const uint32_t lower = row_find(offsets, nbrs, v, u);
     if (lower != 0xFFFFFFFFu && keep[lower] != 0) keep[t] = 1;
 }
 
@@ -230,20 +171,6 @@ __global__ __launch_bounds__(256) void prm_reval_compact_kernel(uint32_t* offset
 // ------------------------------------------------------------------------------------------------
 // launchers
 
-template <typename F>
-static void reval_dim_dispatch(uint32_t dim, F&& f) {
-    switch (dim) {
-        case 1: f(std::integral_constant<int, 1>{}); break;
-        case 2: f(std::integral_constant<int, 2>{}); break;
-        case 3: f(std::integral_constant<int, 3>{}); break;
-        case 4: f(std::integral_constant<int, 4>{}); break;
-        case 5: f(std::integral_constant<int, 5>{}); break;
-        case 6: f(std::integral_constant<int, 6>{}); break;
-        case 7: f(std::integral_constant<int, 7>{}); break;
-        default: f(std::integral_constant<int, 8>{}); break;
-    }
-}
-
 static uint32_t blocks_for(uint64_t work) { return (uint32_t)((work + 255) / 256); }
 
 void launch_prm_plant_offsets(const uint64_t* off64, uint32_t n, uint32_t* off32, uint32_t* viol, hipStream_t s) {
@@ -256,14 +183,9 @@ void launch_prm_plant_entries(const uint32_t* offsets, const uint32_t* nbrs, uin
 }
 
 void launch_prm_reval_valid(bool so3, const DevParams& p, const double* ms, uint32_t n, uint8_t* valid, uint32_t* counters, hipStream_t s) {
-    if (so3) {
-        const So3Cones cones{p.sph_c, p.sph_r, p.n_spheres, p.res};
-        hipLaunchKernelGGL(prm_reval_so3_valid_kernel, dim3(blocks_for(n)), dim3(256), 0, s, cones, ms, n, valid, counters);
-        return;
-    }
-    reval_dim_dispatch(p.dim, [&](auto d) {
+    space_dispatch(so3, p.dim, [&](auto d) {
         constexpr int D = decltype(d)::value;
-        hipLaunchKernelGGL(prm_reval_valid_kernel<D>, dim3(blocks_for(n)), dim3(256), 0, s, p, ms, n, valid, counters);
+        hipLaunchKernelGGL(prm_reval_valid_kernel<D>, dim3(blocks_for(n)), dim3(256), 0, s, SeqSpace<D>::checker(p), ms, n, valid, counters);
     });
 }
 
@@ -277,7 +199,7 @@ void launch_prm_reval_emit(const uint32_t* offsets, const uint32_t* nbrs, const 
 void launch_prm_reval_check(const DevParams& p, const double* ms, const uint32_t* offsets, const uint32_t* nbrs, uint32_t n, uint32_t n_entries,
                             const uint4* pairs, uint32_t n_pairs, uint8_t* keep, hipStream_t s) {
     if (n_pairs == 0) return;
-    reval_dim_dispatch(p.dim, [&](auto d) {
+    dim_dispatch(p.dim, [&](auto d) {
         constexpr int D = decltype(d)::value;
         hipLaunchKernelGGL(prm_reval_check_kernel<D>, dim3(blocks_for(n_pairs)), dim3(256), 0, s, p, ms, pairs, n_pairs, keep);
     });

@@ -19,11 +19,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <type_traits>
-
 #include "oxhip_internal.hpp"
 #include "rrt_device.hpp"
-#include "so3_device.hpp"
+#include "prm_csr.hpp"
+#include "seq_space.hpp"
 
 namespace oxhip {
 
@@ -31,12 +30,9 @@ namespace {
 
 constexpr uint64_t kInfBits = 0x7FF0000000000000ull;   // +inf: no label yet
 constexpr uint32_t kUnset = 0xFFFFFFFFu;               // parent / hops of a milestone in no level
-constexpr uint32_t kRoot = 0x7FFFFFFFu;                // parent of a source (what prm_batch_paths_kernel never follows)
 constexpr uint32_t kThreads = 1024;
 
-// Words another wave of the workgroup wrote (plain stores and atomics alike) are read and written at L2.
-__device__ __forceinline__ uint32_t ld_l2(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_l2(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// the 64-bit labels, at L2 like prm_csr.hpp's words
 __device__ __forceinline__ uint64_t ld_l2(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ uint64_t min_l2(uint64_t* p, uint64_t v) { return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
@@ -44,15 +40,13 @@ __device__ __forceinline__ uint64_t add_bits(uint64_t c, double w) {   // fl(c +
     return (uint64_t)__double_as_longlong(__longlong_as_double((long long)c) + w);
 }
 
-// the space's own distance: DIM = 0 is SO(3) (4 components), else R^DIM -- the bits of oxhip_distance_batch / oxhip_so3_op_batch op 0
+// the space's own distance between two rows (SeqSpace<DIM>::distance: the bits of oxhip_distance_batch / oxhip_so3_op_batch op 0)
 template <int DIM>
-__device__ __forceinline__ double space_distance(const double* __restrict__ a, const double* __restrict__ b) {
-    constexpr int W = DIM == 0 ? 4 : DIM;
-    double x[W], y[W];
-#pragma unroll
-    for (int k = 0; k < W; ++k) { x[k] = a[k]; y[k] = b[k]; }
-    if constexpr (DIM == 0) return so3_distance(x, y);
-    else return sqrt(dist2<W>(x, y, W));
+__device__ __forceinline__ double row_distance(const double* __restrict__ a, const double* __restrict__ b) {
+    double x[SeqSpace<DIM>::W], y[SeqSpace<DIM>::W];
+    SeqSpace<DIM>::load(a, x);
+    SeqSpace<DIM>::load(b, y);
+    return SeqSpace<DIM>::distance(x, y);
 }
 
 }  // namespace
@@ -64,16 +58,11 @@ template <int DIM>
 __global__ __launch_bounds__(256) void prm_shortest_weights_kernel(const double* __restrict__ ms, const uint32_t* __restrict__ offsets,
                                                                    const uint32_t* __restrict__ nbrs, uint32_t n, uint32_t n_entries,
                                                                    double* __restrict__ w) {
-    constexpr uint32_t W = DIM == 0 ? 4 : DIM;
+    constexpr uint32_t W = SeqSpace<DIM>::W;
     const uint32_t e = blockIdx.x * 256 + threadIdx.x;
     if (e >= n_entries) return;
-    uint32_t lo = 0, hi = n;                       // the row u of entry e: the largest u with offsets[u] <= e
-    while (hi - lo > 1u) {
-        const uint32_t mid = lo + (hi - lo) / 2u;
-        if (offsets[mid] <= e) lo = mid; else hi = mid;
-    }
-    const uint32_t v = nbrs[e];
-    w[e] = space_distance<DIM>(ms + (size_t)lo * W, ms + (size_t)v * W);
+    const uint32_t u = row_of(offsets, n, e), v = nbrs[e];
+    w[e] = row_distance<DIM>(ms + (size_t)u * W, ms + (size_t)v * W);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -81,7 +70,7 @@ __global__ __launch_bounds__(256) void prm_shortest_weights_kernel(const double*
 
 template <int DIM>
 __global__ __launch_bounds__(256) void prm_shortest_init_kernel(PrmBatchArgs b, PrmShortestArgs a) {
-    constexpr uint32_t W = DIM == 0 ? 4 : DIM;
+    constexpr uint32_t W = SeqSpace<DIM>::W;
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     const uint32_t c = blockIdx.y;
     if (i >= b.n) return;
@@ -89,7 +78,7 @@ __global__ __launch_bounds__(256) void prm_shortest_init_kernel(PrmBatchArgs b, 
     uint64_t l = kInfBits;
     if (b.flags[at] & 1u) {
         double d = a.mode == 1u ? 1.0 : 0.0;
-        if (a.mode == 0u) d = space_distance<DIM>(b.starts + ((size_t)b.q0 + c) * W, b.ms + (size_t)i * W);
+        if (a.mode == 0u) d = row_distance<DIM>(b.starts + ((size_t)b.q0 + c) * W, b.ms + (size_t)i * W);
         l = (uint64_t)__double_as_longlong(d);
     }
     a.label[at] = l;
@@ -273,21 +262,6 @@ __global__ __launch_bounds__(kThreads) void prm_shortest_levels_kernel(PrmBatchA
 
 // ------------------------------------------------------------------------------------------------
 // launchers
-
-template <typename F>
-static void space_dispatch(bool so3, uint32_t dim, F&& f) {
-    if (so3) { f(std::integral_constant<int, 0>{}); return; }
-    switch (dim) {
-        case 1: f(std::integral_constant<int, 1>{}); break;
-        case 2: f(std::integral_constant<int, 2>{}); break;
-        case 3: f(std::integral_constant<int, 3>{}); break;
-        case 4: f(std::integral_constant<int, 4>{}); break;
-        case 5: f(std::integral_constant<int, 5>{}); break;
-        case 6: f(std::integral_constant<int, 6>{}); break;
-        case 7: f(std::integral_constant<int, 7>{}); break;
-        default: f(std::integral_constant<int, 8>{}); break;
-    }
-}
 
 void launch_prm_shortest_weights(bool so3, uint32_t dim, const double* ms, const uint32_t* offsets, const uint32_t* nbrs, uint32_t n,
                                  uint32_t n_entries, double* w, hipStream_t s) {

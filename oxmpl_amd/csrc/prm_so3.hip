@@ -11,12 +11,13 @@
 //        the reference's binary64 dot (4 mul + 3 add, unfused), then distance < r decided by bands of |dot| computed on the
 //        host (above hi: in, below lo: out, in between: so3_distance itself, ox_acos included)
 //   3. prm_so3_edge_kernel    check_motion(m_j -> m_i) per candidate (so3_interpolate), cones in LDS; both directed keys
-//   4. prm_so3_query_kernel   start validity, start connections, goal milestones (prm.rs:243-264)
+// The query sets are prm_kernels.hip's prm_query_kernel over SeqSpace<0> (seq_space.hpp).
 // The keys go through prm_kernels.hip's sort and CSR extraction, so every node's `edges` list ends up ascending.
 #include "oxhip_internal.hpp"
 #include "rrt_device.hpp"
 #include "so3_device.hpp"
-#include "so3_motion_seq.hpp"
+#include "prm_stage.hpp"
+#include "seq_space.hpp"
 
 namespace oxhip {
 
@@ -156,30 +157,10 @@ constexpr int kSo3PairThreads = 256;
 constexpr int kSo3PairR = 4;                                   // milestones j held in registers per thread
 constexpr int kSo3PairJB = kSo3PairThreads * kSo3PairR;        // j per workgroup
 constexpr int kSo3PairIC = 256;                                // i per workgroup
-constexpr int kSo3Stage = 512;                                 // per-wave LDS staging of hits
-
-struct So3Stage {
-    uint2* buf;
-    uint32_t cnt;   // wave-uniform
-};
-
-// one global atomic per flush (a counter bumped per hit serialises at the L2)
-__device__ __forceinline__ void so3_stage_flush(const PrmArgs& a, So3Stage& st, uint32_t lane) {
-    if (st.cnt == 0) return;
-    unsigned long long base = 0;
-    if (lane == 0) base = atomicAdd(&a.state->n_cand, (unsigned long long)st.cnt);
-    base = uni64(base);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    for (uint32_t e = lane; e < st.cnt; e += 64) {
-        const unsigned long long slot = base + e;
-        if (slot < (unsigned long long)a.cand_cap) a.cand[slot] = st.buf[e];
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    st.cnt = 0;
-}
+                                                               // (the hits' staging in LDS and its flush: prm_stage.hpp)
 
 template <bool DIAG>
-__device__ __forceinline__ void so3_pairs_range(const PrmArgs& a, So3Stage& st, uint32_t lane, const double (&cj)[kSo3PairR][4],
+__device__ __forceinline__ void so3_pairs_range(const PrmArgs& a, PairStage& st, uint32_t lane, const double (&cj)[kSo3PairR][4],
                                                 const uint32_t (&jr)[kSo3PairR], const double* __restrict__ ms, uint32_t lo_i,
                                                 uint32_t hi_i, double lo, double hi, double r) {
     for (uint32_t i = lo_i; i < hi_i; ++i) {
@@ -213,14 +194,14 @@ __device__ __forceinline__ void so3_pairs_range(const PrmArgs& a, So3Stage& st, 
                 if (in[q]) st.buf[st.cnt + (uint32_t)__popcll(m & below_mask(lane))] = make_uint2(jr[q], i);
                 st.cnt += (uint32_t)__popcll(m);
             }
-            if (st.cnt > (uint32_t)(kSo3Stage - 64 * kSo3PairR)) so3_stage_flush(a, st, lane);   // room for one more i
+            if (st.cnt > (uint32_t)(kStage - 64 * kSo3PairR)) stage_flush(a, st, lane);   // room for one more i
         }
     }
 }
 
 __global__ __launch_bounds__(kSo3PairThreads) void prm_so3_pairs_kernel(PrmArgs a, const double* __restrict__ ms, uint32_t j0, uint32_t j1,
                                                                          double lo, double hi, double r) {
-    __shared__ uint2 stage[kSo3PairThreads / 64][kSo3Stage];
+    __shared__ uint2 stage[kSo3PairThreads / 64][kStage];
     const uint32_t tid = threadIdx.x, lane = tid & 63;
     const uint32_t jb0 = j0 + blockIdx.y * kSo3PairJB;
     const uint32_t jb1 = jb0 + kSo3PairJB < j1 ? jb0 + kSo3PairJB : j1;
@@ -235,11 +216,11 @@ __global__ __launch_bounds__(kSo3PairThreads) void prm_so3_pairs_kernel(PrmArgs 
 #pragma unroll
         for (int k = 0; k < 4; ++k) cj[q][k] = jr[q] < jb1 ? ms[(size_t)jr[q] * 4 + k] : __builtin_nan("");
     }
-    So3Stage st{stage[tid >> 6], 0u};
+    PairStage st{stage[tid >> 6], 0u};
     const uint32_t i_mid = i_hi < jb0 ? i_hi : (i_lo > jb0 ? i_lo : jb0);
     so3_pairs_range<false>(a, st, lane, cj, jr, ms, i_lo, i_mid, lo, hi, r);
     so3_pairs_range<true>(a, st, lane, cj, jr, ms, i_mid, i_hi, lo, hi, r);
-    so3_stage_flush(a, st, lane);
+    stage_flush(a, st, lane);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -280,34 +261,7 @@ __global__ __launch_bounds__(256) void prm_so3_edge_kernel(So3Cones p, const uin
         }
         ok = so3_motion_valid_seq(cc, stride, cr, nc, from, to, p.res);
     }
-    const uint64_t bal = __ballot(ok);
-    if (bal == 0) return;
-    uint32_t base = 0;
-    if (lane == 0) base = atomicAdd(n_keys, 2u * (uint32_t)__popcll(bal));
-    base = uni(base);
-    if (ok) {
-        const uint32_t slot = base + 2u * (uint32_t)__popcll(bal & below_mask(lane));
-        keys[slot] = ((uint64_t)pr.x << key_shift) | pr.y;       // i in j's list
-        keys[slot + 1] = ((uint64_t)pr.y << key_shift) | pr.x;   // j in i's list (prm.rs:143-145)
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// 4. query (prm.rs:243-264): start validity, start connections, goal milestones
-
-__global__ __launch_bounds__(256) void prm_so3_query_kernel(So3Cones p, const double* __restrict__ ms, uint32_t n, PrmQuery q, double r,
-                                                             uint8_t* flags, uint32_t* start_valid) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    const double s[4] = {q.start[0], q.start[1], q.start[2], q.start[3]};
-    const double g[4] = {q.goal_c[0], q.goal_c[1], q.goal_c[2], q.goal_c[3]};
-    const uint32_t nc = p.n;
-    if (i == 0) *start_valid = so3_cone_hit(p.c, nc, p.r, nc, s) ? 0u : 1u;   // prm.rs:244
-    if (i >= n) return;
-    const double m[4] = {ms[(size_t)i * 4], ms[(size_t)i * 4 + 1], ms[(size_t)i * 4 + 2], ms[(size_t)i * 4 + 3]};
-    uint8_t f = 0;
-    if (so3_distance(s, m) < r && so3_motion_valid_seq(p.c, nc, p.r, nc, s, m, p.res)) f |= 1;   // prm.rs:251-252
-    if (so3_distance(m, g) <= q.goal_thr) f |= 2;   // goal.is_satisfied: distance(state, target) <= radius (prm.rs:261)
-    flags[i] = f;
+    append_edge_keys(ok, pr.x, pr.y, keys, n_keys, key_shift, lane);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -331,7 +285,7 @@ void launch_prm_so3_pairs(const PrmArgs& a, uint32_t j0, uint32_t j1, double lo,
 void launch_prm_so3_edges(const DevParams& p, const PrmArgs& a, uint32_t n_cand, hipStream_t s) {
     if (n_cand == 0) return;
     const uint32_t shift = prm_key_shift(a.cap);
-    const So3Cones cones{p.sph_c, p.sph_r, p.n_spheres, p.res};
+    const So3Cones cones = SeqSpace<0>::checker(p);
     uint32_t* n_keys = &a.state->n_keys;
     if (p.n_spheres <= (uint32_t)kSo3LdsCones)
         hipLaunchKernelGGL(prm_so3_edge_kernel<true>, dim3((n_cand + 255) / 256), dim3(256), 0, s, cones, (const uint2*)a.cand,
@@ -339,13 +293,6 @@ void launch_prm_so3_edges(const DevParams& p, const PrmArgs& a, uint32_t n_cand,
     else
         hipLaunchKernelGGL(prm_so3_edge_kernel<false>, dim3((n_cand + 255) / 256), dim3(256), 0, s, cones, (const uint2*)a.cand,
                            (const double*)a.ms, a.keys, n_keys, n_cand, shift);
-}
-
-void launch_prm_so3_query(const DevParams& p, const PrmArgs& a, uint32_t n, const PrmQuery& q, double r, uint8_t* flags,
-                          uint32_t* start_valid, hipStream_t s) {
-    const uint32_t blocks = n ? (n + 255) / 256 : 1;
-    const So3Cones cones{p.sph_c, p.sph_r, p.n_spheres, p.res};
-    hipLaunchKernelGGL(prm_so3_query_kernel, dim3(blocks), dim3(256), 0, s, cones, (const double*)a.ms, n, q, r, flags, start_valid);
 }
 
 }  // namespace oxhip

@@ -108,8 +108,8 @@ def test_prm_batch_kernels_resource_shape(tmp_path):
                            "-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, "prm_batch.hip")], stderr=subprocess.DEVNULL)
     kernels = _kernels(open(out).read())
     names = sorted(kernels)
-    assert sum("prm_batch_flags_kernel" in k for k in names) == 8          # dim 1 .. 8
-    assert sum("prm_batch_so3_flags_kernel" in k for k in names) == 1
+    assert sum("prm_batch_flags_kernel" in k for k in names) == 9          # dim 1 .. 8, and DIM = 0:
+    assert sum("prm_batch_flags_kernelILi0E" in k for k in names) == 1     # SO(3)
     assert sum("prm_batch_search_kernel" in k for k in names) == 10        # 4, 8, 16, 32, 64 lanes per level node x visited bits in LDS or not
     assert sum("prm_batch_paths_kernel" in k for k in names) == 1
     assert len(names) == 20

@@ -89,8 +89,9 @@ def test_prm_revalidate_kernels_resource_shape(tmp_path):
                            "-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, "prm_revalidate.hip")], stderr=subprocess.DEVNULL)
     meta = _kernel_metadata(open(out).read())
     own = {k: m for k, m in meta.items() if "prm_plant_" in k or "prm_reval_" in k}   # (the rest are the scan library's)
-    for family, count in (("prm_plant_offsets_kernel", 1), ("prm_plant_entries_kernel", 1), ("prm_reval_valid_kernel", 8),
-                          ("prm_reval_so3_valid_kernel", 1), ("prm_reval_emit_kernel", 1), ("prm_reval_check_kernel", 8),
+    for family, count in (("prm_plant_offsets_kernel", 1), ("prm_plant_entries_kernel", 1),
+                          ("prm_reval_valid_kernel", 9), ("prm_reval_valid_kernelILi0E", 1),   # R^1 .. R^8 and DIM = 0: SO(3)
+                          ("prm_reval_emit_kernel", 1), ("prm_reval_check_kernel", 8),
                           ("prm_reval_keys_kernel", 1), ("prm_reval_mirror_kernel", 1), ("prm_reval_compact_kernel", 1)):
         assert sum(1 for k in own if family in k) == count, (family, sorted(own))
     assert len(own) == 23

@@ -29,7 +29,7 @@ def random_csr(rnd, n, p, hub=None):
 
 
 def row_of(offsets, n, e):
-    """reval_row_of: the last u with offsets[u] <= e"""
+    """row_of (prm_csr.hpp): the last u with offsets[u] <= e"""
     lo, hi = 0, n
     while hi - lo > 1:
         mid = lo + ((hi - lo) >> 1)
@@ -41,7 +41,7 @@ def row_of(offsets, n, e):
 
 
 def find(offsets, nbrs, row, want):
-    """reval_find: the entry of `row` that holds `want`"""
+    """row_find (prm_csr.hpp): the entry of `row` that holds `want`"""
     lo, hi = offsets[row], offsets[row + 1]
     while lo < hi:
         mid = lo + ((hi - lo) >> 1)

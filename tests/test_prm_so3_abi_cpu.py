@@ -130,9 +130,13 @@ def test_prm_so3_kernels_have_no_scratch_and_no_flat_loads(tmp_path):
     out = str(tmp_path / "prm_so3.s")
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
                            "-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, "prm_so3.hip")], stderr=subprocess.DEVNULL)
-    asm = open(out).read()
-    meta = {k: v for k, v in _kernels(asm).items() if "prm_so3_" in k}
-    for part in ("sample_spec", "sample_scan", "sample_compact", "pairs_kernel", "edge_kernelILb1", "edge_kernelILb0", "query_kernel"):
+    # the query kernel over SO(3) is prm_kernels.hip's prm_query_kernel<0> (seq_space.hpp): judged here with the file's own
+    out_q = str(tmp_path / "prm_kernels.s")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
+                           "-S", "--cuda-device-only", "-o", out_q, os.path.join(CSRC, "prm_kernels.hip")], stderr=subprocess.DEVNULL)
+    asm = open(out).read() + open(out_q).read()
+    meta = {k: v for k, v in _kernels(asm).items() if "prm_so3_" in k or "prm_query_kernelILi0E" in k}
+    for part in ("sample_spec", "sample_scan", "sample_compact", "pairs_kernel", "edge_kernelILb1", "edge_kernelILb0", "query_kernelILi0E"):
         assert any(part in k for k in meta), part
     for name, m in meta.items():
         assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0, (name, m)

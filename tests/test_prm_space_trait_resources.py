@@ -1,0 +1,76 @@
+"""CPU: the PRM / path kernels written once over SeqSpace<DIM> (oxmpl_amd/csrc/seq_space.hpp), compiled to gfx950 ISA (no GPU
+needed): one kernel template per role, instantiated for R^1..R^8 and SO(3) (DIM = 0), no spill to scratch, no LDS, and no
+instantiation needs more registers or spills more SGPRs than the hand-copied kernels it replaced.  The literals are the figures
+of the commit before the trait, cross-compiled with the Makefile's flags; columns are D = 1..8, then SO(3)."""
+import os
+import re
+import subprocess
+
+import pytest
+
+from test_kernel_resources import CSRC, HIPCC, _kernels
+
+SOURCES = ["prm_kernels.hip", "prm_batch.hip", "prm_revalidate.hip", "path_simplify.hip", "prm_shortest.hip"]
+DIMS = [1, 2, 3, 4, 5, 6, 7, 8, 0]
+
+# kernel -> (vgpr_count, sgpr_spill_count) per D of DIMS; None: no such instantiation (no caller reaches it)
+BEFORE = {
+    "prm_query_kernel": ([28, 36, 46, 56, 66, 76, 86, 97, 85], [0, 0, 0, 4, 8, 47, 73, 117, 16]),
+    "prm_batch_flags_kernel": ([28, 36, 46, 56, 66, 76, 87, 97, 85], [0, 0, 0, 8, 35, 58, 102, 122, 24]),
+    "prm_reval_valid_kernel": ([18, 26, 32, 38, 44, 44, 60, 68, 40], [0] * 9),
+    "prm_reval_check_kernel": ([40, 48, 58, 68, 78, 88, 98, 110, None], [0] * 8 + [None]),   # SO(3) re-checks through prm_so3_edge_kernel
+    "path_pairs_kernel": ([None, 36, 46, 56, 66, 77, 87, 97, 93], [None, 0, 0, 0, 0, 11, 30, 64, 6]),   # an RRT batch has dim >= 2
+    "prm_shortest_weights_kernel": ([12, 14, 18, 22, 26, 30, 34, 38, 24], [0] * 9),
+    "prm_shortest_init_kernel": ([12, 12, 12, 12, 15, 16, 19, 20, 24], [0] * 9),
+}
+
+
+@pytest.fixture(scope="module")
+def trait_kernels(tmp_path_factory):
+    """mangled name -> metadata of every kernel of the five sources (compiled side by side)"""
+    d = tmp_path_factory.mktemp("asm_space_trait")
+    procs = []
+    for src in SOURCES:
+        out = str(d / (src[:-4] + ".s"))
+        procs.append((out, subprocess.Popen([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
+                                             "-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, src)], stderr=subprocess.DEVNULL)))
+    meta = {}
+    for out, p in procs:
+        assert p.wait() == 0, out
+        meta.update(_kernels(open(out).read()))
+    return meta
+
+
+def _instantiations(meta, kernel):
+    """D -> metadata of kernel<D>"""
+    found = {}
+    for name, m in meta.items():
+        hit = re.search(r"\d+" + kernel + r"ILi(\d+)EEE", name)
+        if hit:
+            assert int(hit.group(1)) not in found, name
+            found[int(hit.group(1))] = m
+    return found
+
+
+@pytest.mark.parametrize("kernel", sorted(BEFORE))
+def test_one_template_per_role_within_the_figures_before_the_trait(trait_kernels, kernel):
+    vgpr, spill = BEFORE[kernel]
+    inst = _instantiations(trait_kernels, kernel)
+    assert sorted(inst) == sorted(d for d, v in zip(DIMS, vgpr) if v is not None)      # 9 instantiations (8: see BEFORE)
+    for d, v, s in zip(DIMS, vgpr, spill):
+        if v is None:
+            continue
+        m = inst[d]
+        assert m["vgpr_spill_count"] == 0 and m["private_segment_fixed_size"] == 0 and m["group_segment_fixed_size"] == 0, (kernel, d, m)
+        assert m["vgpr_count"] <= v and m["sgpr_spill_count"] <= s, (kernel, d, m, v, s)
+        if kernel.startswith("prm_reval"):
+            assert m["sgpr_spill_count"] == 0, (kernel, d, m)                          # the obstacle tables' pointers travel in VGPRs
+
+
+def test_no_hand_copied_so3_twin_is_left(trait_kernels):
+    for name in trait_kernels:
+        for gone in ("so3_query", "so3_flags", "so3_valid", "pairs_so3"):
+            assert gone not in name, name
+    for kernel in BEFORE:   # and no second kernel of the role under another name: every symbol of the role is the template's
+        names = [n for n in trait_kernels if kernel in n]
+        assert len(names) == len(_instantiations(trait_kernels, kernel)), names
