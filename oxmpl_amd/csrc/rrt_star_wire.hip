@@ -66,7 +66,7 @@ __global__ __launch_bounds__(kPairThreads, 8) void star_pairs_kernel(DevParams p
     // the counting pass also keeps what it finds: a lane collects its hits in LDS and writes them out 32 at a time as a chunk
     // (owner node, ordinal, 32 neighbour indices) wherever the problem's chunk cursor points; when all of a round's pending
     // nodes fit (the usual case) the edge kernel builds the lists from the chunks and the second search (FILL) is not run
-    __shared__ uint16_t hitbuf[FILL ? 1 : kChunk][FILL ? 1 : kPairThreads];   // (node indices fit 16 bits: the lane-per-query kernel holds at most 20,480 nodes)
+    __shared__ uint16_t hitbuf[FILL ? 1 : kChunk][FILL ? 1 : kPairThreads];   // (node indices fit 16 bits: the larger geometry kernel's limit, cells_supported, is a capacity of 65,535)
     const uint32_t prob = blockIdx.y;
     const uint32_t n = p.state[prob].n_nodes;
     const uint32_t w0 = p.wired[prob];

@@ -2,7 +2,11 @@
 fixtures: node count, iteration count, checksum (iteration polynomial over nearest / q_new / verdict + wiring polynomial over
 chosen parent / cost bits / rewired count and index sum), tree bits, parents after rewiring, costs, path.
 Every test runs on the designs "decoupled" (geometry by rrt_cells.hip or rrt_lanes.hip, wiring by rrt_star_wire.hip) and
-"one_kernel" (KERNEL_STREAM: rrt_star.hip).  PARITY UNPINNED against oxmpl itself."""
+"one_kernel" (KERNEL_STREAM: rrt_star.hip).  PARITY UNPINNED against oxmpl itself.
+These are the golden scenes (R^2, R^3, at most 64 spheres) and what derives from them.  Dimensions 1 and 4 .. 8, rewiring and refused
+neighbour motions in every dimension, exact cost ties, spheres beyond the 64th next to a box, batches whose problems differ and node
+indices beyond 2^15 are tests/test_gpu_rrt_star_limits.py's, on the scenes of tests/rrt_star_limits_shapes.py (held on the CPU by
+tests/test_rrt_star_limits_model.py), through the same assert_same contract."""
 import json
 import os
 
