@@ -428,14 +428,15 @@ __global__ __launch_bounds__(kPairThreads) void prm_pairs_kernel(PrmArgs a, cons
 #pragma unroll
         for (int k = 0; k < DIM; ++k) cj32[r2][k] = pair_f32x2{(float)cj[2 * r2][k], (float)cj[2 * r2 + 1][k]};
     // the radius rule has one threshold for every pair; the k-nearest variant's candidate search gives every row j its own
-    // (thr_row[j]: a radius expected to hold several times k earlier milestones)
+    // (thr_row[j]: a radius expected to hold several times k earlier milestones).  A slot beyond the range takes no pair under
+    // either rule: its d2 is +inf, which the +inf that the k-nearest search passes as thr_all would admit
     double thr[kPairR];
     float thr32[kPairR];
 #pragma unroll
     for (int r = 0; r < kPairR; ++r) {
-        const bool row = thr_row != nullptr && jr[r] < jb1;
-        thr[r] = row ? thr_row[jr[r]] : thr_all;
-        thr32[r] = row ? thr32_row[jr[r]] : thr32_all;
+        const bool mine = jr[r] < jb1, row = thr_row != nullptr && mine;
+        thr[r] = !mine ? -1.0 : row ? thr_row[jr[r]] : thr_all;
+        thr32[r] = !mine ? -1.0f : row ? thr32_row[jr[r]] : thr32_all;
     }
     PairStage st{stage[tid >> 6], 0u};
     // i below every j of the block: no index test; the rest of the range (the diagonal blocks) tests i < j

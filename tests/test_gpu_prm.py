@@ -7,49 +7,14 @@ PARITY UNPINNED against oxmpl itself (no reference-held vectors; the reference c
 import numpy as np
 import pytest
 
-from helpers import unhex, bits, params_spheres, params_boxes, is_path_valid
-from prm_helpers import csr_checksum, states_checksum, make_oracle_prm, STATUS_NAME
+from helpers import unhex, bits, params_boxes, is_path_valid
+from prm_helpers import (csr_checksum, states_checksum, make_oracle_prm, make_gpu_prm, assert_same_roadmap,  # noqa: F401
+                         assert_same_query, STATUS_NAME)
 
 pytestmark = pytest.mark.gpu
 
 from oxmpl_amd import capi, scenarios  # noqa: E402
 from oracle import oracle_py as orc  # noqa: E402
-
-
-def make_gpu_prm(P, **kw):
-    args = dict(max_milestones=P["max_milestones"], lvs_fraction=P["fraction"], seed=P["seed"], stream=P["stream"],
-                max_samples=0 if P["max_samples"] >= 10 ** 9 else P["max_samples"])
-    args.update(kw)
-    g = capi.PRMRoadmap(P["dim"], P["bounds"], P["radius"], **args)
-    if P["spheres"]:
-        g.set_spheres(*params_spheres(P))
-    if P["boxes"]:
-        g.set_boxes(*params_boxes(P))
-    return g
-
-
-def assert_same_roadmap(g, o):
-    n, e, s = g.sizes()
-    assert n == o.num_milestones and s == o.num_samples
-    gs, goff, gn = g.roadmap()
-    os_, ooff, on = o.roadmap()
-    assert np.array_equal(bits(gs), bits(os_))
-    assert np.array_equal(goff, ooff)
-    assert np.array_equal(gn, on)
-    return gs, goff, gn
-
-
-def assert_same_query(g, o, timeout=0.0):
-    st, path = g.solve(timeout)
-    ost = o.solve()
-    assert st == ost
-    if st not in (capi.ERR_INVALID_START_STATE, capi.ERR_UNSAMPLED_STATE_SPACE, capi.ERR_PLANNER_UNINITIALISED):
-        sc, gi = g.query_sets()
-        assert np.array_equal(sc, o.start_connections())
-        assert np.array_equal(gi, o.goal_indices())
-    opath = o.path()
-    assert path.shape == opath.shape and np.array_equal(bits(path), bits(opath))
-    return st, path
 
 
 @pytest.mark.parametrize("key", ["wall", "r3", "r6", "sample_cap"])

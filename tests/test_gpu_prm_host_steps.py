@@ -1,6 +1,7 @@
 """GPU: what the PRM host loop alone decides (oxhip_prm_api.hip), against tests/golden/prm_host_counters.json, the counters the
 library of the commit named there reported for the same configs: milestones, edge entries, samples drawn, candidate pairs,
-replayed sample batches, k-nearest rows searched exactly; the rounds and statuses of a chunked batch.  Also the phase_ms slots
+replayed sample batches, k-nearest rows searched exactly; the rounds and statuses of a chunked batch (one counter corrected since:
+the file's "_corrected" entry, held to the oracle by tests/test_prm_limits_model.py).  Also the phase_ms slots
 and the handle-level refusals, whose texts are the literals of that commit's source."""
 import ctypes as C
 import json
