@@ -149,8 +149,10 @@ typedef enum oxhip_debug_flag {
     OXHIP_DEBUG_SE2_NO_SEGMENT_GRID = 128,/* rrt_connect_se2.hip / rrt_connect.hip: every interpolated state is tested against every segment / sphere (no grid lookup) */
     OXHIP_DEBUG_SE2_SMALL_LDS = 256,      /* rrt_connect_se2.hip: the shape for batches larger than the chip (512-node shadows, segments from HBM / L2) whatever the batch size */
     OXHIP_DEBUG_SO3_SERIAL_SAMPLER = 512, /* rrt_so3.hip, rrt_connect_se3.hip: sample_uniform attempt by attempt on one lane instead of 64 attempts side by side */
-    OXHIP_DEBUG_SE3_BRANCHY_SWEEP = 1024  /* rrt_connect_se3.hip: the motion check decides every (body sphere, obstacle) pair as it meets it (the first kernel's sweep)
+    OXHIP_DEBUG_SE3_BRANCHY_SWEEP = 1024, /* rrt_connect_se3.hip: the motion check decides every (body sphere, obstacle) pair as it meets it (the first kernel's sweep)
                                              instead of sweeping without a branch and deciding only the pairs it could not clear */
+    OXHIP_DEBUG_CELLS_NO_PACING = 2048    /* rrt_cells.hip, frozen launches: the waves report their progress to the board as always, but none changes its
+                                             issue priority by it (every wave stays at priority 0) */
 } oxhip_debug_flag;
 
 typedef enum oxhip_kernel_kind {
@@ -356,10 +358,22 @@ int32_t oxhip_rrt_batch_last_timing(oxhip_rrt_batch* b, double* kernel_ms, uint3
  * [54] too), [50] / [51] / [52] sum, bitwise complement of the minimum, and maximum of the lifetimes of all waves, in cycles,
  * [53] lanes offered minus iterations run (0 in a frozen launch), [45] and [54] ambiguous-query events (band or whole tree), [55] memo hits, [56] conflict
  * cuts, [59] forced cuts (OXHIP_DEBUG_ONE_LANE_ROUNDS), [60] shell searches (past the first ring of cells), [61] regrids
- * inside a growing launch (not the prepare pass's builds). */
+ * inside a growing launch (not the prepare pass's builds), [3] (OXHIP_STAMP_CELLS_BOARD; written by get_stamps, not summed over
+ * launches) the progress board of the last frozen launch as that launch left it, summed over the XCDs: every wave has reported
+ * its whole quota, so it equals the live problems times oxhip_cells_problem_quota. */
 #define OXHIP_STAMP_WORDS 64
+#define OXHIP_STAMP_CELLS_BOARD 3
 int32_t oxhip_rrt_batch_enable_stamps(oxhip_rrt_batch* b, uint32_t enable);
 int32_t oxhip_rrt_batch_get_stamps(oxhip_rrt_batch* b, uint64_t* out, uint32_t cap_words);
+
+/* rrt_cells.hip's frozen launches, host arithmetic only (no device is touched): how a launch of `rounds` rounds of 64 queries is
+ * cut into `split` parts (1 .. 64), and the progress units the pacing of the parts counts in -- 16 per round a part runs, 1 per
+ * round it skips over to reach its start (parts of a launch of up to 4 parts find their own starts).  part_begin: the first round
+ * of part `part` (`rounds` for part >= split); part_quota: the units part `part` reports in all (0 for part >= split);
+ * problem_quota: the parts' quotas together, which the launch hands to the kernel. */
+uint32_t oxhip_cells_part_begin(uint32_t rounds, uint32_t part, uint32_t split);
+uint64_t oxhip_cells_part_quota(uint32_t rounds, uint32_t part, uint32_t split);
+uint64_t oxhip_cells_problem_quota(uint32_t rounds, uint32_t split);
 
 /* ---- stand-alone batched primitives (same device functions as the planner kernels) ---- */
 

@@ -27,8 +27,10 @@ DEBUG_SE2_NO_SEGMENT_GRID = 128
 DEBUG_SE2_SMALL_LDS = 256
 DEBUG_SO3_SERIAL_SAMPLER = 512
 DEBUG_SE3_BRANCHY_SWEEP = 1024
+DEBUG_CELLS_NO_PACING = 2048
 ABI_VERSION = 2
 STAMP_WORDS = 64
+STAMP_CELLS_BOARD = 3
 PLANNER_RRT, PLANNER_RRT_CONNECT, PLANNER_RRT_STAR = 0, 1, 2
 SPACE_REAL_VECTOR, SPACE_SE2, SPACE_SO3, SPACE_SE3 = 0, 1, 2, 3
 SE3_MAX_BODY = 16
@@ -54,6 +56,7 @@ EXPORTS = [
     "oxhip_rrt_batch_extract_paths", "oxhip_rrt_batch_get_paths", "oxhip_rrt_batch_simplify_paths",
     "oxhip_rrt_batch_get_simplified_paths", "oxhip_rrt_batch_get_simplify_results", "oxhip_rrt_batch_path_valid_matrix",
     "oxhip_rrt_batch_paths_last_timing",
+    "oxhip_cells_part_begin", "oxhip_cells_part_quota", "oxhip_cells_problem_quota",
 ]
 
 
@@ -179,9 +182,15 @@ def lib():
         L.oxhip_rrt_batch_get_simplify_results.argtypes = [C.c_void_p, _dp, _dp, _u64p]
         L.oxhip_rrt_batch_path_valid_matrix.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, _u8p, C.c_uint64, _u32p]
         L.oxhip_rrt_batch_paths_last_timing.argtypes = [C.c_void_p, _dp, _dp, _dp, _u32p]
+        L.oxhip_cells_part_begin.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+        L.oxhip_cells_part_quota.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+        L.oxhip_cells_problem_quota.argtypes = [C.c_uint32, C.c_uint32]
         for name in EXPORTS:
             if name not in ("oxhip_status_string", "oxhip_last_error_string"):
                 getattr(L, name).restype = C.c_int32
+        L.oxhip_cells_part_begin.restype = C.c_uint32
+        L.oxhip_cells_part_quota.restype = C.c_uint64
+        L.oxhip_cells_problem_quota.restype = C.c_uint64
         _lib = L
     return _lib
 

@@ -66,6 +66,7 @@ struct oxhip_rrt_batch {
     // the one-problem Planner::solve pays for every one of them), carved at 256-byte boundaries
     DevBuf<uint8_t> cell_arena;
     CellMeta* cell_meta_p = nullptr;
+    int32_t cells_board_last = -1;  // parity of the last frozen cells launch (its progress board: get_stamps), -1: none yet
     uint64_t* sph_grid_p = nullptr;
     uint64_t* star_grid_p = nullptr;   // RRT*'s edge checks: the mask grid for motions up to search_radius long
     DevBuf<double> star_filt;
@@ -420,6 +421,7 @@ static int32_t alloc_cells(oxhip_rrt_batch* b) {
     size_t off = 0;
     auto carve = [&](size_t bytes) { const size_t at = off; off = (off + bytes + 255u) & ~(size_t)255u; return at; };
     const size_t o_meta = carve((size_t)P * sizeof(CellMeta)), o_acc = carve((size_t)P * sizeof(CellAcc));   // (zeroed together)
+    const size_t o_board = carve(2 * kCellsBoardWords * sizeof(uint64_t));   // the frozen launches' progress boards: zero before the first
     const size_t zero_bytes = off;
     const size_t o_pos = carve((size_t)P * 64 * sizeof(uint64_t)), o_grid = carve(grid_cells * sizeof(uint64_t));
     const size_t o_grid2 = carve(b->star_wired ? grid_cells * sizeof(uint64_t) : 0);
@@ -436,6 +438,8 @@ static int32_t alloc_cells(oxhip_rrt_batch* b) {
     dp.cell_xyz = reinterpret_cast<double*>(base + o_xyz); dp.cell_meta = b->cell_meta_p;
     dp.cell_acc = reinterpret_cast<CellAcc*>(base + o_acc); dp.cell_part_pos = reinterpret_cast<uint64_t*>(base + o_pos);
     dp.sph_grid = b->sph_grid_p;
+    dp.cell_board = reinterpret_cast<uint64_t*>(base + o_board);
+    dp.cells_parity = 0;
     return OXHIP_OK;
 }
 
@@ -923,7 +927,11 @@ static int32_t solve_real_vector(oxhip_rrt_batch* b) {
         OX_TRY(wire_new_nodes(b));
     }
     else if (b->cfg.planner == OXHIP_PLANNER_RRT_STAR) launch_rrt_star(b->dp, b->stream);
-    else if (kind == OXHIP_KERNEL_CELLS) { launch_rrt_cells(b->dp, b->stream); b->dp.cells_meta_ok = 1; }
+    else if (kind == OXHIP_KERNEL_CELLS) {
+        launch_rrt_cells(b->dp, b->stream);
+        b->dp.cells_meta_ok = 1;
+        if (b->dp.freeze) { b->cells_board_last = (int32_t)b->dp.cells_parity; b->dp.cells_parity ^= 1u; }   // (the next frozen launch counts on the board this one cleared)
+    }
     else if (kind == OXHIP_KERNEL_LANES) launch_rrt_lanes(b->dp, b->stream);
     else if (kind == OXHIP_KERNEL_RESIDENT) launch_rrt_resident(b->dp, b->stream);
     else launch_rrt_stream(b->dp, b->stream);
@@ -1401,6 +1409,14 @@ int32_t oxhip_rrt_batch_get_stamps(oxhip_rrt_batch* b, uint64_t* out, uint32_t c
     const uint32_t n = cap_words < OXHIP_STAMP_WORDS ? cap_words : OXHIP_STAMP_WORDS;
     if (n) HIP_TRY(hipMemcpyAsync(out, b->dbg.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
+    if (n > OXHIP_STAMP_CELLS_BOARD && b->dp.cell_board && b->cells_board_last >= 0) {
+        // rrt_cells.hip: what the last frozen launch's progress board holds, summed over the XCDs
+        std::vector<uint64_t> board(kCellsBoardWords);
+        HIP_TRY(hipMemcpy(board.data(), b->dp.cell_board + (size_t)b->cells_board_last * kCellsBoardWords, kCellsBoardWords * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        uint64_t sum = 0;
+        for (uint32_t x = 0; x < 8; ++x) sum += board[x * (kCellsBoardWords / 8)];
+        out[OXHIP_STAMP_CELLS_BOARD] = sum;
+    }
     return OXHIP_OK;
 }
 

@@ -553,6 +553,35 @@ __host__ __device__ __forceinline__ uint32_t cells_part_begin(uint32_t rounds, u
     for (uint32_t i = 0; i < split; ++i) { full *= ci; keep_s *= ci - 1u; keep_p *= i < part ? ci - 1u : ci; }
     return (uint32_t)(((uint64_t)rounds * (full - keep_p)) / (full - keep_s));
 }
+// PACING of a frozen launch.  Its waves start together, three to a SIMD, and none is backfilled; between waves of equal priority
+// the SIMD issues the oldest first, so on every SIMD one wave ran ahead and left early and the youngest ran the last stretch
+// alone.  Every wave therefore reports its progress to a board -- one counter per XCD (DevParams::cell_board) -- and takes its
+// issue priority from where it stands against the XCD's mean: behind it, priority 2; ahead of it, 0; else 1.  Waves that all
+// track their XCD's mean fraction stay in step with their SIMD mates too, whom they cannot see.  Nothing ever waits for the board:
+// a stale or wrong value costs time at worst.
+// The unit of progress is 1 / OXHIP_CELLS_SKIP_COST_INV of a round: a round run counts OXHIP_CELLS_SKIP_COST_INV, a round a part
+// skips on the way to its start (cells_part_begin) counts 1.  A part's quota -- what it has reported when it exits:
+__host__ __device__ __forceinline__ uint64_t cells_part_quota(uint32_t rounds, uint32_t part, uint32_t split) {
+    if (part >= split) return 0;
+    const uint32_t begin = cells_part_begin(rounds, part, split), end = cells_part_begin(rounds, part + 1u, split);
+    const uint64_t skipped = split > 1u && split <= kSelfSkipMax ? begin : 0u;   // (more parts: cells_prepare_kernel finds the starts)
+    return (uint64_t)(end - begin) * OXHIP_CELLS_SKIP_COST_INV + skipped;
+}
+// ... and the quotas of a problem's parts together (the host, per launch: DevParams::cells_quota)
+__host__ __device__ __forceinline__ uint64_t cells_problem_quota(uint32_t rounds, uint32_t split) {
+    uint64_t sum = 0;
+    for (uint32_t part = 0; part < split; ++part) sum += cells_part_quota(rounds, part, split);
+    return sum;
+}
+#ifndef OXHIP_CELLS_PACE_BAND
+#define OXHIP_CELLS_PACE_BAND OXHIP_CELLS_SKIP_COST_INV   // the dead band, in units: one round (measured against a half and a quarter: profiles/frozen_pacing/)
+#endif
+#ifndef OXHIP_CELLS_PACE_BEHIND
+#define OXHIP_CELLS_PACE_BEHIND 2   // the priority of a wave that is behind its XCD's mean by more than the band (ahead: 0, else OXHIP_CELLS_PACE_LEVEL)
+#endif
+#ifndef OXHIP_CELLS_PACE_LEVEL
+#define OXHIP_CELLS_PACE_LEVEL 1
+#endif
 
 #ifndef OXHIP_CELLS_WAVES_PER_EU
 #define OXHIP_CELLS_WAVES_PER_EU 2
@@ -604,6 +633,16 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
     CellMeta& meta = p.cell_meta[live ? prob : 0u];
     CellGrid grid;
     grid_load<DIM>(meta, grid);
+    // pacing (the comment at cells_part_quota): the counter of this wave's XCD on the launch's board, the wave's quota and the
+    // XCD's (its live problems' quotas), the latter shifted down to 32 bits for the cross-products of the comparison
+    uint64_t* const pace_ctr = p.cell_board + (size_t)(p.cells_parity & 1u) * kCellsBoardWords + (size_t)xcd * (kCellsBoardWords / 8u);
+    uint32_t pace_quota = 0, pace_xcd = 0, pace_sent = 0;
+    if (FROZEN) {
+        if (live) pace_quota = (uint32_t)cells_part_quota(((uint32_t)p.budget + 63u) / 64u, part, split);
+        pace_xcd = (uint32_t)(((uint64_t)(p.n_problems > xcd ? (p.n_problems - xcd + 7u) / 8u : 0u) * p.cells_quota) >> p.cells_quota_shift);
+        // one lane per XCD clears the other board, which nobody counts on in this launch, for the next one
+        if (blockIdx.x < 8u && tid == 0) p.cell_board[(size_t)((p.cells_parity & 1u) ^ 1u) * kCellsBoardWords + (size_t)xcd * (kCellsBoardWords / 8u)] = 0;
+    }
     LMargins mg;
     {
         double h = (double)lbits_f32(uni(meta.mabs_bits)) * (1.0 + 0x1p-23);
@@ -618,7 +657,10 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
     }
     __syncthreads();   // the launch's only barrier: the obstacle tables are in LDS
     if (!live) return;
-    if (p.stop_at_goal && st0.goal_node >= 0) return;
+    if (p.stop_at_goal && st0.goal_node >= 0) {
+        if (FROZEN && lane == 0 && pace_quota != 0) __hip_atomic_fetch_add(pace_ctr, (uint64_t)pace_quota, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (its whole quota: the XCD's counts on it)
+        return;
+    }
 
     const size_t cap = p.cap;
     double* tree = p.tree + (size_t)prob * DIM * cap;
@@ -657,6 +699,7 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
         for (uint32_t r0 = 0; r0 < j_lo; r0 += 64u) cells_sample_block<DIM, false>(rng, p, goal_c, goal_radius, 64u, lane, sh, r0);
         pos_start = rng.pos;
     }
+    const uint32_t pace_skipped = split > 1 && split <= kSelfSkipMax ? j_lo / 64u : 0u;   // (reported with the first round)
     ProblemState st = st0;
     if (split > 1) { st.checksum = 0; st.accepted = 0; st.iterations = 0; }   // this part's own sums (combined at the end)
     uint64_t draws_done = pos_start;
@@ -1002,6 +1045,35 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
         // the screen's own claim, checked on the binary64 value (turns a corrupted record into an unproven lane)
         bool clear = nearest != kNoNode && fabs(sqrt(g) * grid.inv_h - sqrt((double)t2.s1)) <= A + sqrt((double)t2.s1) * 0x1p-19 + 1e-30;
         if (p.dbg_flags & OXHIP_DEBUG_ALL_WHOLE_TREE) clear = false;   // (tests: no screen verdict is trusted)
+        // pacing: lane 0 reports the units done since the last report -- one returning atomic -- and the wave takes its priority from
+        // what comes back.  Returns come in order, so a load issued before the atomic and used after it waits for the atomic as well:
+        // it is issued behind the first use of the winners' coordinates and read behind the round's next wait, the midpoint filter's
+        // lookup, with the steer in between.  (In front of the round's first cell loads it would also hold two registers across four
+        // cell blocks in flight, which spills inside the round; read any later than the lookup, it spills there too.)
+        uint64_t pace_seen = 0;
+        auto pace_report = [&]() {
+            const uint32_t now = pace_skipped + (uint32_t)(((uint64_t)jr * OXHIP_CELLS_SKIP_COST_INV) >> 6);
+            // (through an opaque vector offset of 0: for an address it can prove wave-uniform the compiler rewrites the atomic into
+            //  one that hands its result to every lane -- and waits for it on the spot)
+            uint32_t zv = 0;
+            asm volatile("" : "+v"(zv));
+            if (lane == 0) pace_seen = __hip_atomic_fetch_add(pace_ctr + zv, (uint64_t)(now - pace_sent), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            pace_sent = now;
+        };
+        // own fraction done against the XCD's, cross-multiplied: clearly behind -> this wave issues first, clearly ahead -> last.
+        // (Wave-uniform: each s_setprio stands alone under a scalar branch.)
+        auto pace_apply = [&]() {
+            if ((p.dbg_flags & OXHIP_DEBUG_CELLS_NO_PACING) != 0) return;
+            uint32_t seen_lo = (uint32_t)pace_seen, seen_hi = (uint32_t)(pace_seen >> 32);
+            asm volatile("" : "+v"(seen_lo), "+v"(seen_hi));   // (read here, not where the atomic is issued)
+            const uint64_t seen = ((uint64_t)uni(seen_hi) << 32) | uni(seen_lo);
+            const uint64_t mean = (seen >> p.cells_quota_shift) * pace_quota, own = (uint64_t)pace_sent * pace_xcd;
+            const uint64_t band = (uint64_t)OXHIP_CELLS_PACE_BAND * pace_xcd;
+            if (own + band < mean) __builtin_amdgcn_s_setprio(OXHIP_CELLS_PACE_BEHIND);
+            else if (own > mean + band) __builtin_amdgcn_s_setprio(0);
+            else __builtin_amdgcn_s_setprio(OXHIP_CELLS_PACE_LEVEL);
+        };
+        if constexpr (FROZEN) pace_report();
         if (from_memo) {   // the whole-tree path's last answer, for this very query on this very tree
             nearest = memo_idx;
             g = memo_g;
@@ -1058,11 +1130,14 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
                 const uint64_t m = p.sph_grid[D == 3 ? (ci[2] * p.sph_grid_G + ci[1]) * p.sph_grid_G + ci[0] : ci[1] * p.sph_grid_G + ci[0]];
                 cand = inside ? m : ~0ull;
             }
+            if constexpr (FROZEN) pace_apply();
             if (ns64 < 64) cand &= (1ull << ns64) - 1ull;
             const uint64_t maybe = spheres_maybe_hit<D>(shared.obs, cand, mid);   // (the binary64 filter)
             OXHIP_CPHASE(2);   // sphere filter
             const bool need = !(OXHIP_ABLATE & 4) && act && !amb && (maybe != 0 || extras);
             bad = motion_own_lane_short<D>(p, shared.obs, shared.steps, need, maybe, q_near, qn, ns64, nobs);
+        } else {
+            if constexpr (FROZEN) pace_apply();
         }
         OXHIP_CPHASE(3);   // motion check
         bool ok = act && !bad;
@@ -1376,6 +1451,8 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
     }
 #undef OXHIP_CPHASE
     if (!FROZEN) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");   // (a frozen launch has stored nothing)
+    // pacing: what is left of the quota (the last round's units; all of it when the part had no round)
+    if (FROZEN && lane == 0 && pace_quota != pace_sent) __hip_atomic_fetch_add(pace_ctr, (uint64_t)(pace_quota - pace_sent), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (split > 1) {
         // this part's sums into the problem's accumulator; the last part to arrive writes the state.
         // H_final = H0 P^N + sum_parts Hpart P^(N - j_hi)
@@ -1544,8 +1621,14 @@ uint32_t cells_head_blocks(uint32_t dim, uint32_t cap) {
 }
 
 template <int DIM>
-static void launch_cells_dim(const DevParams& p, hipStream_t stream) {
+static void launch_cells_dim(const DevParams& p0, hipStream_t stream) {
+    DevParams p = p0;
     const uint32_t split = p.freeze ? p.cells_split : 1u;
+    if (p.freeze) {   // pacing: a problem's quota, and the shift at which an XCD's fits 32 bits
+        p.cells_quota = cells_problem_quota(((uint32_t)p.budget + 63u) / 64u, split);
+        p.cells_quota_shift = 0;
+        while ((((uint64_t)((p.n_problems + 7u) / 8u) * p.cells_quota) >> p.cells_quota_shift) > 0xFFFFFFFFull) ++p.cells_quota_shift;
+    }
     // the prepare pass builds missing grids and hands many-part launches their stream positions; a launch that needs neither skips it
     if (!(p.cells_meta_ok != 0 && split <= kSelfSkipMax))
         hipLaunchKernelGGL((cells_prepare_kernel<DIM>), dim3(p.n_problems), dim3(64), 0, stream, p);
@@ -1567,3 +1650,15 @@ void launch_rrt_cells(const DevParams& p, hipStream_t stream) {
 }
 
 }  // namespace oxhip
+
+extern "C" {
+uint32_t oxhip_cells_part_begin(uint32_t rounds, uint32_t part, uint32_t split) {
+    return split >= 1 && split <= oxhip::kMaxSplit ? oxhip::cells_part_begin(rounds, part, split) : rounds;
+}
+uint64_t oxhip_cells_part_quota(uint32_t rounds, uint32_t part, uint32_t split) {
+    return split >= 1 && split <= oxhip::kMaxSplit ? oxhip::cells_part_quota(rounds, part, split) : 0;
+}
+uint64_t oxhip_cells_problem_quota(uint32_t rounds, uint32_t split) {
+    return split >= 1 && split <= oxhip::kMaxSplit ? oxhip::cells_problem_quota(rounds, split) : 0;
+}
+}

@@ -79,6 +79,7 @@ struct CellAcc {
     uint64_t chk, accepted, pos;
     uint32_t done, pad;
 };
+constexpr uint32_t kCellsBoardWords = 8 * 32;   // a progress board (DevParams::cell_board): one 64-bit counter per XCD, 256 bytes apart
 
 // kernel arguments (by value)
 struct DevParams {
@@ -152,6 +153,12 @@ struct DevParams {
     uint64_t* cell_part_pos; // [P][8] stream position at which each part of a split frozen launch starts
     uint32_t cell_blocks, cell_level_max, cells_split;
     uint32_t cells_meta_ok;  // host: every problem's grid record was written by a launch since the last setup / set_tree (no prepare pass needed)
+    // the progress board of the frozen launches (rrt_cells.hip, "pacing"): two boards of one 64-bit counter per XCD, 256 bytes
+    // apart; the launch of parity e counts on board e and clears the other for the launch after it
+    uint64_t* cell_board;      // [2][8][32]
+    uint64_t cells_quota;      // host, per frozen launch: progress units of one problem's parts together (cells_problem_quota)
+    uint32_t cells_parity;     // host: flipped after every frozen launch
+    uint32_t cells_quota_shift;   // host: an XCD's quota and its board's counter are compared this many bits down (they fit 32 bits then)
     // the spheres a motion's midpoint can meet, looked up instead of screened: bit j of sph_grid[cell] is set when sphere j's filter
     // ball (sph_filt) reaches the cell's box (sph_grid_G cells along every axis of the bounds, dimensions 2 / 3)
     const uint64_t* sph_grid;

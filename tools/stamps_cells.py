@@ -32,6 +32,9 @@ def show(tag, g, iters):
     print("   neighbour trips by number (trips: lanes asking / cells asked for, per trip): " +
           ", ".join("%d: %.1f / %.1f" % (int(s[24 + i]), int(s[16 + i]) / max(1, int(s[24 + i])), int(s[ci[i]]) / max(1, int(s[24 + i]))) for i in range(8)))
     print("   tail passes %d, pairs per pass %.1f" % (int(s[1]), int(s[2]) / max(1, int(s[1]))))
+    if "steady" in tag:
+        print("   progress board of the launch, summed over the XCDs: %d units (the problems' quota: %d)"
+              % (int(s[capi.STAMP_CELLS_BOARD]), P * int(capi.lib().oxhip_cells_problem_quota((4096 + 63) // 64, split))))
     print("   commit split: before insert %d, insert (atomic) %d, reductions %d, checksum+rest %d per round" % tuple(int(v) // rounds for v in (s[62], s[63], s[49], s[0])))
 
 
