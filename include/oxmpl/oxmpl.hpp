@@ -249,6 +249,30 @@ class RRT {
         return path;
     }
 
+    // Re-checks every edge of the tree against the obstacles of `checker` as they are now (oxhip_rrt_batch_revalidate_trees):
+    // every node that a failed edge cuts off from the start is dropped, the rest keep their order, counters and the random
+    // stream stay, and a later solve() continues from the pruned tree.  Returns the number of removed nodes.  RRT only:
+    // an RRTConnect or RRTStar planner is refused (NoSolutionFound; oxhip_last_error_string() says why).
+    Result<uint32_t, base::PlanningError> revalidate(const std::shared_ptr<base::StateValidityChecker>& checker) {
+        if (!batch_ || !pd_ || !checker || last_status_ != OXHIP_OK) return base::PlanningError::PlannerUninitialised;
+        std::vector<double> c, r, lo, hi;
+        for (auto& s : checker->spheres()) { c.insert(c.end(), s.centre.begin(), s.centre.end()); r.push_back(s.radius); }
+        for (auto& b : checker->boxes()) { lo.insert(lo.end(), b.lo.begin(), b.lo.end()); hi.insert(hi.end(), b.hi.begin(), b.hi.end()); }
+        int32_t st = oxhip_rrt_batch_set_spheres(batch_, c.data(), r.data(), (uint32_t)r.size());
+        if (st == OXHIP_OK) st = oxhip_rrt_batch_set_boxes(batch_, lo.data(), hi.data(), (uint32_t)(lo.size() / pd_->space->dimension));
+        if (st != OXHIP_OK) return base::PlanningError::NoSolutionFound;
+        vc_ = checker;
+        return revalidate();
+    }
+    Result<uint32_t, base::PlanningError> revalidate() {
+        if (!batch_ || last_status_ != OXHIP_OK) return base::PlanningError::PlannerUninitialised;
+        uint32_t removed = 0;
+        const int32_t st = oxhip_rrt_batch_revalidate_trees(batch_, &removed, nullptr);
+        if (st == OXHIP_ERR_PLANNER_UNINITIALISED) return base::PlanningError::PlannerUninitialised;
+        if (st != OXHIP_OK) return base::PlanningError::NoSolutionFound;
+        return removed;
+    }
+
     // batched StateValidityChecker::is_valid / RRT::check_motion on the device (test helpers)
     bool is_valid(const base::RealVectorState& s) const {
         uint8_t ok = 0;

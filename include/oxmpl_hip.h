@@ -254,6 +254,37 @@ int32_t oxhip_rrt_batch_setup(oxhip_rrt_batch* b, const double* starts /*[P][dim
 int32_t oxhip_rrt_batch_set_tree(oxhip_rrt_batch* b, uint32_t problem, const double* states,
                                  const int32_t* parents, uint32_t n_nodes);
 
+/* ---- re-checking the trees against the obstacles as they are now (rrt_revalidate.hip) ----
+ * The semantics are this build's own (the reference has no such call).  OXHIP_PLANNER_RRT over OXHIP_SPACE_REAL_VECTOR (every
+ * dimension, spheres and boxes) and OXHIP_SPACE_SO3 (cones), every kernel kind.  For every problem, against the batch's current
+ * spheres / boxes / cones (the midpoint filter and the sphere grid are refreshed first, as solve does):
+ *   edge_ok[i], i >= 1, is the verdict of the batch's own check_motion(from = node parent[i], to = node i) -- the direction the
+ *     planner checked the edge in, the bits of oxhip_rrt_batch_check_motion on the same two rows, for an edge of any length (a
+ *     planted tree may hold such).  With unchanged obstacles every edge a kernel grew passes and the call changes nothing.
+ *   Node 0 is never tested and always kept (setup() does not test the start); node i >= 1 stays iff edge_ok[i] and its parent
+ *     stays.  Survivors keep their relative order: new_index[i] = survivors below i, -1 for a removed node; parents are remapped
+ *     through new_index; n_nodes becomes the survivor count.  Tree, parents and skip flags afterwards are exactly what
+ *     oxhip_rrt_batch_set_tree(problem, pruned states, pruned parents) leaves for a tree that set_tree planted or a kernel that
+ *     keeps skip flags grew (a node carries the flag iff a SURVIVING node of lower index has equal coordinates).
+ *   iterations, accepted, checksum and the RNG position do not change.
+ *   goal_node becomes the lowest new index i >= 1 whose state satisfies the problem's goal (the planner's own comparison), -1 if
+ *     there is none; the old value is not read (set_tree can leave it stale).  For a kernel-grown tree that is "the old goal node,
+ *     remapped, if it survived".  goal_lost[p] = 1 iff goal_node was >= 0 and in range before and is -1 now.  stop_reason
+ *     becomes OXHIP_STOP_NONE: the next solve runs the problem again.
+ *   What set_tree drops is dropped for all problems: extracted / simplified paths, the binary32 shadows, the cell grids.  The
+ *     next launch rebuilds them; this call rebuilds none.
+ * n_removed[P], goal_lost[P]: may be NULL.  RRTConnect and RRT* batches: OXHIP_ERR_BAD_ARG (RRT* would need its costs and wiring
+ * cursors pruned as well); SE(2) / SE(3) are RRTConnect only.  Without setup(): OXHIP_ERR_PLANNER_UNINITIALISED. */
+int32_t oxhip_rrt_batch_revalidate_trees(oxhip_rrt_batch* b, uint32_t* n_removed /*[P] or NULL*/,
+                                         uint8_t* goal_lost /*[P] or NULL*/);
+/* new_index and edge_ok (edge_ok[0] = 1) of the last revalidate_trees for one problem, n_before entries each: a test hook, and
+ * the way to remap per-node annotations of the caller's own.  Holds until the next setup / solve / set_tree / revalidate_trees;
+ * after that, and before the first call, OXHIP_ERR_BAD_ARG.  cap < n_before: OXHIP_ERR_CAPACITY, *n_before still written. */
+int32_t oxhip_rrt_batch_get_revalidate_map(oxhip_rrt_batch* b, uint32_t problem, int32_t* new_index /*[n_before] or NULL*/,
+                                           uint8_t* edge_ok /*[n_before] or NULL*/, uint32_t cap, uint32_t* n_before);
+/* HIP-event times (ms) of the last revalidate_trees: phase_ms[4] = {edge checks, survival, scan, compaction + remap + skip flags} */
+int32_t oxhip_rrt_batch_revalidate_last_timing(oxhip_rrt_batch* b, double* phase_ms /*[4]*/);
+
 /* Planner::solve (rrt.rs:158-227).  Runs every unfinished problem for at most max_iterations
  * further iterations (one iteration = one pass of rrt.rs:170-225).  timeout_s bounds wall time
  * (checked between kernel launches of at most 2048 iterations; 0 or +inf = none; NaN or negative =

@@ -56,6 +56,7 @@ EXPORTS = [
     "oxhip_rrt_batch_extract_paths", "oxhip_rrt_batch_get_paths", "oxhip_rrt_batch_simplify_paths",
     "oxhip_rrt_batch_get_simplified_paths", "oxhip_rrt_batch_get_simplify_results", "oxhip_rrt_batch_path_valid_matrix",
     "oxhip_rrt_batch_paths_last_timing",
+    "oxhip_rrt_batch_revalidate_trees", "oxhip_rrt_batch_get_revalidate_map", "oxhip_rrt_batch_revalidate_last_timing",
     "oxhip_cells_part_begin", "oxhip_cells_part_quota", "oxhip_cells_problem_quota",
 ]
 
@@ -182,6 +183,9 @@ def lib():
         L.oxhip_rrt_batch_get_simplify_results.argtypes = [C.c_void_p, _dp, _dp, _u64p]
         L.oxhip_rrt_batch_path_valid_matrix.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, _u8p, C.c_uint64, _u32p]
         L.oxhip_rrt_batch_paths_last_timing.argtypes = [C.c_void_p, _dp, _dp, _dp, _u32p]
+        L.oxhip_rrt_batch_revalidate_trees.argtypes = [C.c_void_p, _u32p, _u8p]
+        L.oxhip_rrt_batch_get_revalidate_map.argtypes = [C.c_void_p, C.c_uint32, _i32p, _u8p, C.c_uint32, _u32p]
+        L.oxhip_rrt_batch_revalidate_last_timing.argtypes = [C.c_void_p, _dp]
         L.oxhip_cells_part_begin.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
         L.oxhip_cells_part_quota.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
         L.oxhip_cells_problem_quota.argtypes = [C.c_uint32, C.c_uint32]
@@ -426,6 +430,34 @@ class RRTBatch:
         e, pr, dp, r = C.c_double(), C.c_double(), C.c_double(), C.c_uint32()
         _check(lib().oxhip_rrt_batch_paths_last_timing(self._h, C.byref(e), C.byref(pr), C.byref(dp), C.byref(r)))
         return dict(extract_ms=e.value, pairs_ms=pr.value, dp_ms=dp.value, rounds=r.value)
+
+    # ---- the trees re-checked against the obstacles as they are now
+
+    def revalidate_trees(self):
+        """Re-check every tree edge against the current spheres / boxes / cones, drop every node whose chain to the root holds a
+        failed edge, compact in place (include/oxmpl_hip.h states the semantics) -> dict(n_removed [P] u32, goal_lost [P] bool)"""
+        P = self.n_problems
+        removed, lost = np.zeros(P, dtype=np.uint32), np.zeros(P, dtype=np.uint8)
+        _check(lib().oxhip_rrt_batch_revalidate_trees(self._h, _p(removed, _u32p), _p(lost, _u8p)))
+        return dict(n_removed=removed, goal_lost=lost.astype(bool))
+
+    def revalidate_map(self, problem):
+        """(new_index [n_before] i32, edge_ok [n_before] bool) of the last revalidate_trees: where every old node went (-1:
+        removed) and the verdict of its edge from its parent (the root's is True)"""
+        n = C.c_uint32()
+        st = lib().oxhip_rrt_batch_get_revalidate_map(self._h, problem, None, None, 0, C.byref(n))
+        if st not in (OK, ERR_CAPACITY):
+            _check(st)
+        new_index = np.zeros(max(n.value, 1), dtype=np.int32)
+        edge_ok = np.zeros(max(n.value, 1), dtype=np.uint8)
+        _check(lib().oxhip_rrt_batch_get_revalidate_map(self._h, problem, _p(new_index, _i32p), _p(edge_ok, _u8p), n.value, C.byref(n)))
+        return new_index[:n.value], edge_ok[:n.value].astype(bool)
+
+    def revalidate_last_timing(self):
+        """dict(phase_ms=[edge checks, survival, scan, compaction + remap + skip flags]) of the last revalidate_trees"""
+        ms = np.zeros(4)
+        _check(lib().oxhip_rrt_batch_revalidate_last_timing(self._h, _p(ms)))
+        return dict(phase_ms=ms)
 
     def last_timing(self):
         ms, launches, kind = C.c_double(), C.c_uint32(), C.c_uint32()

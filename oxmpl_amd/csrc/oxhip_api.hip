@@ -114,8 +114,16 @@ struct oxhip_rrt_batch {
     DevBuf<double> path_rows, sp_cost, sp_raw, sp_simp;
     double paths_ms[3] = {0.0, 0.0, 0.0};         // extraction kernels, pair matrix, DP of the last calls
     uint32_t paths_rounds = 0;
+    // rrt_revalidate.hip: the workspace of revalidate_trees (allocated on first use and kept) and the map of its last call,
+    // which belongs to the trees as that call left them: setup / solve / set_tree drop it (drop_paths)
+    bool reval_ok = false;
+    DevBuf<uint8_t> rv_edge_ok, rv_alive, rv_goal_lost, rv_stage;
+    DevBuf<int32_t> rv_new_index, rv_jump;
+    DevBuf<uint32_t> rv_n_after, rv_n_removed;
+    std::vector<uint32_t> rv_n_before;            // [P] tree sizes before the last call
+    double reval_ms[4] = {0.0, 0.0, 0.0, 0.0};    // edge checks, survival, scan, compaction + remap + skip flags
 };
-static void drop_paths(oxhip_rrt_batch* b) { b->paths_ok = b->simp_ok = false; }
+static void drop_paths(oxhip_rrt_batch* b) { b->paths_ok = b->simp_ok = b->reval_ok = false; }
 template <typename T>
 static hipError_t grow(DevBuf<T>& buf, size_t count) {   // keeps a buffer that is large enough (a round reuses the last one's)
     if (buf.p && buf.n >= count) return hipSuccess;
@@ -1148,7 +1156,7 @@ int32_t oxhip_rrt_batch_get_costs(oxhip_rrt_batch* b, uint32_t problem, double* 
 
 int32_t oxhip_rrt_batch_extract_paths(oxhip_rrt_batch* b) {
     OX_TRY(ready(b));
-    drop_paths(b);
+    b->paths_ok = b->simp_ok = false;   // (the trees stay: a revalidation map stays with them)
     const uint32_t P = b->cfg.n_problems, dim = b->cfg.dim;
     HIP_TRY(grow(b->path_len, P));
     HIP_TRY(grow(b->path_len_a, P));
@@ -1466,6 +1474,107 @@ int32_t oxhip_interpolate_batch(int32_t device, uint32_t dim, const double* from
     if (dim == 0 || dim > OXHIP_MAX_DIM) return fail(OXHIP_ERR_BAD_ARG, "dim must be in 1..8");
     return op_batch(device, from, to, t, n, out, dim, dim, dim, true, true,
                     [=](const double* da, const double* db, const double* dt, double* dout, hipStream_t s) { launch_interpolate(dim, da, db, dt, n, dout, s); });
+}
+
+// ------------------------------------------------------------------ re-checking the trees (rrt_revalidate.hip)
+int32_t oxhip_rrt_batch_revalidate_trees(oxhip_rrt_batch* b, uint32_t* n_removed, uint8_t* goal_lost) {
+    if (!b) return fail(OXHIP_ERR_BAD_ARG, "null batch");
+    drop_paths(b);   // (and the last call's map)
+    OX_TRY(setup_done(b));
+    if (b->cfg.planner == OXHIP_PLANNER_RRT_CONNECT)
+        return fail(OXHIP_ERR_BAD_ARG, "revalidate_trees is for the RRT planner (an RRTConnect batch keeps two trees and their connection)");
+    if (b->cfg.planner != OXHIP_PLANNER_RRT)
+        return fail(OXHIP_ERR_BAD_ARG, "revalidate_trees is for the RRT planner (an RRT* batch would need its costs and wiring cursors pruned as well)");
+    OX_TRY(select_device(b->cfg.device));
+    if (space_of(b).midpoint_filter) OX_TRY(refresh_filter(b));   // as solve does: the next launch reads them
+    const uint32_t P = b->cfg.n_problems, cap = b->dp.cap;
+    const bool so3 = b->cfg.space == OXHIP_SPACE_SO3;
+    RevalArgs a{};
+    OX_TRY(pair_params(b, a.filt_base));   // (R^n: the radii and the absolute margin of motion_seq.hpp's midpoint filter)
+    std::vector<ProblemState> states;
+    OX_TRY(read_states(b, states));        // one read of the state array: the node counts
+    b->rv_n_before.resize(P);
+    uint32_t max_n = 1;
+    for (uint32_t p = 0; p < P; ++p) {
+        b->rv_n_before[p] = states[p].n_nodes;
+        if (states[p].n_nodes == 0 || states[p].n_nodes > cap) return fail(OXHIP_ERR_HIP, "revalidate_trees: a tree size outside 1..capacity");
+        max_n = std::max(max_n, states[p].n_nodes);
+    }
+    a.tiles = (max_n + 255u) / 256u;
+    if ((uint64_t)P * a.tiles * 256u > 0x7FFFFFFFull) return fail(OXHIP_ERR_CAPACITY, "revalidate_trees: more than 2^31 node slots");
+    const size_t slots = (size_t)P * cap;
+    HIP_TRY(grow(b->rv_edge_ok, slots));
+    HIP_TRY(grow(b->rv_alive, slots));
+    HIP_TRY(grow(b->rv_new_index, slots));
+    HIP_TRY(grow(b->rv_jump, slots));
+    HIP_TRY(grow(b->rv_n_after, P));
+    HIP_TRY(grow(b->rv_n_removed, P));
+    HIP_TRY(grow(b->rv_goal_lost, P));
+    if (so3) {
+        // 65 bytes per staged edge (two rows and a verdict) out of 6 bytes per slot: with the 10 above, 16 bytes per slot
+        // (one block of 64 edges at the least)
+        const size_t edges = std::max<size_t>(64, std::min<size_t>(slots * 6 / 65, (size_t)P * a.tiles * 256u));
+        HIP_TRY(grow(b->rv_stage, edges * 65));
+        a.stage_cap = (uint32_t)std::min<size_t>(edges, 0x7FFFFF00u);
+        a.stage_from = reinterpret_cast<double*>(b->rv_stage.p);
+        a.stage_to = a.stage_from + (size_t)a.stage_cap * 4;
+        a.stage_out = reinterpret_cast<uint8_t*>(a.stage_to + (size_t)a.stage_cap * 4);
+    }
+    a.tree = b->tree.p; a.parent = b->parent.p; a.skip = b->skip.p; a.state = b->state.p;
+    a.goal_c = b->goal_c.p; a.goal_thr = b->goal_thr.p;
+    a.edge_ok = b->rv_edge_ok.p; a.alive = b->rv_alive.p; a.new_index = b->rv_new_index.p; a.jump = b->rv_jump.p;
+    a.n_after = b->rv_n_after.p; a.n_removed = b->rv_n_removed.p; a.goal_lost = b->rv_goal_lost.p;
+    a.cap = cap;
+    hipEvent_t ev[5] = {};
+    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 5; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
+    for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventRecord(ev[0], b->stream));
+    launch_rrt_reval_edges(b->dp, a, P, b->stream);
+    HIP_TRY(hipEventRecord(ev[1], b->stream));
+    launch_rrt_reval_survive(a, P, b->stream);
+    HIP_TRY(hipEventRecord(ev[2], b->stream));
+    launch_rrt_reval_scan(a, P, b->stream);
+    HIP_TRY(hipEventRecord(ev[3], b->stream));
+    launch_rrt_reval_compact(b->dp, a, P, b->stream);
+    HIP_TRY(hipEventRecord(ev[4], b->stream));
+    HIP_TRY(hipGetLastError());
+    // what set_tree drops, for every problem: the fl32 shadows start over, the cell grids too
+    if (b->shadow_state.p) HIP_TRY(hipMemsetAsync(b->shadow_state.p, 0, (size_t)P * 2 * sizeof(uint32_t), b->stream));
+    if (b->cell_meta_p) HIP_TRY(hipMemsetAsync(b->cell_meta_p, 0, (size_t)P * sizeof(CellMeta), b->stream));
+    b->dp.cells_meta_ok = 0;
+    if (n_removed) HIP_TRY(hipMemcpyAsync(n_removed, b->rv_n_removed.p, (size_t)P * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+    if (goal_lost) HIP_TRY(hipMemcpyAsync(goal_lost, b->rv_goal_lost.p, P, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    for (int i = 0; i < 4; ++i) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+        b->reval_ms[i] = ms;
+    }
+    b->reval_ok = true;
+    return OXHIP_OK;
+}
+
+int32_t oxhip_rrt_batch_get_revalidate_map(oxhip_rrt_batch* b, uint32_t problem, int32_t* new_index, uint8_t* edge_ok, uint32_t cap,
+                                           uint32_t* n_before) {
+    if (!b || !n_before) return fail(OXHIP_ERR_BAD_ARG, "null argument");
+    OX_TRY(setup_done(b, problem));
+    if (!b->reval_ok)
+        return fail(OXHIP_ERR_BAD_ARG, "no revalidation map: call oxhip_rrt_batch_revalidate_trees after the last setup / solve / set_tree");
+    OX_TRY(select_device(b->cfg.device));
+    const uint32_t n = b->rv_n_before[problem];
+    *n_before = n;
+    if (cap < n) return fail(OXHIP_ERR_CAPACITY, "map buffer too small");
+    const size_t base = (size_t)problem * b->dp.cap;
+    if (new_index) HIP_TRY(hipMemcpyAsync(new_index, b->rv_new_index.p + base, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+    if (edge_ok) HIP_TRY(hipMemcpyAsync(edge_ok, b->rv_edge_ok.p + base, n, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return OXHIP_OK;
+}
+
+int32_t oxhip_rrt_batch_revalidate_last_timing(oxhip_rrt_batch* b, double* phase_ms) {
+    if (!b || !phase_ms) return fail(OXHIP_ERR_BAD_ARG, "null argument");
+    for (int i = 0; i < 4; ++i) phase_ms[i] = b->reval_ms[i];
+    return OXHIP_OK;
 }
 
 int32_t oxhip_rrt_batch_is_valid(oxhip_rrt_batch* b, const double* states, uint32_t n, uint8_t* out) {

@@ -190,6 +190,36 @@ hipError_t prm_reval_scan(void* tmp, size_t& tmp_bytes, const uint8_t* keep, uin
 void launch_prm_reval_compact(uint32_t* offsets, const uint32_t* nbrs, const uint8_t* keep, const uint32_t* pos, uint32_t n, uint32_t n_entries,
                               uint32_t* nbrs_out, hipStream_t s);
 
+// rrt_revalidate.hip: the trees of an RRT batch re-checked against the current obstacles and compacted in place (DESIGN.md
+// section 21).  The per-slot arrays are [P][cap], indexed like DevParams::parent.
+struct ProblemState;
+struct RevalArgs {
+    double* tree;                // DevParams::tree, parent, skip, state, goal_c, goal_thr
+    int32_t* parent;
+    uint8_t* skip;
+    ProblemState* state;
+    const double* goal_c;
+    const double* goal_thr;
+    uint8_t* edge_ok;            // verdict of check_motion(parent[i] -> i); 1 for the root
+    uint8_t* alive;              // no edge on the chain to the root failed
+    int32_t* new_index;          // survivors below i, -1 for a removed node
+    int32_t* jump;               // the survival pass's pointers
+    uint32_t* n_after;           // [P] survivors
+    uint32_t* n_removed;         // [P]
+    uint8_t* goal_lost;          // [P]
+    uint32_t cap, tiles;         // tiles: 256-node tiles that cover the largest tree (the grids of the per-node kernels)
+    // SO(3): the edges go through launch_so3_check_motion, stage_cap at a time: rows (from, to) AoS [stage_cap][4] and its verdicts
+    double* stage_from;
+    double* stage_to;
+    uint8_t* stage_out;
+    uint32_t stage_cap, pad;
+    double filt_base;            // the midpoint filter's absolute margin from the bounds and the sphere centres (R^n)
+};
+void launch_rrt_reval_edges(const DevParams& p, const RevalArgs& a, uint32_t n_problems, hipStream_t s);
+void launch_rrt_reval_survive(const RevalArgs& a, uint32_t n_problems, hipStream_t s);
+void launch_rrt_reval_scan(const RevalArgs& a, uint32_t n_problems, hipStream_t s);
+void launch_rrt_reval_compact(const DevParams& p, const RevalArgs& a, uint32_t n_problems, hipStream_t s);   // + the skip flags
+
 // prm_batch.hip: a batch of queries on the constructed roadmap, breadth-first search and path extraction on the device
 // (DESIGN.md section 17).  One round answers the queries [q0, q0 + n_chunk) of the batch; row c of a per-round array is query q0 + c.
 struct PrmBatchArgs {

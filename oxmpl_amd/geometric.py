@@ -162,6 +162,33 @@ class RRT:
         """the checker's predicate, evaluated on the device (the reference calls the user's callable)"""
         return bool(self._batch.is_valid(np.array([state.values]))[0])
 
+    def revalidate(self, validity_checker=None):
+        """Re-checks every edge of the tree against the obstacles as they are now -- `validity_checker`'s when one is given (it
+        replaces the planner's), else the ones already set -- and drops every node that a failed edge cuts off from the start
+        (DESIGN.md section 21).  Returns the number of removed nodes; a later solve() continues from the pruned tree, with the
+        counters and the random stream where they were.  Not part of the reference's surface.  RRT only."""
+        if self._PLANNER != capi.PLANNER_RRT:
+            raise TypeError("revalidate is built for RRT only (not RRTConnect, not RRTStar)")
+        if self._batch is None:
+            raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
+        if validity_checker is not None:
+            if isinstance(self._pd.space, SO3StateSpace):
+                if not isinstance(validity_checker, SO3ConeValidityChecker):
+                    raise TypeError("an SO(3) tree is re-checked against an SO3ConeValidityChecker")
+                self._batch.set_spheres([c for c, _ in validity_checker.cones], [r for _, r in validity_checker.cones])
+            else:
+                if not isinstance(validity_checker, SphereBoxValidityChecker):
+                    raise TypeError("describe the obstacles with oxmpl_amd.base.SphereBoxValidityChecker")
+                self._batch.set_spheres([c for c, _ in validity_checker.spheres], [r for _, r in validity_checker.spheres])
+                self._batch.set_boxes([lo for lo, _ in validity_checker.boxes], [hi for _, hi in validity_checker.boxes])
+            self._checker = validity_checker
+        try:
+            return int(self._batch.revalidate_trees()["n_removed"][0])
+        except capi.OxhipError as e:
+            if e.status in _MESSAGES:
+                raise Exception(_MESSAGES[e.status]) from None
+            raise
+
     @property
     def num_nodes(self):
         return int(self._batch.counts()["nodes"][0])

@@ -264,6 +264,10 @@ extern "C" {
     pub fn oxhip_prm_set_roadmap(p: *mut OxhipPrm, states: *const f64, n: u32, offsets: *const u64, neighbours: *const u32) -> i32;
     pub fn oxhip_prm_revalidate(p: *mut OxhipPrm, milestone_valid: *mut u8, n_invalid_milestones: *mut u32, n_removed_entries: *mut u64) -> i32;
     pub fn oxhip_prm_revalidate_last_timing(p: *mut OxhipPrm, phase_ms: *mut f64) -> i32;
+    // rrt_revalidate.hip: the trees of an RRT batch re-checked against the current obstacles
+    pub fn oxhip_rrt_batch_revalidate_trees(b: *mut OxhipRrtBatch, n_removed: *mut u32, goal_lost: *mut u8) -> i32;
+    pub fn oxhip_rrt_batch_get_revalidate_map(b: *mut OxhipRrtBatch, problem: u32, new_index: *mut i32, edge_ok: *mut u8, cap: u32, n_before: *mut u32) -> i32;
+    pub fn oxhip_rrt_batch_revalidate_last_timing(b: *mut OxhipRrtBatch, phase_ms: *mut f64) -> i32;
 }
 
 #[cfg(test)]

@@ -266,6 +266,21 @@ impl<D: DeviceValidityChecker, G: DeviceGoal> HipRRT<D, G> {
         }
         Ok(Path(flat.chunks(dim).map(|c| RealVectorState::new(c.to_vec())).collect()))
     }
+
+    /// Re-checks every edge of the tree against the batch's current obstacles (`oxhip_rrt_batch_revalidate_trees`): every
+    /// node that a failed edge cuts off from the start is dropped, the rest keep their order, counters and the random
+    /// stream stay, and a later `solve` continues from the pruned tree.  Returns the number of removed nodes.  RRT only:
+    /// an RRTConnect or RRT* planner gets `NoSolutionFound` (the library refuses it with `OXHIP_ERR_BAD_ARG`).
+    pub fn revalidate(&mut self) -> Result<u32, PlanningError> {
+        if self.batch.is_null() {
+            return Err(PlanningError::PlannerUninitialised);
+        }
+        let mut removed = 0u32;
+        match unsafe { ffi::oxhip_rrt_batch_revalidate_trees(self.batch, &mut removed, ptr::null_mut()) } {
+            ffi::OXHIP_OK => Ok(removed),
+            rc => Err(to_planning_error(rc)),
+        }
+    }
 }
 
 impl<D: DeviceValidityChecker, G: DeviceGoal> Drop for HipRRT<D, G> {
