@@ -59,8 +59,48 @@ constexpr int kMaxShell = 6;                         // the cooperative search g
 #define OXHIP_CELLS_FILL_X2 7ull
 #endif
 #ifndef OXHIP_CELLS_TAIL
-#define OXHIP_CELLS_TAIL 64                          // at most this many outstanding (query, cell) pairs: one pair per lane (0: off)
+#define OXHIP_CELLS_TAIL 64                          // the dealt pass holds this many outstanding (query, cell) pairs per pair a lane takes (0: off)
 #endif
+// THE DEALT PASS of the neighbour walk (the comment in the round's neighbour loop), per specialisation:
+//   DEPTH  pairs a lane takes in one pass, all their blocks in flight together: 1 .. the trip's depth; capacity = DEPTH x OXHIP_CELLS_TAIL
+//   FLIGHT of them at most this many blocks on their way at a time (the registers of an evaluated block take the next one)
+//   EARLY  1: the pairs are dealt as soon as they fit, right after the first trip; 0: only after an ordinary trip
+//   MERGE  0: every owner collects its pairs' results from per-pair lists; 1: the evaluating lanes merge into per-owner slots with LDS atomics
+// OXHIP_CELLS_DEAL_LEGACY is the walk as it was before the deep pass -- one pair per lane, only after a trip, owner loop -- in one setting.
+#ifdef OXHIP_CELLS_DEAL_LEGACY
+#define OXHIP_CELLS_DEAL_DEPTH_FROZEN 1
+#define OXHIP_CELLS_DEAL_EARLY_FROZEN 0
+#define OXHIP_CELLS_DEAL_MERGE_FROZEN 0
+#endif
+#ifndef OXHIP_CELLS_DEAL_DEPTH_FROZEN
+#define OXHIP_CELLS_DEAL_DEPTH_FROZEN OXHIP_CELLS_NB_FROZEN
+#endif
+#ifndef OXHIP_CELLS_DEAL_EARLY_FROZEN
+#define OXHIP_CELLS_DEAL_EARLY_FROZEN 1
+#endif
+#ifndef OXHIP_CELLS_DEAL_MERGE_FROZEN
+#define OXHIP_CELLS_DEAL_MERGE_FROZEN 1
+#endif
+#ifndef OXHIP_CELLS_DEAL_FLIGHT_FROZEN
+#define OXHIP_CELLS_DEAL_FLIGHT_FROZEN 2               // (three in flight spill inside the round: profiles/frozen_deal/)
+#endif
+#ifndef OXHIP_CELLS_DEAL_FLIGHT
+#define OXHIP_CELLS_DEAL_FLIGHT OXHIP_CELLS_NB
+#endif
+#ifndef OXHIP_CELLS_DEAL_DEPTH                        // a growing launch: as before (not measured with the deep pass)
+#define OXHIP_CELLS_DEAL_DEPTH 1
+#endif
+#ifndef OXHIP_CELLS_DEAL_EARLY
+#define OXHIP_CELLS_DEAL_EARLY 0
+#endif
+#ifndef OXHIP_CELLS_DEAL_MERGE
+#define OXHIP_CELLS_DEAL_MERGE 0
+#endif
+static_assert(OXHIP_CELLS_TAIL == 0 || OXHIP_CELLS_TAIL == 64, "a lane takes the pairs lane, lane + 64, ...");
+static_assert(OXHIP_CELLS_DEAL_DEPTH_FROZEN >= 1 && OXHIP_CELLS_DEAL_DEPTH_FROZEN <= OXHIP_CELLS_NB_FROZEN, "no more blocks in flight than a trip holds");
+static_assert(OXHIP_CELLS_DEAL_DEPTH >= 1 && OXHIP_CELLS_DEAL_DEPTH <= OXHIP_CELLS_NB, "no more blocks in flight than a trip holds");
+constexpr uint32_t kDealListMax = 64u * (OXHIP_CELLS_DEAL_DEPTH_FROZEN > OXHIP_CELLS_DEAL_DEPTH ? OXHIP_CELLS_DEAL_DEPTH_FROZEN : OXHIP_CELLS_DEAL_DEPTH);
+constexpr bool kDealAtomics = OXHIP_CELLS_DEAL_MERGE_FROZEN != 0 || OXHIP_CELLS_DEAL_MERGE != 0;
 
 typedef float cfloat4 __attribute__((ext_vector_type(4)));
 typedef uint32_t cuint4 __attribute__((ext_vector_type(4)));
@@ -82,9 +122,10 @@ struct CellsWaveLds {
     uint64_t pos_after[64];
     double newn[DIM][64];         // the round's would-be new nodes, by rank
     float newn32[64][4];          // ... as the dot-product pre-screen holds them: fl32(x - c0), fl32(|.|^2)
-    uint32_t tail_pair[64];       // the tail pass: (owner lane | neighbour number << 8) of the k-th outstanding (query, cell) pair ...
-    float tail_s1[64], tail_s2[64];   // ... and what lane k found in that cell
-    uint32_t tail_i1[64];
+    uint32_t tail_pair[kDealListMax];   // the dealt pass: (owner lane | neighbour number << 8) of the k-th outstanding (query, cell) pair ...
+    float tail_s1[64], tail_s2[64];   // ... and what lane k found in that cell (one pair per lane; a deeper pass with the owner loop lists its
+    uint32_t tail_i1[64];             //     results over newn / newn32); under the atomic merge tail_i1[o] is owner o's second smallest value
+    uint64_t deal_best[kDealAtomics ? 64 : 1];   // the atomic merge: owner o's smallest (value bits << 32 | entry word)
 };
 // What a launch computes once and every round reads: wave-uniform, written before the launch's barrier.  (The frozen kernel has
 // no registers to hold them across the round loop: there the compiler spills them and reloads them from scratch every round.)
@@ -750,7 +791,9 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
         for (int k = 0; k < D; ++k) {
             tq[k] = (float)((q[k] - grid.lo[k]) * grid.inv_h);
             const float fl = floorf(tq[k]);
-            cq[k] = fl > 0.0f ? (fl < (float)grid.G[k] ? (uint32_t)fl : grid.G[k] - 1u) : 0u;   // (NaN -> 0)
+            uint32_t gk = grid.G[k];   // (a frozen round converts it here: as a loop invariant the binary32 value is a register held across the rounds)
+            if (FROZEN) asm volatile("" : "+s"(gk));
+            cq[k] = fl > 0.0f ? (fl < (float)gk ? (uint32_t)fl : grid.G[k] - 1u) : 0u;   // (NaN -> 0)
         }
         const uint32_t gmax = grid.G[0] > grid.G[1] ? (grid.G[0] > grid.G[2] ? grid.G[0] : grid.G[2]) : (grid.G[1] > grid.G[2] ? grid.G[1] : grid.G[2]);
         const double A = sqrt((double)D) * (grid.delta_node + (double)(gmax + 8u) * 0x1p-23) * 1.01 + 1e-30;
@@ -893,53 +936,137 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
                 constexpr uint64_t w0 = 12ull | 14ull << 5 | 10ull << 10 | 16ull << 15 | 9ull << 20 | 11ull << 25 | 15ull << 30 | 17ull << 35;
                 return (uint32_t)(w0 >> (b * 5u)) & 31u;
             };
+            constexpr int NB = FROZEN ? OXHIP_CELLS_NB_FROZEN : OXHIP_CELLS_NB;
+            // the dealt pass (the macros beside OXHIP_CELLS_TAIL).  The owner loop of a pass deeper than one pair per lane lists its
+            // results over newn / newn32, which only a growing launch stages nodes in: as many pairs as fit there.
+            constexpr bool kDealEarly = (FROZEN ? OXHIP_CELLS_DEAL_EARLY_FROZEN : OXHIP_CELLS_DEAL_EARLY) != 0;
+            constexpr bool kDealAtomic = (FROZEN ? OXHIP_CELLS_DEAL_MERGE_FROZEN : OXHIP_CELLS_DEAL_MERGE) != 0;
+            constexpr int kDealAsked = OXHIP_CELLS_TAIL == 0 ? 0 : (FROZEN ? OXHIP_CELLS_DEAL_DEPTH_FROZEN : OXHIP_CELLS_DEAL_DEPTH);
+            constexpr int kDealFit = (int)((sizeof(CellsWaveLds<DIM>::newn) + sizeof(CellsWaveLds<DIM>::newn32)) / (64u * 3u * sizeof(float)));
+            constexpr int kDealDepth = (kDealAtomic || kDealAsked <= 1) ? kDealAsked : (kDealAsked < kDealFit ? kDealAsked : kDealFit);
+            constexpr uint32_t kDealCap = 64u * (uint32_t)kDealDepth;
+            constexpr int kDealFlight = FROZEN ? OXHIP_CELLS_DEAL_FLIGHT_FROZEN : OXHIP_CELLS_DEAL_FLIGHT;
+            static_assert(kDealDepth <= 1 || kDealAtomic || FROZEN, "a growing launch stages its new nodes where the owner loop's lists would lie");
+            static_assert(kDealCap <= kDealListMax, "the pair list holds a pass");
             while (__ballot(need != 0) != 0) {
-                if (OXHIP_CELLS_TAIL != 0 && trip_no != 0) {
-                    // THE TAIL: after a trip few lanes still ask, each for several cells -- a further trip would run every lane
-                    // through four block evaluations for their sake.  When the outstanding (query, cell) pairs fit one per
-                    // lane, they are dealt out instead: lane k evaluates pair k, the owners collect.
+                if (kDealDepth != 0 && (kDealEarly || trip_no != 0)) {
+                    // THE DEALT PASS: after the first trip two lanes in three still ask, very unevenly -- a lane whose first trip found
+                    // nothing asks for every cell, most ask for two or three -- and a trip runs every lane through NB block evaluations
+                    // for the fullest lane's sake.  When the outstanding (query, cell) pairs fit kDealDepth per lane they are dealt out
+                    // instead: a prefix sum over the lanes' counts places them in a list, lane k takes the pairs k, k + 64, ..., keeps
+                    // kDealFlight of their blocks on the way (all of them: one memory round trip; a frozen launch has registers for two,
+                    // and the first block's take the third), evaluates them one after the other, and the owners get the results.
+                    // When they do not fit, an ordinary trip runs first, re-prunes, and what is left is dealt.
+                    // EXACTNESS.  Nothing is re-pruned between the first trip and the pass, so the pass visits a superset of the cells the
+                    // trips would have visited: d1 only shrinks, so a cell the trips would have dropped on the way holds no node that
+                    // beats or ties the winner, and a cell skipped here was provably too far already.  The band resolver's premise --
+                    // every cell of the block within its bound was visited -- holds all the more, and s2 over a superset is still the
+                    // true second smallest value of what was visited: the margin clause only gets stricter.
                     const uint32_t cntl = (uint32_t)__popc(need);
                     const uint32_t incl = wave_scan_u32(cntl);
                     const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-                    if (total <= (uint32_t)OXHIP_CELLS_TAIL) {
+                    if (total <= kDealCap) {
                         if (STAMP) { ++n_tail; n_tail_pairs += total; }
                         const uint32_t first = incl - cntl;
+                        // (the pass's LDS addresses from an opaque copy of the lane number: formed here, not held across the rounds)
+                        uint32_t lane_d = lane;
+                        if (FROZEN) asm volatile("" : "+v"(lane_d));
                         {
                             uint32_t nd = need, pos = first;
                             while (__ballot(nd != 0) != 0) {
                                 if (nd != 0) {
-                                    sh->tail_pair[pos & 63u] = lane | ((uint32_t)(__ffs((int)nd) - 1) << 8);
+                                    if (pos < kDealCap) sh->tail_pair[pos] = lane_d | ((uint32_t)(__ffs((int)nd) - 1) << 8);   // (always: pos < total)
                                     nd &= nd - 1u;
                                     ++pos;
                                 }
                             }
                         }
-                        const bool mine = lane < total;
-                        const uint32_t pr = sh->tail_pair[mine ? lane : 0u];
-                        const uint32_t owner = pr & 63u;
-                        float tqo[3];
-                        uint32_t cqo[3], cco[3];
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) {
-                            tqo[k] = k < DIM ? lbits_f32((uint32_t)__builtin_amdgcn_ds_bpermute((int)(owner << 2), (int)lf32_bits(tq[k]))) : 0.0f;
-                            cqo[k] = k < DIM ? (uint32_t)__builtin_amdgcn_ds_bpermute((int)(owner << 2), (int)cq[k]) : 0u;
+                        // the per-pair result lists of the owner loop
+                        float* const rs1 = kDealDepth > 1 ? reinterpret_cast<float*>(&sh->newn[0][0]) : sh->tail_s1;
+                        float* const rs2 = kDealDepth > 1 ? rs1 + kDealCap : sh->tail_s2;
+                        uint32_t* const ri1 = kDealDepth > 1 ? reinterpret_cast<uint32_t*>(rs2 + kDealCap) : sh->tail_i1;
+                        if (kDealAtomic) {   // (the owner's slots start from what its walk holds, so the running pair need not be held across the pass)
+                            sh->deal_best[lane_d] = ((uint64_t)lf32_bits(t2.s1) << 32) | t2.i1;
+                            sh->tail_i1[lane_d] = lf32_bits(t2.s2);
                         }
-                        const uint32_t o = mine ? order_o(pr >> 8) : 13u;
-                        const uint32_t o3 = (o * 11u) >> 5, o9 = (o3 * 11u) >> 5;   // o / 3, o / 9 for o < 27
-                        cco[0] = cqo[0] + (o - 3u * o3) - 1u;
-                        cco[1] = cqo[1] + (o3 - 3u * o9) - 1u;
-                        cco[2] = cqo[2] + o9 - 1u;
-                        Top2 tp{__builtin_inff(), __builtin_inff(), kNoNode};
-                        cell_visit<DIM>(blk, mine ? (cco[2] * grid.G[1] + cco[1]) * grid.G[0] + cco[0] : 0u, mine, cco, tqo, tp);
-                        sh->tail_s1[lane] = tp.s1;
-                        sh->tail_s2[lane] = tp.s2;
-                        sh->tail_i1[lane] = tp.i1;
-                        for (uint32_t t = 0; __ballot(t < cntl) != 0; ++t) {
-                            const uint32_t at = (first + (t < cntl ? t : 0u)) & 63u;
-                            const float a1 = sh->tail_s1[at], a2 = sh->tail_s2[at];
-                            const uint32_t ai = sh->tail_i1[at];
-                            top2_push(t2, t < cntl ? a1 : __builtin_inff(), ai);
-                            top2_push(t2, t < cntl ? a2 : __builtin_inff(), kNoNode);
+                        constexpr int ND = kDealDepth > 0 ? kDealDepth : 1;
+                        constexpr int NF = kDealFlight < ND ? kDealFlight : ND;   // blocks in flight
+                        bool mine[ND];
+                        float offo[NF][3];
+                        cuint4 v[NF][4];
+                        auto fetch = [&](int u) {   // pair lane + 64 u: its owner's query, its cell, its block on the way
+                            const int f = u % NF;
+                            const uint32_t kk = lane_d + 64u * (uint32_t)u;
+                            mine[u] = kk < total;
+                            const uint32_t pr = sh->tail_pair[mine[u] ? kk : 0u];
+                            const uint32_t ow = pr & 63u;
+                            float tqo[3];
+                            uint32_t cqo[3], cco[3];
+#pragma unroll
+                            for (int k = 0; k < 3; ++k) {
+                                tqo[k] = k < DIM ? lbits_f32((uint32_t)__builtin_amdgcn_ds_bpermute((int)(ow << 2), (int)lf32_bits(tq[k]))) : 0.0f;
+                                cqo[k] = k < DIM ? (uint32_t)__builtin_amdgcn_ds_bpermute((int)(ow << 2), (int)cq[k]) : 0u;
+                            }
+                            const uint32_t o = mine[u] ? order_o(pr >> 8) : 13u;
+                            const uint32_t o3 = (o * 11u) >> 5, o9 = (o3 * 11u) >> 5;   // o / 3, o / 9 for o < 27
+                            cco[0] = cqo[0] + (o - 3u * o3) - 1u;
+                            cco[1] = cqo[1] + (o3 - 3u * o9) - 1u;
+                            cco[2] = cqo[2] + o9 - 1u;
+#pragma unroll
+                            for (int k = 0; k < 3; ++k) offo[f][k] = ((float)cco[k] + 0x1p-17f) - tqo[k];   // (as cell_visit forms it)
+                            block_load(blk, mine[u] ? (cco[2] * grid.G[1] + cco[1]) * grid.G[0] + cco[0] : 0u, v[f]);
+                        };
+#pragma unroll
+                        for (int u = 0; u < ND; ++u) mine[u] = false;
+#pragma unroll
+                        for (int u = 0; u < NF; ++u) fetch(u);
+                        // a block is evaluated and its result handed on before the next one is touched: no per-pair Top2s pile up
+#pragma unroll
+                        for (int u = 0; u < ND; ++u) {
+                            if (u > 0 && __ballot(mine[u]) == 0) break;   // (uniform)
+                            Top2 tp{__builtin_inff(), __builtin_inff(), kNoNode};
+                            const int f = u % NF;
+                            const uint32_t cnt = mine[u] ? v[f][0][0] : 0u;
+                            block_eval<DIM>(v[f], cnt < kBlkEntries ? cnt : kBlkEntries, offo[f], tp);
+                            if (__ballot(cnt > kBlkEntries) != 0) chain_follow<DIM>(blk, v[f][0][1], cnt, mine[u], offo[f], tp);
+                            if (u + NF < ND && total > 64u * (uint32_t)(u + NF)) fetch(u + NF);   // (uniform) the freed registers take the next block
+                            const uint32_t kk = lane_d + 64u * (uint32_t)u;
+                            if (kDealAtomic) {
+                                // MERGE THROUGH LDS ATOMICS: a returning 64-bit unsigned min of (bits(s1) << 32 | entry word) into the owner's
+                                // slot.  Non-negative binary32 values order like their bit patterns and a NaN's pattern lies above +inf's: it
+                                // loses, as it does under top2_push's '<'.  Whichever of the two words does not stay in the slot -- this pair's,
+                                // or the one it displaced -- goes, with this pair's s2, into a 32-bit min on the owner's second slot: every
+                                // value but the final best loses exactly once, so that slot ends as the second smallest value of all pairs.
+                                // On an exact tie in s1 the slot may name another node than the owner loop's push order would; then s2 == s1,
+                                // the margin clause fails and the query is settled exactly, from s1 alone: no result can differ.
+                                // (The owner is read from the list again: held, it is a register per block in flight.)
+                                const uint32_t ow = sh->tail_pair[mine[u] ? kk : 0u] & 63u;
+                                const uint64_t pk = ((uint64_t)lf32_bits(tp.s1) << 32) | tp.i1;
+                                if (mine[u]) {
+                                    const uint64_t was = __hip_atomic_fetch_min(&sh->deal_best[ow], pk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                                    const uint32_t lost = (uint32_t)((was > pk ? was : pk) >> 32), s2b = lf32_bits(tp.s2);
+                                    __hip_atomic_fetch_min(&sh->tail_i1[ow], lost < s2b ? lost : s2b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                                }
+                            } else {
+                                rs1[kk] = tp.s1;
+                                rs2[kk] = tp.s2;
+                                ri1[kk] = tp.i1;
+                            }
+                        }
+                        __builtin_amdgcn_wave_barrier();   // (the wave's LDS operations complete in order; this only pins the program order)
+                        if (kDealAtomic) {
+                            const uint64_t b1 = sh->deal_best[lane_d];
+                            t2.s1 = lbits_f32((uint32_t)(b1 >> 32));
+                            t2.i1 = (uint32_t)b1;
+                            t2.s2 = lbits_f32(sh->tail_i1[lane_d]);
+                        } else {
+                            for (uint32_t t = 0; __ballot(t < cntl) != 0; ++t) {
+                                const uint32_t at = t < cntl ? first + t : 0u;
+                                const float a1 = rs1[at], a2 = rs2[at];
+                                const uint32_t ai = ri1[at];
+                                top2_push(t2, t < cntl ? a1 : __builtin_inff(), ai);
+                                top2_push(t2, t < cntl ? a2 : __builtin_inff(), kNoNode);
+                            }
                         }
                         need = 0;
                         break;
@@ -953,7 +1080,6 @@ __global__ __launch_bounds__(kCellsWaves * 64, FROZEN ? OXHIP_CELLS_WAVES_PER_EU
                     ++h_trips[tn];
                 }
                 ++trip_no;
-                constexpr int NB = FROZEN ? OXHIP_CELLS_NB_FROZEN : OXHIP_CELLS_NB;
                 bool on[NB];
                 uint32_t cc[NB][3], cnt[NB];
                 cuint4 v[NB][4];

@@ -31,7 +31,7 @@ def show(tag, g, iters):
     ci = (40, 41, 42, 43, 44, 46, 47, 48)
     print("   neighbour trips by number (trips: lanes asking / cells asked for, per trip): " +
           ", ".join("%d: %.1f / %.1f" % (int(s[24 + i]), int(s[16 + i]) / max(1, int(s[24 + i])), int(s[ci[i]]) / max(1, int(s[24 + i]))) for i in range(8)))
-    print("   tail passes %d, pairs per pass %.1f" % (int(s[1]), int(s[2]) / max(1, int(s[1]))))
+    print("   dealt passes %d (per round %.2f), pairs per dealt pass %.1f" % (int(s[1]), int(s[1]) / rounds, int(s[2]) / max(1, int(s[1]))))
     if "steady" in tag:
         print("   progress board of the launch, summed over the XCDs: %d units (the problems' quota: %d)"
               % (int(s[capi.STAMP_CELLS_BOARD]), P * int(capi.lib().oxhip_cells_problem_quota((4096 + 63) // 64, split))))
