@@ -5,8 +5,11 @@ RRTBatch.check_motion for every bit of the pair matrix, the Python DP of tests/s
 distance_batch / so3_op_batch for whole results, and tests/golden/simplify_golden.json (the CPU oracle's own paths, verdicts and
 distances) for the scenes that have an oracle check_motion.
 
-L = 1 cannot be produced through the ABI: goal_node is only ever a node that solve inserted, so the shortest path a batch can
-hold has two states (the kernels take L = 1 as the model does; tests/test_simplify_dp_model.py covers it there)."""
+Every path here comes from a solve.  A path of any other shape can be planted: set_tree, then revalidate_trees() while the batch has
+no obstacles (nothing is removed, goal_node becomes the lowest index >= 1 whose state satisfies the goal), then the obstacles;
+tests/test_gpu_simplify_limits.py does that for long, tying, far-away and degenerate paths.  L = 1 alone cannot be produced through the
+ABI, since goal_node is never the root: the shortest path a batch can hold has two states (the kernels take L = 1 as the model does;
+tests/test_simplify_dp_model.py covers it there)."""
 import json
 import math
 import os
