@@ -37,6 +37,16 @@ def csr(edge_lists):
     return offsets, nbrs
 
 
+def symmetric_lists(n, pairs):
+    """the ascending edge lists of n milestones joined by the undirected pairs (u, v), u != v (a pair named twice counts once)"""
+    rows = [set() for _ in range(n)]
+    for u, v in pairs:
+        assert u != v
+        rows[u].add(int(v))
+        rows[v].add(int(u))
+    return [sorted(r) for r in rows]
+
+
 def edge_lists(offsets, nbrs):
     return [[int(v) for v in nbrs[int(offsets[i]):int(offsets[i + 1])]] for i in range(len(offsets) - 1)]
 
