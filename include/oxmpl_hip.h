@@ -111,10 +111,27 @@ typedef enum oxhip_space_kind {
                                      validity = cones (oxhip_rrt_batch_set_spheres; set_boxes is OXHIP_ERR_BAD_ARG).
                                      PRM (oxhip_prm_config.space, prm_so3.hip): radius rule only (knn_k must be 0); cones by
                                      oxhip_prm_set_spheres (set_boxes is OXHIP_ERR_BAD_ARG); goal = ball in the SO(3) distance */
-    OXHIP_SPACE_SE3 = 3           /* R^3 x SO(3), see above: dim must be 7; planner must be OXHIP_PLANNER_RRT_CONNECT with kernel
+    OXHIP_SPACE_SE3 = 3,          /* R^3 x SO(3), see above: dim must be 7; planner must be OXHIP_PLANNER_RRT_CONNECT with kernel
                                      OXHIP_KERNEL_AUTO or OXHIP_KERNEL_STREAM (both run rrt_connect_se3.hip); goal sampler CENTRE;
                                      validity = oxhip_rrt_batch_set_body + oxhip_rrt_batch_set_spheres (set_boxes and
                                      set_segments are OXHIP_ERR_BAD_ARG).  Not a PRM space. */
+    OXHIP_SPACE_SO2 = 16          /* SO2StateSpace  oxmpl/src/base/spaces/so2_state_space.rs (rrt_so2.hip): dim
+                                     must be 1, one angle per state.  bounds[0..1] = (lo, hi): !(lo < hi) is OXHIP_ERR_ZERO_VOLUME -- the
+                                     reference's InvalidBound for lo >= hi, and a NaN bound is refused the same way, as the SE(2)
+                                     heading's is; clamped to [-PI, PI] (the full circle is (-PI, PI)); bounds[2..] are ignored.
+                                     States are taken as given: starts, goal centres and planted trees are NOT normalised
+                                     (SO2State::new normalises, a struct literal does not; the caller chooses).
+                                     distance = |rem_euclid(a - b + PI, 2 PI) - PI|; interpolate = the shortest way round on the
+                                     normalised ends, from + diff * t on the un-normalised `from`, then normalise; sample =
+                                     random_range(lo..hi); extent PI, lvsl = PI * fraction, check_motion steps of lvsl * 0.1 (more than
+                                     1e6 validity checks per edge are refused).  Add, subtract, multiply, divide and fmod only: apart
+                                     from the RNG stream a run is bit-identical to the reference.
+                                     Planner must be OXHIP_PLANNER_RRT with kernel OXHIP_KERNEL_AUTO or OXHIP_KERNEL_STREAM (both run
+                                     rrt_so2.hip); goal = distance(s, target) <= radius, sample_goal = OXHIP_GOAL_SAMPLE_CENTRE.
+                                     Validity = forbidden arcs: oxhip_rrt_batch_set_boxes with 1-wide rows (min, max), any number; a
+                                     state is valid iff its normalised value lies in no closed arc [min, max] (the
+                                     ForbiddenAngleChecker of oxmpl/tests/rrt_so2ss_tests.rs).  set_spheres, set_segments and set_body
+                                     are OXHIP_ERR_BAD_ARG.  Not a PRM space.  (The values 4 .. 15 stay unknown space kinds.) */
 } oxhip_space_kind;
 
 /* GoalSampleableRegion::sample_goal of the ball goal (goal.rs:35-41; the trait leaves the distribution to the implementor).
@@ -224,6 +241,7 @@ int32_t oxhip_rrt_batch_destroy(oxhip_rrt_batch* b);
  * (the wall of oxmpl/tests/rrt_rvss_tests.rs:24-36).  Replaces any earlier field. */
 int32_t oxhip_rrt_batch_set_spheres(oxhip_rrt_batch* b, const double* centres /*[n][dim]*/,
                                     const double* radii /*[n]*/, uint32_t n);
+/* (OXHIP_SPACE_SO2: set_boxes takes the forbidden arcs, 1-wide rows: lo[j] = an arc's minimum, hi[j] = its maximum.) */
 int32_t oxhip_rrt_batch_set_boxes(oxhip_rrt_batch* b, const double* lo /*[n][dim]*/,
                                   const double* hi /*[n][dim]*/, uint32_t n);
 
@@ -256,8 +274,8 @@ int32_t oxhip_rrt_batch_set_tree(oxhip_rrt_batch* b, uint32_t problem, const dou
 
 /* ---- re-checking the trees against the obstacles as they are now (rrt_revalidate.hip) ----
  * The semantics are this build's own (the reference has no such call).  OXHIP_PLANNER_RRT over OXHIP_SPACE_REAL_VECTOR (every
- * dimension, spheres and boxes) and OXHIP_SPACE_SO3 (cones), every kernel kind.  For every problem, against the batch's current
- * spheres / boxes / cones (the midpoint filter and the sphere grid are refreshed first, as solve does):
+ * dimension, spheres and boxes), OXHIP_SPACE_SO3 (cones) and OXHIP_SPACE_SO2 (arcs), every kernel kind.  For every problem,
+ * against the batch's current spheres / boxes / cones / arcs (the midpoint filter and the sphere grid are refreshed first, as solve does):
  *   edge_ok[i], i >= 1, is the verdict of the batch's own check_motion(from = node parent[i], to = node i) -- the direction the
  *     planner checked the edge in, the bits of oxhip_rrt_batch_check_motion on the same two rows, for an edge of any length (a
  *     planted tree may hold such).  With unchanged obstacles every edge a kernel grew passes and the call changes nothing.
@@ -343,8 +361,8 @@ int32_t oxhip_rrt_batch_get_costs(oxhip_rrt_batch* b, uint32_t problem, double* 
  *                 oxhip_distance_batch / oxhip_so3_op_batch op 0.
  *   outputs       the simplified path is the parent chain from L - 1; simplified_cost = cost[L - 1]; raw_cost is the
  *                 left-to-right sum over adjacent edges.  Hence simplified_cost <= raw_cost exactly, and both ends are kept.
- * Built for OXHIP_SPACE_REAL_VECTOR (dim 2 .. 8, spheres and boxes, RRT / RRTConnect / RRT*) and OXHIP_SPACE_SO3; SE(2) and
- * SE(3) batches return OXHIP_ERR_BAD_ARG ("not built").  chunk_problems: problems per device round, 0 = automatic (a round's
+ * Built for OXHIP_SPACE_REAL_VECTOR (dim 2 .. 8, spheres and boxes, RRT / RRTConnect / RRT*), OXHIP_SPACE_SO3 and
+ * OXHIP_SPACE_SO2 (an edge costs its SO(2) distance); SE(2) and SE(3) batches return OXHIP_ERR_BAD_ARG ("not built").  chunk_problems: problems per device round, 0 = automatic (a round's
  * bit matrices stay within 1 GiB; a single path whose matrix is larger is OXHIP_ERR_CAPACITY: pass a max_span); results never
  * depend on it.  get_simplified_paths: problem p's simplified states are rows offsets[p] .. offsets[p+1] of `states`, `indices`
  * their positions in the raw path; any of the three may be NULL.  get_simplify_results: per problem raw_cost, simplified_cost
@@ -423,7 +441,7 @@ int32_t oxhip_interpolate_batch(int32_t device, uint32_t dim, const double* from
 
 /* StateValidityChecker::is_valid for n states and RRT::check_motion (rrt.rs:90-116) for n
  * (from,to) pairs against the batch's current sphere/box field and space resolution (SE(2): segments; SO(3): cones,
- * interpolated as the SO(3) space does). */
+ * interpolated as the SO(3) space does; SO(2): arcs, interpolated the shortest way round). */
 int32_t oxhip_rrt_batch_is_valid(oxhip_rrt_batch* b, const double* states, uint32_t n, uint8_t* out);
 int32_t oxhip_rrt_batch_check_motion(oxhip_rrt_batch* b, const double* from, const double* to,
                                      uint32_t n, uint8_t* out);

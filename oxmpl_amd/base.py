@@ -162,6 +162,74 @@ class SO3ConeValidityChecker:
             self.cones.append((list(c), float(radius)))
 
 
+def _so2_normalise(v):
+    # (v + PI).rem_euclid(2 PI) - PI: math.fmod is C's fmod, exact, as Rust's `%` on f64
+    r = math.fmod(v + math.pi, 2.0 * math.pi)
+    if r < 0.0:
+        r = r + 2.0 * math.pi
+    return r - math.pi
+
+
+class SO2State:
+    """oxmpl_py.base.SO2State: an angle in radians.  SO2State(value) normalises to [-PI, PI) as SO2State::new does
+    (oxmpl/src/base/states/so2_state.rs:33-37)."""
+
+    def __init__(self, value):
+        self.value = _so2_normalise(float(value))
+
+    @property
+    def values(self):
+        return [self.value]
+
+    def __eq__(self, other):
+        return isinstance(other, SO2State) and self.value == other.value
+
+    def __repr__(self):
+        return "<SO2State value=%r>" % self.value
+
+
+class SO2StateSpace:
+    """oxmpl_py.base.SO2StateSpace: SO2StateSpace(bounds=None | (lo, hi)).  None: the full circle (-PI, PI).  lo >= hi is
+    ValueError (StateSpaceError::InvalidBound); the bounds are clamped to [-PI, PI]
+    (oxmpl/src/base/spaces/so2_state_space.rs:57-74).  `distance` is add, subtract and fmod only: evaluated here, the bits
+    are the device's."""
+
+    def __init__(self, bounds=None):
+        lo, hi = (-math.pi, math.pi) if bounds is None else (float(bounds[0]), float(bounds[1]))
+        if not lo < hi:
+            raise ValueError("Invalid bound: lower %s must be less than upper %s." % (lo, hi))
+        self.bounds = (max(lo, -math.pi), min(hi, math.pi))
+        self.dimension = 1
+        self.longest_valid_segment_fraction = 0.05
+
+    def distance(self, state1, state2):
+        return abs(_so2_normalise(state1.value - state2.value))
+
+    def get_maximum_extent(self):
+        return math.pi
+
+    def set_longest_valid_segment_fraction(self, fraction):
+        if 0.0 < fraction <= 1.0:
+            self.longest_valid_segment_fraction = float(fraction)
+        elif fraction <= 0.0:
+            self.longest_valid_segment_fraction = 0.0
+        else:
+            self.longest_valid_segment_fraction = 1.0
+
+    def config_bounds(self):
+        """the C ABI's reading of oxhip_rrt_config.bounds for SO(2): (lo, hi)"""
+        return [self.bounds[0], self.bounds[1]]
+
+
+class SO2ArcValidityChecker:
+    """Device-describable StateValidityChecker of SO(2): a state is valid iff its normalised value lies in no arc
+    [min, max], closed on both ends -- the ForbiddenAngleChecker of oxmpl/tests/rrt_so2ss_tests.rs, any number of them.
+    Pass it to RRT.setup() with an SO(2) ProblemDefinition."""
+
+    def __init__(self, arcs=()):
+        self.arcs = [(float(lo), float(hi)) for lo, hi in arcs]
+
+
 class SE3State:
     """A rigid-body pose: position (x, y, z) and a rotation (SO3State).  The reference has no SE(3) state yet
     (docs/BACKLOG.md:12-14); this is the compound of its RealVectorState and SO3State.  `values` is the C ABI's row
@@ -272,6 +340,18 @@ class ProblemDefinition:
             raise TypeError("the GPU path needs a ball goal: an object with `target` and `radius` attributes")
         if not isinstance(start_state, SO3State) or not isinstance(goal.target, SO3State):
             raise TypeError("start_state and goal.target must be SO3State")
+        return ProblemDefinition(space, start_state, goal)
+
+    @staticmethod
+    def from_so2(space, start_state, goal):
+        """oxmpl_py ProblemDefinition.from_so2.  `goal`: any object with a `target` (SO2State) and a `radius`;
+        is_satisfied(s) = distance(s, target) <= radius, sample_goal() = target (the fixture's arc sampler is not built)."""
+        if not isinstance(space, SO2StateSpace):
+            raise TypeError("space must be an SO2StateSpace")
+        if not hasattr(goal, "target") or not hasattr(goal, "radius"):
+            raise TypeError("the GPU path needs a ball goal: an object with `target` and `radius` attributes")
+        if not isinstance(start_state, SO2State) or not isinstance(goal.target, SO2State):
+            raise TypeError("start_state and goal.target must be SO2State")
         return ProblemDefinition(space, start_state, goal)
 
     @staticmethod

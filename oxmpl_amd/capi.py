@@ -33,6 +33,7 @@ STAMP_WORDS = 64
 STAMP_CELLS_BOARD = 3
 PLANNER_RRT, PLANNER_RRT_CONNECT, PLANNER_RRT_STAR = 0, 1, 2
 SPACE_REAL_VECTOR, SPACE_SE2, SPACE_SO3, SPACE_SE3 = 0, 1, 2, 3
+SPACE_SO2 = 16   # (4 .. 15 are no space kinds)
 SE3_MAX_BODY = 16
 
 # every symbol include/oxmpl_hip.h declares (tests check the library exports them all)
@@ -235,6 +236,9 @@ class RRTBatch:
     space=SPACE_SO3 (dim 4, quaternions (x, y, z, w)): `bounds` is (cx, cy, cz, cw, max_angle) -- SO3StateSpace's centre
     quaternion and cone of freedom, as include/oxmpl_hip.h reinterprets the config's bounds -- and set_spheres takes the
     forbidden cones (centre quaternion, radius in the SO(3) distance).
+
+    space=SPACE_SO2 (dim 1, one angle per state, taken as given): `bounds` is (lo, hi), clamped to [-PI, PI] by the library, and
+    set_boxes takes the forbidden arcs as 1-wide rows: lo = the arcs' minima, hi = their maxima.
 
     space=SPACE_SE3 (dim 7, states (x, y, z, qx, qy, qz, qw); planner=PLANNER_RRT_CONNECT): `bounds` holds eleven values, the
     (lo, hi) pairs of x, y, z and then (cx, cy, cz, cw, max_angle) of the rotation; set_body gives the rigid body's spheres

@@ -131,7 +131,7 @@ static hipError_t grow(DevBuf<T>& buf, size_t count) {   // keeps a buffer that 
 }
 
 // ------------------------------------------------------------------ the spaces
-// One row per oxhip_space: what create(), the set_* calls, setup, solve and the path entry points need to know about a space,
+// One row per oxhip_space (kinds 0 .. OXHIP_SPACE_SE3 by index, OXHIP_SPACE_SO2 = 16 behind them: space_row): what create(), the set_* calls, setup, solve and the path entry points need to know about a space,
 // as data.  A refusal text that is null means "accepted".  Adding a space = adding a row (and its launchers).
 struct SpaceRow {
     uint32_t dim;               const char* bad_dim;       // the cfg.dim the space requires (0 = any), and the refusal
@@ -152,7 +152,8 @@ static constexpr uint32_t kRrt = 1u << OXHIP_PLANNER_RRT, kConnect = 1u << OXHIP
 static const char* const kNoSegments = "segments describe the SE(2) checker";
 static const char* const kNoBody = "a body describes the SE(3) checker";
 static const char* const kNoSimplifySe = "simplify_paths is not built for SE(2) / SE(3) batches (their motion checks live inside their planners' kernels)";
-static const SpaceRow kSpaces[OXHIP_SPACE_SE3 + 1] = {
+static const char* const kSo2Arcs = "SO(2) batches take forbidden arcs (oxhip_rrt_batch_set_boxes with 1-wide rows (min, max))";
+static const SpaceRow kSpaces[OXHIP_SPACE_SE3 + 2] = {
     /* OXHIP_SPACE_REAL_VECTOR */ {
         0, nullptr, kRrt | kConnect | kStar, nullptr, nullptr,
         0, nullptr, nullptr, kNoSegments, kNoBody,
@@ -183,8 +184,22 @@ static const SpaceRow kSpaces[OXHIP_SPACE_SE3 + 1] = {
         [](oxhip_rrt_batch* b) -> int32_t { launch_rrt_connect_se3(b->dp, b->se3, b->stream); return OXHIP_OK; },
         [](oxhip_rrt_batch* b, const double* s, uint32_t n, uint8_t* out) { launch_se3_is_valid(b->dp, b->se3, s, n, out, b->stream); },
         [](oxhip_rrt_batch* b, const double* f, const double* t, uint32_t n, uint8_t* out) { launch_se3_check_motion(b->dp, b->se3, f, t, n, out, b->stream); }},
+    /* OXHIP_SPACE_SO2 */ {   // arcs: min <= normalise(v) <= max, closed; rrt_so2.hip tests every arc
+        1, "SO(2) states are one angle: dim must be 1", kRrt, "SO(2) is built for RRT only",
+        "SO(2) RRT runs on rrt_so2.hip: kernel must be OXHIP_KERNEL_AUTO or OXHIP_KERNEL_STREAM",
+        0, kSo2Arcs, nullptr, kSo2Arcs, kSo2Arcs,
+        false, true, false, nullptr,
+        [](oxhip_rrt_batch* b) -> int32_t { launch_rrt_so2(b->dp, b->stream); return OXHIP_OK; },
+        [](oxhip_rrt_batch* b, const double* s, uint32_t n, uint8_t* out) { launch_so2_is_valid(b->dp, s, n, out, b->stream); },
+        [](oxhip_rrt_batch* b, const double* f, const double* t, uint32_t n, uint8_t* out) { launch_so2_check_motion(b->dp, f, t, n, out, b->stream); }},
 };
-static const SpaceRow& space_of(const oxhip_rrt_batch* b) { return kSpaces[b->cfg.space]; }   // (create() refused other kinds)
+// the row of a space kind, null for an unknown one (the kinds are not contiguous: 4 .. 15 are no spaces)
+static const SpaceRow* space_row(uint32_t space) {
+    if (space <= OXHIP_SPACE_SE3) return &kSpaces[space];
+    if (space == OXHIP_SPACE_SO2) return &kSpaces[OXHIP_SPACE_SE3 + 1];
+    return nullptr;
+}
+static const SpaceRow& space_of(const oxhip_rrt_batch* b) { return *space_row(b->cfg.space); }   // (create() refused other kinds)
 
 // ------------------------------------------------------------------ the entry points' shared openings
 // The batch exists, setup() ran and `problem` (if one is given) is in range: what most entry points check first.  Pure host code.
@@ -240,8 +255,8 @@ static int32_t validate_config(const oxhip_rrt_config* cfg, Resolved& r) {
         return fail(OXHIP_ERR_BAD_ARG, "the disc sampler (rrt_rvss_tests.rs:55-66) is defined for RealVectorStateSpace(2)");
     if (cfg->goal_sampler == OXHIP_GOAL_SAMPLE_UNIFORM_DISC && (cfg->planner == OXHIP_PLANNER_RRT_CONNECT || cfg->kernel == OXHIP_KERNEL_RESIDENT))
         return fail(OXHIP_ERR_BAD_ARG, "the disc sampler is built for RRT / RRT* on the stream, lane-per-query and cell-grid kernels");
-    if (cfg->space > OXHIP_SPACE_SE3) return fail(OXHIP_ERR_BAD_ARG, "unknown space kind");
-    const SpaceRow& row = kSpaces[cfg->space];
+    if (!space_row(cfg->space)) return fail(OXHIP_ERR_BAD_ARG, "unknown space kind");
+    const SpaceRow& row = *space_row(cfg->space);
     if (row.dim != 0 && cfg->dim != row.dim) return fail(OXHIP_ERR_BAD_ARG, row.bad_dim);
     if (((row.planners >> cfg->planner) & 1u) == 0) return fail(OXHIP_ERR_BAD_ARG, row.bad_planner);
     if (row.one_kernel && cfg->kernel != OXHIP_KERNEL_AUTO && cfg->kernel != OXHIP_KERNEL_STREAM) return fail(OXHIP_ERR_BAD_ARG, row.one_kernel);
@@ -259,6 +274,8 @@ static int32_t validate_config(const oxhip_rrt_config* cfg, Resolved& r) {
     } else if (cfg->space == OXHIP_SPACE_SO3) {
         OX_TRY(so3_space_resolution(cfg->dim, cfg->bounds, r.fraction, r.res, r.so3_max_angle));   // centre, max_angle, fraction
         rot = cfg->bounds;
+    } else if (cfg->space == OXHIP_SPACE_SO2) {
+        OX_TRY(so2_space_resolution(cfg->bounds, r.fraction, r.res, r.lo[0], r.hi[0]));   // (lo, hi) clamped, fraction
     } else if (cfg->space == OXHIP_SPACE_SE2) {
         // SO2StateSpace::new (so2_state_space.rs:57-72): lo >= hi is InvalidBound; bounds clamped to [-PI, PI]
         const double pi = 3.14159265358979323846;
@@ -1229,7 +1246,7 @@ static int32_t pair_params(oxhip_rrt_batch* b, double& filt_base) {
 
 static int32_t simplify_supported(const oxhip_rrt_batch* b) {
     if (space_of(b).no_simplify) return fail(OXHIP_ERR_BAD_ARG, space_of(b).no_simplify);
-    if (b->cfg.dim < 2)   // (R^1: every other space is wider)
+    if (b->cfg.dim < 2 && b->cfg.space == OXHIP_SPACE_REAL_VECTOR)   // (R^1; SO(2)'s one angle is built)
         return fail(OXHIP_ERR_BAD_ARG, "simplify_paths is not built for dim 1 (R^2 .. R^8 and SO(3))");
     return OXHIP_OK;
 }

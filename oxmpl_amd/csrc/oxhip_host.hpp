@@ -2,7 +2,7 @@
 // RRTConnect batches and primitives; oxhip_prm_api.hip: PRM).  Not installed.
 //
 // What oxhip_api.hip builds from them: the table of spaces (kSpaces, one row per oxhip_space) and create() in its steps --
-// validate_config (pure host code: space_resolution, se_space_resolution and so3_space_resolution below), fill_params,
+// validate_config (pure host code: space_resolution, se_space_resolution, so3_space_resolution and so2_space_resolution below), fill_params,
 // alloc_common (alloc_star at its place), the kernel kind, alloc_cells, alloc_shadow -- and the entry points' shared openings
 // (setup_done / ready) and bodies (copy_tree, op_batch with a TmpStream).  oxhip_prm_api.hip takes the same resolution helpers for
 // validate_prm_config, DevBuf::reserve for its workspaces and prm_bfs_path, the graph search of Planner::solve.  No device code.
@@ -210,6 +210,23 @@ inline int32_t so3_space_resolution(uint32_t dim, const double* bounds, double& 
     res = lvsl * 0.1;
     if (!(res > 0.0)) return fail(OXHIP_ERR_BAD_ARG, "longest valid segment length is 0: check_motion would never terminate");
     if (0.5 * pi / res > 1e6) return fail(OXHIP_ERR_BAD_ARG, "more than 1e6 validity checks per edge");
+    return OXHIP_OK;
+}
+
+// SO2StateSpace::new + get_longest_valid_segment_length for a config whose bounds[0..1] are (lo, hi) (include/oxmpl_hip.h,
+// OXHIP_SPACE_SO2): lo >= hi is StateSpaceError::InvalidBound (so2_state_space.rs:57-74; written !(lo < hi), which refuses a NaN
+// bound too), the bounds are clamped to [-PI, PI], the fraction is clamped (:83-91) and res = PI * fraction * 0.1 (extent PI,
+// :78-80; rrt.rs:97).  No SO(2) distance exceeds PI, which bounds the step count of every motion.
+inline int32_t so2_space_resolution(const double* bounds, double& fraction, double& res, double& lo, double& hi) {
+    const double pi = 3.14159265358979323846;
+    if (!(bounds[0] < bounds[1])) return fail(OXHIP_ERR_ZERO_VOLUME, "SO(2): lower bound >= upper bound");
+    lo = bounds[0] > -pi ? bounds[0] : -pi;   // f64::max / f64::min
+    hi = bounds[1] < pi ? bounds[1] : pi;
+    if (fraction > 0.0 && fraction <= 1.0) {} else if (fraction <= 0.0) fraction = 0.0; else fraction = 1.0;
+    const double lvsl = pi * fraction;
+    res = lvsl * 0.1;
+    if (!(res > 0.0)) return fail(OXHIP_ERR_BAD_ARG, "longest valid segment length is 0: check_motion would never terminate");
+    if (pi / res > 1e6) return fail(OXHIP_ERR_BAD_ARG, "more than 1e6 validity checks per edge");
     return OXHIP_OK;
 }
 

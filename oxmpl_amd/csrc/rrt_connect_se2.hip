@@ -17,38 +17,10 @@
 #include "oxhip_internal.hpp"
 #include "rrt_device.hpp"
 #include "lane_sampler.hpp"
+#include "so2_device.hpp"
 
 namespace oxhip {
 
-#define OXHIP_PI 3.14159265358979323846   // std::f64::consts::PI = 0x400921FB54442D18
-
-// f64::rem_euclid(a, 2*PI): r = a % (2*PI); if r < 0.0 { r + 2*PI } else { r }.  fmod is exact, and for
-// -2*PI < a < 4*PI it needs no division: a in [2*PI, 4*PI) gives a - 2*PI (exact by Sterbenz' lemma, which is
-// fmod's value), a in [0, 2*PI) gives a, a in (-2*PI, 0) gives a, to which the reference then adds 2*PI -- the
-// same rounded addition.  Everything a planner run produces lies in that window; the rest takes fmod.
-__device__ __forceinline__ double rem_euclid_2pi(double a) {
-    const double b = 2.0 * OXHIP_PI;
-    // the window, by selects (one uniform branch instead of a chain of divergent ones: this runs several times per extend)
-    double r = a;                                  // a in [0, b), a in (-b, 0), -0.0: fmod's value is a itself
-    r = (a >= b) ? a - b : r;                      // a in [b, 2 b): fmod's value, exactly (Sterbenz)
-    if (__builtin_expect(__ballot(!(a > -b && a < 2.0 * b)) != 0, 0)) {   // outside the window (or NaN): fmod proper
-        if (!(a > -b && a < 2.0 * b)) r = fmod(a, b);
-    }
-    return r < 0.0 ? r + b : r;
-}
-__device__ __forceinline__ double so2_normalise(double v) { return rem_euclid_2pi(v + OXHIP_PI) - OXHIP_PI; }
-__device__ __forceinline__ double so2_distance(double a, double b) {
-    double diff = a - b;
-    diff = rem_euclid_2pi(diff + OXHIP_PI) - OXHIP_PI;
-    return fabs(diff);
-}
-__device__ __forceinline__ double so2_interpolate(double from, double to, double t) {
-    double d = so2_normalise(to) - so2_normalise(from);
-    if (d > OXHIP_PI) d -= 2.0 * OXHIP_PI;
-    else if (d < -OXHIP_PI) d += 2.0 * OXHIP_PI;
-    const double out = from + d * t;
-    return so2_normalise(out);
-}
 __device__ __forceinline__ double se2_distance(const double a[3], const double b[3]) {
     const double dr = sqrt(dist2<2>(a, b, 2));
     const double ws = 0.5 * so2_distance(a[2], b[2]);

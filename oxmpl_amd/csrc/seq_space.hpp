@@ -1,13 +1,15 @@
 // seq_space.hpp -- the state space as ONE thread sees it: the kernels in which a thread owns a state or a motion of its own (PRM's
 // query sets, the re-check, the shortcutter's pair matrix, the shortest paths' weights) are written once over SeqSpace<DIM>.
-// DIM = 1..8 is R^DIM, DIM = 0 is SO(3) (unit quaternions among forbidden cones).  The members forward to motion_seq.hpp /
-// so3_motion_seq.hpp / so3_device.hpp, so every bit is the one those functions give.  space_dispatch is the host's way in.
+// DIM = 1..8 is R^DIM, DIM = 0 is SO(3) (unit quaternions among forbidden cones), DIM = -1 is SO(2) (one angle among forbidden
+// arcs).  The members forward to motion_seq.hpp / so3_motion_seq.hpp / so3_device.hpp / so2_device.hpp, so every bit is the one
+// those functions give.  space_dispatch is the host's way in (R^n or SO(3); the SO(2) instantiations live in rrt_so2_services.hip).
 #pragma once
 #include <type_traits>
 #include <utility>
 
 #include "rrt_device.hpp"
 #include "motion_seq.hpp"
+#include "so2_device.hpp"
 #include "so3_device.hpp"
 #include "so3_motion_seq.hpp"
 
@@ -85,6 +87,25 @@ struct SeqSpace<0> {                               // SO(3)
     static __device__ __forceinline__ bool state_valid(const Checker& p, const double s[4]) { return !so3_cone_hit(p.c, p.n, p.r, p.n, s); }
     static __device__ __forceinline__ bool motion_valid(const Checker& p, const double from[4], const double to[4], double = 0.0) {   // no filter
         return so3_motion_valid_seq(p.c, p.n, p.r, p.n, from, to, p.res);
+    }
+    static __device__ __forceinline__ double motion_margin(double base, const double*, const double*) { return base; }
+    static __device__ __forceinline__ Checker vgpr_pointers(const Checker& p) { return p; }   // (four scalars: nothing spills)
+};
+
+template <>
+struct SeqSpace<-1> {                              // SO(2)
+    static constexpr int W = 1;
+    using Checker = So2Arcs;
+    static Checker checker(const DevParams& p) { return So2Arcs{p.box_lo, p.box_hi, p.n_boxes, p.res}; }
+
+    static __device__ __forceinline__ void load(const double* row, double out[1]) { out[0] = row[0]; }
+    static __device__ __forceinline__ double distance(const double a[1], const double b[1]) { return so2_distance(a[0], b[0]); }
+    static __device__ __forceinline__ bool connects(const double s[1], const double m[1], double near) { return so2_distance(s[0], m[0]) < near; }
+    // goal.is_satisfied: distance(state, target) <= radius
+    static __device__ __forceinline__ double goal_measure(const double m[1], const double g[1]) { return so2_distance(m[0], g[0]); }
+    static __device__ __forceinline__ bool state_valid(const Checker& p, const double s[1]) { return !so2_arc_hit(p.lo, p.hi, p.n, s[0]); }
+    static __device__ __forceinline__ bool motion_valid(const Checker& p, const double from[1], const double to[1], double = 0.0) {   // no filter
+        return so2_motion_valid_seq(p.lo, p.hi, p.n, from[0], to[0], p.res);
     }
     static __device__ __forceinline__ double motion_margin(double base, const double*, const double*) { return base; }
     static __device__ __forceinline__ Checker vgpr_pointers(const Checker& p) { return p; }   // (four scalars: nothing spills)

@@ -11,7 +11,8 @@ import numpy as np
 
 from . import capi
 from .base import (Path, ProblemDefinition, RealVectorState, SE3RigidBodyValidityChecker, SE3State, SE3StateSpace,
-                   SO3ConeValidityChecker, SO3State, SO3StateSpace, SphereBoxValidityChecker)
+                   SO2ArcValidityChecker, SO2State, SO2StateSpace, SO3ConeValidityChecker, SO3State, SO3StateSpace,
+                   SphereBoxValidityChecker)
 
 _MESSAGES = {  # Display strings of PlanningError (oxmpl/src/base/error.rs:110-136)
     capi.ERR_TIMEOUT: "No solution found within timeout.",
@@ -46,7 +47,10 @@ class RRT:
 
     def setup(self, validity_checker):
         """Planner::setup (rrt.rs:140-156).  The reference takes a Python callable here; the GPU path
-        takes a SphereBoxValidityChecker (see oxmpl_amd.base), or an SO3ConeValidityChecker for an SO(3) problem (RRT only)."""
+        takes a SphereBoxValidityChecker (see oxmpl_amd.base), or an SO3ConeValidityChecker for an SO(3) problem (RRT only),
+        or an SO2ArcValidityChecker for an SO(2) problem (RRT only)."""
+        if isinstance(self._pd.space, SO2StateSpace):
+            return self._setup_so2(validity_checker)
         if isinstance(self._pd.space, SO3StateSpace):
             return self._setup_so3(validity_checker)
         if isinstance(self._pd.space, SE3StateSpace):
@@ -96,6 +100,36 @@ class RRT:
         self._batch = b
         self._checker = validity_checker
 
+    def _setup_so2(self, validity_checker):
+        if self._PLANNER != capi.PLANNER_RRT:
+            raise TypeError("SO(2) is built for RRT only")
+        if not isinstance(validity_checker, SO2ArcValidityChecker):
+            raise TypeError("the GPU path cannot call a Python function per interpolated state; "
+                            "describe the forbidden arcs with oxmpl_amd.base.SO2ArcValidityChecker")
+        pd = self._pd
+        if self._batch is not None:
+            self._batch.close()
+        try:
+            b = capi.RRTBatch(1, pd.space.config_bounds(), self.max_distance, self.goal_bias, 1,
+                              lvs_fraction=pd.space.longest_valid_segment_fraction, stop_at_goal=True, planner=capi.PLANNER_RRT,
+                              space=capi.SPACE_SO2, **self._opts)
+        except capi.OxhipError as e:
+            if e.status in (capi.ERR_ZERO_VOLUME, capi.ERR_BAD_ARG):
+                raise ValueError(str(e)) from None
+            raise
+        b.set_boxes([[lo] for lo, _ in validity_checker.arcs], [[hi] for _, hi in validity_checker.arcs])
+        b.setup(pd.start_state.values, pd.goal.target.values, float(pd.goal.radius))
+        self._batch = b
+        self._checker = validity_checker
+
+    def _so2_path(self, rows):
+        states = []
+        for row in rows:   # a tree's states are stored as the planner made them: no second normalisation
+            s = SO2State(0.0)
+            s.value = float(row[0])
+            states.append(s)
+        return Path(states)
+
     def _setup_se3(self, validity_checker):
         if self._PLANNER != capi.PLANNER_RRT_CONNECT:
             raise TypeError("SE(3) is built for RRTConnect only")
@@ -135,6 +169,8 @@ class RRT:
         st = self._batch.solve(1 << 40, timeout_s=timeout_secs)
         if st[0] != capi.OK:
             raise Exception(_MESSAGES.get(int(st[0]), capi.status_string(int(st[0]))))
+        if isinstance(self._pd.space, SO2StateSpace):
+            return self._so2_path(self._batch.path(0))
         if isinstance(self._pd.space, SO3StateSpace):
             return Path([SO3State(*row) for row in self._batch.path(0)])
         if isinstance(self._pd.space, SE3StateSpace):
@@ -154,6 +190,8 @@ class RRT:
             raise Exception(_MESSAGES[capi.ERR_NO_SOLUTION_FOUND])
         self._batch.simplify_paths(int(max_span))
         rows = self._batch.simplified_paths()[1]
+        if isinstance(self._pd.space, SO2StateSpace):
+            return self._so2_path(rows)
         if isinstance(self._pd.space, SO3StateSpace):
             return Path([SO3State(*row) for row in rows])
         return Path([RealVectorState(row) for row in rows])
@@ -172,7 +210,11 @@ class RRT:
         if self._batch is None:
             raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
         if validity_checker is not None:
-            if isinstance(self._pd.space, SO3StateSpace):
+            if isinstance(self._pd.space, SO2StateSpace):
+                if not isinstance(validity_checker, SO2ArcValidityChecker):
+                    raise TypeError("an SO(2) tree is re-checked against an SO2ArcValidityChecker")
+                self._batch.set_boxes([[lo] for lo, _ in validity_checker.arcs], [[hi] for _, hi in validity_checker.arcs])
+            elif isinstance(self._pd.space, SO3StateSpace):
                 if not isinstance(validity_checker, SO3ConeValidityChecker):
                     raise TypeError("an SO(3) tree is re-checked against an SO3ConeValidityChecker")
                 self._batch.set_spheres([c for c, _ in validity_checker.cones], [r for _, r in validity_checker.cones])
@@ -242,7 +284,9 @@ class PRM:
 
     def setup(self, validity_checker):
         """Planner::setup (prm.rs:217-225): stores problem and checker, clears the roadmap.  An SO(3) problem takes an
-        SO3ConeValidityChecker (the radius rule; milestones and path states are SO3State)."""
+        SO3ConeValidityChecker (the radius rule; milestones and path states are SO3State).  SO(2) is built for RRT only."""
+        if isinstance(self._pd.space, SO2StateSpace):
+            raise TypeError("SO(2) is built for RRT only")
         if isinstance(self._pd.space, SO3StateSpace):
             return self._setup_so3(validity_checker)
         if not isinstance(validity_checker, SphereBoxValidityChecker):
@@ -381,7 +425,11 @@ class PRM:
         if self._prm is None:
             raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
         if validity_checker is not None:
-            if isinstance(self._pd.space, SO3StateSpace):
+            if isinstance(self._pd.space, SO2StateSpace):
+                if not isinstance(validity_checker, SO2ArcValidityChecker):
+                    raise TypeError("an SO(2) tree is re-checked against an SO2ArcValidityChecker")
+                self._batch.set_boxes([[lo] for lo, _ in validity_checker.arcs], [[hi] for _, hi in validity_checker.arcs])
+            elif isinstance(self._pd.space, SO3StateSpace):
                 if not isinstance(validity_checker, SO3ConeValidityChecker):
                     raise TypeError("an SO(3) roadmap is re-checked against an SO3ConeValidityChecker")
                 self._prm.set_spheres([c for c, _ in validity_checker.cones], [r for _, r in validity_checker.cones])

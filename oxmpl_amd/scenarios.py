@@ -196,6 +196,24 @@ def make_se3_batch(sc, n_problems, max_nodes=10000, seed=42, first_problem_id=0,
     return b
 
 
+def so2_band():
+    """The reference's SO(2) fixture (oxmpl/tests/rrt_so2ss_tests.rs): the full circle, start -PI/2, target PI/2 with radius
+    0.1, one forbidden arc [-0.5, 0.5] between them, RRT(0.2, 0.05), fraction 0.05: every path goes round through +-PI."""
+    pi = 3.141592653589793
+    return dict(dim=1, bounds=(-pi, pi), max_distance=0.2, goal_bias=0.05, lvs_fraction=0.05,
+                start=[-pi / 2.0], goal_centre=[pi / 2.0], goal_radius=0.1, arcs=[(-0.5, 0.5)])
+
+
+def make_so2_batch(sc, n_problems, max_nodes=10000, stop_at_goal=True, seed=42, first_problem_id=0, device=0, kernel=0):
+    """RRT over SO(2) among sc["arcs"] (oxmpl_amd.capi.SPACE_SO2), set up and ready to solve."""
+    from .capi import RRTBatch, PLANNER_RRT, SPACE_SO2
+    b = RRTBatch(1, sc["bounds"], sc["max_distance"], sc["goal_bias"], n_problems, max_nodes, sc["lvs_fraction"], stop_at_goal,
+                 seed, first_problem_id, device, kernel, PLANNER_RRT, 0.0, SPACE_SO2)
+    b.set_boxes([[lo] for lo, _ in sc["arcs"]], [[hi] for _, hi in sc["arcs"]])
+    b.setup(sc["start"], sc["goal_centre"], sc["goal_radius"])
+    return b
+
+
 def config5():
     start, goal = [1.0] * 6, [9.0] * 6
     return dict(dim=6, bounds=[(0.0, 10.0)] * 6, connection_radius=2.0, lvs_fraction=0.05, max_milestones=50000,

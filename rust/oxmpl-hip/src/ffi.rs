@@ -35,6 +35,9 @@ pub const OXHIP_SPACE_SE2: u32 = 1;
 /// SO3StateSpace (rrt_so3.hip): dim 4, quaternions (x, y, z, w); bounds[0..4] = centre quaternion, bounds[4] = max_angle
 pub const OXHIP_SPACE_SO3: u32 = 2;
 pub const OXHIP_SPACE_SE3: u32 = 3;
+/// SO2StateSpace (rrt_so2.hip): dim 1, bounds[0..1] = (lo, hi), forbidden arcs through `oxhip_rrt_batch_set_boxes`.  The
+/// values 4 .. 15 are no space kinds.
+pub const OXHIP_SPACE_SO2: u32 = 16;
 // oxhip_goal_sampler: what GoalSampleableRegion::sample_goal draws (goal.rs:35-41)
 pub const OXHIP_GOAL_SAMPLE_CENTRE: u32 = 0;
 pub const OXHIP_GOAL_SAMPLE_UNIFORM_DISC: u32 = 1;

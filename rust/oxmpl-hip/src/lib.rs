@@ -33,7 +33,7 @@ use oxmpl::base::error::PlanningError;
 use oxmpl::base::goal::GoalSampleableRegion;
 use oxmpl::base::planner::{Path, Planner};
 use oxmpl::base::problem_definition::ProblemDefinition;
-use oxmpl::base::space::{RealVectorStateSpace, SO3StateSpace, StateSpace};
+use oxmpl::base::space::{RealVectorStateSpace, SO2StateSpace, SO3StateSpace, StateSpace};
 use oxmpl::base::state::{RealVectorState, SO3State};
 use oxmpl::base::validity::StateValidityChecker;
 
@@ -707,6 +707,40 @@ pub fn so3_rrt_config(space: &SO3StateSpace, max_distance: f64, goal_bias: f64, 
         planner: ffi::OXHIP_PLANNER_RRT,
         search_radius: 0.0,
         space: ffi::OXHIP_SPACE_SO3,
+        goal_sampler: ffi::OXHIP_GOAL_SAMPLE_CENTRE,
+        debug_flags: 0,
+        star_pool_share: 0,
+        frozen_split: 0,
+        reserved: 0,
+    }
+}
+
+/// `oxhip_rrt_config` of an SO(2) RRT batch of one problem: RRT::new(max_distance, goal_bias) over `space`.  The config's
+/// bounds carry SO2StateSpace::bounds (lo, hi), already clamped to [-PI, PI] by SO2StateSpace::new; `lvs_fraction` is the
+/// space's longest_valid_segment_fraction (0.05 unless set).  States cross the boundary as their `value`, un-normalised
+/// (SO2State::new normalises; the device takes what it is given).  Forbidden arcs go in through
+/// `oxhip_rrt_batch_set_boxes` with 1-wide rows (min, max).
+pub fn so2_rrt_config(space: &SO2StateSpace, max_distance: f64, goal_bias: f64, lvs_fraction: f64, options: &HipOptions) -> ffi::OxhipRrtConfig {
+    let mut bounds = [0.0f64; 2 * ffi::OXHIP_MAX_DIM];
+    bounds[0] = space.bounds.0;
+    bounds[1] = space.bounds.1;
+    ffi::OxhipRrtConfig {
+        struct_size: ffi::OXHIP_RRT_CONFIG_SIZE as u32,
+        dim: 1,
+        bounds,
+        max_distance,
+        goal_bias,
+        lvs_fraction,
+        n_problems: 1,
+        max_nodes: options.max_nodes,
+        stop_at_goal: 1,
+        kernel: ffi::OXHIP_KERNEL_AUTO,
+        seed: options.seed,
+        first_problem_id: options.stream,
+        device: options.device,
+        planner: ffi::OXHIP_PLANNER_RRT,
+        search_radius: 0.0,
+        space: ffi::OXHIP_SPACE_SO2,
         goal_sampler: ffi::OXHIP_GOAL_SAMPLE_CENTRE,
         debug_flags: 0,
         star_pool_share: 0,
