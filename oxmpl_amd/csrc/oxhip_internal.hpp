@@ -39,15 +39,6 @@ void launch_se2_check_motion(const DevParams& p, const double* from, const doubl
 void launch_rrt_so2(const DevParams& p, hipStream_t stream);
 void launch_so2_is_valid(const DevParams& p, const double* states, uint32_t n, uint8_t* out, hipStream_t s);
 void launch_so2_check_motion(const DevParams& p, const double* from, const double* to, uint32_t n, uint8_t* out, hipStream_t s);
-// rrt_so2_services.hip: the SO(2) instantiations of the re-check's and the shortcutter's kernels (they need RevalArgs / PairArgs /
-// SimplifyOut, declared below)
-struct RevalArgs;
-struct PairArgs;
-struct SimplifyOut;
-void launch_so2_reval_edges(const DevParams& p, const RevalArgs& a, uint32_t n_problems, hipStream_t s);
-void launch_so2_reval_compact(const RevalArgs& a, uint32_t n_problems, hipStream_t s);
-void launch_so2_path_pairs(const DevParams& p, const PairArgs& a, hipStream_t s);
-void launch_so2_path_dp(const PairArgs& a, const SimplifyOut& o, hipStream_t s);
 // rrt_so3.hip: RRT over SO3StateSpace with the forbidden-cone checker, one wave per problem
 void launch_rrt_so3(const DevParams& p, hipStream_t stream);
 void launch_so3_op(uint32_t op, const double* a, const double* b, const double* t, uint32_t n, double* out, hipStream_t s);

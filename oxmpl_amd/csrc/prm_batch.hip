@@ -251,7 +251,7 @@ __global__ __launch_bounds__(64) void prm_batch_paths_kernel(PrmBatchArgs b, con
 
 void launch_prm_batch_flags(bool so3, const DevParams& p, const PrmBatchArgs& b, double near, hipStream_t s) {
     const dim3 grid(b.n ? (b.n + 255) / 256 : 1, b.n_chunk);
-    space_dispatch(so3, p.dim, [&](auto d) {
+    space_dispatch(prm_space(so3), p.dim, [&](auto d) {
         constexpr int D = decltype(d)::value;
         hipLaunchKernelGGL(prm_batch_flags_kernel<D>, grid, dim3(256), 0, s, SeqSpace<D>::checker(p), b, near);
     });

@@ -730,7 +730,7 @@ void launch_prm_csr(const uint64_t* sorted, uint32_t n_keys, uint32_t n_nodes, u
 void launch_prm_query(bool so3, const DevParams& p, const PrmArgs& a, uint32_t n, const PrmQuery& q, double near, uint8_t* flags,
                       uint32_t* start_valid, hipStream_t s) {
     const uint32_t blocks = n ? (n + 255) / 256 : 1;
-    space_dispatch(so3, p.dim, [&](auto d) {
+    space_dispatch(prm_space(so3), p.dim, [&](auto d) {
         constexpr int D = decltype(d)::value;
         hipLaunchKernelGGL(prm_query_kernel<D>, dim3(blocks), dim3(256), 0, s, SeqSpace<D>::checker(p), a, n, q, near, flags, start_valid);
     });

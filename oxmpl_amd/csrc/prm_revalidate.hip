@@ -183,7 +183,7 @@ void launch_prm_plant_entries(const uint32_t* offsets, const uint32_t* nbrs, uin
 }
 
 void launch_prm_reval_valid(bool so3, const DevParams& p, const double* ms, uint32_t n, uint8_t* valid, uint32_t* counters, hipStream_t s) {
-    space_dispatch(so3, p.dim, [&](auto d) {
+    space_dispatch(prm_space(so3), p.dim, [&](auto d) {
         constexpr int D = decltype(d)::value;
         hipLaunchKernelGGL(prm_reval_valid_kernel<D>, dim3(blocks_for(n)), dim3(256), 0, s, SeqSpace<D>::checker(p), ms, n, valid, counters);
     });

@@ -266,7 +266,7 @@ __global__ __launch_bounds__(kThreads) void prm_shortest_levels_kernel(PrmBatchA
 void launch_prm_shortest_weights(bool so3, uint32_t dim, const double* ms, const uint32_t* offsets, const uint32_t* nbrs, uint32_t n,
                                  uint32_t n_entries, double* w, hipStream_t s) {
     if (n == 0 || n_entries == 0) return;
-    space_dispatch(so3, dim, [&](auto d) {
+    space_dispatch(prm_space(so3), dim, [&](auto d) {
         constexpr int D = decltype(d)::value;
         hipLaunchKernelGGL(prm_shortest_weights_kernel<D>, dim3((n_entries + 255) / 256), dim3(256), 0, s, ms, offsets, nbrs, n, n_entries, w);
     });
@@ -274,7 +274,7 @@ void launch_prm_shortest_weights(bool so3, uint32_t dim, const double* ms, const
 
 void launch_prm_shortest_init(bool so3, const PrmBatchArgs& b, const PrmShortestArgs& a, hipStream_t s) {
     const dim3 grid(b.n ? (b.n + 255) / 256 : 1, b.n_chunk);
-    space_dispatch(so3, b.dim, [&](auto d) {
+    space_dispatch(prm_space(so3), b.dim, [&](auto d) {
         constexpr int D = decltype(d)::value;
         hipLaunchKernelGGL(prm_shortest_init_kernel<D>, grid, dim3(256), 0, s, b, a);
     });

@@ -15,10 +15,12 @@
 //   motion    the interpolated states of check_motion (rrt.rs:90-116) are dealt to the lanes, 64 per pass, each against every arc
 //   insert    lane 0 stores node n (HBM + LDS mirror), then the goal test distance(q_new, target) <= radius
 // The checksum is the per-iteration polynomial of ABI 2 (rrt_device.hpp, iter_digest) over the one coordinate.
+// The wave-local fence and the motion pass are rrt_wave.hpp's, shared with rrt_so3.hip.
 #include "oxhip_internal.hpp"
 #include "rrt_device.hpp"
 #include "lane_sampler.hpp"
 #include "so2_device.hpp"
+#include "rrt_wave.hpp"
 
 namespace oxhip {
 
@@ -35,35 +37,20 @@ struct So2Shared {
 };
 static_assert(sizeof(So2Shared<kSo2LdsArcs>) <= 40960, "four problems per CU");
 
-// what one lane stores and another loads: LDS is in order per wave, the fences keep the compiler from moving either access
-__device__ __forceinline__ void so2_wave_publish() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
+// the space as rrt_wave.hpp's motion pass sees it: the arithmetic on 1-wide states, and the arcs wherever they lie
+struct So2Checker {
+    static constexpr int W = 1;
+    const double* lo;
+    const double* hi;
+    uint32_t na;
 
-// check_motion (rrt.rs:90-116) by one wave: lane s tests state s + 1 of the steps 1 ..= nsteps (or `to` alone when nsteps <= 1)
-// against every arc; returns the wave-uniform verdict "some state is invalid".  is_valid is pure, so testing a whole pass of
-// states equals the reference's first-invalid early exit.
-__device__ __forceinline__ bool so2_motion_invalid_wave(const double* lo, const double* hi, uint32_t na, double from, double to,
-                                                        double res, uint32_t lane) {
-    if (na == 0) return false;
-    const uint32_t nsteps = num_steps_u32(so2_distance(from, to), res);
-    const uint32_t S = nsteps <= 1u ? 1u : nsteps;
-    const double dn = (double)nsteps;
-    for (uint32_t s0 = 0; s0 < S; s0 += 64u) {
-        const uint32_t s = s0 + lane;
-        bool bad = false;
-        if (s < S) {
-            double st = to;
-            if (nsteps > 1u) st = so2_interpolate(from, to, (double)(s + 1u) / dn);
-            bad = so2_arc_hit(lo, hi, na, st);
-        }
-        if (__ballot(bad) != 0) return true;
-        if (s0 + 64u < s0) break;   // (no wrap at 2^32)
+    static __device__ __forceinline__ double distance(const double a[1], const double b[1]) { return so2_distance(a[0], b[0]); }
+    static __device__ __forceinline__ void interpolate(const double a[1], const double b[1], double t, double out[1]) {
+        out[0] = so2_interpolate(a[0], b[0], t);
     }
-    return false;
-}
+    __device__ __forceinline__ bool free() const { return na == 0; }
+    __device__ __forceinline__ bool state_hit(const double s[1]) const { return so2_arc_hit(lo, hi, na, s[0]); }
+};
 
 template <bool LDS_ARCS>
 __global__ __launch_bounds__(64) void rrt_so2_kernel(DevParams p) {
@@ -71,16 +58,15 @@ __global__ __launch_bounds__(64) void rrt_so2_kernel(DevParams p) {
     __shared__ So2Shared<LDS_ARCS ? kSo2LdsArcs : 1> sh;
     ProblemState st = p.state[prob];
     if (p.stop_at_goal && st.goal_node >= 0) return;   // already solved: solve() is idempotent
-    const uint32_t na = p.n_boxes;
-    const double* alo = p.box_lo;
-    const double* ahi = p.box_hi;
+    So2Checker arcs{p.box_lo, p.box_hi, p.n_boxes};
+    const uint32_t na = arcs.na;
     if (LDS_ARCS) {   // the checker's table at LDS latency
         for (uint32_t i = lane; i < na; i += 64u) {
             sh.arc_lo[i] = p.box_lo[i];
             sh.arc_hi[i] = p.box_hi[i];
         }
-        alo = sh.arc_lo;
-        ahi = sh.arc_hi;
+        arcs.lo = sh.arc_lo;
+        arcs.hi = sh.arc_hi;
     }
     const size_t cap = p.cap;
     double* tree = p.tree + (size_t)prob * cap;
@@ -111,7 +97,7 @@ __global__ __launch_bounds__(64) void rrt_so2_kernel(DevParams p) {
                 sh.pos_after[b] = pos_after;
             });
             sampled += m;
-            so2_wave_publish();
+            rrt_wave_publish();
         }
         const uint32_t slot = (uint32_t)it & 63u;
         const double q = sh.q[slot];
@@ -144,9 +130,9 @@ __global__ __launch_bounds__(64) void rrt_so2_kernel(DevParams p) {
         if (min_dist > p.max_distance) q_new = so2_interpolate(q_near, q, p.max_distance / min_dist);
 
         // 5. check_motion (rrt.rs:211 -> :90-116)
-        const bool ok = !so2_motion_invalid_wave(alo, ahi, na, q_near, q_new, p.res, lane);
+        const double q_near1[1] = {q_near}, q_new1[1] = {q_new};
+        const bool ok = !rrt_wave_motion_invalid(arcs, q_near1, q_new1, p.res, lane);
 
-        const double q_new1[1] = {q_new};
         h = chk_push(h, iter_digest<1>(nearest, q_new1, 1, ok));
         st.iterations++;
 
@@ -161,7 +147,7 @@ __global__ __launch_bounds__(64) void rrt_so2_kernel(DevParams p) {
                     if (n < (uint32_t)kSo2N) sh.node[n] = q_new;
                 }
                 // the next scan is this wave's own and LDS is in order per wave (the fences keep the compiler from moving the store)
-                so2_wave_publish();
+                rrt_wave_publish();
                 ++n;
                 // 7. goal test (rrt.rs:220-223)
                 if (so2_distance(q_new, target) <= goal_radius) {
@@ -202,7 +188,8 @@ __global__ __launch_bounds__(256) void so2_check_motion_kernel(DevParams p, cons
                                                                 uint8_t* out) {
     const uint32_t m = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (m >= n) return;
-    const bool any = so2_motion_invalid_wave(p.box_lo, p.box_hi, p.n_boxes, from[m], to[m], p.res, lane);
+    const double f[1] = {from[m]}, g[1] = {to[m]};
+    const bool any = rrt_wave_motion_invalid(So2Checker{p.box_lo, p.box_hi, p.n_boxes}, f, g, p.res, lane);   // the planner's own
     if (lane == 0) out[m] = any ? 0 : 1;
 }
 void launch_so2_check_motion(const DevParams& p, const double* from, const double* to, uint32_t n, uint8_t* out, hipStream_t s) {

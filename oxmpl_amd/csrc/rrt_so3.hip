@@ -15,10 +15,12 @@
 //   motion    the interpolated states of check_motion (rrt.rs:90-116) are dealt to the lanes, 64 per pass
 //   insert    lane 0 stores node n (HBM + LDS mirror), then the goal test distance(q_new, target) <= radius
 // The checksum is the per-iteration polynomial of ABI 2 (rrt_device.hpp, iter_digest) over the four coordinates.
+// The wave-local fence and the motion pass are rrt_wave.hpp's, shared with rrt_so2.hip.
 #include "oxhip_internal.hpp"
 #include "rrt_device.hpp"
 #include "so3_device.hpp"
 #include "so3_sampler.hpp"
+#include "rrt_wave.hpp"
 
 namespace oxhip {
 
@@ -48,28 +50,20 @@ __device__ __forceinline__ void so3_sample(RngWindow& rng, const DevParams& p, c
     so3_sample_uniform_wave(rng, p, lane, q);
 }
 
-// check_motion (rrt.rs:90-116) by one wave: lane s tests state s + 1 of the steps 1 ..= nsteps (or `to` alone when nsteps <= 1)
-// against every cone; returns the wave-uniform verdict "some state is invalid".  is_valid is pure, so testing a whole pass of
-// states equals the reference's first-invalid early exit.
-__device__ __forceinline__ bool so3_motion_invalid_wave(const double* cc, uint32_t stride, const double* cr, uint32_t nc,
-                                                        const double from[4], const double to[4], double res, uint32_t lane) {
-    if (nc == 0) return false;
-    const uint32_t nsteps = num_steps_u32(so3_distance(from, to), res);
-    const uint32_t S = nsteps <= 1u ? 1u : nsteps;
-    const double dn = (double)nsteps;
-    for (uint32_t s0 = 0; s0 < S; s0 += 64u) {
-        const uint32_t s = s0 + lane;
-        bool bad = false;
-        if (s < S) {
-            double st[4] = {to[0], to[1], to[2], to[3]};
-            if (nsteps > 1u) so3_interpolate(from, to, (double)(s + 1u) / dn, st);
-            bad = so3_cone_hit(cc, stride, cr, nc, st);
-        }
-        if (__ballot(bad) != 0) return true;
-        if (s0 + 64u < s0) break;   // (no wrap at 2^32)
+// the space as rrt_wave.hpp's motion pass sees it: the arithmetic on quaternions, and the cones wherever they lie
+struct So3Checker {
+    static constexpr int W = 4;
+    const double* cc;    // centres, SoA [4][stride]
+    const double* cr;    // radii as given
+    uint32_t stride, nc;
+
+    static __device__ __forceinline__ double distance(const double a[4], const double b[4]) { return so3_distance(a, b); }
+    static __device__ __forceinline__ void interpolate(const double a[4], const double b[4], double t, double out[4]) {
+        so3_interpolate(a, b, t, out);
     }
-    return false;
-}
+    __device__ __forceinline__ bool free() const { return nc == 0; }
+    __device__ __forceinline__ bool state_hit(const double s[4]) const { return so3_cone_hit(cc, stride, cr, nc, s); }
+};
 
 template <bool LDS_CONES>
 __global__ __launch_bounds__(64) void rrt_so3_kernel(DevParams p) {
@@ -77,19 +71,17 @@ __global__ __launch_bounds__(64) void rrt_so3_kernel(DevParams p) {
     __shared__ So3Shared<LDS_CONES ? kSo3LdsCones : 1> sh;
     ProblemState st = p.state[prob];
     if (p.stop_at_goal && st.goal_node >= 0) return;   // already solved: solve() is idempotent
-    const uint32_t nc = p.n_spheres;
-    const double* cc = p.sph_c;
-    const double* cr = p.sph_r;
-    uint32_t stride = nc;
+    So3Checker cones{p.sph_c, p.sph_r, p.n_spheres, p.n_spheres};
+    const uint32_t nc = cones.nc;
     if (LDS_CONES) {   // the checker's table at LDS latency
         for (uint32_t i = lane; i < nc; i += 64u) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) sh.cone_c[k][i] = p.sph_c[(size_t)k * nc + i];
             sh.cone_r[i] = p.sph_r[i];
         }
-        cc = &sh.cone_c[0][0];
-        cr = sh.cone_r;
-        stride = (uint32_t)kSo3LdsCones;
+        cones.cc = &sh.cone_c[0][0];
+        cones.cr = sh.cone_r;
+        cones.stride = (uint32_t)kSo3LdsCones;
     }
     const size_t cap = p.cap;
     double* tree = p.tree + (size_t)prob * 4 * cap;
@@ -158,7 +150,7 @@ __global__ __launch_bounds__(64) void rrt_so3_kernel(DevParams p) {
         }
 
         // 5. check_motion (rrt.rs:211 -> :90-116)
-        const bool ok = !so3_motion_invalid_wave(cc, stride, cr, nc, q_near, q_new, p.res, lane);
+        const bool ok = !rrt_wave_motion_invalid(cones, q_near, q_new, p.res, lane);
 
         h = chk_push(h, iter_digest<4>(nearest, q_new, 4, ok));
         st.iterations++;
@@ -175,9 +167,7 @@ __global__ __launch_bounds__(64) void rrt_so3_kernel(DevParams p) {
                     if (n < (uint32_t)kSo3N) sh.node[n] = make_double4(q_new[0], q_new[1], q_new[2], q_new[3]);
                 }
                 // the next scan is this wave's own and LDS is in order per wave (the fences keep the compiler from moving the store)
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                rrt_wave_publish();
                 ++n;
                 // 7. goal test (rrt.rs:220-223)
                 if (so3_distance(q_new, target) <= goal_radius) {
@@ -237,7 +227,7 @@ __global__ __launch_bounds__(256) void so3_check_motion_kernel(DevParams p, cons
     if (m >= n) return;
     const double f[4] = {from[4 * (size_t)m], from[4 * (size_t)m + 1], from[4 * (size_t)m + 2], from[4 * (size_t)m + 3]};
     const double g[4] = {to[4 * (size_t)m], to[4 * (size_t)m + 1], to[4 * (size_t)m + 2], to[4 * (size_t)m + 3]};
-    const bool any = so3_motion_invalid_wave(p.sph_c, p.n_spheres, p.sph_r, p.n_spheres, f, g, p.res, lane);
+    const bool any = rrt_wave_motion_invalid(So3Checker{p.sph_c, p.sph_r, p.n_spheres, p.n_spheres}, f, g, p.res, lane);
     if (lane == 0) out[m] = any ? 0 : 1;
 }
 void launch_so3_check_motion(const DevParams& p, const double* from, const double* to, uint32_t n, uint8_t* out, hipStream_t s) {

@@ -2,7 +2,7 @@
 // query sets, the re-check, the shortcutter's pair matrix, the shortest paths' weights) are written once over SeqSpace<DIM>.
 // DIM = 1..8 is R^DIM, DIM = 0 is SO(3) (unit quaternions among forbidden cones), DIM = -1 is SO(2) (one angle among forbidden
 // arcs).  The members forward to motion_seq.hpp / so3_motion_seq.hpp / so3_device.hpp / so2_device.hpp, so every bit is the one
-// those functions give.  space_dispatch is the host's way in (R^n or SO(3); the SO(2) instantiations live in rrt_so2_services.hip).
+// those functions give.  space_dispatch is the host's way in: R^n or SO(3), and SO(2) for the callers that ask for it.
 #pragma once
 #include <type_traits>
 #include <utility>
@@ -112,7 +112,9 @@ struct SeqSpace<-1> {                              // SO(2)
 };
 
 // The host's way to an instantiation: f(std::integral_constant<int, D>{}) with D = dim in LO..8 (a caller that never sees R^1
-// passes LO = 2) -- for kernels that exist over R^n only -- and space_dispatch below it, with D = 0 for SO(3).
+// passes LO = 2) -- for kernels that exist over R^n only -- and space_dispatch below it, which takes the oxhip_space_kind: D = 0
+// for SO(3) and, for a caller that opts in with SO2 = true, D = -1 for SO(2).  Without the opt-in nothing is instantiated over
+// SO(2): the PRM files do not ask (no roadmap is built over SO(2)), the RRT re-check and the shortcutter do.
 template <int LO = 1, typename F>
 void dim_dispatch(uint32_t dim, F&& f) {
     if constexpr (LO <= 1)
@@ -127,10 +129,14 @@ void dim_dispatch(uint32_t dim, F&& f) {
         default: f(std::integral_constant<int, 8>{}); break;
     }
 }
-template <int LO = 1, typename F>
-void space_dispatch(bool so3, uint32_t dim, F&& f) {
-    if (so3) f(std::integral_constant<int, 0>{});
-    else dim_dispatch<LO>(dim, std::forward<F>(f));
+template <int LO = 1, bool SO2 = false, typename F>
+void space_dispatch(uint32_t space, uint32_t dim, F&& f) {
+    if (space == OXHIP_SPACE_SO3) return f(std::integral_constant<int, 0>{});
+    if constexpr (SO2)
+        if (space == OXHIP_SPACE_SO2) return f(std::integral_constant<int, -1>{});
+    dim_dispatch<LO>(dim, std::forward<F>(f));
 }
+// the PRM launchers' `bool so3` as a space kind
+constexpr uint32_t prm_space(bool so3) { return so3 ? OXHIP_SPACE_SO3 : OXHIP_SPACE_REAL_VECTOR; }
 
 }  // namespace oxhip

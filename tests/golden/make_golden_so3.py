@@ -197,10 +197,13 @@ def is_so3_path_valid(path, cones, fraction=0.05):
 
 
 def rrt_solve(bounds, max_distance, goal_bias, fraction, cones, start, target, goal_r, seed, pid, max_iterations, max_nodes,
-              stop_at_goal=True, freeze=False, tree=None, parents=None):
-    """RRT::solve over SO(3) for at most max_iterations iterations; tree / parents: a warm start (set_tree after setup)"""
+              stop_at_goal=True, freeze=False, tree=None, parents=None, draws=0):
+    """RRT::solve over SO(3) for at most max_iterations iterations; tree / parents: a warm start (set_tree after setup);
+    draws: words of the stream already consumed (a warm start after an earlier solve)"""
     centre, max_angle = space_bounds(bounds)
     rng = mg.ChaCha12Rng(seed, pid)
+    for _ in range(draws):
+        rng.next_u64()
     states = [list(map(float, s)) for s in tree] if tree is not None else [list(map(float, start))]
     par = list(parents) if parents is not None else [-1]
     chk = mg.FNV_BASIS

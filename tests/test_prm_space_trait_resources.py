@@ -1,7 +1,9 @@
 """CPU: the PRM / path kernels written once over SeqSpace<DIM> (oxmpl_amd/csrc/seq_space.hpp), compiled to gfx950 ISA (no GPU
 needed): one kernel template per role, instantiated for R^1..R^8 and SO(3) (DIM = 0), no spill to scratch, no LDS, and no
 instantiation needs more registers or spills more SGPRs than the hand-copied kernels it replaced.  The literals are the figures
-of the commit before the trait, cross-compiled with the Makefile's flags; columns are D = 1..8, then SO(3)."""
+of the commit before the trait, cross-compiled with the Makefile's flags; columns are D = 1..8, then SO(3), then SO(2)
+(DIM = -1: the shortcutter's pair matrix alone -- its figures are those of the commit before SO(2) joined space_dispatch -- and
+no PRM kernel)."""
 import os
 import re
 import subprocess
@@ -11,17 +13,17 @@ import pytest
 from test_kernel_resources import CSRC, HIPCC, _kernels
 
 SOURCES = ["prm_kernels.hip", "prm_batch.hip", "prm_revalidate.hip", "path_simplify.hip", "prm_shortest.hip"]
-DIMS = [1, 2, 3, 4, 5, 6, 7, 8, 0]
+DIMS = [1, 2, 3, 4, 5, 6, 7, 8, 0, -1]
 
 # kernel -> (vgpr_count, sgpr_spill_count) per D of DIMS; None: no such instantiation (no caller reaches it)
 BEFORE = {
-    "prm_query_kernel": ([28, 36, 46, 56, 66, 76, 86, 97, 85], [0, 0, 0, 4, 8, 47, 73, 117, 16]),
-    "prm_batch_flags_kernel": ([28, 36, 46, 56, 66, 76, 87, 97, 85], [0, 0, 0, 8, 35, 58, 102, 122, 24]),
-    "prm_reval_valid_kernel": ([18, 26, 32, 38, 44, 44, 60, 68, 40], [0] * 9),
-    "prm_reval_check_kernel": ([40, 48, 58, 68, 78, 88, 98, 110, None], [0] * 8 + [None]),   # SO(3) re-checks through prm_so3_edge_kernel
-    "path_pairs_kernel": ([None, 36, 46, 56, 66, 77, 87, 97, 93], [None, 0, 0, 0, 0, 11, 30, 64, 6]),   # an RRT batch has dim >= 2
-    "prm_shortest_weights_kernel": ([12, 14, 18, 22, 26, 30, 34, 38, 24], [0] * 9),
-    "prm_shortest_init_kernel": ([12, 12, 12, 12, 15, 16, 19, 20, 24], [0] * 9),
+    "prm_query_kernel": ([28, 36, 46, 56, 66, 76, 86, 97, 85, None], [0, 0, 0, 4, 8, 47, 73, 117, 16, None]),
+    "prm_batch_flags_kernel": ([28, 36, 46, 56, 66, 76, 87, 97, 85, None], [0, 0, 0, 8, 35, 58, 102, 122, 24, None]),
+    "prm_reval_valid_kernel": ([18, 26, 32, 38, 44, 44, 60, 68, 40, None], [0] * 9 + [None]),
+    "prm_reval_check_kernel": ([40, 48, 58, 68, 78, 88, 98, 110, None, None], [0] * 8 + [None, None]),   # SO(3) re-checks through prm_so3_edge_kernel
+    "path_pairs_kernel": ([None, 36, 46, 56, 66, 77, 87, 97, 93, 40], [None, 0, 0, 0, 0, 11, 30, 64, 6, 0]),   # an RRT batch has dim >= 2
+    "prm_shortest_weights_kernel": ([12, 14, 18, 22, 26, 30, 34, 38, 24, None], [0] * 9 + [None]),
+    "prm_shortest_init_kernel": ([12, 12, 12, 12, 15, 16, 19, 20, 24, None], [0] * 9 + [None]),
 }
 
 
@@ -42,13 +44,14 @@ def trait_kernels(tmp_path_factory):
 
 
 def _instantiations(meta, kernel):
-    """D -> metadata of kernel<D>"""
+    """D -> metadata of kernel<D>  (a negative D mangles as n<digits>: -1 is ILin1E)"""
     found = {}
     for name, m in meta.items():
-        hit = re.search(r"\d+" + kernel + r"ILi(\d+)EEE", name)
+        hit = re.search(r"\d+" + kernel + r"ILi(n?)(\d+)EEE", name)
         if hit:
-            assert int(hit.group(1)) not in found, name
-            found[int(hit.group(1))] = m
+            d = -int(hit.group(2)) if hit.group(1) else int(hit.group(2))
+            assert d not in found, name
+            found[d] = m
     return found
 
 
@@ -56,7 +59,7 @@ def _instantiations(meta, kernel):
 def test_one_template_per_role_within_the_figures_before_the_trait(trait_kernels, kernel):
     vgpr, spill = BEFORE[kernel]
     inst = _instantiations(trait_kernels, kernel)
-    assert sorted(inst) == sorted(d for d, v in zip(DIMS, vgpr) if v is not None)      # 9 instantiations (8: see BEFORE)
+    assert sorted(inst) == sorted(d for d, v in zip(DIMS, vgpr) if v is not None)      # exactly these instantiations (see BEFORE)
     for d, v, s in zip(DIMS, vgpr, spill):
         if v is None:
             continue

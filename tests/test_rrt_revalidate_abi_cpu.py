@@ -99,11 +99,11 @@ def test_rrt_revalidate_kernels_resource_shape(tmp_path):
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
                            "-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, "rrt_revalidate.hip")], stderr=subprocess.DEVNULL)
     own = {k: m for k, m in _kernel_metadata(open(out).read()).items() if "rrt_reval_" in k}
-    for family, count in (("rrt_reval_edge_kernel", 8), ("rrt_reval_stage_kernel", 1), ("rrt_reval_unstage_kernel", 1),
+    for family, count in (("rrt_reval_edge_kernel", 9), ("rrt_reval_stage_kernel", 1), ("rrt_reval_unstage_kernel", 1),
                           ("rrt_reval_survive_kernel", 1), ("rrt_reval_scan_kernel", 1),
-                          ("rrt_reval_compact_kernel", 9), ("rrt_reval_skip_kernel", 9)):   # R^1 .. R^8 (and DIM = 0: SO(3))
+                          ("rrt_reval_compact_kernel", 10), ("rrt_reval_skip_kernel", 10)):   # R^1 .. R^8, DIM = -1: SO(2) (and DIM = 0: SO(3))
         assert sum(1 for k in own if family in k) == count, (family, sorted(own))
-    assert len(own) == 30
+    assert len(own) == 33
     misses = [(name, m) for name, m in own.items()
               if not (m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0
                       and m["vgpr_count"] < 128 and m["max_flat_workgroup_size"] == 256)]

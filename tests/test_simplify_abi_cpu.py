@@ -102,10 +102,11 @@ def test_path_simplify_kernels_resource_shape(tmp_path):
                            "-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, "path_simplify.hip")], stderr=subprocess.DEVNULL)
     asm = open(out).read()
     meta = _kernels(asm)
-    # chain walk (2), pair matrix in R^2 .. R^8 and SO(3), DP in R^n and SO(3)
+    # chain walk (2), pair matrix in R^2 .. R^8, SO(3) and SO(2), DP in R^n, SO(3) and SO(2)
     assert sum("path_len_kernel" in k or "path_rows_kernel" in k for k in meta) == 2
-    assert sum("path_pairs_kernel" in k for k in meta) == 8 and sum("path_pairs_kernelILi0E" in k for k in meta) == 1   # (D = 0: SO(3))
-    assert sum("path_dp_kernel" in k for k in meta) == 2 and len(meta) == 12
+    assert sum("path_pairs_kernel" in k for k in meta) == 9 and sum("path_pairs_kernelILi0E" in k for k in meta) == 1   # (D = 0: SO(3))
+    assert sum("path_pairs_kernelILin1E" in k for k in meta) == 1                                                        # (D = -1: SO(2))
+    assert sum("path_dp_kernel" in k for k in meta) == 3 and len(meta) == 14
     for name, m in meta.items():
         assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0, (name, m)
         body = asm.split("\n" + name + ":")[1].split("s_endpgm")[0]
