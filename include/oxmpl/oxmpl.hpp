@@ -542,6 +542,25 @@ class PRM {
         if (st != OXHIP_OK) return to_error(st);
         return out;
     }
+    // Adds up to n_more milestones to the roadmap as it stands -- built, planted or re-checked -- under the obstacles as they
+    // are now (oxhip_prm_grow_roadmap).  `new_stream` null continues the planner's own sampler stream where construct_roadmap
+    // or the last grow stopped; a planted roadmap has no such position and needs a stream id.  A refused argument
+    // (OXHIP_ERR_BAD_ARG / _CAPACITY, kept in last_grow_status(), the text in oxhip_last_error_string()) comes back as
+    // NoSolutionFound and leaves the roadmap as it was.
+    struct Growth { uint32_t added = 0; uint64_t samples_drawn = 0; };
+    Result<Growth, base::PlanningError> grow_roadmap(uint32_t n_more, uint64_t max_samples = 0, const uint64_t* new_stream = nullptr) {
+        if (!prm_) return base::PlanningError::PlannerUninitialised;
+        oxhip_prm_grow_config g{};
+        g.struct_size = sizeof g;
+        g.n_more = n_more;
+        g.max_samples = max_samples;
+        if (new_stream) { g.flags = OXHIP_PRM_GROW_NEW_STREAM; g.stream = *new_stream; }
+        Growth out;
+        grow_status_ = oxhip_prm_grow_roadmap(prm_, &g, &out.added, &out.samples_drawn);
+        if (grow_status_ != OXHIP_OK) return to_error(grow_status_);
+        return out;
+    }
+    int32_t last_grow_status() const { return grow_status_; }
     int32_t last_status() const { return last_status_; }
 
   private:
@@ -562,6 +581,7 @@ class PRM {
     std::shared_ptr<base::ProblemDefinition> pd_;
     int32_t last_status_ = OXHIP_ERR_PLANNER_UNINITIALISED;
     int32_t set_roadmap_status_ = OXHIP_OK;
+    int32_t grow_status_ = OXHIP_OK;
 };
 
 }  // namespace geometric

@@ -645,6 +645,43 @@ int32_t oxhip_prm_revalidate(oxhip_prm* prm, uint8_t* milestone_valid /*[n] or N
  * compaction (scan + move)} */
 int32_t oxhip_prm_revalidate_last_timing(oxhip_prm* prm, double* phase_ms /*[4]*/);
 
+/* ---- growing a roadmap in place (prm_grow.hip) ----
+ * oxhip_prm_grow_roadmap continues the reference's construction loop (prm.rs:117-147) on the roadmap as it stands -- built,
+ * planted or re-checked -- under the obstacles as they are now: OMPL's PRM::growRoadmap.  The semantics are this build's own.
+ * Bounded by counts, not by cfg.timeout.  Old milestone indices, states and the old part of every old row do not change; new
+ * milestones get the indices n, n + 1, ... in sample order.  An old milestone i is LIVE iff is_valid(milestone i) holds now
+ * (oxhip_prm_revalidate's milestone test, evaluated when the call starts); a new milestone is live.  A new milestone j gets the
+ * edge {i < j} iff i is live, distance(j, i) < connection_radius (strict, construction's device test) and
+ * check_motion(from = j, to = i) -- the rule oxhip_prm_revalidate keeps edges by, so a re-check right after a grow removes
+ * nothing.  A dead milestone keeps its row and gets no new entry.  k-nearest handles (knn_k > 0): a new row takes its k nearest
+ * earlier milestones as construction does; with any dead milestone the call is OXHIP_ERR_BAD_ARG (k-nearest growth over invalid
+ * milestones is not built).
+ * Sampler: flags = 0 continues the handle's stream at the word where its last construct_roadmap / grow_roadmap stopped, so
+ * construct to N1 + grow N2 equals construct to N1 + N2 bit for bit (with cfg.timeout = 0).  revalidate, set_spheres, set_boxes
+ * and set_problem keep that position; setup and set_roadmap forget it, and a handle without one refuses flags = 0 with
+ * OXHIP_ERR_BAD_ARG (starting silently at word 0 would re-draw the milestones a saved roadmap was built from).
+ * OXHIP_PRM_GROW_NEW_STREAM starts at word 0 of stream `stream` (key = cfg.seed), which becomes the handle's stream for later
+ * default grows.  n_samples (oxhip_prm_get_sizes) keeps counting from where it stood, 0 after set_roadmap.
+ * Capacity: n + n_more may exceed cfg.max_milestones, up to 2^26 in all (beyond: OXHIP_ERR_CAPACITY); the handle's buffers are
+ * then moved once to the next power of two.
+ * OXHIP_ERR_BAD_ARG for a null pointer, a wrong struct_size, n_more = 0 or an unknown flag (before any device call);
+ * OXHIP_ERR_PLANNER_UNINITIALISED without setup(); OXHIP_ERR_UNSAMPLED_STATE_SPACE on an empty roadmap (construct_roadmap
+ * builds one).  max_samples exhausted is OXHIP_OK with *n_added < n_more.  A refused call leaves the handle as it was.
+ * Success drops what belonged to the roadmap before, as oxhip_prm_revalidate does. */
+#define OXHIP_PRM_GROW_NEW_STREAM 1u
+typedef struct {
+    uint32_t struct_size;
+    uint32_t n_more;        /* milestones to add; 0 is OXHIP_ERR_BAD_ARG */
+    uint64_t max_samples;   /* sample_uniform calls this call may make; 0 = 4096 * n_more + 2^22, construct's rule */
+    uint32_t flags;         /* OXHIP_PRM_GROW_NEW_STREAM = 1 */
+    uint32_t pad;
+    uint64_t stream;        /* with NEW_STREAM: the ChaCha12 stream id to start at word 0 of (key = cfg.seed) */
+} oxhip_prm_grow_config;
+int32_t oxhip_prm_grow_roadmap(oxhip_prm* prm, const oxhip_prm_grow_config* g, uint32_t* n_added, uint64_t* n_samples_drawn);
+/* HIP-event times (ms) of the last oxhip_prm_grow_roadmap: phase_ms[6] = {liveness mask, keys from CSR, sample,
+ * pairs (+ filter), edges, sort + CSR} */
+int32_t oxhip_prm_grow_last_timing(oxhip_prm* prm, double* phase_ms /*[6]*/);
+
 #ifdef __cplusplus
 }
 #endif

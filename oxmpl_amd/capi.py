@@ -54,6 +54,7 @@ EXPORTS = [
     "oxhip_prm_batch_last_timing",
     "oxhip_prm_solve_batch_shortest", "oxhip_prm_batch_get_costs", "oxhip_prm_batch_get_labels", "oxhip_prm_batch_get_search_stats",
     "oxhip_prm_set_roadmap", "oxhip_prm_revalidate", "oxhip_prm_revalidate_last_timing",
+    "oxhip_prm_grow_roadmap", "oxhip_prm_grow_last_timing",
     "oxhip_rrt_batch_extract_paths", "oxhip_rrt_batch_get_paths", "oxhip_rrt_batch_simplify_paths",
     "oxhip_rrt_batch_get_simplified_paths", "oxhip_rrt_batch_get_simplify_results", "oxhip_rrt_batch_path_valid_matrix",
     "oxhip_rrt_batch_paths_last_timing",
@@ -80,6 +81,16 @@ class PrmConfig(C.Structure):
         ("timeout", C.c_double), ("connection_radius", C.c_double), ("lvs_fraction", C.c_double),
         ("max_milestones", C.c_uint32), ("device", C.c_int32), ("max_samples", C.c_uint64),
         ("seed", C.c_uint64), ("stream", C.c_uint64), ("knn_k", C.c_uint32), ("space", C.c_uint32),
+    ]
+
+
+PRM_GROW_NEW_STREAM = 1   # OXHIP_PRM_GROW_NEW_STREAM
+
+
+class PrmGrowConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_more", C.c_uint32), ("max_samples", C.c_uint64),
+        ("flags", C.c_uint32), ("pad", C.c_uint32), ("stream", C.c_uint64),
     ]
 
 
@@ -177,6 +188,8 @@ def lib():
         L.oxhip_prm_set_roadmap.argtypes = [C.c_void_p, _dp, C.c_uint32, _u64p, _u32p]
         L.oxhip_prm_revalidate.argtypes = [C.c_void_p, _u8p, _u32p, _u64p]
         L.oxhip_prm_revalidate_last_timing.argtypes = [C.c_void_p, _dp]
+        L.oxhip_prm_grow_roadmap.argtypes = [C.c_void_p, C.POINTER(PrmGrowConfig), _u32p, _u64p]
+        L.oxhip_prm_grow_last_timing.argtypes = [C.c_void_p, _dp]
         L.oxhip_rrt_batch_extract_paths.argtypes = [C.c_void_p]
         L.oxhip_rrt_batch_get_paths.argtypes = [C.c_void_p, _u64p, _dp, C.c_uint64, _u64p]
         L.oxhip_rrt_batch_simplify_paths.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
@@ -791,4 +804,26 @@ class PRMRoadmap:
         """dict(phase_ms=[milestone validity, pair emission, edge checks, compaction]) of the last revalidate"""
         ms = np.zeros(4, dtype=np.float64)
         _check(lib().oxhip_prm_revalidate_last_timing(self._h, _p(ms)))
+        return dict(phase_ms=[float(v) for v in ms])
+
+    # ---- the roadmap grown in place (DESIGN.md section 23)
+
+    def grow(self, n_more, max_samples=0, new_stream=None):
+        """Adds up to n_more milestones to the roadmap as it stands, under the obstacles as they are now (oxhip_prm_grow_roadmap).
+        new_stream=None continues the handle's own sampler stream where construct_roadmap / the last grow stopped;
+        new_stream=id starts stream `id` at its first word (what a planted roadmap needs).  max_samples=0 is construct's rule.
+        Returns (n_added, n_samples_drawn)."""
+        g = PrmGrowConfig()
+        g.struct_size = C.sizeof(PrmGrowConfig)
+        g.n_more, g.max_samples = n_more, max_samples
+        if new_stream is not None:
+            g.flags, g.stream = PRM_GROW_NEW_STREAM, new_stream
+        added, drawn = C.c_uint32(), C.c_uint64()
+        _check(lib().oxhip_prm_grow_roadmap(self._h, C.byref(g), C.byref(added), C.byref(drawn)))
+        return added.value, drawn.value
+
+    def grow_timing(self):
+        """dict(phase_ms=[liveness mask, keys from CSR, sample, pairs (+ filter), edges, sort + CSR]) of the last grow"""
+        ms = np.zeros(6, dtype=np.float64)
+        _check(lib().oxhip_prm_grow_last_timing(self._h, _p(ms)))
         return dict(phase_ms=[float(v) for v in ms])

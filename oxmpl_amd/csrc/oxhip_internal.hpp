@@ -194,6 +194,15 @@ hipError_t prm_reval_scan(void* tmp, size_t& tmp_bytes, const uint8_t* keep, uin
 void launch_prm_reval_compact(uint32_t* offsets, const uint32_t* nbrs, const uint8_t* keep, const uint32_t* pos, uint32_t n, uint32_t n_entries,
                               uint32_t* nbrs_out, hipStream_t s);
 
+// prm_grow.hip: what growing a roadmap in place adds to construction's kernels
+// keys[e] = (row of CSR entry e << shift) | nbrs[e], e < n_entries
+void launch_prm_grow_keys(const uint32_t* offsets, const uint32_t* nbrs, uint32_t n, uint32_t n_entries, uint32_t shift, uint64_t* keys,
+                          hipStream_t s);
+// the candidates (j, i) whose i is a milestone of this call (i >= n_old) or valid[i] != 0, into out ([n_cand]); *count (zeroed by
+// the caller) counts them
+void launch_prm_grow_filter(const uint2* cand, uint32_t n_cand, const uint8_t* valid, uint32_t n_old, uint2* out, uint32_t* count,
+                            hipStream_t s);
+
 // rrt_revalidate.hip: the trees of an RRT batch re-checked against the current obstacles and compacted in place (DESIGN.md
 // section 21).  The per-slot arrays are [P][cap], indexed like DevParams::parent.
 struct ProblemState;

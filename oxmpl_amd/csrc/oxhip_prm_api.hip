@@ -6,7 +6,8 @@
 // fill_prm_params, alloc_prm; construct_roadmap = the reference's loop over sample_until, knn_row_radii, find_pairs, knn_select,
 // reserve_keys, check_edges, then build_csr; solve = query_sets, prm_bfs_path (oxhip_host.hpp, on the CSR roadmap copied back once per
 // construction), the path; solve_batch[_shortest] (DESIGN.md sections 17, 19) = stage_batch, reserve_batch_workspace, then per round
-// run_round, scatter_round, extract_round_paths.  The space is named by the dispatchers below the handle, the per-space part of
+// run_round, scatter_round, extract_round_paths; grow_roadmap = liveness_mask, grow_capacity, keys_from_csr,
+// then grow_round: construction's steps for the new milestones, with drop_dead_candidates before the edges.  The space is named by the dispatchers below the handle, the per-space part of
 // the sampler, the steps of create, the two obstacle setters and the prm_shortest launches that take it as an argument.
 #include <algorithm>
 #include <chrono>
@@ -101,6 +102,13 @@ struct oxhip_prm {
     DevBuf<uint64_t> rv_keys;
     DevBuf<PrmState> rv_state;
     double reval_ms[4] = {};   // milestone validity, pair emission, edge checks, compaction
+    // oxhip_prm_grow_roadmap: where the sampler stopped (stream id, u64 word), the filtered candidates, the
+    // phase times of the last call
+    bool pos_valid = false;    // set by construct_roadmap / grow_roadmap, forgotten by setup / set_roadmap
+    uint64_t pos_stream = 0, pos_draws = 0;
+    DevBuf<uint2> gw_cand;
+    DevBuf<uint32_t> gw_count;
+    double grow_ms[6] = {};    // liveness mask, keys from CSR, sample, pairs (+ filter), edges, sort + CSR
 };
 
 namespace {
@@ -200,6 +208,7 @@ void clear_roadmap(oxhip_prm* h) {
     h->n_keys = 0;
     h->n_samples = 0;
     h->redraw_batches = 0;
+    h->pos_valid = false;   // (setup, set_roadmap: the stream position belonged to the roadmap that went)
     drop_derived(h);
 }
 
@@ -672,6 +681,7 @@ int32_t oxhip_prm_construct_roadmap(oxhip_prm* h) {
     h->n = st.n_milestones;
     h->n_samples = st.n_samples;
     h->redraw_batches = st.redraw_batches;
+    h->pos_valid = true; h->pos_stream = h->cfg.stream; h->pos_draws = st.draws;   // where oxhip_prm_grow_roadmap continues
     return OXHIP_OK;
 }
 
@@ -1245,6 +1255,169 @@ int32_t oxhip_prm_revalidate(oxhip_prm* h, uint8_t* milestone_valid, uint32_t* n
 int32_t oxhip_prm_revalidate_last_timing(oxhip_prm* h, double* phase_ms) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
     if (phase_ms) for (int i = 0; i < 4; ++i) phase_ms[i] = h->reval_ms[i];
+    return OXHIP_OK;
+}
+
+}  // extern "C"
+
+// ---- a roadmap grown in place: oxhip_prm_grow_roadmap in its steps
+
+namespace {
+
+// which earlier milestones are live: is_valid(milestone i) now, by the re-check's own kernel, into rv_valid; n_dead = its zeros
+int32_t liveness_mask(oxhip_prm* h, uint32_t& n_dead) {
+    uint32_t cnt[kRevalCounters] = {};
+    HIP_TRY(h->rv_valid.reserve(h->n)); HIP_TRY(h->rv_counters.reserve(kRevalCounters));
+    HIP_TRY(hipMemsetAsync(h->rv_counters.p, 0, sizeof cnt, h->stream));
+    HIP_TRY(hipEventRecord(h->ev[0], h->stream));
+    launch_prm_reval_valid(h->so3, h->dp, h->ms.p, h->n, h->rv_valid.p, h->rv_counters.p, h->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[1], h->stream));
+    HIP_TRY(hipMemcpyAsync(cnt, h->rv_counters.p, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->grow_ms[0] = elapsed_ms(h->ev[0], h->ev[1]);
+    n_dead = cnt[kRevalInvalid];
+    return OXHIP_OK;
+}
+
+// every buffer alloc_prm sizes by the capacity, moved to `cap` with the roadmap's part of its contents (the query flags hold
+// nothing between calls)
+int32_t grow_capacity(oxhip_prm* h, uint32_t cap) {
+    const size_t dim = h->cfg.dim, n = h->n;
+    DevBuf<double> ms;
+    DevBuf<float> ms32;
+    DevBuf<uint8_t> flags;
+    DevBuf<uint32_t> offsets;
+    HIP_TRY(ms.alloc(dim * cap)); HIP_TRY(flags.alloc(cap)); HIP_TRY(offsets.alloc((size_t)cap + 1));
+    if (!h->so3) HIP_TRY(ms32.alloc(dim * cap));
+    HIP_TRY(hipMemcpyAsync(ms.p, h->ms.p, n * dim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    if (!h->so3) HIP_TRY(hipMemcpyAsync(ms32.p, h->ms32.p, n * dim * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(offsets.p, h->offsets.p, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    std::swap(ms.p, h->ms.p); std::swap(ms.n, h->ms.n);
+    std::swap(ms32.p, h->ms32.p); std::swap(ms32.n, h->ms32.n);
+    std::swap(flags.p, h->flags.p); std::swap(flags.n, h->flags.n);
+    std::swap(offsets.p, h->offsets.p); std::swap(offsets.n, h->offsets.n);
+    h->args.ms = h->ms.p; h->args.ms32 = h->ms32.p; h->args.cap = cap;
+    return OXHIP_OK;
+}
+
+// the directed keys of the roadmap as it stands, under the current capacity's shift: what this call's edge keys are appended to
+int32_t keys_from_csr(oxhip_prm* h) {
+    HIP_TRY(h->keys.reserve(std::max<size_t>(h->n_keys, 1)));
+    h->args.keys = h->keys.p;
+    HIP_TRY(hipEventRecord(h->ev[0], h->stream));
+    launch_prm_grow_keys(h->offsets.p, h->nbrs.p, h->n, h->n_keys, prm_key_shift(h->args.cap), h->keys.p, h->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[1], h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->grow_ms[1] = elapsed_ms(h->ev[0], h->ev[1]);
+    return OXHIP_OK;
+}
+
+// the candidates whose earlier end is live, into gw_cand: `pairs` and st.n_cand come back as what the edge step reads
+int32_t drop_dead_candidates(oxhip_prm* h, PrmState& st, uint32_t n_old, uint2*& pairs) {
+    const uint32_t nc = (uint32_t)st.n_cand;
+    uint32_t kept = 0;
+    HIP_TRY(h->gw_cand.reserve(std::max<uint32_t>(nc, 1))); HIP_TRY(h->gw_count.reserve(1));
+    HIP_TRY(hipMemsetAsync(h->gw_count.p, 0, sizeof(uint32_t), h->stream));
+    HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+    launch_prm_grow_filter(pairs, nc, h->rv_valid.p, n_old, h->gw_cand.p, h->gw_count.p, h->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[3], h->stream));
+    HIP_TRY(hipMemcpyAsync(&kept, h->gw_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->t_ms[1] += elapsed_ms(h->ev[2], h->ev[3]);
+    st.n_cand = kept;
+    pairs = h->gw_cand.p;
+    return OXHIP_OK;
+}
+
+// construction's round for the milestones [n_old, n_now) on the roadmap that exists: sample, pairs, edges, sort + CSR
+int32_t grow_round(oxhip_prm* h, PrmState& st, uint32_t n_more, uint64_t sample_limit, bool any_dead) {
+    const uint32_t n_old = h->n, knn_k = h->cfg.knn_k;
+    OX_TRY(write_state(h, st));
+    HIP_TRY(hipEventRecord(h->ev[0], h->stream));
+    OX_TRY(sample_until(h, st, n_old + n_more, sample_limit));
+    HIP_TRY(hipEventRecord(h->ev[1], h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->t_ms[0] = elapsed_ms(h->ev[0], h->ev[1]);
+    const uint32_t n_now = st.n_milestones;
+    if (n_now > n_old && n_now >= 2 && (h->thr_conn >= 0.0 || knn_k)) {   // (construct_roadmap's condition)
+        if (knn_k) OX_TRY(knn_row_radii(h, st, n_old, n_now));
+        OX_TRY(find_pairs(h, st, n_old, n_now));
+        uint2* pairs = h->cand.p;
+        if (knn_k) OX_TRY(knn_select(h, st, n_old, n_now, pairs));
+        else if (any_dead) OX_TRY(drop_dead_candidates(h, st, n_old, pairs));   // no dead milestone: exactly construction's candidates
+        OX_TRY(reserve_keys(h, st));
+        OX_TRY(check_edges(h, st, pairs));
+    }
+    return build_csr(h, n_now, st.n_keys);
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t oxhip_prm_grow_roadmap(oxhip_prm* h, const oxhip_prm_grow_config* g, uint32_t* n_added, uint64_t* n_samples_drawn) {
+    if (!h || !g || !n_added || !n_samples_drawn) return fail(OXHIP_ERR_BAD_ARG, "null argument");
+    if (g->struct_size != sizeof(oxhip_prm_grow_config)) return fail(OXHIP_ERR_BAD_ARG, "struct_size mismatch");
+    *n_added = 0;
+    *n_samples_drawn = 0;
+    if (g->n_more == 0) return fail(OXHIP_ERR_BAD_ARG, "n_more must be at least 1");
+    if (g->flags & ~OXHIP_PRM_GROW_NEW_STREAM) return fail(OXHIP_ERR_BAD_ARG, "unknown flag (OXHIP_PRM_GROW_NEW_STREAM is the only one)");
+    if (!h->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
+    if (h->n == 0) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "the roadmap holds no milestones: construct_roadmap() builds one");
+    const bool new_stream = (g->flags & OXHIP_PRM_GROW_NEW_STREAM) != 0;
+    if (!new_stream && !h->pos_valid)
+        return fail(OXHIP_ERR_BAD_ARG, "this roadmap was not constructed by this handle, so there is no stream position to continue: "
+                                       "pass OXHIP_PRM_GROW_NEW_STREAM with a stream id");
+    const uint32_t n_old = h->n;
+    if ((uint64_t)n_old + g->n_more > (1ull << 26)) return fail(OXHIP_ERR_CAPACITY, "n + n_more exceeds 2^26 milestones");
+    OX_TRY(select_device(h->cfg.device));
+    uint32_t n_dead = 0;
+    OX_TRY(liveness_mask(h, n_dead));
+    if (h->cfg.knn_k && n_dead)
+        return fail(OXHIP_ERR_BAD_ARG, "k-nearest growth over invalid milestones is not built (" + std::to_string(n_dead) + " are invalid now)");
+    if (n_old + g->n_more > h->args.cap) {
+        uint32_t cap = 1024;   // the next power of two: above alloc_prm's multiple of 1024, at most 2^26
+        while (cap < n_old + g->n_more) cap *= 2;
+        OX_TRY(grow_capacity(h, cap));
+    }
+    OX_TRY(keys_from_csr(h));
+    // construction's phase times are its own: this call's go to grow_ms
+    double construct_ms[6];
+    std::memcpy(construct_ms, h->t_ms, sizeof construct_ms);
+    for (double& t : h->t_ms) t = 0.0;
+    const uint64_t budget = g->max_samples ? g->max_samples : 4096ull * g->n_more + (1ull << 22);
+    const uint64_t sample_limit = budget > ~0ull - h->n_samples ? ~0ull : h->n_samples + budget;
+    PrmState st{};
+    st.draws = new_stream ? 0 : h->pos_draws;
+    st.n_samples = h->n_samples;
+    st.n_milestones = n_old;
+    st.n_keys = h->n_keys;
+    st.redraw_batches = h->redraw_batches;
+    h->args.stream = new_stream ? g->stream : h->pos_stream;
+    const int32_t status = grow_round(h, st, g->n_more, sample_limit, n_dead != 0);
+    const uint64_t stream_used = h->args.stream;
+    h->args.stream = h->cfg.stream;   // construct_roadmap after a setup() draws from the configured stream
+    for (int i = 0; i < 4; ++i) h->grow_ms[2 + i] = h->t_ms[i];
+    std::memcpy(h->t_ms, construct_ms, sizeof construct_ms);
+    if (status != OXHIP_OK) return status;
+    *n_added = st.n_milestones - n_old;
+    *n_samples_drawn = st.n_samples - h->n_samples;
+    h->n = st.n_milestones;
+    h->n_keys = st.n_keys;
+    h->n_samples = st.n_samples;
+    h->redraw_batches = st.redraw_batches;
+    h->pos_valid = true; h->pos_stream = stream_used; h->pos_draws = st.draws;
+    drop_derived(h);   // the host copy, the last solve's sets, the last batch, the edge weights
+    return OXHIP_OK;
+}
+
+int32_t oxhip_prm_grow_last_timing(oxhip_prm* h, double* phase_ms) {
+    if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
+    if (phase_ms) for (int i = 0; i < 6; ++i) phase_ms[i] = h->grow_ms[i];
     return OXHIP_OK;
 }
 

@@ -445,6 +445,23 @@ class PRM:
                 raise Exception(_MESSAGES[e.status]) from None
             raise
 
+    def grow_roadmap(self, n_more, max_samples=0, new_stream=None):
+        """Adds up to n_more milestones to the roadmap as it stands -- built, loaded or re-checked -- under the obstacles as they
+        are now (oxhip_prm_grow_roadmap; OMPL's PRM::growRoadmap).  Old indices and rows stay; a milestone that is invalid now
+        gets no new edge.  new_stream=None continues the planner's own sampler where construct_roadmap or the last grow
+        stopped; a loaded roadmap has no such position and needs new_stream=<stream id>.  ValueError for a refused argument or
+        too many milestones.  Returns (milestones added, samples drawn)."""
+        if self._prm is None:
+            raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
+        try:
+            return self._prm.grow(int(n_more), int(max_samples), None if new_stream is None else int(new_stream))
+        except capi.OxhipError as e:
+            if e.status in (capi.ERR_BAD_ARG, capi.ERR_CAPACITY):
+                raise ValueError(str(e)) from None
+            if e.status in _MESSAGES:
+                raise Exception(_MESSAGES[e.status]) from None
+            raise
+
     def save_roadmap(self, path):
         """The roadmap as a .npz file: states, offsets, neighbours, the space's kind and the width of a state."""
         import numpy as np

@@ -134,6 +134,34 @@ pub const OXHIP_PRM_CONFIG_LAYOUT: &[(&str, usize, usize)] = &[
 ];
 pub const OXHIP_PRM_CONFIG_SIZE: usize = 200;
 
+/// `oxhip_prm_grow_config` (include/oxmpl_hip.h): what one `oxhip_prm_grow_roadmap` call adds and where its sampler starts.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct OxhipPrmGrowConfig {
+    pub struct_size: u32,
+    /// milestones to add; 0 is OXHIP_ERR_BAD_ARG
+    pub n_more: u32,
+    /// sample_uniform calls this call may make; 0 = 4096 * n_more + 2^22
+    pub max_samples: u64,
+    /// OXHIP_PRM_GROW_NEW_STREAM or 0
+    pub flags: u32,
+    pub pad: u32,
+    /// with OXHIP_PRM_GROW_NEW_STREAM: the ChaCha12 stream id to start at word 0
+    pub stream: u64,
+}
+pub const OXHIP_PRM_GROW_NEW_STREAM: u32 = 1;
+
+/// (field, byte offset, byte size) of `oxhip_prm_grow_config`
+pub const OXHIP_PRM_GROW_CONFIG_LAYOUT: &[(&str, usize, usize)] = &[
+    ("struct_size", 0, 4),
+    ("n_more", 4, 4),
+    ("max_samples", 8, 8),
+    ("flags", 16, 4),
+    ("pad", 20, 4),
+    ("stream", 24, 8),
+];
+pub const OXHIP_PRM_GROW_CONFIG_SIZE: usize = 32;
+
 /// opaque handles (owned by the library; freed with the matching `_destroy`)
 #[repr(C)]
 pub struct OxhipRrtBatch {
@@ -267,6 +295,9 @@ extern "C" {
     pub fn oxhip_prm_set_roadmap(p: *mut OxhipPrm, states: *const f64, n: u32, offsets: *const u64, neighbours: *const u32) -> i32;
     pub fn oxhip_prm_revalidate(p: *mut OxhipPrm, milestone_valid: *mut u8, n_invalid_milestones: *mut u32, n_removed_entries: *mut u64) -> i32;
     pub fn oxhip_prm_revalidate_last_timing(p: *mut OxhipPrm, phase_ms: *mut f64) -> i32;
+    // prm_grow.hip: the roadmap grown in place
+    pub fn oxhip_prm_grow_roadmap(p: *mut OxhipPrm, g: *const OxhipPrmGrowConfig, n_added: *mut u32, n_samples_drawn: *mut u64) -> i32;
+    pub fn oxhip_prm_grow_last_timing(p: *mut OxhipPrm, phase_ms: *mut f64) -> i32;
     // rrt_revalidate.hip: the trees of an RRT batch re-checked against the current obstacles
     pub fn oxhip_rrt_batch_revalidate_trees(b: *mut OxhipRrtBatch, n_removed: *mut u32, goal_lost: *mut u8) -> i32;
     pub fn oxhip_rrt_batch_get_revalidate_map(b: *mut OxhipRrtBatch, problem: u32, new_index: *mut i32, edge_ok: *mut u8, cap: u32, n_before: *mut u32) -> i32;
@@ -299,5 +330,7 @@ mod tests {
              seed, first_problem_id, device, planner, search_radius, space, goal_sampler, debug_flags, star_pool_share, frozen_split, reserved]);
         check_layout!(OxhipPrmConfig, OXHIP_PRM_CONFIG_LAYOUT, OXHIP_PRM_CONFIG_SIZE,
             [struct_size, dim, bounds, timeout, connection_radius, lvs_fraction, max_milestones, device, max_samples, seed, stream, knn_k, space]);
+        check_layout!(OxhipPrmGrowConfig, OXHIP_PRM_GROW_CONFIG_LAYOUT, OXHIP_PRM_GROW_CONFIG_SIZE,
+            [struct_size, n_more, max_samples, flags, pad, stream]);
     }
 }

@@ -538,6 +538,29 @@ impl<D: DeviceValidityChecker, G: DeviceGoal> HipPRM<D, G> {
         }
     }
 
+    /// Adds up to `n_more` milestones to the roadmap as it stands -- built, planted or re-checked -- under the handle's current
+    /// obstacles (`oxhip_prm_grow_roadmap`).  `new_stream: None` continues the planner's own sampler stream where
+    /// `construct_roadmap` or the last grow stopped; a planted roadmap has no such position and needs `Some(stream id)`.
+    /// Returns (milestones added, samples drawn); `Err` carries the library's message and the roadmap is then unchanged.
+    pub fn grow_roadmap(&mut self, n_more: u32, max_samples: u64, new_stream: Option<u64>) -> Result<(u32, u64), String> {
+        if self.prm.is_null() {
+            return Err("setup() was not called".to_string());
+        }
+        let g = ffi::OxhipPrmGrowConfig {
+            struct_size: std::mem::size_of::<ffi::OxhipPrmGrowConfig>() as u32,
+            n_more,
+            max_samples,
+            flags: if new_stream.is_some() { ffi::OXHIP_PRM_GROW_NEW_STREAM } else { 0 },
+            pad: 0,
+            stream: new_stream.unwrap_or(0),
+        };
+        let (mut added, mut drawn) = (0u32, 0u64);
+        match unsafe { ffi::oxhip_prm_grow_roadmap(self.prm, &g, &mut added, &mut drawn) } {
+            ffi::OXHIP_OK => Ok((added, drawn)),
+            _ => Err(last_error()),
+        }
+    }
+
     /// Many problem definitions on the roadmap already built, in one device call (`oxhip_prm_solve_batch`): per problem what
     /// `set_problem_definition` + `solve` would return, the breadth-first search included on the GPU.  The planner's own
     /// problem definition is left as it is.
