@@ -561,6 +561,48 @@ class PRM {
         return out;
     }
     int32_t last_grow_status() const { return grow_status_; }
+    // The roadmap's connected components (oxhip_prm_components): label[i] = the lowest milestone index of i's component,
+    // size[i] = its milestones; the largest component's ties go to the lowest label.  Only the graph is read.
+    struct Components {
+        std::vector<uint32_t> label, size;
+        uint32_t n_components = 0, largest_label = 0, largest_size = 0;
+    };
+    Result<Components, base::PlanningError> components() {
+        if (!prm_) return base::PlanningError::PlannerUninitialised;
+        Components out;
+        const uint32_t n = (uint32_t)num_milestones();
+        out.label.assign(n, 0);
+        out.size.assign(n, 0);
+        const int32_t st = oxhip_prm_components(prm_, n ? out.label.data() : nullptr, n ? out.size.data() : nullptr, n, &out.n_components,
+                                                &out.largest_label, &out.largest_size);
+        if (st != OXHIP_OK) return to_error(st);
+        return out;
+    }
+    // Removes milestones and renumbers the rest in their old order (oxhip_prm_prune).  `flags` = OXHIP_PRM_PRUNE_INVALID |
+    // _MASK | _MIN_SIZE | _LARGEST; `keep` (one byte per milestone) iff _MASK.  A refused argument or a call that would keep no
+    // milestone (OXHIP_ERR_BAD_ARG, kept in last_prune_status(), the text in oxhip_last_error_string()) comes back as
+    // NoSolutionFound and leaves the roadmap as it was.
+    struct Pruning {
+        std::vector<int32_t> new_index;   // [milestones before] -1 = dropped
+        uint32_t kept = 0;
+        uint64_t removed_entries = 0;
+    };
+    Result<Pruning, base::PlanningError> prune(uint32_t flags, uint32_t min_size = 0, const std::vector<uint8_t>* keep = nullptr) {
+        if (!prm_) return base::PlanningError::PlannerUninitialised;
+        oxhip_prm_prune_config c{};
+        c.struct_size = sizeof c;
+        c.flags = flags;
+        c.min_size = min_size;
+        Pruning out;
+        const size_t n = num_milestones();
+        if (keep && keep->size() != n) { prune_status_ = OXHIP_ERR_BAD_ARG; return to_error(prune_status_); }
+        out.new_index.assign(n, -1);
+        prune_status_ = oxhip_prm_prune(prm_, &c, keep ? keep->data() : nullptr, n ? out.new_index.data() : nullptr, &out.kept,
+                                        &out.removed_entries);
+        if (prune_status_ != OXHIP_OK) return to_error(prune_status_);
+        return out;
+    }
+    int32_t last_prune_status() const { return prune_status_; }
     int32_t last_status() const { return last_status_; }
 
   private:
@@ -582,6 +624,7 @@ class PRM {
     int32_t last_status_ = OXHIP_ERR_PLANNER_UNINITIALISED;
     int32_t set_roadmap_status_ = OXHIP_OK;
     int32_t grow_status_ = OXHIP_OK;
+    int32_t prune_status_ = OXHIP_OK;
 };
 
 }  // namespace geometric

@@ -682,6 +682,50 @@ int32_t oxhip_prm_grow_roadmap(oxhip_prm* prm, const oxhip_prm_grow_config* g, u
  * pairs (+ filter), edges, sort + CSR} */
 int32_t oxhip_prm_grow_last_timing(oxhip_prm* prm, double* phase_ms /*[6]*/);
 
+/* ---- the roadmap as a graph: connected components, and pruning (prm_components.hip) ----
+ * label[i] = the lowest milestone index of i's connected component (so label[i] <= i and label[label[i]] == label[i]);
+ * size[i] = the number of milestones in i's component.  A row without entries -- isolated or dead -- is a component of its own.
+ * Only the CSR is read: no obstacle, no state.  *largest_label = the label of the component with the most milestones, ties to the
+ * lowest label; *largest_size its size.  Any out pointer may be NULL; label/size non-NULL with cap < n: OXHIP_ERR_CAPACITY.
+ * OXHIP_ERR_BAD_ARG for a null handle, OXHIP_ERR_PLANNER_UNINITIALISED without setup(), OXHIP_ERR_UNSAMPLED_STATE_SPACE on an
+ * empty roadmap.  The labels stay on the device until the roadmap changes, so a second call only copies. */
+int32_t oxhip_prm_components(oxhip_prm* prm, uint32_t* label /*[n]*/, uint32_t* size /*[n]*/, uint32_t cap,
+                             uint32_t* n_components, uint32_t* largest_label, uint32_t* largest_size);
+/* HIP-event times (ms) of the last oxhip_prm_components: phase_ms[4] = {init + hook, flatten, sizes + summary, copies} (the first
+ * three are 0 when the call was answered from the labels kept on the device); *launches = the kernels a computation launches,
+ * a constant of the code that does not depend on the graph.  Either pointer may be NULL. */
+int32_t oxhip_prm_components_last_timing(oxhip_prm* prm, double* phase_ms /*[4]*/, uint32_t* launches);
+
+/* oxhip_prm_prune removes milestones and renumbers the rest.  The semantics are this build's own: the reference has no such call.
+ * Two stages.  Stage 1: a milestone survives iff every requested one of INVALID (is_valid holds now) and MASK (keep[i] != 0)
+ * holds.  Stage 2: MIN_SIZE and LARGEST are evaluated on the components of the graph that survives stage 1 -- an entry with a
+ * dropped end connects nothing -- so INVALID | LARGEST drops, in the same call, the smaller piece an invalid cut milestone
+ * leaves behind.  Survivors keep their relative order (new_index is monotone), so rows stay ascending and symmetric; an entry
+ * stays iff both its ends stay; states move bit for bit (with the binary32 shadow of an R^n handle).  Not a re-check: an edge
+ * between two kept milestones is never tested.  n_samples, the sampler's stream position (a default grow still works) and the
+ * capacity stay as they are.  Derived state is dropped as oxhip_prm_revalidate drops it, whether or not anything was removed:
+ * the host copy, the last solve's query sets, the last batch's results, the edge weights, the kept component labels.
+ * new_index [n before the call] (or NULL) receives where each milestone went, -1 = dropped; *n_kept and *n_removed_entries
+ * may be NULL.  R^n radius, R^n k-nearest and SO(3) handles alike.
+ * Refused before the handle is read, OXHIP_ERR_BAD_ARG: a null handle or config, a wrong struct_size, flags == 0 or an unknown
+ * flag, pad != 0, MASK without keep or keep without MASK, MIN_SIZE with min_size == 0.  Then OXHIP_ERR_PLANNER_UNINITIALISED
+ * without setup(), OXHIP_ERR_UNSAMPLED_STATE_SPACE on an empty roadmap, and OXHIP_ERR_BAD_ARG ("would keep no milestone") when
+ * nothing would survive.  A refused call leaves the handle exactly as it was. */
+#define OXHIP_PRM_PRUNE_INVALID  1u   /* drop milestones whose is_valid is false NOW (revalidate's milestone test) */
+#define OXHIP_PRM_PRUNE_MASK     2u   /* drop milestones with keep[i] == 0 */
+#define OXHIP_PRM_PRUNE_MIN_SIZE 4u   /* drop components with fewer than min_size milestones */
+#define OXHIP_PRM_PRUNE_LARGEST  8u   /* keep only the largest component (ties: lowest label) */
+typedef struct {
+    uint32_t struct_size;
+    uint32_t flags;         /* OXHIP_PRM_PRUNE_*, at least one */
+    uint32_t min_size;      /* with MIN_SIZE: at least 1 */
+    uint32_t pad;           /* 0 */
+} oxhip_prm_prune_config;   /* 16 bytes */
+int32_t oxhip_prm_prune(oxhip_prm* prm, const oxhip_prm_prune_config* c, const uint8_t* keep /*[n] iff MASK*/,
+                        int32_t* new_index /*[n_before] or NULL: -1 = dropped*/, uint32_t* n_kept, uint64_t* n_removed_entries);
+/* HIP-event times (ms) of the last oxhip_prm_prune: phase_ms[5] = {masks, components, scans, move entries, move states} */
+int32_t oxhip_prm_prune_last_timing(oxhip_prm* prm, double* phase_ms /*[5]*/);
+
 #ifdef __cplusplus
 }
 #endif

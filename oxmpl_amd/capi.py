@@ -55,6 +55,7 @@ EXPORTS = [
     "oxhip_prm_solve_batch_shortest", "oxhip_prm_batch_get_costs", "oxhip_prm_batch_get_labels", "oxhip_prm_batch_get_search_stats",
     "oxhip_prm_set_roadmap", "oxhip_prm_revalidate", "oxhip_prm_revalidate_last_timing",
     "oxhip_prm_grow_roadmap", "oxhip_prm_grow_last_timing",
+    "oxhip_prm_components", "oxhip_prm_components_last_timing", "oxhip_prm_prune", "oxhip_prm_prune_last_timing",
     "oxhip_rrt_batch_extract_paths", "oxhip_rrt_batch_get_paths", "oxhip_rrt_batch_simplify_paths",
     "oxhip_rrt_batch_get_simplified_paths", "oxhip_rrt_batch_get_simplify_results", "oxhip_rrt_batch_path_valid_matrix",
     "oxhip_rrt_batch_paths_last_timing",
@@ -92,6 +93,13 @@ class PrmGrowConfig(C.Structure):
         ("struct_size", C.c_uint32), ("n_more", C.c_uint32), ("max_samples", C.c_uint64),
         ("flags", C.c_uint32), ("pad", C.c_uint32), ("stream", C.c_uint64),
     ]
+
+
+PRM_PRUNE_INVALID, PRM_PRUNE_MASK, PRM_PRUNE_MIN_SIZE, PRM_PRUNE_LARGEST = 1, 2, 4, 8   # OXHIP_PRM_PRUNE_*
+
+
+class PrmPruneConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("min_size", C.c_uint32), ("pad", C.c_uint32)]
 
 
 class OxhipError(RuntimeError):
@@ -190,6 +198,10 @@ def lib():
         L.oxhip_prm_revalidate_last_timing.argtypes = [C.c_void_p, _dp]
         L.oxhip_prm_grow_roadmap.argtypes = [C.c_void_p, C.POINTER(PrmGrowConfig), _u32p, _u64p]
         L.oxhip_prm_grow_last_timing.argtypes = [C.c_void_p, _dp]
+        L.oxhip_prm_components.argtypes = [C.c_void_p, _u32p, _u32p, C.c_uint32, _u32p, _u32p, _u32p]
+        L.oxhip_prm_components_last_timing.argtypes = [C.c_void_p, _dp, _u32p]
+        L.oxhip_prm_prune.argtypes = [C.c_void_p, C.POINTER(PrmPruneConfig), _u8p, _i32p, _u32p, _u64p]
+        L.oxhip_prm_prune_last_timing.argtypes = [C.c_void_p, _dp]
         L.oxhip_rrt_batch_extract_paths.argtypes = [C.c_void_p]
         L.oxhip_rrt_batch_get_paths.argtypes = [C.c_void_p, _u64p, _dp, C.c_uint64, _u64p]
         L.oxhip_rrt_batch_simplify_paths.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
@@ -826,4 +838,53 @@ class PRMRoadmap:
         """dict(phase_ms=[liveness mask, keys from CSR, sample, pairs (+ filter), edges, sort + CSR]) of the last grow"""
         ms = np.zeros(6, dtype=np.float64)
         _check(lib().oxhip_prm_grow_last_timing(self._h, _p(ms)))
+        return dict(phase_ms=[float(v) for v in ms])
+
+    # ---- the roadmap as a graph: connected components, and pruning (DESIGN.md section 24)
+
+    def components(self):
+        """(label [n] u32, size [n] u32, n_components, largest_label, largest_size): label[i] is the lowest milestone index of
+        i's connected component, size[i] its number of milestones; the largest component's ties go to the lowest label.  Only
+        the CSR is read; a row without entries is a component of its own (oxhip_prm_components)."""
+        n = self.sizes()[0]
+        label, size = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+        nc, ll, ls = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _check(lib().oxhip_prm_components(self._h, _p(label, _u32p), _p(size, _u32p), n, C.byref(nc), C.byref(ll), C.byref(ls)))
+        return label[:n], size[:n], nc.value, ll.value, ls.value
+
+    def components_timing(self):
+        """dict(phase_ms=[init + hook, flatten, sizes + summary, copies], launches) of the last components()"""
+        ms = np.zeros(4, dtype=np.float64)
+        launches = C.c_uint32()
+        _check(lib().oxhip_prm_components_last_timing(self._h, _p(ms), C.byref(launches)))
+        return dict(phase_ms=[float(v) for v in ms], launches=launches.value)
+
+    def prune(self, invalid=False, keep=None, min_size=0, largest=False):
+        """Removes milestones and renumbers the rest, order kept (oxhip_prm_prune).  Stage 1: invalid=True drops the milestones
+        that are invalid now, keep=[n] bools drops those with a false entry.  Stage 2, on the components of what stage 1 left:
+        min_size > 0 drops components with fewer milestones, largest=True keeps only the largest component.  Not a re-check:
+        no edge is tested.  Returns (new_index [n before] i32 with -1 = dropped, n_kept, n_removed_entries)."""
+        n = self.sizes()[0]
+        c = PrmPruneConfig()
+        c.struct_size = C.sizeof(PrmPruneConfig)
+        c.flags = ((PRM_PRUNE_INVALID if invalid else 0) | (PRM_PRUNE_MASK if keep is not None else 0)
+                   | (PRM_PRUNE_MIN_SIZE if min_size else 0) | (PRM_PRUNE_LARGEST if largest else 0))
+        c.min_size = min_size
+        mask = None
+        if keep is not None:
+            mask = np.ascontiguousarray(np.asarray(keep).reshape(-1) != 0, dtype=np.uint8)
+            if mask.size != n:
+                raise OxhipError(ERR_BAD_ARG, "keep must hold one entry per milestone")
+            if mask.size == 0:
+                mask = np.zeros(1, dtype=np.uint8)
+        new_index = np.zeros(max(n, 1), dtype=np.int32)
+        kept, removed = C.c_uint32(), C.c_uint64()
+        _check(lib().oxhip_prm_prune(self._h, C.byref(c), None if mask is None else _p(mask, _u8p), _p(new_index, _i32p),
+                                     C.byref(kept), C.byref(removed)))
+        return new_index[:n], kept.value, removed.value
+
+    def prune_timing(self):
+        """dict(phase_ms=[masks, components, scans, move entries, move states]) of the last prune"""
+        ms = np.zeros(5, dtype=np.float64)
+        _check(lib().oxhip_prm_prune_last_timing(self._h, _p(ms)))
         return dict(phase_ms=[float(v) for v in ms])

@@ -203,6 +203,34 @@ void launch_prm_grow_keys(const uint32_t* offsets, const uint32_t* nbrs, uint32_
 void launch_prm_grow_filter(const uint2* cand, uint32_t n_cand, const uint8_t* valid, uint32_t n_old, uint2* out, uint32_t* count,
                             hipStream_t s);
 
+// prm_components.hip: a roadmap's connected components, and the roadmap pruned by a keep mask
+enum PrmCcSummary : uint32_t { kCcBest = 0, kCcRoots, kCcSummaryWords };   // (largest size << 32) | (0xFFFFFFFF - its label); the roots
+constexpr uint32_t kCcLaunches = 6;   // kernels of one launch_prm_components, whatever the graph
+struct PrmCcBuffers {
+    uint32_t* parent;              // [n] the union-find forest; scratch once the labels exist
+    uint32_t* label;               // [n] the lowest milestone index of the component
+    uint32_t* count;               // [n] count[root] = milestones of its component (live ones under `alive`)
+    uint32_t* size;                // [n] size[i] = count[label[i]] (0 for a dead i under `alive`)
+    unsigned long long* summary;   // [kCcSummaryWords]
+};
+// the components of the CSR; alive (optional, [n]): a milestone with alive[i] == 0 is a component of its own and its entries
+// connect nothing.  Records after_hook / after_flatten (optional) between its phases; returns the kernels launched (kCcLaunches).
+uint32_t launch_prm_components(const uint32_t* offsets, const uint32_t* nbrs, const uint8_t* alive, uint32_t n, uint32_t n_entries,
+                               const PrmCcBuffers& b, hipEvent_t after_hook, hipEvent_t after_flatten, hipStream_t s);
+// keep[i] = (valid == nullptr || valid[i]) && (mask == nullptr || mask[i]); *kept (zeroed by the caller) counts the ones
+void launch_prm_prune_stage1(const uint8_t* valid, const uint8_t* mask, uint32_t n, uint8_t* keep, uint32_t* kept, hipStream_t s);
+// keep[i] &&= count[label[i]] >= min_size && (!largest || label[i] == the summary's largest label); *kept as above
+void launch_prm_prune_stage2(const PrmCcBuffers& b, uint32_t n, uint32_t min_size, bool largest, uint8_t* keep, uint32_t* kept, hipStream_t s);
+// new_index[i] = keep[i] ? pos[i] : -1 (pos = exclusive scan of keep); ekeep[e] = both ends of entry e are kept
+void launch_prm_prune_flags(const uint32_t* offsets, const uint32_t* nbrs, const uint8_t* keep, const uint32_t* pos, uint32_t n,
+                            uint32_t n_entries, int32_t* new_index, uint8_t* ekeep, hipStream_t s);
+// the kept entries renumbered into nbrs_out at epos (= exclusive scan of ekeep), the n_kept + 1 new offsets into offsets_out
+void launch_prm_prune_entries(const uint32_t* offsets, const uint32_t* nbrs, const uint8_t* ekeep, const uint32_t* epos, const int32_t* new_index,
+                              uint32_t n, uint32_t n_entries, uint32_t n_kept, uint32_t* offsets_out, uint32_t* nbrs_out, hipStream_t s);
+// row i of ms (AoS [n][dim]) and of ms32 (nullptr: no shadow) to row new_index[i] of ms_out / ms32_out, bit for bit
+void launch_prm_prune_states(const double* ms, const float* ms32, const int32_t* new_index, uint32_t n, uint32_t dim, double* ms_out,
+                             float* ms32_out, hipStream_t s);
+
 // rrt_revalidate.hip: the trees of an RRT batch re-checked against the current obstacles and compacted in place (DESIGN.md
 // section 21).  The per-slot arrays are [P][cap], indexed like DevParams::parent.
 struct ProblemState;

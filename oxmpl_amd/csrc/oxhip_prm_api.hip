@@ -7,7 +7,9 @@
 // reserve_keys, check_edges, then build_csr; solve = query_sets, prm_bfs_path (oxhip_host.hpp, on the CSR roadmap copied back once per
 // construction), the path; solve_batch[_shortest] (DESIGN.md sections 17, 19) = stage_batch, reserve_batch_workspace, then per round
 // run_round, scatter_round, extract_round_paths; grow_roadmap = liveness_mask, grow_capacity, keys_from_csr,
-// then grow_round: construction's steps for the new milestones, with drop_dead_candidates before the edges.  The space is named by the dispatchers below the handle, the per-space part of
+// then grow_round: construction's steps for the new milestones, with drop_dead_candidates before the edges; components (DESIGN.md
+// section 24) = components_of, then the copies; prune = prune_stage1_mask, components_of(alive), prune_stage2_mask, compact_roadmap.
+// The space is named by the dispatchers below the handle, the per-space part of
 // the sampler, the steps of create, the two obstacle setters and the prm_shortest launches that take it as an argument.
 #include <algorithm>
 #include <chrono>
@@ -109,6 +111,19 @@ struct oxhip_prm {
     DevBuf<uint2> gw_cand;
     DevBuf<uint32_t> gw_count;
     double grow_ms[6] = {};    // liveness mask, keys from CSR, sample, pairs (+ filter), edges, sort + CSR
+    // oxhip_prm_components / oxhip_prm_prune: the union-find's arrays (the labels, sizes and summary are
+    // kept until the roadmap changes), the prune's masks, scans and second buffers, the phase times of the last calls
+    bool cc_valid = false;     // cc_label / cc_size / cc_summary describe the roadmap as it stands
+    DevBuf<uint32_t> cc_parent, cc_label, cc_count, cc_size;
+    DevBuf<unsigned long long> cc_summary;
+    DevBuf<uint8_t> pr_keep, pr_mask, pr_ekeep;
+    DevBuf<uint32_t> pr_pos, pr_epos, pr_kept, pr_offsets, pr_nbrs;
+    DevBuf<int32_t> pr_index;
+    DevBuf<double> pr_ms;
+    DevBuf<float> pr_ms32;
+    hipEvent_t cev[10] = {};
+    double cc_ms[4] = {};      // init + hook, flatten, sizes + summary, copies
+    double prune_ms[5] = {};   // masks, components, scans, move entries, move states
 };
 
 namespace {
@@ -201,6 +216,7 @@ void drop_derived(oxhip_prm* h) {
     h->goal_idx.clear();
     h->batch_valid = false;   // the batch's results are about the roadmap that just went
     h->w_valid = false;       // and so are the edge weights
+    h->cc_valid = false;      // and the component labels
 }
 
 void clear_roadmap(oxhip_prm* h) {
@@ -374,6 +390,7 @@ int32_t alloc_prm(oxhip_prm* h) {
     for (auto& ev : h->ev) chk(hipEventCreate(&ev));
     for (auto& ev : h->bev) chk(hipEventCreate(&ev));
     for (auto& ev : h->sev) chk(hipEventCreate(&ev));
+    for (auto& ev : h->cev) chk(hipEventCreate(&ev));
     chk(h->ms.alloc((size_t)dim * cap));
     if (!h->so3) chk(h->ms32.alloc((size_t)dim * cap));   // (the SO(3) pair search screens nothing)
     chk(h->state.alloc(1));
@@ -569,6 +586,7 @@ int32_t oxhip_prm_destroy(oxhip_prm* h) {
     for (auto& ev : h->ev) if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : h->bev) if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : h->sev) if (ev) (void)hipEventDestroy(ev);
+    for (auto& ev : h->cev) if (ev) (void)hipEventDestroy(ev);
     if (h->stream) oxhip_stream_release(h->cfg.device, h->stream);
     delete h;
     return OXHIP_OK;
@@ -677,6 +695,7 @@ int32_t oxhip_prm_construct_roadmap(oxhip_prm* h) {
     OX_TRY(build_csr(h, st.n_milestones, st.n_keys));
     h->n_keys = st.n_keys;
     h->w_valid = false;     // the edge weights of the roadmap before this one
+    h->cc_valid = false;    // and its component labels
     h->host_copy = false;   // fetched by the first get_roadmap / solve
     h->n = st.n_milestones;
     h->n_samples = st.n_samples;
@@ -1418,6 +1437,208 @@ int32_t oxhip_prm_grow_roadmap(oxhip_prm* h, const oxhip_prm_grow_config* g, uin
 int32_t oxhip_prm_grow_last_timing(oxhip_prm* h, double* phase_ms) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
     if (phase_ms) for (int i = 0; i < 6; ++i) phase_ms[i] = h->grow_ms[i];
+    return OXHIP_OK;
+}
+
+}  // extern "C"
+
+// ---- the roadmap as a graph: its connected components, and the roadmap pruned
+
+namespace {
+
+PrmCcBuffers cc_buffers(oxhip_prm* h) { return PrmCcBuffers{h->cc_parent.p, h->cc_label.p, h->cc_count.p, h->cc_size.p, h->cc_summary.p}; }
+
+// the union-find's arrays for the roadmap as it stands: before any timed region (hipMalloc is a blocking call)
+int32_t reserve_components(oxhip_prm* h) {
+    const size_t n = h->n;
+    HIP_TRY(h->cc_parent.reserve(n)); HIP_TRY(h->cc_label.reserve(n)); HIP_TRY(h->cc_count.reserve(n)); HIP_TRY(h->cc_size.reserve(n));
+    HIP_TRY(h->cc_summary.reserve(kCcSummaryWords));
+    return OXHIP_OK;
+}
+
+// labels, sizes and summary of the CSR into the cc_ buffers; alive (device, [n], or null): prune's stage-1 survivors.  Records
+// the events first .. first + 3 around its three phases; the kept labels are the whole roadmap's only without a mask.
+int32_t components_of(oxhip_prm* h, const uint8_t* alive, uint32_t first) {
+    h->cc_valid = false;
+    HIP_TRY(hipEventRecord(h->cev[first], h->stream));
+    launch_prm_components(h->offsets.p, h->nbrs.p, alive, h->n, h->n_keys, cc_buffers(h), h->cev[first + 1], h->cev[first + 2], h->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->cev[first + 3], h->stream));
+    return OXHIP_OK;
+}
+
+// every refusal of oxhip_prm_prune that needs neither the handle's contents nor a device
+int32_t validate_prune_args(const oxhip_prm* h, const oxhip_prm_prune_config* c, const uint8_t* keep) {
+    constexpr uint32_t known = OXHIP_PRM_PRUNE_INVALID | OXHIP_PRM_PRUNE_MASK | OXHIP_PRM_PRUNE_MIN_SIZE | OXHIP_PRM_PRUNE_LARGEST;
+    if (!h || !c) return fail(OXHIP_ERR_BAD_ARG, "null argument");
+    if (c->struct_size != sizeof(oxhip_prm_prune_config)) return fail(OXHIP_ERR_BAD_ARG, "struct_size mismatch");
+    if (c->flags == 0) return fail(OXHIP_ERR_BAD_ARG, "flags must name at least one of OXHIP_PRM_PRUNE_INVALID, _MASK, _MIN_SIZE, _LARGEST");
+    if (c->flags & ~known) return fail(OXHIP_ERR_BAD_ARG, "unknown flag (OXHIP_PRM_PRUNE_INVALID, _MASK, _MIN_SIZE and _LARGEST are the four)");
+    if (c->pad != 0) return fail(OXHIP_ERR_BAD_ARG, "pad must be 0");
+    if ((c->flags & OXHIP_PRM_PRUNE_MASK) && !keep) return fail(OXHIP_ERR_BAD_ARG, "OXHIP_PRM_PRUNE_MASK needs a keep mask");
+    if (!(c->flags & OXHIP_PRM_PRUNE_MASK) && keep) return fail(OXHIP_ERR_BAD_ARG, "a keep mask needs OXHIP_PRM_PRUNE_MASK");
+    if ((c->flags & OXHIP_PRM_PRUNE_MIN_SIZE) && c->min_size == 0) return fail(OXHIP_ERR_BAD_ARG, "OXHIP_PRM_PRUNE_MIN_SIZE needs min_size >= 1");
+    return OXHIP_OK;
+}
+
+// every buffer of a prune before its timed region: masks, scans, the second buffers the compaction writes
+int32_t reserve_prune(oxhip_prm* h, uint32_t flags, size_t& tmp_bytes) {
+    const size_t n = h->n, ne = h->n_keys, dim = h->cfg.dim, cap = h->args.cap;
+    HIP_TRY(h->pr_keep.reserve(n)); HIP_TRY(h->pr_pos.reserve(n)); HIP_TRY(h->pr_index.reserve(n)); HIP_TRY(h->pr_kept.reserve(2));
+    if (flags & OXHIP_PRM_PRUNE_MASK) HIP_TRY(h->pr_mask.reserve(n));
+    if (flags & OXHIP_PRM_PRUNE_INVALID) { HIP_TRY(h->rv_valid.reserve(n)); HIP_TRY(h->rv_counters.reserve(kRevalCounters)); }
+    if (flags & (OXHIP_PRM_PRUNE_MIN_SIZE | OXHIP_PRM_PRUNE_LARGEST)) OX_TRY(reserve_components(h));
+    HIP_TRY(h->pr_ekeep.reserve(std::max<size_t>(ne, 1))); HIP_TRY(h->pr_epos.reserve(std::max<size_t>(ne, 1)));
+    HIP_TRY(h->pr_nbrs.reserve(std::max<size_t>(ne, 1)));
+    if (h->pr_offsets.n != cap + 1) HIP_TRY(h->pr_offsets.alloc(cap + 1));   // swapped with offsets: the capacity's size exactly
+    if (h->pr_ms.n != dim * cap) HIP_TRY(h->pr_ms.alloc(dim * cap));
+    if (!h->so3 && h->pr_ms32.n != dim * cap) HIP_TRY(h->pr_ms32.alloc(dim * cap));
+    size_t a = 0, b = 0;
+    HIP_TRY(prm_reval_scan(nullptr, a, h->pr_keep.p, h->pr_pos.p, (uint32_t)n, h->stream));
+    if (ne) HIP_TRY(prm_reval_scan(nullptr, b, h->pr_ekeep.p, h->pr_epos.p, (uint32_t)ne, h->stream));
+    tmp_bytes = std::max(a, b);
+    HIP_TRY(h->rv_tmp.reserve(tmp_bytes));
+    return OXHIP_OK;
+}
+
+// stage 1 into pr_keep: INVALID by the re-check's own milestone kernel (as liveness_mask), MASK from the caller's bytes (pr_mask)
+int32_t prune_stage1_mask(oxhip_prm* h, uint32_t flags) {
+    const uint8_t *valid = nullptr, *mask = nullptr;
+    if (flags & OXHIP_PRM_PRUNE_INVALID) {
+        HIP_TRY(hipMemsetAsync(h->rv_counters.p, 0, kRevalCounters * sizeof(uint32_t), h->stream));
+        launch_prm_reval_valid(h->so3, h->dp, h->ms.p, h->n, h->rv_valid.p, h->rv_counters.p, h->stream);
+        HIP_TRY(hipGetLastError());
+        valid = h->rv_valid.p;
+    }
+    if (flags & OXHIP_PRM_PRUNE_MASK) mask = h->pr_mask.p;
+    launch_prm_prune_stage1(valid, mask, h->n, h->pr_keep.p, h->pr_kept.p, h->stream);
+    HIP_TRY(hipGetLastError());
+    return OXHIP_OK;
+}
+
+// stage 2 on the components of the stage-1 survivors (cc_ buffers): MIN_SIZE and LARGEST into pr_keep
+int32_t prune_stage2_mask(oxhip_prm* h, const oxhip_prm_prune_config* c) {
+    launch_prm_prune_stage2(cc_buffers(h), h->n, (c->flags & OXHIP_PRM_PRUNE_MIN_SIZE) ? c->min_size : 0u,
+                            (c->flags & OXHIP_PRM_PRUNE_LARGEST) != 0, h->pr_keep.p, h->pr_kept.p + 1, h->stream);
+    HIP_TRY(hipGetLastError());
+    return OXHIP_OK;
+}
+
+// the roadmap of the n_kept milestones of pr_keep, into the second buffers; the handle takes them when everything has run
+int32_t compact_roadmap(oxhip_prm* h, uint32_t n_kept, size_t tmp_bytes, int32_t* new_index, uint32_t& n_entries_new) {
+    const uint32_t n = h->n, ne = h->n_keys, dim = h->cfg.dim;
+    HIP_TRY(hipEventRecord(h->cev[6], h->stream));
+    HIP_TRY(prm_reval_scan(h->rv_tmp.p, tmp_bytes, h->pr_keep.p, h->pr_pos.p, n, h->stream));
+    launch_prm_prune_flags(h->offsets.p, h->nbrs.p, h->pr_keep.p, h->pr_pos.p, n, ne, h->pr_index.p, h->pr_ekeep.p, h->stream);
+    HIP_TRY(hipGetLastError());
+    if (ne) HIP_TRY(prm_reval_scan(h->rv_tmp.p, tmp_bytes, h->pr_ekeep.p, h->pr_epos.p, ne, h->stream));
+    HIP_TRY(hipEventRecord(h->cev[7], h->stream));
+    if (ne) launch_prm_prune_entries(h->offsets.p, h->nbrs.p, h->pr_ekeep.p, h->pr_epos.p, h->pr_index.p, n, ne, n_kept, h->pr_offsets.p,
+                                     h->pr_nbrs.p, h->stream);
+    else HIP_TRY(hipMemsetAsync(h->pr_offsets.p, 0, ((size_t)n_kept + 1) * sizeof(uint32_t), h->stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->cev[8], h->stream));
+    launch_prm_prune_states(h->ms.p, h->so3 ? nullptr : h->ms32.p, h->pr_index.p, n, dim, h->pr_ms.p, h->so3 ? nullptr : h->pr_ms32.p, h->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->cev[9], h->stream));
+    n_entries_new = 0;
+    if (ne) HIP_TRY(hipMemcpyAsync(&n_entries_new, h->pr_offsets.p + n_kept, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (new_index) HIP_TRY(hipMemcpyAsync(new_index, h->pr_index.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    std::swap(h->offsets.p, h->pr_offsets.p); std::swap(h->offsets.n, h->pr_offsets.n);
+    std::swap(h->nbrs.p, h->pr_nbrs.p); std::swap(h->nbrs.n, h->pr_nbrs.n);
+    std::swap(h->ms.p, h->pr_ms.p); std::swap(h->ms.n, h->pr_ms.n);
+    if (!h->so3) { std::swap(h->ms32.p, h->pr_ms32.p); std::swap(h->ms32.n, h->pr_ms32.n); }
+    h->args.ms = h->ms.p; h->args.ms32 = h->ms32.p;
+    return OXHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t oxhip_prm_components(oxhip_prm* h, uint32_t* label, uint32_t* size, uint32_t cap, uint32_t* n_components, uint32_t* largest_label,
+                             uint32_t* largest_size) {
+    if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
+    if (!h->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
+    if (h->n == 0) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "the roadmap holds no milestones");
+    if ((label || size) && cap < h->n) return fail(OXHIP_ERR_CAPACITY, "label / size buffers too small");
+    OX_TRY(select_device(h->cfg.device));
+    const uint32_t n = h->n;
+    const bool compute = !h->cc_valid;
+    if (compute) {
+        OX_TRY(reserve_components(h));
+        OX_TRY(components_of(h, nullptr, 0));
+    }
+    unsigned long long summary[kCcSummaryWords] = {};
+    HIP_TRY(hipEventRecord(h->cev[4], h->stream));
+    HIP_TRY(hipMemcpyAsync(summary, h->cc_summary.p, sizeof summary, hipMemcpyDeviceToHost, h->stream));
+    if (label) HIP_TRY(hipMemcpyAsync(label, h->cc_label.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (size) HIP_TRY(hipMemcpyAsync(size, h->cc_size.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipEventRecord(h->cev[5], h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->cc_ms[0] = compute ? elapsed_ms(h->cev[0], h->cev[1]) : 0.0;
+    h->cc_ms[1] = compute ? elapsed_ms(h->cev[1], h->cev[2]) : 0.0;
+    h->cc_ms[2] = compute ? elapsed_ms(h->cev[2], h->cev[3]) : 0.0;
+    h->cc_ms[3] = elapsed_ms(h->cev[4], h->cev[5]);
+    h->cc_valid = true;
+    if (n_components) *n_components = (uint32_t)summary[kCcRoots];
+    if (largest_label) *largest_label = 0xFFFFFFFFu - (uint32_t)summary[kCcBest];
+    if (largest_size) *largest_size = (uint32_t)(summary[kCcBest] >> 32);
+    return OXHIP_OK;
+}
+
+int32_t oxhip_prm_components_last_timing(oxhip_prm* h, double* phase_ms, uint32_t* launches) {
+    if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
+    if (phase_ms) for (int i = 0; i < 4; ++i) phase_ms[i] = h->cc_ms[i];
+    if (launches) *launches = kCcLaunches;
+    return OXHIP_OK;
+}
+
+int32_t oxhip_prm_prune(oxhip_prm* h, const oxhip_prm_prune_config* c, const uint8_t* keep, int32_t* new_index, uint32_t* n_kept,
+                        uint64_t* n_removed_entries) {
+    OX_TRY(validate_prune_args(h, c, keep));
+    if (!h->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
+    if (h->n == 0) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "the roadmap holds no milestones");
+    OX_TRY(select_device(h->cfg.device));
+    const uint32_t n = h->n, n_old = h->n_keys;
+    const bool stage2 = (c->flags & (OXHIP_PRM_PRUNE_MIN_SIZE | OXHIP_PRM_PRUNE_LARGEST)) != 0;
+    size_t tmp_bytes = 0;
+    OX_TRY(reserve_prune(h, c->flags, tmp_bytes));
+    if (c->flags & OXHIP_PRM_PRUNE_MASK) HIP_TRY(hipMemcpyAsync(h->pr_mask.p, keep, n, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(h->pr_kept.p, 0, 2 * sizeof(uint32_t), h->stream));
+    HIP_TRY(hipEventRecord(h->cev[4], h->stream));
+    OX_TRY(prune_stage1_mask(h, c->flags));
+    if (stage2) {   // (the labels of the stage-1 survivors are not the roadmap's: components_of forgets the kept ones)
+        OX_TRY(components_of(h, h->pr_keep.p, 0));
+        OX_TRY(prune_stage2_mask(h, c));
+    }
+    HIP_TRY(hipEventRecord(h->cev[5], h->stream));
+    uint32_t kept[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(kept, h->pr_kept.p, sizeof kept, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const uint32_t n_new = stage2 ? kept[1] : kept[0];
+    if (n_new == 0) return fail(OXHIP_ERR_BAD_ARG, "would keep no milestone");   // only workspace was written so far
+    uint32_t n_entries_new = 0;
+    OX_TRY(compact_roadmap(h, n_new, tmp_bytes, new_index, n_entries_new));
+    // masks = stage 1 and stage 2 around the components; components = the union-find's three phases
+    const double comp = stage2 ? elapsed_ms(h->cev[0], h->cev[3]) : 0.0;
+    h->prune_ms[0] = stage2 ? elapsed_ms(h->cev[4], h->cev[0]) + elapsed_ms(h->cev[3], h->cev[5]) : elapsed_ms(h->cev[4], h->cev[5]);
+    h->prune_ms[1] = comp;
+    h->prune_ms[2] = elapsed_ms(h->cev[6], h->cev[7]);
+    h->prune_ms[3] = elapsed_ms(h->cev[7], h->cev[8]);
+    h->prune_ms[4] = elapsed_ms(h->cev[8], h->cev[9]);
+    h->n = n_new;
+    h->n_keys = n_entries_new;
+    drop_derived(h);   // the host copy, the last solve's sets, the last batch, the edge weights, the kept component labels
+    if (n_kept) *n_kept = n_new;
+    if (n_removed_entries) *n_removed_entries = (uint64_t)n_old - n_entries_new;
+    return OXHIP_OK;
+}
+
+int32_t oxhip_prm_prune_last_timing(oxhip_prm* h, double* phase_ms) {
+    if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
+    if (phase_ms) for (int i = 0; i < 5; ++i) phase_ms[i] = h->prune_ms[i];
     return OXHIP_OK;
 }
 

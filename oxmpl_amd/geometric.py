@@ -462,6 +462,36 @@ class PRM:
                 raise Exception(_MESSAGES[e.status]) from None
             raise
 
+    def components(self):
+        """The roadmap's connected components (oxhip_prm_components): (label [n], size [n], n_components, largest_label,
+        largest_size), label[i] being the lowest milestone index of i's component.  Two milestones can be joined by a path
+        on the roadmap iff their labels are equal."""
+        if self._prm is None:
+            raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
+        try:
+            return self._prm.components()
+        except capi.OxhipError as e:
+            if e.status in _MESSAGES:
+                raise Exception(_MESSAGES[e.status]) from None
+            raise
+
+    def prune_roadmap(self, invalid=False, keep=None, min_size=0, largest=False):
+        """Removes milestones from the roadmap and renumbers the rest in their old order (oxhip_prm_prune): first the ones that
+        are invalid now (invalid=True) and the ones keep[i] is false for, then -- on the components of what is left --
+        components below min_size milestones and, with largest=True, all but the largest component.  No edge is re-checked.
+        ValueError for a refused argument or a call that would keep no milestone.  Returns (new_index [n before] with -1 =
+        dropped, milestones kept, edge entries removed)."""
+        if self._prm is None:
+            raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
+        try:
+            return self._prm.prune(bool(invalid), keep, int(min_size), bool(largest))
+        except capi.OxhipError as e:
+            if e.status in (capi.ERR_BAD_ARG, capi.ERR_CAPACITY):
+                raise ValueError(str(e)) from None
+            if e.status in _MESSAGES:
+                raise Exception(_MESSAGES[e.status]) from None
+            raise
+
     def save_roadmap(self, path):
         """The roadmap as a .npz file: states, offsets, neighbours, the space's kind and the width of a state."""
         import numpy as np

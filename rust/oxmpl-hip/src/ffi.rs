@@ -162,6 +162,31 @@ pub const OXHIP_PRM_GROW_CONFIG_LAYOUT: &[(&str, usize, usize)] = &[
 ];
 pub const OXHIP_PRM_GROW_CONFIG_SIZE: usize = 32;
 
+/// `oxhip_prm_prune_config` (include/oxmpl_hip.h): which milestones one `oxhip_prm_prune` call drops.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct OxhipPrmPruneConfig {
+    pub struct_size: u32,
+    /// OXHIP_PRM_PRUNE_*, at least one
+    pub flags: u32,
+    /// with OXHIP_PRM_PRUNE_MIN_SIZE: at least 1
+    pub min_size: u32,
+    pub pad: u32,
+}
+pub const OXHIP_PRM_PRUNE_INVALID: u32 = 1;
+pub const OXHIP_PRM_PRUNE_MASK: u32 = 2;
+pub const OXHIP_PRM_PRUNE_MIN_SIZE: u32 = 4;
+pub const OXHIP_PRM_PRUNE_LARGEST: u32 = 8;
+
+/// (field, byte offset, byte size) of `oxhip_prm_prune_config`
+pub const OXHIP_PRM_PRUNE_CONFIG_LAYOUT: &[(&str, usize, usize)] = &[
+    ("struct_size", 0, 4),
+    ("flags", 4, 4),
+    ("min_size", 8, 4),
+    ("pad", 12, 4),
+];
+pub const OXHIP_PRM_PRUNE_CONFIG_SIZE: usize = 16;
+
 /// opaque handles (owned by the library; freed with the matching `_destroy`)
 #[repr(C)]
 pub struct OxhipRrtBatch {
@@ -298,6 +323,11 @@ extern "C" {
     // prm_grow.hip: the roadmap grown in place
     pub fn oxhip_prm_grow_roadmap(p: *mut OxhipPrm, g: *const OxhipPrmGrowConfig, n_added: *mut u32, n_samples_drawn: *mut u64) -> i32;
     pub fn oxhip_prm_grow_last_timing(p: *mut OxhipPrm, phase_ms: *mut f64) -> i32;
+    // prm_components.hip: the roadmap's connected components, and the roadmap pruned
+    pub fn oxhip_prm_components(p: *mut OxhipPrm, label: *mut u32, size: *mut u32, cap: u32, n_components: *mut u32, largest_label: *mut u32, largest_size: *mut u32) -> i32;
+    pub fn oxhip_prm_components_last_timing(p: *mut OxhipPrm, phase_ms: *mut f64, launches: *mut u32) -> i32;
+    pub fn oxhip_prm_prune(p: *mut OxhipPrm, c: *const OxhipPrmPruneConfig, keep: *const u8, new_index: *mut i32, n_kept: *mut u32, n_removed_entries: *mut u64) -> i32;
+    pub fn oxhip_prm_prune_last_timing(p: *mut OxhipPrm, phase_ms: *mut f64) -> i32;
     // rrt_revalidate.hip: the trees of an RRT batch re-checked against the current obstacles
     pub fn oxhip_rrt_batch_revalidate_trees(b: *mut OxhipRrtBatch, n_removed: *mut u32, goal_lost: *mut u8) -> i32;
     pub fn oxhip_rrt_batch_get_revalidate_map(b: *mut OxhipRrtBatch, problem: u32, new_index: *mut i32, edge_ok: *mut u8, cap: u32, n_before: *mut u32) -> i32;
@@ -332,5 +362,7 @@ mod tests {
             [struct_size, dim, bounds, timeout, connection_radius, lvs_fraction, max_milestones, device, max_samples, seed, stream, knn_k, space]);
         check_layout!(OxhipPrmGrowConfig, OXHIP_PRM_GROW_CONFIG_LAYOUT, OXHIP_PRM_GROW_CONFIG_SIZE,
             [struct_size, n_more, max_samples, flags, pad, stream]);
+        check_layout!(OxhipPrmPruneConfig, OXHIP_PRM_PRUNE_CONFIG_LAYOUT, OXHIP_PRM_PRUNE_CONFIG_SIZE,
+            [struct_size, flags, min_size, pad]);
     }
 }

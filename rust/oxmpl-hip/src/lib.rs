@@ -561,6 +561,70 @@ impl<D: DeviceValidityChecker, G: DeviceGoal> HipPRM<D, G> {
         }
     }
 
+    /// The roadmap's connected components (`oxhip_prm_components`): (label, size, n_components, largest_label, largest_size),
+    /// `label[i]` being the lowest milestone index of i's component and `size[i]` its number of milestones.  Only the graph is read.
+    #[allow(clippy::type_complexity)]
+    pub fn components(&mut self) -> Result<(Vec<u32>, Vec<u32>, u32, u32, u32), PlanningError> {
+        if self.prm.is_null() {
+            return Err(PlanningError::PlannerUninitialised);
+        }
+        let (mut n, mut entries, mut samples) = (0u32, 0u64, 0u64);
+        unsafe { ffi::oxhip_prm_get_sizes(self.prm, &mut n, &mut entries, &mut samples) };
+        let mut label = vec![0u32; (n as usize).max(1)];
+        let mut size = vec![0u32; (n as usize).max(1)];
+        let (mut count, mut largest_label, mut largest_size) = (0u32, 0u32, 0u32);
+        match unsafe {
+            ffi::oxhip_prm_components(self.prm, label.as_mut_ptr(), size.as_mut_ptr(), n, &mut count, &mut largest_label, &mut largest_size)
+        } {
+            ffi::OXHIP_OK => {
+                label.truncate(n as usize);
+                size.truncate(n as usize);
+                Ok((label, size, count, largest_label, largest_size))
+            }
+            st => Err(to_planning_error(st)),
+        }
+    }
+
+    /// Removes milestones and renumbers the rest in their old order (`oxhip_prm_prune`): `invalid` drops the ones that are
+    /// invalid now, `keep` the ones with a false entry; then, on the components of what is left, `min_size > 0` drops the
+    /// components with fewer milestones and `largest` all but the largest.  No edge is re-checked.  Returns (new_index with
+    /// -1 = dropped, milestones kept, edge entries removed); `Err` carries the library's message and the roadmap is then unchanged.
+    pub fn prune(&mut self, invalid: bool, keep: Option<&[bool]>, min_size: u32, largest: bool) -> Result<(Vec<i32>, u32, u64), String> {
+        if self.prm.is_null() {
+            return Err("setup() was not called".to_string());
+        }
+        let (mut n, mut entries, mut samples) = (0u32, 0u64, 0u64);
+        unsafe { ffi::oxhip_prm_get_sizes(self.prm, &mut n, &mut entries, &mut samples) };
+        if keep.is_some_and(|k| k.len() != n as usize) {
+            return Err("keep must hold one entry per milestone".to_string());
+        }
+        let mut flags = 0u32;
+        if invalid {
+            flags |= ffi::OXHIP_PRM_PRUNE_INVALID;
+        }
+        if keep.is_some() {
+            flags |= ffi::OXHIP_PRM_PRUNE_MASK;
+        }
+        if min_size > 0 {
+            flags |= ffi::OXHIP_PRM_PRUNE_MIN_SIZE;
+        }
+        if largest {
+            flags |= ffi::OXHIP_PRM_PRUNE_LARGEST;
+        }
+        let c = ffi::OxhipPrmPruneConfig { struct_size: std::mem::size_of::<ffi::OxhipPrmPruneConfig>() as u32, flags, min_size, pad: 0 };
+        let mask: Option<Vec<u8>> = keep.map(|k| if k.is_empty() { vec![0u8] } else { k.iter().map(|&b| b as u8).collect() });
+        let mut new_index = vec![-1i32; (n as usize).max(1)];
+        let (mut kept, mut removed) = (0u32, 0u64);
+        let keep_ptr = mask.as_ref().map_or(std::ptr::null(), |m| m.as_ptr());
+        match unsafe { ffi::oxhip_prm_prune(self.prm, &c, keep_ptr, new_index.as_mut_ptr(), &mut kept, &mut removed) } {
+            ffi::OXHIP_OK => {
+                new_index.truncate(n as usize);
+                Ok((new_index, kept, removed))
+            }
+            _ => Err(last_error()),
+        }
+    }
+
     /// Many problem definitions on the roadmap already built, in one device call (`oxhip_prm_solve_batch`): per problem what
     /// `set_problem_definition` + `solve` would return, the breadth-first search included on the GPU.  The planner's own
     /// problem definition is left as it is.
