@@ -537,7 +537,9 @@ int32_t oxhip_prm_get_query_sets(oxhip_prm* prm, uint32_t* start_connections, ui
                                  uint32_t* goal_indices, uint32_t cap_goal, uint32_t* n_goal);
 /* HIP-event times (ms) of the last construct_roadmap / solve: phase_ms[6] = {sampling, all-pairs radius
  * search, edge check_motion, key sort + CSR, query kernel, host BFS}; in-radius pairs examined; sample batches
- * replayed because rand's range sampler rejected a draw */
+ * replayed because rand's range sampler rejected a draw.  The phase times are the calls' own: oxhip_prm_grow_roadmap leaves
+ * them as they were (its phases: oxhip_prm_grow_last_timing).  The pair count is the roadmap's: a grow adds the pairs it examined,
+ * as it adds its exactly searched rows to oxhip_prm_knn_exact_rows. */
 int32_t oxhip_prm_last_timing(oxhip_prm* prm, double* phase_ms /*[6]*/, uint64_t* n_candidates,
                               uint32_t* redraw_batches);
 /* k-nearest variant, last construct_roadmap: rows whose candidate radius held fewer than k earlier milestones and that were

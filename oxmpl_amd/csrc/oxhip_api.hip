@@ -1269,9 +1269,8 @@ int32_t oxhip_rrt_batch_simplify_paths(oxhip_rrt_batch* b, uint32_t max_span, ui
     HIP_TRY(grow(b->sp_simp, P));
     HIP_TRY(grow(b->sp_checks, P));
     const SimplifyOut out{b->sp_cost.p, b->sp_par.p, b->sp_idx.p, b->sp_len.p, b->sp_raw.p, b->sp_simp.p, b->sp_checks.p};
-    hipEvent_t ev2 = nullptr;
-    HIP_TRY(hipEventCreate(&ev2));
-    struct EvGuard { hipEvent_t e; ~EvGuard() { (void)hipEventDestroy(e); } } guard{ev2};
+    enum { kPairsBegin, kPairsEnd, kDpEnd };
+    PhaseClock clk(3);
     b->paths_ms[1] = b->paths_ms[2] = 0.0;
     b->paths_rounds = 0;
     std::vector<uint64_t> woff;
@@ -1291,19 +1290,16 @@ int32_t oxhip_rrt_batch_simplify_paths(oxhip_rrt_batch* b, uint32_t max_span, ui
         HIP_TRY(grow(b->sp_bits, woff.back()));
         HIP_TRY(hipMemcpyAsync(b->sp_woff.p, woff.data(), woff.size() * sizeof(uint64_t), hipMemcpyHostToDevice, b->stream));
         const PairArgs a{b->d_path_off.p, b->path_len.p, b->path_rows.p, b->sp_woff.p, b->sp_bits.p, woff.back(), q0, n_chunk, max_span, 0, filt_base};
-        HIP_TRY(hipEventRecord(b->ev0, b->stream));
+        HIP_TRY(clk.mark(kPairsBegin, b->stream));
         launch_path_pairs(b->dp, a, b->stream);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(b->ev1, b->stream));
+        HIP_TRY(clk.mark(kPairsEnd, b->stream));
         launch_path_dp(b->dp, a, out, b->stream);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ev2, b->stream));
+        HIP_TRY(clk.mark(kDpEnd, b->stream));
         HIP_TRY(hipStreamSynchronize(b->stream));   // (woff is rebuilt by the next round)
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, b->ev0, b->ev1));
-        b->paths_ms[1] += ms;
-        HIP_TRY(hipEventElapsedTime(&ms, b->ev1, ev2));
-        b->paths_ms[2] += ms;
+        b->paths_ms[1] += clk.ms(kPairsBegin, kPairsEnd);
+        b->paths_ms[2] += clk.ms(kPairsEnd, kDpEnd);
         b->paths_rounds++;
         q0 = q1;
     }
@@ -1542,18 +1538,17 @@ int32_t oxhip_rrt_batch_revalidate_trees(oxhip_rrt_batch* b, uint32_t* n_removed
     a.edge_ok = b->rv_edge_ok.p; a.alive = b->rv_alive.p; a.new_index = b->rv_new_index.p; a.jump = b->rv_jump.p;
     a.n_after = b->rv_n_after.p; a.n_removed = b->rv_n_removed.p; a.goal_lost = b->rv_goal_lost.p;
     a.cap = cap;
-    hipEvent_t ev[5] = {};
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 5; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
-    for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(ev[0], b->stream));
+    enum { kBegin, kEdgesEnd, kSurviveEnd, kScanEnd, kCompactEnd };   // reval_ms[i]: mark i to mark i + 1
+    PhaseClock clk(5);
+    HIP_TRY(clk.mark(kBegin, b->stream));
     launch_rrt_reval_edges(b->dp, a, P, b->stream);
-    HIP_TRY(hipEventRecord(ev[1], b->stream));
+    HIP_TRY(clk.mark(kEdgesEnd, b->stream));
     launch_rrt_reval_survive(a, P, b->stream);
-    HIP_TRY(hipEventRecord(ev[2], b->stream));
+    HIP_TRY(clk.mark(kSurviveEnd, b->stream));
     launch_rrt_reval_scan(a, P, b->stream);
-    HIP_TRY(hipEventRecord(ev[3], b->stream));
+    HIP_TRY(clk.mark(kScanEnd, b->stream));
     launch_rrt_reval_compact(b->dp, a, P, b->stream);
-    HIP_TRY(hipEventRecord(ev[4], b->stream));
+    HIP_TRY(clk.mark(kCompactEnd, b->stream));
     HIP_TRY(hipGetLastError());
     // what set_tree drops, for every problem: the fl32 shadows start over, the cell grids too
     if (b->shadow_state.p) HIP_TRY(hipMemsetAsync(b->shadow_state.p, 0, (size_t)P * 2 * sizeof(uint32_t), b->stream));
@@ -1562,11 +1557,7 @@ int32_t oxhip_rrt_batch_revalidate_trees(oxhip_rrt_batch* b, uint32_t* n_removed
     if (n_removed) HIP_TRY(hipMemcpyAsync(n_removed, b->rv_n_removed.p, (size_t)P * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
     if (goal_lost) HIP_TRY(hipMemcpyAsync(goal_lost, b->rv_goal_lost.p, P, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
-    for (int i = 0; i < 4; ++i) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-        b->reval_ms[i] = ms;
-    }
+    for (int i = kBegin; i < kCompactEnd; ++i) b->reval_ms[i] = clk.ms(i, i + 1);
     b->reval_ok = true;
     return OXHIP_OK;
 }

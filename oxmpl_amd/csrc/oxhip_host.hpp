@@ -5,7 +5,8 @@
 // validate_config (pure host code: space_resolution, se_space_resolution, so3_space_resolution and so2_space_resolution below), fill_params,
 // alloc_common (alloc_star at its place), the kernel kind, alloc_cells, alloc_shadow -- and the entry points' shared openings
 // (setup_done / ready) and bodies (copy_tree, op_batch with a TmpStream).  oxhip_prm_api.hip takes the same resolution helpers for
-// validate_prm_config, DevBuf::reserve for its workspaces and prm_bfs_path, the graph search of Planner::solve.  No device code.
+// validate_prm_config, DevBuf for its workspaces and its roadmap, prm_bfs_path, the graph search of Planner::solve, and a PhaseClock
+// per service for its phase times (two calls of oxhip_api.hip time themselves with a local one).  No device code.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -17,6 +18,7 @@
 #include <limits>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/oxmpl_hip.h"
@@ -100,6 +102,28 @@ struct DevBuf {
         return hipMalloc((void**)&p, count * sizeof(T));
     }
     hipError_t reserve(size_t count) { return n < count ? alloc(count) : hipSuccess; }   // grow to at least `count`; contents not preserved
+    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(n, o.n); }
+};
+
+// The clock of one service of a handle, or of one call: n events, made with their owner (which create() builds, and a call declares,
+// once the device is current) and destroyed with it: like DevBuf, after destroy() has made the device current.  The owner names its
+// marks with an enum.  mark(i) records mark i on the stream; once the stream is synchronised, ms(i, j) is the GPU time from mark i
+// to mark j (0 where the runtime refuses).  A service reads only marks that it recorded itself, in the same call.  `made` is the
+// first error of making the events, for the owner's create() to refuse with; event(i) is for a launcher that records a mark itself.
+struct PhaseClock {
+    std::vector<hipEvent_t> ev;
+    hipError_t made = hipSuccess;
+    explicit PhaseClock(int n) : ev(n, nullptr) {
+        for (hipEvent_t& e : ev) {
+            const hipError_t r = hipEventCreate(&e);
+            if (r != hipSuccess) { e = nullptr; if (made == hipSuccess) made = r; }
+        }
+    }
+    PhaseClock(const PhaseClock&) = delete;
+    ~PhaseClock() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    hipError_t mark(int i, hipStream_t s) { return hipEventRecord(ev[i], s); }
+    hipEvent_t event(int i) const { return ev[i]; }
+    double ms(int i, int j) const { float t = 0.f; return hipEventElapsedTime(&t, ev[i], ev[j]) == hipSuccess ? (double)t : 0.0; }
 };
 
 // what create() answers when one of its device allocations failed
@@ -233,9 +257,11 @@ inline int32_t so2_space_resolution(const double* bounds, double& fraction, doub
 // PRM's Planner::solve from the query sets on (prm.rs:266-304) and reconstruct_path (prm.rs:189-208), on the CSR roadmap (every
 // row ascending): pure host code.  flags[i] & 2 marks a goal milestone; start_conn are the start connections, enqueued twice, as
 // the reference does.  The clock starts here and is read at every pop (prm.rs:285-287); timeout_s = +inf: no limit, and no clock read.
-// found: out_chain = goal milestone ... root connection (the path's states in reverse).
+// found: out_chain = goal milestone ... root connection (the path's states in reverse).  Starts on a 64-byte line: the same
+// instructions ran 10 % slower on SO(3) roadmaps where the linker happened to start them at 16 mod 64 -- the figure to check again
+// is tools/bench_prm_queries.py's SO(3) loop.host_bfs_ms_sum (profiles/prm_handle_parts/README.md, section 1).
 enum class PrmBfs { found, unreachable, timed_out, empty_set };
-inline PrmBfs prm_bfs_path(const std::vector<uint32_t>& offsets, const std::vector<uint32_t>& nbrs, const std::vector<uint8_t>& flags,
+__attribute__((aligned(64))) inline PrmBfs prm_bfs_path(const std::vector<uint32_t>& offsets, const std::vector<uint32_t>& nbrs, const std::vector<uint8_t>& flags,
                            const std::vector<uint32_t>& start_conn, double timeout_s, std::vector<uint32_t>& out_chain) {
     const auto t0 = std::chrono::steady_clock::now();
     out_chain.clear();

@@ -2,19 +2,21 @@
 //
 // Host side of oxmpl's PRM (oxmpl/src/geometric/planners/prm.rs): owns the device roadmap and drives the kernels of prm_kernels.hip
 // (space = OXHIP_SPACE_SO3: prm_so3.hip).  No CPU fallback: without a HIP device every computing entry point fails.
-// Each entry point is a sequence of named steps ("PRM host side"): create = validate_prm_config, select_device,
-// fill_prm_params, alloc_prm; construct_roadmap = the reference's loop over sample_until, knn_row_radii, find_pairs, knn_select,
-// reserve_keys, check_edges, then build_csr; solve = query_sets, prm_bfs_path (oxhip_host.hpp, on the CSR roadmap copied back once per
-// construction), the path; solve_batch[_shortest] (DESIGN.md sections 17, 19) = stage_batch, reserve_batch_workspace, then per round
-// run_round, scatter_round, extract_round_paths; grow_roadmap = liveness_mask, grow_capacity, keys_from_csr,
-// then grow_round: construction's steps for the new milestones, with drop_dead_candidates before the edges; components (DESIGN.md
-// section 24) = components_of, then the copies; prune = prune_stage1_mask, components_of(alive), prune_stage2_mask, compact_roadmap.
-// The space is named by the dispatchers below the handle, the per-space part of
-// the sampler, the steps of create, the two obstacle setters and the prm_shortest launches that take it as an argument.
+// The handle (struct oxhip_prm) holds the roadmap as one value (PrmRoadmap) and one member per service -- sampler, k-nearest,
+// construction's workspace and tally, single query, batch, shortest, re-check, growth, components, prune -- each with its clock
+// (PhaseClock, oxhip_host.hpp), phase times and validity flag.  Each entry point is a sequence of named steps (DESIGN.md section 1,
+// "PRM host side"): create = validate_prm_config, select_device, fill_prm_params, alloc_prm; construct_roadmap = the reference's loop
+// over sample_until, knn_row_radii, find_pairs, knn_select, reserve_keys, check_edges, then build_csr, adding up into the tally their
+// caller gives them; solve = query_sets, prm_bfs_path (oxhip_host.hpp, on the CSR roadmap copied back once per roadmap), the path;
+// solve_batch[_shortest] (sections 17, 19) = stage_batch, reserve_batch_workspace, then per round run_round, scatter_round,
+// extract_round_paths; revalidate (section 20) and the two below start from milestone_validity; grow_roadmap (section 23) = that
+// liveness mask, grow_capacity, keys_from_csr, then grow_round: construction's steps into growth's tally, with drop_dead_candidates
+// before the edges; components (section 24) = components_of, then the copies; prune = prune_stage1_mask, components_of(alive),
+// prune_stage2_mask, compact_roadmap.  The space is named by the dispatchers below the handle, the per-space part of the sampler,
+// the steps of create, the two obstacle setters and the prm_shortest launches that take it as an argument.
 #include <algorithm>
 #include <chrono>
 #include <cstring>
-#include <deque>
 
 #include "oxhip_host.hpp"
 #include "oxhip_internal.hpp"
@@ -22,6 +24,34 @@
 
 using namespace oxhip;
 
+// The roadmap as one value: what replaces one of its buffers ends in bind_roadmap, what changes it in drop_derived / clear_roadmap.
+struct PrmBuffers {
+    DevBuf<double> ms;                // milestones, [dim][capacity]
+    DevBuf<float> ms32;               // their fl32 shadow (the R^n pair-search screen; SO(3) has none)
+    DevBuf<uint32_t> offsets, nbrs;   // CSR: [capacity + 1], [n_keys]
+};
+struct PrmRoadmap : PrmBuffers {
+    uint32_t n = 0, n_keys = 0;       // milestones, directed edge entries
+};
+
+// What the steps of a construction or of a growth add up, given to them by their caller, with the clock they time themselves by:
+// each step brackets itself (kBegin, kEnd) and reads the clock before the next one starts.
+enum Span { kBegin, kEnd };
+struct PrmBuildTally {
+    PhaseClock clk{2};
+    double ms[4] = {};          // sample, pairs (+ k-nearest selection, + growth's filter), edges, sort + CSR
+    uint64_t candidates = 0;    // in-radius pairs found
+    uint32_t exact_rows = 0;    // k-nearest rows that needed the exact search
+    void reset() { for (double& t : ms) t = 0.0; candidates = 0; exact_rows = 0; }
+};
+
+// the other clocks' marks (kLabelsEnd: shortest paths only; kCcBegin .. kCcEnd and kPrCcBegin .. kPrCcEnd: components_of's four)
+enum BatchMark { kRoundBegin, kFlagsEnd, kLabelsEnd, kSearchEnd, kResultsEnd, kPathsBegin, kPathsEnd, kRowsEnd };
+enum RevalMark { kRvBegin, kRvValidEnd, kRvEmitEnd, kRvEdgesBegin, kRvEdgesEnd, kRvCompactEnd };
+enum CcMark { kCcBegin, kCcHooked, kCcFlat, kCcEnd, kCcCopyBegin, kCcCopyEnd };
+enum PruneMark { kPrBegin, kPrCcBegin, kPrCcEnd = kPrCcBegin + 3, kPrMasksEnd, kPrScanBegin, kPrScanEnd, kPrEntriesEnd, kPrStatesEnd };
+
+// The handle: the configuration, the roadmap, and per service its workspace, clock, last call's phase times (ms) and validity flag.
 struct oxhip_prm {
     oxhip_prm_config cfg{};
     DevParams dp{};           // space, resolution and validity field (the RRT fields stay zero)
@@ -29,113 +59,124 @@ struct oxhip_prm {
     double thr_conn = -1.0;   // d2 <= thr_conn  <=>  distance < connection_radius
     bool so3 = false;         // OXHIP_SPACE_SO3: quaternion milestones, cones, prm_so3.hip
     double so3_lo = -1.0, so3_hi = -1.0;   // |dot| bands of the SO(3) radius test (so3_radius_bands)
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[6] = {};
-    DevBuf<double> ms, sph_c, sph_thr, sph_r, box_lo, box_hi;
-    DevBuf<float> ms32;   // fl32 shadow of the milestones (pair-search screen)
     double maxabs = 1.0;      // largest |coordinate| of bounds and sphere centres (midpoint filter margin)
-    DevBuf<PrmState> state;
-    DevBuf<uint2> cand;
-    // k-nearest variant: per-row candidate radii, the sorted candidates and their distances, the selected pairs
-    DevBuf<double> knn_thr, knn_dist;
-    DevBuf<float> knn_thr32;
-    DevBuf<uint64_t> knn_keys, knn_sorted;
-    DevBuf<uint2> knn_sel;
-    DevBuf<uint32_t> knn_counters, knn_failed;
-    uint32_t knn_failed_rows = 0;   // rows of the last construct_roadmap that needed the exact search
-    DevBuf<uint64_t> keys, keys_sorted;
-    DevBuf<uint8_t> sort_tmp;
-    uint32_t n_keys = 0;       // directed edge entries of the constructed roadmap
-    bool host_copy = false;    // h_offsets / h_nbrs / h_states are current
-    DevBuf<uint32_t> offsets, nbrs, start_valid;
-    DevBuf<uint8_t> flags;
-    // parallel sampler scratch (one round)
-    DevBuf<double> spec_tmp;
-    DevBuf<uint64_t> spec_vbits;
-    DevBuf<uint32_t> spec_off, spec_flag;
-    DevBuf<uint64_t> spec_abits;   // SO(3) sampler: accepted-attempt ballots and counts
-    DevBuf<uint32_t> spec_acnt;
-    double valid_rate = 1.0;   // running estimate of P(sample is valid), sizes the rounds
     bool is_setup = false;
-    PrmQuery query{};
-    // host copy of the constructed roadmap
-    uint32_t n = 0;
-    uint64_t n_samples = 0;
-    uint32_t redraw_batches = 0;
-    std::vector<uint32_t> h_offsets, h_nbrs;
-    std::vector<double> h_states;  // AoS [n][dim]
-    // last query
-    std::vector<uint32_t> start_conn, goal_idx;
-    // phase timings of the last construct / solve (ms): sample, pairs, edges, sort+csr, query kernel, bfs (host)
-    double t_ms[6] = {};
-    uint64_t n_candidates = 0;
-    // last oxhip_prm_solve_batch: its queries, per-query results and all paths; per-round device workspace
-    bool batch_valid = false;
-    uint32_t batch_rounds = 0;
-    double batch_ms[4] = {};   // flag kernels, search kernels, path extraction, device-to-host copies
-    std::vector<double> b_starts, b_goals, b_thr, b_filt;       // as uploaded: [Q][dim], [Q][dim], [Q], [Q]
-    std::vector<int32_t> b_status, b_goal_node;
-    std::vector<uint32_t> b_len, b_nstart, b_ngoal, b_nodes;
-    std::vector<uint64_t> b_off;                                // [Q + 1] row offsets of the paths
-    std::vector<double> b_rows;
-    DevBuf<double> bd_starts, bd_goals, bd_thr, bd_filt, bd_rows;
-    DevBuf<uint8_t> bd_flags;
-    DevBuf<uint32_t> bd_start_valid, bd_parent, bd_queue, bd_res, bd_nodes;
-    DevBuf<uint64_t> bd_off;
-    hipEvent_t bev[7] = {};
-    // oxhip_prm_solve_batch_shortest: the edge weights live until the roadmap changes; the rest is the last batch's
-    int32_t batch_mode = -1;   // weights mode of the last batch, -1: it was the breadth-first oxhip_prm_solve_batch
-    bool w_valid = false;      // w_edges holds the distances of the roadmap's CSR entries
-    DevBuf<double> w_edges;
-    double short_ms[6] = {};   // edge weights (when this batch computed them), flags + initial labels, label rounds, tight levels, paths, copies
-    std::vector<double> b_cost;
-    std::vector<uint32_t> b_rounds;
-    std::vector<uint64_t> b_relaxed;
-    DevBuf<uint64_t> bd_label;
-    DevBuf<uint32_t> bd_stamp, bd_rounds;
-    DevBuf<double> bd_cost;
-    DevBuf<unsigned long long> bd_relaxed;
-    hipEvent_t sev[2] = {};
-    // oxhip_prm_revalidate: its workspace and the phase times of the last call
-    DevBuf<uint8_t> rv_valid, rv_keep, rv_tmp;
-    DevBuf<uint32_t> rv_pos, rv_nbrs, rv_counters;
-    DevBuf<uint4> rv_pairs;
-    DevBuf<uint2> rv_cand;       // SO(3): the pairs as construction's edge kernel reads them, the keys it emits and their count
-    DevBuf<uint64_t> rv_keys;
-    DevBuf<PrmState> rv_state;
-    double reval_ms[4] = {};   // milestone validity, pair emission, edge checks, compaction
-    // oxhip_prm_grow_roadmap: where the sampler stopped (stream id, u64 word), the filtered candidates, the
-    // phase times of the last call
-    bool pos_valid = false;    // set by construct_roadmap / grow_roadmap, forgotten by setup / set_roadmap
-    uint64_t pos_stream = 0, pos_draws = 0;
-    DevBuf<uint2> gw_cand;
-    DevBuf<uint32_t> gw_count;
-    double grow_ms[6] = {};    // liveness mask, keys from CSR, sample, pairs (+ filter), edges, sort + CSR
-    // oxhip_prm_components / oxhip_prm_prune: the union-find's arrays (the labels, sizes and summary are
-    // kept until the roadmap changes), the prune's masks, scans and second buffers, the phase times of the last calls
-    bool cc_valid = false;     // cc_label / cc_size / cc_summary describe the roadmap as it stands
-    DevBuf<uint32_t> cc_parent, cc_label, cc_count, cc_size;
-    DevBuf<unsigned long long> cc_summary;
-    DevBuf<uint8_t> pr_keep, pr_mask, pr_ekeep;
-    DevBuf<uint32_t> pr_pos, pr_epos, pr_kept, pr_offsets, pr_nbrs;
-    DevBuf<int32_t> pr_index;
-    DevBuf<double> pr_ms;
-    DevBuf<float> pr_ms32;
-    hipEvent_t cev[10] = {};
-    double cc_ms[4] = {};      // init + hook, flatten, sizes + summary, copies
-    double prune_ms[5] = {};   // masks, components, scans, move entries, move states
+    hipStream_t stream = nullptr;
+    struct { DevBuf<double> sph_c, sph_thr, sph_r, box_lo, box_hi; } obs;
+    PrmRoadmap rm;
+    PrmBuffers spare;   // the second buffers a prune compacts into, swapped with rm's buffer by buffer
+    struct {   // parallel sampler scratch (one round), and where the roadmap's samples came from
+        DevBuf<double> tmp;
+        DevBuf<uint64_t> vbits;
+        DevBuf<uint32_t> off, flag;
+        DevBuf<uint64_t> abits;    // SO(3) sampler: accepted-attempt ballots and counts
+        DevBuf<uint32_t> acnt;
+        double valid_rate = 1.0;   // running estimate of P(sample is valid), sizes the rounds
+        uint64_t n_samples = 0;
+        uint32_t redraw_batches = 0;
+        // where the sampler stopped (stream id, u64 word), for oxhip_prm_grow_roadmap: set by construct_roadmap / grow_roadmap,
+        // forgotten by setup / set_roadmap
+        bool pos_valid = false;
+        uint64_t pos_stream = 0, pos_draws = 0;
+    } sampler;
+    struct {   // k-nearest variant: per-row candidate radii, the sorted candidates and their distances, the selected pairs
+        DevBuf<double> thr, dist;
+        DevBuf<float> thr32;
+        DevBuf<uint64_t> keys, sorted;
+        DevBuf<uint2> sel;
+        DevBuf<uint32_t> counters, failed;
+    } knn;
+    struct {   // construction's device state, candidate pairs, directed keys and their sort
+        DevBuf<PrmState> state;
+        DevBuf<uint2> cand;
+        DevBuf<uint64_t> keys, keys_sorted;
+        DevBuf<uint8_t> sort_tmp;
+    } work;
+    PrmBuildTally built;   // the last construct_roadmap (its two counters: plus every grow since, see oxhip_prm_grow_roadmap)
+    struct {   // the single query (oxhip_prm_solve): the host copy of the roadmap it searches, the last query and its sets
+        PhaseClock clk{2};
+        double ms[2] = {};         // query kernel, bfs (host); zeroed by construct_roadmap with its own four
+        bool host_copy = false;    // h_offsets / h_nbrs / h_states are current
+        std::vector<uint32_t> h_offsets, h_nbrs;
+        std::vector<double> h_states;  // AoS [n][dim]
+        PrmQuery query{};
+        DevBuf<uint8_t> flags;     // [capacity]
+        DevBuf<uint32_t> start_valid;
+        std::vector<uint32_t> start_conn, goal_idx;
+    } single;
+    struct {   // the last oxhip_prm_solve_batch[_shortest]: its queries, per-query results and all paths
+        PhaseClock clk{8};
+        double ms[4] = {};   // flag kernels, search kernels, path extraction, device-to-host copies
+        bool valid = false;
+        uint32_t rounds = 0;
+        int32_t mode = -1;   // weights mode of the last batch, -1: it was the breadth-first oxhip_prm_solve_batch
+        std::vector<double> starts, goals, thr, filt;   // as uploaded: [Q][dim], [Q][dim], [Q], [Q]
+        std::vector<int32_t> status, goal_node;
+        std::vector<uint32_t> len, nstart, ngoal, nodes;
+        std::vector<uint64_t> off;                      // [Q + 1] row offsets of the paths
+        std::vector<double> rows;
+        // d_: the per-round device workspace
+        DevBuf<double> d_starts, d_goals, d_thr, d_filt, d_rows;
+        DevBuf<uint8_t> d_flags;
+        DevBuf<uint32_t> d_start_valid, d_parent, d_queue, d_res, d_nodes;
+        DevBuf<uint64_t> d_off;
+    } batch;
+    struct {   // oxhip_prm_solve_batch_shortest: the edge weights live until the roadmap changes; the rest is the last batch's
+        PhaseClock clk{2};   // the edge weights' bracket (a round is timed by the batch's clock)
+        double ms[6] = {};   // edge weights (when this batch computed them), flags + initial labels, label rounds, tight levels, paths, copies
+        bool w_valid = false;      // w_edges holds the distances of the roadmap's CSR entries
+        DevBuf<double> w_edges;
+        std::vector<double> cost;
+        std::vector<uint32_t> rounds;
+        std::vector<uint64_t> relaxed;
+        DevBuf<uint64_t> d_label;
+        DevBuf<uint32_t> d_stamp, d_rounds;
+        DevBuf<double> d_cost;
+        DevBuf<unsigned long long> d_relaxed;
+    } shortest;
+    struct {   // oxhip_prm_revalidate: its workspace and the phase times of the last call
+        PhaseClock clk{6};
+        double ms[4] = {};   // milestone validity, pair emission, edge checks, compaction
+        DevBuf<uint8_t> valid, keep, tmp;   // (valid, counters: milestone_validity's, so growth's and prune's too; tmp: prune's scans too)
+        DevBuf<uint32_t> pos, counters;
+        DevBuf<uint32_t> nbrs;       // the second neighbour buffer the compaction writes, swapped with rm.nbrs
+        DevBuf<uint4> pairs;
+        DevBuf<uint2> cand;          // SO(3): the pairs as construction's edge kernel reads them, the keys it emits and their count
+        DevBuf<uint64_t> keys;
+        DevBuf<PrmState> state;
+    } reval;
+    struct {   // oxhip_prm_grow_roadmap: what the last call's steps added up, the filtered candidates
+        PrmBuildTally tally;
+        double mask_ms = 0.0, keys_ms = 0.0;   // liveness mask, keys from CSR (timed by the tally's clock, before its steps)
+        DevBuf<uint2> cand;
+        DevBuf<uint32_t> count;
+    } grow;
+    struct {   // oxhip_prm_components: the union-find's arrays
+        PhaseClock clk{6};
+        double ms[4] = {};      // init + hook, flatten, sizes + summary, copies
+        bool valid = false;     // label / size / summary describe the roadmap as it stands: kept until it changes
+        DevBuf<uint32_t> parent, label, count, size;
+        DevBuf<unsigned long long> summary;
+    } cc;
+    struct {   // oxhip_prm_prune: its masks and scans (it labels into cc's arrays and compacts into `spare`)
+        PhaseClock clk{10};
+        double ms[5] = {};   // masks, components, scans, move entries, move states
+        DevBuf<uint8_t> keep, mask, ekeep;
+        DevBuf<uint32_t> pos, epos, kept;
+        DevBuf<int32_t> index;
+    } prune;
 };
 
 namespace {
 
 int32_t read_state(oxhip_prm* h, PrmState& st) {
-    HIP_TRY(hipMemcpyAsync(&st, h->state.p, sizeof(PrmState), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(&st, h->work.state.p, sizeof(PrmState), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return OXHIP_OK;
 }
 
 int32_t write_state(oxhip_prm* h, const PrmState& st) {
-    HIP_TRY(hipMemcpyAsync(h->state.p, &st, sizeof(PrmState), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->work.state.p, &st, sizeof(PrmState), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return OXHIP_OK;
 }
@@ -143,7 +184,7 @@ int32_t write_state(oxhip_prm* h, const PrmState& st) {
 // ---- the one place that names the space: which launcher, and whether a radius travels as given or as its squared threshold
 void launch_pairs(oxhip_prm* h, uint32_t j0, uint32_t j1) {   // the k-nearest variant searches its per-row radii (knn_row_radii)
     if (h->so3) launch_prm_so3_pairs(h->args, j0, j1, h->so3_lo, h->so3_hi, h->cfg.connection_radius, h->stream);
-    else if (h->cfg.knn_k) launch_prm_pairs(h->dp, h->args, j0, j1, std::numeric_limits<double>::infinity(), h->stream, h->knn_thr.p, h->knn_thr32.p);
+    else if (h->cfg.knn_k) launch_prm_pairs(h->dp, h->args, j0, j1, std::numeric_limits<double>::infinity(), h->stream, h->knn.thr.p, h->knn.thr32.p);
     else launch_prm_pairs(h->dp, h->args, j0, j1, h->thr_conn, h->stream);
 }
 void launch_edges(oxhip_prm* h, const PrmArgs& a, uint32_t n_cand) {
@@ -154,33 +195,33 @@ void launch_edges(oxhip_prm* h, const PrmArgs& a, uint32_t n_cand) {
 double near_threshold(const oxhip_prm* h) { return h->so3 ? h->cfg.connection_radius : h->thr_conn; }
 void launch_query(oxhip_prm* h) {
     DevParams qdp = h->dp;   // the start may lie anywhere: widen the filter's absolute margin for this launch
-    for (uint32_t k = 0; k < h->cfg.dim; ++k) qdp.filt_abs = std::fmax(qdp.filt_abs, 1e-9 * std::fabs(h->query.start[k]));
-    launch_prm_query(h->so3, qdp, h->args, h->n, h->query, near_threshold(h), h->flags.p, h->start_valid.p, h->stream);
+    for (uint32_t k = 0; k < h->cfg.dim; ++k) qdp.filt_abs = std::fmax(qdp.filt_abs, 1e-9 * std::fabs(h->single.query.start[k]));
+    launch_prm_query(h->so3, qdp, h->args, h->rm.n, h->single.query, near_threshold(h), h->single.flags.p, h->single.start_valid.p, h->stream);
 }
 void launch_batch_flags(oxhip_prm* h, const PrmBatchArgs& b) { launch_prm_batch_flags(h->so3, h->dp, b, near_threshold(h), h->stream); }
 // a planted roadmap's fl32 shadow, which the R^n pair search screens with (the SO(3) pair search screens nothing)
 void launch_planted_shadow(oxhip_prm* h, uint32_t n) {
-    if (!h->so3) launch_prm_shadow(h->ms.p, h->ms32.p, (uint64_t)n * h->cfg.dim, h->stream);
+    if (!h->so3) launch_prm_shadow(h->rm.ms.p, h->rm.ms32.p, (uint64_t)n * h->cfg.dim, h->stream);
 }
 // the re-check's pair list: R^n (entry, u, v) for its own check kernel; SO(3) construction's candidate layout, with a key array
 // and a counter of the re-check's own, for construction's edge kernel
 int32_t reserve_reval_pairs(oxhip_prm* h, uint32_t pair_cap) {
-    if (!h->so3) { HIP_TRY(h->rv_pairs.reserve(pair_cap)); return OXHIP_OK; }
-    HIP_TRY(h->rv_cand.reserve(pair_cap)); HIP_TRY(h->rv_keys.reserve(2 * (size_t)pair_cap)); HIP_TRY(h->rv_state.reserve(1));
-    HIP_TRY(hipMemsetAsync(h->rv_state.p, 0, sizeof(PrmState), h->stream));
+    if (!h->so3) { HIP_TRY(h->reval.pairs.reserve(pair_cap)); return OXHIP_OK; }
+    HIP_TRY(h->reval.cand.reserve(pair_cap)); HIP_TRY(h->reval.keys.reserve(2 * (size_t)pair_cap)); HIP_TRY(h->reval.state.reserve(1));
+    HIP_TRY(hipMemsetAsync(h->reval.state.p, 0, sizeof(PrmState), h->stream));
     return OXHIP_OK;
 }
-uint2* reval_cand(oxhip_prm* h) { return h->so3 ? h->rv_cand.p : nullptr; }   // (the emit launcher fills rv_pairs when this is null)
+uint2* reval_cand(oxhip_prm* h) { return h->so3 ? h->reval.cand.p : nullptr; }   // (the emit launcher fills reval.pairs when this is null)
 // check_motion(from = u, to = v) per pair of the list; a valid one keeps its two entries
 int32_t launch_reval_edges(oxhip_prm* h, uint32_t n_pairs, uint32_t n, uint32_t n_old) {
     if (!h->so3) {
-        launch_prm_reval_check(h->dp, h->ms.p, h->offsets.p, h->nbrs.p, n, n_old, h->rv_pairs.p, n_pairs, h->rv_keep.p, h->stream);
+        launch_prm_reval_check(h->dp, h->rm.ms.p, h->rm.offsets.p, h->rm.nbrs.p, n, n_old, h->reval.pairs.p, n_pairs, h->reval.keep.p, h->stream);
     } else if (n_pairs) {
         PrmArgs a = h->args;   // construction's kernel, the re-check's buffers: nothing of construction's workspace is touched
-        a.cand = h->rv_cand.p; a.keys = h->rv_keys.p; a.state = h->rv_state.p;
+        a.cand = h->reval.cand.p; a.keys = h->reval.keys.p; a.state = h->reval.state.p;
         launch_edges(h, a, n_pairs);   // both directed keys of every valid pair
         HIP_TRY(hipGetLastError());
-        launch_prm_reval_keys(h->rv_keys.p, h->rv_state.p, 2 * n_pairs, prm_key_shift(h->args.cap), h->offsets.p, h->nbrs.p, n, h->rv_keep.p,
+        launch_prm_reval_keys(h->reval.keys.p, h->reval.state.p, 2 * n_pairs, prm_key_shift(h->args.cap), h->rm.offsets.p, h->rm.nbrs.p, n, h->reval.keep.p,
                               h->stream);
     }
     return OXHIP_OK;
@@ -199,32 +240,30 @@ int32_t check_query_points(const double* starts, const double* goal_centres, siz
 int32_t set_query(oxhip_prm* h, const double* start, const double* goal_centre, double goal_radius) {
     const uint32_t dim = h->cfg.dim;
     OX_TRY(check_query_points(start, goal_centre, dim));
-    h->query = PrmQuery{};
-    std::memcpy(h->query.start, start, dim * sizeof(double));
-    std::memcpy(h->query.goal_c, goal_centre, dim * sizeof(double));
-    h->query.goal_thr = goal_threshold(h, goal_radius);
+    h->single.query = PrmQuery{};
+    std::memcpy(h->single.query.start, start, dim * sizeof(double));
+    std::memcpy(h->single.query.goal_c, goal_centre, dim * sizeof(double));
+    h->single.query.goal_thr = goal_threshold(h, goal_radius);
     return OXHIP_OK;
 }
 
-// what belongs to the roadmap as it was: gone whenever the roadmap is cleared, replaced (set_roadmap) or pruned (revalidate)
+// the kernels' view of the milestones, re-derived from the roadmap: whatever replaces one of its buffers ends here
+void bind_roadmap(oxhip_prm* h) { h->args.ms = h->rm.ms.p; h->args.ms32 = h->rm.ms32.p; }
+
+// What is derived from the roadmap as it was -- the host copy, the single query's sets, the last batch's results (batch.valid), the
+// edge weights (shortest.w_valid), the component labels (cc.valid) -- and so is gone when it changes: every function that changes `rm` ends here.
 void drop_derived(oxhip_prm* h) {
-    h->host_copy = false;
-    h->h_offsets.clear();
-    h->h_nbrs.clear();
-    h->h_states.clear();
-    h->start_conn.clear();
-    h->goal_idx.clear();
-    h->batch_valid = false;   // the batch's results are about the roadmap that just went
-    h->w_valid = false;       // and so are the edge weights
-    h->cc_valid = false;      // and the component labels
+    h->single.host_copy = false;
+    h->single.h_offsets.clear(); h->single.h_nbrs.clear(); h->single.h_states.clear();
+    h->single.start_conn.clear(); h->single.goal_idx.clear();
+    h->batch.valid = h->shortest.w_valid = h->cc.valid = false;
 }
 
-void clear_roadmap(oxhip_prm* h) {
-    h->n = 0;
-    h->n_keys = 0;
-    h->n_samples = 0;
-    h->redraw_batches = 0;
-    h->pos_valid = false;   // (setup, set_roadmap: the stream position belonged to the roadmap that went)
+// setup: no roadmap; set_roadmap: one of n milestones that this handle did not sample.  The samples and the stream position
+// belonged to the roadmap that went.
+void clear_roadmap(oxhip_prm* h, uint32_t n = 0, uint32_t n_keys = 0) {
+    h->rm.n = n; h->rm.n_keys = n_keys;
+    h->sampler.n_samples = 0; h->sampler.redraw_batches = 0; h->sampler.pos_valid = false;
     drop_derived(h);
 }
 
@@ -232,17 +271,17 @@ void clear_roadmap(oxhip_prm* h) {
 // attempts, attempt a at stream word pos0 + 4 a.
 int32_t sample_round(oxhip_prm* h, const PrmState& st, uint32_t m) {
     if (h->so3) {
-        HIP_TRY(h->spec_abits.reserve((m + 63) / 64)); HIP_TRY(h->spec_acnt.reserve((m + 63) / 64));
+        HIP_TRY(h->sampler.abits.reserve((m + 63) / 64)); HIP_TRY(h->sampler.acnt.reserve((m + 63) / 64));
         PrmSo3Spec sp{};
         sp.pos0 = st.draws; sp.m = m;
-        sp.tmp = h->spec_tmp.p; sp.vbits = h->spec_vbits.p; sp.abits = h->spec_abits.p; sp.voff = h->spec_off.p; sp.acnt = h->spec_acnt.p;
-        sp.redraw_flag = h->spec_flag.p; sp.result = h->state.p;
+        sp.tmp = h->sampler.tmp.p; sp.vbits = h->sampler.vbits.p; sp.abits = h->sampler.abits.p; sp.voff = h->sampler.off.p; sp.acnt = h->sampler.acnt.p;
+        sp.redraw_flag = h->sampler.flag.p; sp.result = h->work.state.p;
         launch_prm_so3_sample(h->dp, h->args, sp, st.n_milestones, h->stream);
     } else {
         PrmSpec sp{};
         sp.pos0 = st.draws; sp.m = m;
-        sp.tmp = h->spec_tmp.p; sp.vbits = h->spec_vbits.p; sp.wave_off = h->spec_off.p;
-        sp.redraw_flag = h->spec_flag.p; sp.result = h->state.p;   // the scan kernel advances the device state
+        sp.tmp = h->sampler.tmp.p; sp.vbits = h->sampler.vbits.p; sp.wave_off = h->sampler.off.p;
+        sp.redraw_flag = h->sampler.flag.p; sp.result = h->work.state.p;   // the scan kernel advances the device state
         launch_prm_sample_spec(h->dp, h->args, sp, st.n_milestones, h->stream);
     }
     HIP_TRY(hipGetLastError());
@@ -261,32 +300,36 @@ int32_t flagged_round(oxhip_prm* h, PrmState& st, uint32_t m) {
     return read_state(h, st);
 }
 
-// Draw samples until `target` milestones exist or `max_samples` were drawn: rounds of the parallel sampler, sized by the observed
-// rate of milestones per sample (SO(3): per attempt; its kernel stops at args.max_samples itself, so its rounds are not clamped).
-int32_t sample_until(oxhip_prm* h, PrmState& st, uint32_t target, uint64_t max_samples) {
+// Draw samples until `target` milestones exist or `max_samples` were drawn, timed into t's sample phase: rounds of the parallel sampler, sized
+// by the observed rate of milestones per sample (SO(3): per attempt; its kernel stops at args.max_samples itself, so its rounds are not clamped).
+int32_t sample_until(oxhip_prm* h, PrmBuildTally& t, PrmState& st, uint32_t target, uint64_t max_samples) {
     constexpr uint64_t kRoundMax = 1ull << 22;
     const bool so3 = h->so3;
+    HIP_TRY(t.clk.mark(kBegin, h->stream));
     h->args.n_target = target;
     if (so3) h->args.max_samples = max_samples;
     while (st.n_milestones < target && st.n_samples < max_samples) {
         const uint32_t need = target - st.n_milestones;
-        uint64_t want = std::min((uint64_t)((double)need / h->valid_rate * 1.02) + 256, kRoundMax);
+        uint64_t want = std::min((uint64_t)((double)need / h->sampler.valid_rate * 1.02) + 256, kRoundMax);
         if (!so3) want = std::min(want, max_samples - st.n_samples);
         const uint32_t m = (uint32_t)want, nw = (m + 63) / 64;
-        HIP_TRY(h->spec_tmp.reserve((size_t)m * h->cfg.dim)); HIP_TRY(h->spec_flag.reserve(1));   // (SO(3): dim is 4)
-        HIP_TRY(h->spec_vbits.reserve(nw)); HIP_TRY(h->spec_off.reserve(nw));
-        HIP_TRY(hipMemsetAsync(h->spec_flag.p, 0, sizeof(uint32_t), h->stream));
+        HIP_TRY(h->sampler.tmp.reserve((size_t)m * h->cfg.dim)); HIP_TRY(h->sampler.flag.reserve(1));   // (SO(3): dim is 4)
+        HIP_TRY(h->sampler.vbits.reserve(nw)); HIP_TRY(h->sampler.off.reserve(nw));
+        HIP_TRY(hipMemsetAsync(h->sampler.flag.p, 0, sizeof(uint32_t), h->stream));
         OX_TRY(sample_round(h, st, m));
         PrmState after{};
         uint32_t flag = 0;
-        HIP_TRY(hipMemcpyAsync(&after, h->state.p, sizeof(PrmState), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(&flag, h->spec_flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(&after, h->work.state.p, sizeof(PrmState), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(&flag, h->sampler.flag.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
         if (flag != 0) { OX_TRY(flagged_round(h, st, m)); continue; }
         const double got = (double)(after.n_milestones - st.n_milestones), drawn = so3 ? (double)m : (double)(after.n_samples - st.n_samples);
-        h->valid_rate = std::max(so3 ? 1e-6 : 1.0 / 64.0, std::min(1.0, (got + 1.0) / (drawn + 1.0)));
+        h->sampler.valid_rate = std::max(so3 ? 1e-6 : 1.0 / 64.0, std::min(1.0, (got + 1.0) / (drawn + 1.0)));
         st = after;
     }
+    HIP_TRY(t.clk.mark(kEnd, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    t.ms[0] += t.clk.ms(kBegin, kEnd);
     return OXHIP_OK;
 }
 
@@ -306,24 +349,19 @@ void so3_radius_bands(double r, double& lo, double& hi) {
 
 // host copy of the roadmap for get_roadmap and the breadth-first query (once per construction)
 int32_t fetch_roadmap(oxhip_prm* h) {
-    if (h->host_copy) return OXHIP_OK;
-    const uint32_t n = h->n, n_keys = h->n_keys;
-    h->h_offsets.assign((size_t)n + 1, 0);
-    h->h_nbrs.assign(n_keys, 0);
-    h->h_states.assign((size_t)n * h->cfg.dim, 0.0);
+    if (h->single.host_copy) return OXHIP_OK;
+    const uint32_t n = h->rm.n, n_keys = h->rm.n_keys;
+    h->single.h_offsets.assign((size_t)n + 1, 0);
+    h->single.h_nbrs.assign(n_keys, 0);
+    h->single.h_states.assign((size_t)n * h->cfg.dim, 0.0);
     if (n) {
-        HIP_TRY(hipMemcpyAsync(h->h_offsets.data(), h->offsets.p, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-        if (n_keys) HIP_TRY(hipMemcpyAsync(h->h_nbrs.data(), h->nbrs.p, (size_t)n_keys * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->h_states.data(), h->ms.p, (size_t)n * h->cfg.dim * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->single.h_offsets.data(), h->rm.offsets.p, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        if (n_keys) HIP_TRY(hipMemcpyAsync(h->single.h_nbrs.data(), h->rm.nbrs.p, (size_t)n_keys * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->single.h_states.data(), h->rm.ms.p, (size_t)n * h->cfg.dim * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
-    h->host_copy = true;
+    h->single.host_copy = true;
     return OXHIP_OK;
-}
-
-double elapsed_ms(hipEvent_t a, hipEvent_t b) {
-    float ms = 0.f;
-    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? (double)ms : 0.0;
 }
 
 // ---- oxhip_prm_create in its steps
@@ -381,25 +419,23 @@ void fill_prm_params(oxhip_prm* h, const oxhip_prm_config* cfg, double fraction,
     h->thr_conn = sqrt_lt_threshold(cfg->connection_radius);
 }
 
-// the stream, the events and the buffers that live as long as the handle; the first error wins
+// the stream and the buffers that live as long as the handle (its clocks were made with it); the first error wins
 int32_t alloc_prm(oxhip_prm* h) {
     const uint32_t dim = h->cfg.dim, cap = ((h->cfg.max_milestones + 1023u) / 1024u) * 1024u;
     hipError_t e = hipSuccess;
     auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
     chk(oxhip_stream_acquire(h->cfg.device, &h->stream));
-    for (auto& ev : h->ev) chk(hipEventCreate(&ev));
-    for (auto& ev : h->bev) chk(hipEventCreate(&ev));
-    for (auto& ev : h->sev) chk(hipEventCreate(&ev));
-    for (auto& ev : h->cev) chk(hipEventCreate(&ev));
-    chk(h->ms.alloc((size_t)dim * cap));
-    if (!h->so3) chk(h->ms32.alloc((size_t)dim * cap));   // (the SO(3) pair search screens nothing)
-    chk(h->state.alloc(1));
-    chk(h->flags.alloc(cap));
-    chk(h->start_valid.alloc(1));
-    chk(h->offsets.alloc((size_t)cap + 1));
+    for (const PhaseClock* c : {&h->built.clk, &h->single.clk, &h->batch.clk, &h->shortest.clk, &h->reval.clk, &h->grow.tally.clk, &h->cc.clk, &h->prune.clk})
+        chk(c->made);   // an event that could not be made refuses the create, as a buffer does
+    chk(h->rm.ms.alloc((size_t)dim * cap));
+    if (!h->so3) chk(h->rm.ms32.alloc((size_t)dim * cap));   // (the SO(3) pair search screens nothing)
+    chk(h->work.state.alloc(1));
+    chk(h->single.flags.alloc(cap));
+    chk(h->single.start_valid.alloc(1));
+    chk(h->rm.offsets.alloc((size_t)cap + 1));
     if (e != hipSuccess) return alloc_failed(e);
-    h->args.ms = h->ms.p; h->args.ms32 = h->ms32.p; h->args.state = h->state.p;
-    h->args.cap = cap; h->args.stream = h->cfg.stream;
+    bind_roadmap(h);
+    h->args.state = h->work.state.p; h->args.cap = cap; h->args.stream = h->cfg.stream;
     return OXHIP_OK;
 }
 
@@ -423,71 +459,71 @@ int32_t knn_row_radii(oxhip_prm* h, const PrmState& st, uint32_t n_done, uint32_
         thr[j] = r * r;
         thr32[j] = prm_screen_threshold(h->dp, thr[j]);
     }
-    HIP_TRY(h->knn_thr.reserve(h->args.cap)); HIP_TRY(h->knn_thr32.reserve(h->args.cap));
-    HIP_TRY(hipMemcpyAsync(h->knn_thr.p, thr.data(), thr.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->knn_thr32.p, thr32.data(), thr32.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h->knn.thr.reserve(h->args.cap)); HIP_TRY(h->knn.thr32.reserve(h->args.cap));
+    HIP_TRY(hipMemcpyAsync(h->knn.thr.p, thr.data(), thr.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->knn.thr32.p, thr32.data(), thr32.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return OXHIP_OK;
 }
 
-// pairs (j in [n_done, n_now), i < j) within the connection radius, into h->cand; st.n_cand counts them
-int32_t find_pairs(oxhip_prm* h, PrmState& st, uint32_t n_done, uint32_t n_now) {
-    if (h->cand.n == 0) HIP_TRY(h->cand.alloc(std::min<size_t>(std::max<size_t>(1u << 20, (size_t)64 * h->cfg.max_milestones), (size_t)1 << 28)));
+// pairs (j in [n_done, n_now), i < j) within the connection radius, into h->work.cand; st.n_cand counts them
+int32_t find_pairs(oxhip_prm* h, PrmBuildTally& t, PrmState& st, uint32_t n_done, uint32_t n_now) {
+    if (h->work.cand.n == 0) HIP_TRY(h->work.cand.alloc(std::min<size_t>(std::max<size_t>(1u << 20, (size_t)64 * h->cfg.max_milestones), (size_t)1 << 28)));
     for (;;) {
-        h->args.cand = h->cand.p;
-        h->args.cand_cap = (uint32_t)h->cand.n;
+        h->args.cand = h->work.cand.p;
+        h->args.cand_cap = (uint32_t)h->work.cand.n;
         st.n_cand = 0;
         OX_TRY(write_state(h, st));
-        HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+        HIP_TRY(t.clk.mark(kBegin, h->stream));
         launch_pairs(h, n_done, n_now);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(h->ev[3], h->stream));
+        HIP_TRY(t.clk.mark(kEnd, h->stream));
         PrmState s2{};
         OX_TRY(read_state(h, s2));
-        h->t_ms[1] += elapsed_ms(h->ev[2], h->ev[3]);
+        t.ms[1] += t.clk.ms(kBegin, kEnd);
         st.n_cand = s2.n_cand;
         if (st.n_cand <= h->args.cand_cap) break;
         // candidate buffer too small: the kernel kept counting, so the exact need is known; run again
         if (st.n_cand > 0x7FFFFFFFull) return fail(OXHIP_ERR_CAPACITY, "more than 2^31 in-radius pairs in one round");
-        HIP_TRY(h->cand.alloc((size_t)st.n_cand));
+        HIP_TRY(h->work.cand.alloc((size_t)st.n_cand));
     }
-    h->n_candidates += st.n_cand;
+    t.candidates += st.n_cand;
     return OXHIP_OK;
 }
 
 // k-nearest variant: each row's k nearest among its candidates (sorted by (j, i)), the exact search for rows that fell short.
 // The selected pairs replace the candidates as what the edge step reads: `pairs` and st.n_cand.
-int32_t knn_select(oxhip_prm* h, PrmState& st, uint32_t n_done, uint32_t n_now, uint2*& pairs) {
+int32_t knn_select(oxhip_prm* h, PrmBuildTally& t, PrmState& st, uint32_t n_done, uint32_t n_now, uint2*& pairs) {
     const uint32_t nc = (uint32_t)st.n_cand, rows = n_now - n_done, knn_k = h->cfg.knn_k;
-    HIP_TRY(h->knn_keys.reserve(nc + 1)); HIP_TRY(h->knn_sorted.reserve(nc + 1)); HIP_TRY(h->knn_dist.reserve(nc + 1));
-    HIP_TRY(h->knn_sel.reserve((size_t)rows * knn_k)); HIP_TRY(h->knn_failed.reserve(rows)); HIP_TRY(h->knn_counters.reserve(2));
+    HIP_TRY(h->knn.keys.reserve(nc + 1)); HIP_TRY(h->knn.sorted.reserve(nc + 1)); HIP_TRY(h->knn.dist.reserve(nc + 1));
+    HIP_TRY(h->knn.sel.reserve((size_t)rows * knn_k)); HIP_TRY(h->knn.failed.reserve(rows)); HIP_TRY(h->knn.counters.reserve(2));
     size_t tb = 0;
     if (nc) {
-        HIP_TRY(prm_sort_keys(nullptr, tb, h->knn_keys.p, h->knn_sorted.p, nc, h->args.cap, h->stream));
-        HIP_TRY(h->sort_tmp.reserve(tb));
+        HIP_TRY(prm_sort_keys(nullptr, tb, h->knn.keys.p, h->knn.sorted.p, nc, h->args.cap, h->stream));
+        HIP_TRY(h->work.sort_tmp.reserve(tb));
     }
-    HIP_TRY(hipEventRecord(h->ev[2], h->stream));
-    HIP_TRY(hipMemsetAsync(h->knn_counters.p, 0, 2 * sizeof(uint32_t), h->stream));
-    launch_prm_knn_keys(h->args, nc, h->knn_keys.p, h->stream);
-    if (nc) HIP_TRY(prm_sort_keys(h->sort_tmp.p, tb, h->knn_keys.p, h->knn_sorted.p, nc, h->args.cap, h->stream));
-    launch_prm_knn_select(h->dp, h->args, h->knn_sorted.p, h->knn_dist.p, nc, n_done, n_now, knn_k, h->knn_sel.p, h->knn_counters.p,
-                          h->knn_failed.p, h->stream);
+    HIP_TRY(t.clk.mark(kBegin, h->stream));
+    HIP_TRY(hipMemsetAsync(h->knn.counters.p, 0, 2 * sizeof(uint32_t), h->stream));
+    launch_prm_knn_keys(h->args, nc, h->knn.keys.p, h->stream);
+    if (nc) HIP_TRY(prm_sort_keys(h->work.sort_tmp.p, tb, h->knn.keys.p, h->knn.sorted.p, nc, h->args.cap, h->stream));
+    launch_prm_knn_select(h->dp, h->args, h->knn.sorted.p, h->knn.dist.p, nc, n_done, n_now, knn_k, h->knn.sel.p, h->knn.counters.p,
+                          h->knn.failed.p, h->stream);
     HIP_TRY(hipGetLastError());
     uint32_t cnt[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(cnt, h->knn_counters.p, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(cnt, h->knn.counters.p, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (cnt[1]) {
-        launch_prm_knn_brute(h->dp, h->args, h->knn_failed.p, cnt[1], knn_k, h->knn_sel.p, h->knn_counters.p, h->stream);
+        launch_prm_knn_brute(h->dp, h->args, h->knn.failed.p, cnt[1], knn_k, h->knn.sel.p, h->knn.counters.p, h->stream);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(cnt, h->knn_counters.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(cnt, h->knn.counters.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
-        h->knn_failed_rows += cnt[1];
+        t.exact_rows += cnt[1];
     }
-    HIP_TRY(hipEventRecord(h->ev[3], h->stream));
+    HIP_TRY(t.clk.mark(kEnd, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    h->t_ms[1] += elapsed_ms(h->ev[2], h->ev[3]);
+    t.ms[1] += t.clk.ms(kBegin, kEnd);
     st.n_cand = cnt[0];
-    pairs = h->knn_sel.p;
+    pairs = h->knn.sel.p;
     return OXHIP_OK;
 }
 
@@ -495,69 +531,69 @@ int32_t knn_select(oxhip_prm* h, PrmState& st, uint32_t n_done, uint32_t n_now, 
 int32_t reserve_keys(oxhip_prm* h, const PrmState& st) {
     const uint64_t need = (uint64_t)st.n_keys + 2ull * st.n_cand;
     if (need > 0xFFFFFFFFull) return fail(OXHIP_ERR_CAPACITY, "more than 2^32 directed edges");
-    if (need <= h->keys.n) return OXHIP_OK;
+    if (need <= h->work.keys.n) return OXHIP_OK;
     DevBuf<uint64_t> bigger;
-    HIP_TRY(bigger.alloc(std::max<size_t>((size_t)need, h->keys.n * 2)));
-    if (st.n_keys) HIP_TRY(hipMemcpyAsync(bigger.p, h->keys.p, (size_t)st.n_keys * sizeof(uint64_t), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(bigger.alloc(std::max<size_t>((size_t)need, h->work.keys.n * 2)));
+    if (st.n_keys) HIP_TRY(hipMemcpyAsync(bigger.p, h->work.keys.p, (size_t)st.n_keys * sizeof(uint64_t), hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    std::swap(bigger.p, h->keys.p); std::swap(bigger.n, h->keys.n);
-    h->args.keys = h->keys.p;
+    h->work.keys.swap(bigger);
+    h->args.keys = h->work.keys.p;
     return OXHIP_OK;
 }
 
 // check_motion per pair of `pairs`; the kernel appends the keys of the edges and st comes back with their count
-int32_t check_edges(oxhip_prm* h, PrmState& st, uint2* pairs) {
+int32_t check_edges(oxhip_prm* h, PrmBuildTally& t, PrmState& st, uint2* pairs) {
     PrmArgs a = h->args;
     a.cand = pairs;
-    HIP_TRY(hipEventRecord(h->ev[2], h->stream));
+    HIP_TRY(t.clk.mark(kBegin, h->stream));
     launch_edges(h, a, (uint32_t)st.n_cand);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev[3], h->stream));
+    HIP_TRY(t.clk.mark(kEnd, h->stream));
     OX_TRY(read_state(h, st));
-    h->t_ms[2] += elapsed_ms(h->ev[2], h->ev[3]);
+    t.ms[2] += t.clk.ms(kBegin, kEnd);
     return OXHIP_OK;
 }
 
 // sort the directed keys -> every node's neighbours in ascending order (the reference's `edges`), as CSR
-int32_t build_csr(oxhip_prm* h, uint32_t n, uint32_t n_keys) {
+int32_t build_csr(oxhip_prm* h, PrmBuildTally& t, uint32_t n, uint32_t n_keys) {
     size_t tmp_bytes = 0;
     if (n_keys) {
         // (re)size the sort's buffers before the timed region: hipMalloc is a blocking call
-        HIP_TRY(h->keys_sorted.reserve(n_keys)); HIP_TRY(h->nbrs.reserve(n_keys));
-        HIP_TRY(prm_sort_keys(nullptr, tmp_bytes, h->keys.p, h->keys_sorted.p, n_keys, h->args.cap, h->stream));
-        HIP_TRY(h->sort_tmp.reserve(tmp_bytes));
+        HIP_TRY(h->work.keys_sorted.reserve(n_keys)); HIP_TRY(h->rm.nbrs.reserve(n_keys));
+        HIP_TRY(prm_sort_keys(nullptr, tmp_bytes, h->work.keys.p, h->work.keys_sorted.p, n_keys, h->args.cap, h->stream));
+        HIP_TRY(h->work.sort_tmp.reserve(tmp_bytes));
     }
-    HIP_TRY(hipEventRecord(h->ev[4], h->stream));
+    HIP_TRY(t.clk.mark(kBegin, h->stream));
     if (n_keys) {
-        HIP_TRY(prm_sort_keys(h->sort_tmp.p, tmp_bytes, h->keys.p, h->keys_sorted.p, n_keys, h->args.cap, h->stream));
-        launch_prm_csr(h->keys_sorted.p, n_keys, n, h->args.cap, h->offsets.p, h->nbrs.p, h->stream);
+        HIP_TRY(prm_sort_keys(h->work.sort_tmp.p, tmp_bytes, h->work.keys.p, h->work.keys_sorted.p, n_keys, h->args.cap, h->stream));
+        launch_prm_csr(h->work.keys_sorted.p, n_keys, n, h->args.cap, h->rm.offsets.p, h->rm.nbrs.p, h->stream);
         HIP_TRY(hipGetLastError());
     } else {
-        HIP_TRY(hipMemsetAsync(h->offsets.p, 0, ((size_t)n + 1) * sizeof(uint32_t), h->stream));
+        HIP_TRY(hipMemsetAsync(h->rm.offsets.p, 0, ((size_t)n + 1) * sizeof(uint32_t), h->stream));
     }
-    HIP_TRY(hipEventRecord(h->ev[5], h->stream));
+    HIP_TRY(t.clk.mark(kEnd, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    h->t_ms[3] = elapsed_ms(h->ev[4], h->ev[5]);
+    t.ms[3] = t.clk.ms(kBegin, kEnd);
     return OXHIP_OK;
 }
 
-// start validity, start connections and goal milestones of h->query (prm.rs:243-264), on the device
+// start validity, start connections and goal milestones of h->single.query (prm.rs:243-264), on the device
 int32_t query_sets(oxhip_prm* h, std::vector<uint8_t>& flags) {
-    const uint32_t n = h->n;
+    const uint32_t n = h->rm.n;
     uint32_t start_valid = 0;
-    HIP_TRY(hipEventRecord(h->ev[0], h->stream));
+    HIP_TRY(h->single.clk.mark(kBegin, h->stream));
     launch_query(h);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev[1], h->stream));
+    HIP_TRY(h->single.clk.mark(kEnd, h->stream));
     flags.assign(n, 0);
-    HIP_TRY(hipMemcpyAsync(flags.data(), h->flags.p, n, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(&start_valid, h->start_valid.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(flags.data(), h->single.flags.p, n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(&start_valid, h->single.start_valid.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    h->t_ms[4] = elapsed_ms(h->ev[0], h->ev[1]);
+    h->single.ms[0] = h->single.clk.ms(kBegin, kEnd);
     if (!start_valid) return fail(OXHIP_ERR_INVALID_START_STATE, "start state is in collision");  // prm.rs:243-246
     for (uint32_t i = 0; i < n; ++i) {
-        if (flags[i] & 1) h->start_conn.push_back(i);   // prm.rs:249-256
-        if (flags[i] & 2) h->goal_idx.push_back(i);     // prm.rs:259-264
+        if (flags[i] & 1) h->single.start_conn.push_back(i);   // prm.rs:249-256
+        if (flags[i] & 2) h->single.goal_idx.push_back(i);     // prm.rs:259-264
     }
     return OXHIP_OK;
 }
@@ -583,10 +619,6 @@ int32_t oxhip_prm_destroy(oxhip_prm* h) {
     if (!h) return OXHIP_OK;
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (auto& ev : h->ev) if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : h->bev) if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : h->sev) if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : h->cev) if (ev) (void)hipEventDestroy(ev);
     if (h->stream) oxhip_stream_release(h->cfg.device, h->stream);
     delete h;
     return OXHIP_OK;
@@ -605,10 +637,10 @@ int32_t oxhip_prm_set_spheres(oxhip_prm* h, const double* centres, const double*
         }
         thr[j] = sqrt_le_threshold(radii[j]);
     }
-    OX_TRY(upload(h->sph_c, c, h->stream));
-    OX_TRY(upload(h->sph_thr, thr, h->stream));
-    OX_TRY(upload(h->sph_r, std::vector<double>(radii, radii + n), h->stream));
-    h->dp.n_spheres = n; h->dp.sph_c = h->sph_c.p; h->dp.sph_thr = h->sph_thr.p; h->dp.sph_r = h->sph_r.p;
+    OX_TRY(upload(h->obs.sph_c, c, h->stream));
+    OX_TRY(upload(h->obs.sph_thr, thr, h->stream));
+    OX_TRY(upload(h->obs.sph_r, std::vector<double>(radii, radii + n), h->stream));
+    h->dp.n_spheres = n; h->dp.sph_c = h->obs.sph_c.p; h->dp.sph_thr = h->obs.sph_thr.p; h->dp.sph_r = h->obs.sph_r.p;
     if (!h->so3) set_filter_margin(h, c);   // (cones: distance(centre, q) > radius, compared with sph_r itself; no filter)
     return OXHIP_OK;
 }
@@ -624,9 +656,9 @@ int32_t oxhip_prm_set_boxes(oxhip_prm* h, const double* lo, const double* hi, ui
             l[(size_t)k * n + j] = lo[(size_t)j * dim + k];
             u[(size_t)k * n + j] = hi[(size_t)j * dim + k];
         }
-    OX_TRY(upload(h->box_lo, l, h->stream));
-    OX_TRY(upload(h->box_hi, u, h->stream));
-    h->dp.n_boxes = n; h->dp.box_lo = h->box_lo.p; h->dp.box_hi = h->box_hi.p;
+    OX_TRY(upload(h->obs.box_lo, l, h->stream));
+    OX_TRY(upload(h->obs.box_hi, u, h->stream));
+    h->dp.n_boxes = n; h->dp.box_lo = h->obs.box_lo.p; h->dp.box_hi = h->obs.box_hi.p;
     return OXHIP_OK;
 }
 
@@ -652,38 +684,34 @@ int32_t oxhip_prm_set_problem(oxhip_prm* h, const double* start, const double* g
 int32_t oxhip_prm_construct_roadmap(oxhip_prm* h) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
     if (!h->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");  // prm.rs:97-104
-    if (h->n != 0) return OXHIP_OK;  // prm.rs:106-113: "Roadmap already constructed"
+    if (h->rm.n != 0) return OXHIP_OK;  // prm.rs:106-113: "Roadmap already constructed"
     OX_TRY(select_device(h->cfg.device));
     const auto t0 = std::chrono::steady_clock::now();
     const bool has_timeout = h->cfg.timeout > 0.0 && std::isfinite(h->cfg.timeout);
     const uint32_t n_max = h->cfg.max_milestones, knn_k = h->cfg.knn_k;
     // 0 = "unlimited", which still has to end when (almost) no sample is valid: 4096 draws per requested milestone
     const uint64_t max_samples = h->cfg.max_samples ? h->cfg.max_samples : 4096ull * n_max + (1ull << 22);
-    for (double& t : h->t_ms) t = 0.0;
-    h->n_candidates = 0;
-    h->knn_failed_rows = 0;
+    PrmBuildTally& t = h->built;
+    t.reset();
+    for (double& q : h->single.ms) q = 0.0;   // oxhip_prm_last_timing's six entries start over together
     PrmState st{};
     OX_TRY(write_state(h, st));
-    h->valid_rate = 1.0;
+    h->sampler.valid_rate = 1.0;
     // without a wall clock the roadmap is built in one round; with one, in doubling rounds with the
     // clock read in between (the reference reads it before every sample, prm.rs:118)
     uint32_t target = has_timeout ? std::min<uint32_t>(n_max, 4096u) : n_max;
     uint32_t n_done = 0;  // milestones whose pairs are already connected
     for (;;) {
-        HIP_TRY(hipEventRecord(h->ev[0], h->stream));
-        OX_TRY(sample_until(h, st, target, max_samples));
-        HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        h->t_ms[0] += elapsed_ms(h->ev[0], h->ev[1]);
+        OX_TRY(sample_until(h, t, st, target, max_samples));
         const uint32_t n_now = st.n_milestones;
         // thr_conn >= 0 <=> connection_radius > 0 (sqrt_lt_threshold; NaN was refused), in either space: a radius <= 0 takes no pair
         if (n_now > n_done && n_now >= 2 && (h->thr_conn >= 0.0 || knn_k)) {
             if (knn_k) OX_TRY(knn_row_radii(h, st, n_done, n_now));
-            OX_TRY(find_pairs(h, st, n_done, n_now));
-            uint2* pairs = h->cand.p;
-            if (knn_k) OX_TRY(knn_select(h, st, n_done, n_now, pairs));
+            OX_TRY(find_pairs(h, t, st, n_done, n_now));
+            uint2* pairs = h->work.cand.p;
+            if (knn_k) OX_TRY(knn_select(h, t, st, n_done, n_now, pairs));
             OX_TRY(reserve_keys(h, st));
-            OX_TRY(check_edges(h, st, pairs));
+            OX_TRY(check_edges(h, t, st, pairs));
         }
         n_done = n_now;
         if (n_now < target) break;                       // max_samples exhausted
@@ -692,29 +720,27 @@ int32_t oxhip_prm_construct_roadmap(oxhip_prm* h) {
             break;                                       // prm.rs:118-120
         target = target > n_max / 2 ? n_max : target * 2;
     }
-    OX_TRY(build_csr(h, st.n_milestones, st.n_keys));
-    h->n_keys = st.n_keys;
-    h->w_valid = false;     // the edge weights of the roadmap before this one
-    h->cc_valid = false;    // and its component labels
-    h->host_copy = false;   // fetched by the first get_roadmap / solve
-    h->n = st.n_milestones;
-    h->n_samples = st.n_samples;
-    h->redraw_batches = st.redraw_batches;
-    h->pos_valid = true; h->pos_stream = h->cfg.stream; h->pos_draws = st.draws;   // where oxhip_prm_grow_roadmap continues
+    OX_TRY(build_csr(h, t, st.n_milestones, st.n_keys));
+    h->rm.n = st.n_milestones;
+    h->rm.n_keys = st.n_keys;
+    h->sampler.n_samples = st.n_samples;
+    h->sampler.redraw_batches = st.redraw_batches;
+    h->sampler.pos_valid = true; h->sampler.pos_stream = h->cfg.stream; h->sampler.pos_draws = st.draws;   // where oxhip_prm_grow_roadmap continues
+    drop_derived(h);   // (the host copy is fetched by the first get_roadmap / solve)
     return OXHIP_OK;
 }
 
 int32_t oxhip_prm_knn_exact_rows(oxhip_prm* h, uint32_t* rows) {
     if (!h || !rows) return fail(OXHIP_ERR_BAD_ARG, "null argument");
-    *rows = h->knn_failed_rows;
+    *rows = h->built.exact_rows;
     return OXHIP_OK;
 }
 
 int32_t oxhip_prm_get_sizes(oxhip_prm* h, uint32_t* n_milestones, uint64_t* n_edge_entries, uint64_t* n_samples) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
-    if (n_milestones) *n_milestones = h->n;
-    if (n_edge_entries) *n_edge_entries = h->n_keys;
-    if (n_samples) *n_samples = h->n_samples;
+    if (n_milestones) *n_milestones = h->rm.n;
+    if (n_edge_entries) *n_edge_entries = h->rm.n_keys;
+    if (n_samples) *n_samples = h->sampler.n_samples;
     return OXHIP_OK;
 }
 
@@ -722,17 +748,17 @@ int32_t oxhip_prm_get_sizes(oxhip_prm* h, uint32_t* n_milestones, uint64_t* n_ed
 int32_t oxhip_prm_get_roadmap(oxhip_prm* h, double* states, uint32_t cap_nodes, uint64_t* offsets, uint32_t* neighbours,
                               uint64_t cap_entries) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
-    if (h->n) {
+    if (h->rm.n) {
         OX_TRY(select_device(h->cfg.device));
         OX_TRY(fetch_roadmap(h));
     }
-    if ((states || offsets) && cap_nodes < h->n) return fail(OXHIP_ERR_CAPACITY, "roadmap buffers too small");
-    if (neighbours && cap_entries < h->h_nbrs.size()) return fail(OXHIP_ERR_CAPACITY, "neighbour buffer too small");
-    if (states && h->n) std::memcpy(states, h->h_states.data(), h->h_states.size() * sizeof(double));
+    if ((states || offsets) && cap_nodes < h->rm.n) return fail(OXHIP_ERR_CAPACITY, "roadmap buffers too small");
+    if (neighbours && cap_entries < h->single.h_nbrs.size()) return fail(OXHIP_ERR_CAPACITY, "neighbour buffer too small");
+    if (states && h->rm.n) std::memcpy(states, h->single.h_states.data(), h->single.h_states.size() * sizeof(double));
     if (offsets) {
-        for (uint32_t i = 0; i <= h->n; ++i) offsets[i] = h->h_offsets.empty() ? 0 : h->h_offsets[i];
+        for (uint32_t i = 0; i <= h->rm.n; ++i) offsets[i] = h->single.h_offsets.empty() ? 0 : h->single.h_offsets[i];
     }
-    if (neighbours && !h->h_nbrs.empty()) std::memcpy(neighbours, h->h_nbrs.data(), h->h_nbrs.size() * sizeof(uint32_t));
+    if (neighbours && !h->single.h_nbrs.empty()) std::memcpy(neighbours, h->single.h_nbrs.data(), h->single.h_nbrs.size() * sizeof(uint32_t));
     return OXHIP_OK;
 }
 
@@ -740,10 +766,10 @@ int32_t oxhip_prm_get_roadmap(oxhip_prm* h, double* states, uint32_t cap_nodes, 
 int32_t oxhip_prm_solve(oxhip_prm* h, double timeout_s, double* path, uint32_t cap_states, uint32_t* len) {
     if (!h || !len) return fail(OXHIP_ERR_BAD_ARG, "null argument");
     *len = 0;
-    h->start_conn.clear();
-    h->goal_idx.clear();
+    h->single.start_conn.clear();
+    h->single.goal_idx.clear();
     if (!h->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");      // prm.rs:229-236
-    if (h->n == 0) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "construct_roadmap() left no milestones");  // prm.rs:239-241
+    if (h->rm.n == 0) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "construct_roadmap() left no milestones");  // prm.rs:239-241
     OX_TRY(select_device(h->cfg.device));
     OX_TRY(fetch_roadmap(h));
     std::vector<uint8_t> flags;
@@ -751,9 +777,9 @@ int32_t oxhip_prm_solve(oxhip_prm* h, double timeout_s, double* path, uint32_t c
     const auto t0 = std::chrono::steady_clock::now();
     const bool has_timeout = timeout_s > 0.0 && std::isfinite(timeout_s);
     std::vector<uint32_t> chain;   // goal milestone ... root connection
-    const PrmBfs found = prm_bfs_path(h->h_offsets, h->h_nbrs, flags, h->start_conn, has_timeout ? timeout_s : std::numeric_limits<double>::infinity(), chain);
+    const PrmBfs found = prm_bfs_path(h->single.h_offsets, h->single.h_nbrs, flags, h->single.start_conn, has_timeout ? timeout_s : std::numeric_limits<double>::infinity(), chain);
     if (found == PrmBfs::empty_set) return fail(OXHIP_ERR_NO_SOLUTION_FOUND, "start or goal does not connect to the roadmap");  // prm.rs:266-268
-    h->t_ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    h->single.ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (found == PrmBfs::timed_out) return fail(OXHIP_ERR_TIMEOUT, "graph search timed out");  // prm.rs:285-287
     if (found == PrmBfs::unreachable) return fail(OXHIP_ERR_NO_SOLUTION_FOUND, "goal is not reachable on the roadmap");  // prm.rs:304
     // [start] ++ (root connection ... goal milestone)
@@ -761,33 +787,33 @@ int32_t oxhip_prm_solve(oxhip_prm* h, double timeout_s, double* path, uint32_t c
     *len = (uint32_t)chain.size() + 1;
     if (!path) return OXHIP_OK;
     if (*len > cap_states) return fail(OXHIP_ERR_CAPACITY, "path buffer too small");
-    std::memcpy(path, h->query.start, dim * sizeof(double));
+    std::memcpy(path, h->single.query.start, dim * sizeof(double));
     for (size_t j = 0; j < chain.size(); ++j)
-        std::memcpy(path + (j + 1) * dim, h->h_states.data() + (size_t)chain[chain.size() - 1 - j] * dim, dim * sizeof(double));
+        std::memcpy(path + (j + 1) * dim, h->single.h_states.data() + (size_t)chain[chain.size() - 1 - j] * dim, dim * sizeof(double));
     return OXHIP_OK;
 }
 
 int32_t oxhip_prm_get_query_sets(oxhip_prm* h, uint32_t* start_connections, uint32_t cap_start, uint32_t* n_start,
                                  uint32_t* goal_indices, uint32_t cap_goal, uint32_t* n_goal) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
-    if (n_start) *n_start = (uint32_t)h->start_conn.size();
-    if (n_goal) *n_goal = (uint32_t)h->goal_idx.size();
+    if (n_start) *n_start = (uint32_t)h->single.start_conn.size();
+    if (n_goal) *n_goal = (uint32_t)h->single.goal_idx.size();
     if (start_connections) {
-        if (cap_start < h->start_conn.size()) return fail(OXHIP_ERR_CAPACITY, "start_connections buffer too small");
-        if (!h->start_conn.empty()) std::memcpy(start_connections, h->start_conn.data(), h->start_conn.size() * sizeof(uint32_t));
+        if (cap_start < h->single.start_conn.size()) return fail(OXHIP_ERR_CAPACITY, "start_connections buffer too small");
+        if (!h->single.start_conn.empty()) std::memcpy(start_connections, h->single.start_conn.data(), h->single.start_conn.size() * sizeof(uint32_t));
     }
     if (goal_indices) {
-        if (cap_goal < h->goal_idx.size()) return fail(OXHIP_ERR_CAPACITY, "goal_indices buffer too small");
-        if (!h->goal_idx.empty()) std::memcpy(goal_indices, h->goal_idx.data(), h->goal_idx.size() * sizeof(uint32_t));
+        if (cap_goal < h->single.goal_idx.size()) return fail(OXHIP_ERR_CAPACITY, "goal_indices buffer too small");
+        if (!h->single.goal_idx.empty()) std::memcpy(goal_indices, h->single.goal_idx.data(), h->single.goal_idx.size() * sizeof(uint32_t));
     }
     return OXHIP_OK;
 }
 
 int32_t oxhip_prm_last_timing(oxhip_prm* h, double* phase_ms, uint64_t* n_candidates, uint32_t* redraw_batches) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
-    if (phase_ms) for (int i = 0; i < 6; ++i) phase_ms[i] = h->t_ms[i];
-    if (n_candidates) *n_candidates = h->n_candidates;
-    if (redraw_batches) *redraw_batches = h->redraw_batches;
+    if (phase_ms) for (int i = 0; i < 6; ++i) phase_ms[i] = i < 4 ? h->built.ms[i] : h->single.ms[i - 4];
+    if (n_candidates) *n_candidates = h->built.candidates;
+    if (redraw_batches) *redraw_batches = h->sampler.redraw_batches;
     return OXHIP_OK;
 }
 
@@ -800,33 +826,33 @@ namespace {
 // the arguments of one round of the last batch: queries [q0, q0 + n_chunk) in the workspace rows [0, n_chunk)
 PrmBatchArgs batch_args(oxhip_prm* h, uint32_t q0, uint32_t n_chunk, uint32_t res_cap) {
     PrmBatchArgs b{};
-    b.ms = h->ms.p; b.offsets = h->offsets.p; b.nbrs = h->nbrs.p;
-    b.starts = h->bd_starts.p; b.goals = h->bd_goals.p; b.goal_thr = h->bd_thr.p; b.filt = h->bd_filt.p;
-    b.flags = h->bd_flags.p; b.start_valid = h->bd_start_valid.p; b.parent = h->bd_parent.p; b.queue = h->bd_queue.p;
-    b.status = (int32_t*)h->bd_res.p; b.path_len = h->bd_res.p + res_cap; b.goal_node = (int32_t*)(h->bd_res.p + 2 * (size_t)res_cap);
-    b.n_start = h->bd_res.p + 3 * (size_t)res_cap; b.n_goal = h->bd_res.p + 4 * (size_t)res_cap;
-    b.n = h->n; b.stride = (h->n + 63u) & ~63u; b.dim = h->cfg.dim; b.q0 = q0; b.n_chunk = n_chunk;
+    b.ms = h->rm.ms.p; b.offsets = h->rm.offsets.p; b.nbrs = h->rm.nbrs.p;
+    b.starts = h->batch.d_starts.p; b.goals = h->batch.d_goals.p; b.goal_thr = h->batch.d_thr.p; b.filt = h->batch.d_filt.p;
+    b.flags = h->batch.d_flags.p; b.start_valid = h->batch.d_start_valid.p; b.parent = h->batch.d_parent.p; b.queue = h->batch.d_queue.p;
+    b.status = (int32_t*)h->batch.d_res.p; b.path_len = h->batch.d_res.p + res_cap; b.goal_node = (int32_t*)(h->batch.d_res.p + 2 * (size_t)res_cap);
+    b.n_start = h->batch.d_res.p + 3 * (size_t)res_cap; b.n_goal = h->batch.d_res.p + 4 * (size_t)res_cap;
+    b.n = h->rm.n; b.stride = (h->rm.n + 63u) & ~63u; b.dim = h->cfg.dim; b.q0 = q0; b.n_chunk = n_chunk;
     return b;
 }
 
 PrmShortestArgs shortest_args(oxhip_prm* h, int32_t mode) {
     PrmShortestArgs a{};
-    a.w = h->w_edges.p; a.label = h->bd_label.p; a.stamp = h->bd_stamp.p; a.cost = h->bd_cost.p; a.rounds = h->bd_rounds.p;
-    a.relaxed = h->bd_relaxed.p; a.mode = (uint32_t)mode;
+    a.w = h->shortest.w_edges.p; a.label = h->shortest.d_label.p; a.stamp = h->shortest.d_stamp.p; a.cost = h->shortest.d_cost.p; a.rounds = h->shortest.d_rounds.p;
+    a.relaxed = h->shortest.d_relaxed.p; a.mode = (uint32_t)mode;
     return a;
 }
 
 // the distances of the roadmap's CSR entries, once per roadmap (distance weights only)
 int32_t ensure_edge_weights(oxhip_prm* h) {
-    if (h->w_valid) return OXHIP_OK;
-    HIP_TRY(h->w_edges.reserve(h->n_keys));
-    HIP_TRY(hipEventRecord(h->sev[0], h->stream));
-    launch_prm_shortest_weights(h->so3, h->cfg.dim, h->ms.p, h->offsets.p, h->nbrs.p, h->n, h->n_keys, h->w_edges.p, h->stream);
+    if (h->shortest.w_valid) return OXHIP_OK;
+    HIP_TRY(h->shortest.w_edges.reserve(h->rm.n_keys));
+    HIP_TRY(h->shortest.clk.mark(kBegin, h->stream));
+    launch_prm_shortest_weights(h->so3, h->cfg.dim, h->rm.ms.p, h->rm.offsets.p, h->rm.nbrs.p, h->rm.n, h->rm.n_keys, h->shortest.w_edges.p, h->stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->sev[1], h->stream));
+    HIP_TRY(h->shortest.clk.mark(kEnd, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    h->short_ms[0] = elapsed_ms(h->sev[0], h->sev[1]);
-    h->w_valid = true;
+    h->shortest.ms[0] = h->shortest.clk.ms(kBegin, kEnd);
+    h->shortest.w_valid = true;
     return OXHIP_OK;
 }
 
@@ -847,71 +873,71 @@ int32_t stage_batch(oxhip_prm* h, uint32_t Q, const double* starts, const double
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
     if (Q && (!starts || !goal_centres || !goal_radii)) return fail(OXHIP_ERR_BAD_ARG, "null argument");
     if (!h->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");      // prm.rs:229-236
-    if (h->n == 0) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "construct_roadmap() left no milestones");  // prm.rs:239-241
+    if (h->rm.n == 0) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "construct_roadmap() left no milestones");  // prm.rs:239-241
     const uint32_t dim = h->cfg.dim;
     OX_TRY(check_query_points(starts, goal_centres, (size_t)Q * dim));
     OX_TRY(select_device(h->cfg.device));
-    h->batch_valid = false;
-    h->batch_rounds = 0;
-    h->batch_mode = mode;
-    for (double& t : h->batch_ms) t = 0.0;
-    for (double& t : h->short_ms) t = 0.0;
-    h->b_cost.assign(mode < 0 ? 0 : Q, std::numeric_limits<double>::infinity());
-    h->b_rounds.assign(mode < 0 ? 0 : Q, 0u);
-    h->b_relaxed.assign(mode < 0 ? 0 : Q, 0ull);
-    h->b_starts.assign(starts, starts + (size_t)Q * dim);
-    h->b_goals.assign(goal_centres, goal_centres + (size_t)Q * dim);
-    h->b_thr.resize(Q); h->b_filt.resize(Q);
+    h->batch.valid = false;
+    h->batch.rounds = 0;
+    h->batch.mode = mode;
+    for (double& t : h->batch.ms) t = 0.0;
+    for (double& t : h->shortest.ms) t = 0.0;
+    h->shortest.cost.assign(mode < 0 ? 0 : Q, std::numeric_limits<double>::infinity());
+    h->shortest.rounds.assign(mode < 0 ? 0 : Q, 0u);
+    h->shortest.relaxed.assign(mode < 0 ? 0 : Q, 0ull);
+    h->batch.starts.assign(starts, starts + (size_t)Q * dim);
+    h->batch.goals.assign(goal_centres, goal_centres + (size_t)Q * dim);
+    h->batch.thr.resize(Q); h->batch.filt.resize(Q);
     for (uint32_t q = 0; q < Q; ++q) {
-        h->b_thr[q] = goal_threshold(h, goal_radii[q]);
+        h->batch.thr[q] = goal_threshold(h, goal_radii[q]);
         double f = h->dp.filt_abs;   // the start may lie anywhere: the filter's absolute margin with this start in play
         for (uint32_t k = 0; k < dim; ++k) f = std::fmax(f, 1e-9 * std::fabs(starts[(size_t)q * dim + k]));
-        h->b_filt[q] = f;
+        h->batch.filt[q] = f;
     }
-    h->b_status.assign(Q, OXHIP_ERR_TIMEOUT);
-    h->b_goal_node.assign(Q, -1);
-    h->b_len.assign(Q, 0); h->b_nstart.assign(Q, 0); h->b_ngoal.assign(Q, 0);
-    h->b_off.assign((size_t)Q + 1, 0);
-    h->b_nodes.clear(); h->b_rows.clear();
+    h->batch.status.assign(Q, OXHIP_ERR_TIMEOUT);
+    h->batch.goal_node.assign(Q, -1);
+    h->batch.len.assign(Q, 0); h->batch.nstart.assign(Q, 0); h->batch.ngoal.assign(Q, 0);
+    h->batch.off.assign((size_t)Q + 1, 0);
+    h->batch.nodes.clear(); h->batch.rows.clear();
     if (!Q) return OXHIP_OK;
-    HIP_TRY(h->bd_starts.reserve((size_t)Q * dim)); HIP_TRY(h->bd_goals.reserve((size_t)Q * dim));
-    HIP_TRY(h->bd_thr.reserve(Q)); HIP_TRY(h->bd_filt.reserve(Q));
-    HIP_TRY(hipMemcpyAsync(h->bd_starts.p, h->b_starts.data(), (size_t)Q * dim * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->bd_goals.p, h->b_goals.data(), (size_t)Q * dim * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->bd_thr.p, h->b_thr.data(), (size_t)Q * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->bd_filt.p, h->b_filt.data(), (size_t)Q * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h->batch.d_starts.reserve((size_t)Q * dim)); HIP_TRY(h->batch.d_goals.reserve((size_t)Q * dim));
+    HIP_TRY(h->batch.d_thr.reserve(Q)); HIP_TRY(h->batch.d_filt.reserve(Q));
+    HIP_TRY(hipMemcpyAsync(h->batch.d_starts.p, h->batch.starts.data(), (size_t)Q * dim * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->batch.d_goals.p, h->batch.goals.data(), (size_t)Q * dim * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->batch.d_thr.p, h->batch.thr.data(), (size_t)Q * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->batch.d_filt.p, h->batch.filt.data(), (size_t)Q * sizeof(double), hipMemcpyHostToDevice, h->stream));
     return OXHIP_OK;
 }
 
 // The size of a round -- 9 bytes per query and milestone (21 for shortest paths), sized to keep the workspace within 1 GiB -- and
 // every buffer a round of that size needs; distance weights: the roadmap's edge weights, once per roadmap
 int32_t reserve_batch_workspace(oxhip_prm* h, BatchRun& br, uint32_t chunk_queries) {
-    br.stride = (h->n + 63u) & ~63u;
+    br.stride = (h->rm.n + 63u) & ~63u;
     uint32_t chunk = chunk_queries ? chunk_queries : (uint32_t)std::max<uint64_t>(1, (1ull << 30) / (batch_bytes_per_node(br.mode) * br.stride));
     br.chunk = chunk = std::min(std::min(chunk, br.Q), 65535u);
     const size_t cells = (size_t)chunk * br.stride;
     if (br.mode >= 0) {
-        HIP_TRY(h->bd_label.reserve(cells)); HIP_TRY(h->bd_stamp.reserve(cells));
-        HIP_TRY(h->bd_cost.reserve(chunk)); HIP_TRY(h->bd_rounds.reserve(chunk)); HIP_TRY(h->bd_relaxed.reserve(chunk));
+        HIP_TRY(h->shortest.d_label.reserve(cells)); HIP_TRY(h->shortest.d_stamp.reserve(cells));
+        HIP_TRY(h->shortest.d_cost.reserve(chunk)); HIP_TRY(h->shortest.d_rounds.reserve(chunk)); HIP_TRY(h->shortest.d_relaxed.reserve(chunk));
     }
     if (br.mode == 0) OX_TRY(ensure_edge_weights(h));
     br.sa = shortest_args(h, br.mode);
-    HIP_TRY(h->bd_flags.reserve(cells)); HIP_TRY(h->bd_parent.reserve(cells)); HIP_TRY(h->bd_queue.reserve(cells));
-    HIP_TRY(h->bd_start_valid.reserve(chunk)); HIP_TRY(h->bd_off.reserve(chunk));
-    HIP_TRY(h->bd_res.reserve(5 * (size_t)chunk));   // (the getters take bd_res.n / 5 as a round's row count: never below this one)
-    br.group = prm_batch_group(h->n, h->n_keys);
+    HIP_TRY(h->batch.d_flags.reserve(cells)); HIP_TRY(h->batch.d_parent.reserve(cells)); HIP_TRY(h->batch.d_queue.reserve(cells));
+    HIP_TRY(h->batch.d_start_valid.reserve(chunk)); HIP_TRY(h->batch.d_off.reserve(chunk));
+    HIP_TRY(h->batch.d_res.reserve(5 * (size_t)chunk));   // (the getters take d_res.n / 5 as a round's row count: never below this one)
+    br.group = prm_batch_group(h->rm.n, h->rm.n_keys);
     br.res.resize(5 * (size_t)chunk); br.off.resize(chunk);
     return OXHIP_OK;
 }
 
-// flags, initial labels, label rounds and tight levels of the queries of `b`; `timed`: a batch's round, which records its events between
+// flags, initial labels, label rounds and tight levels of the queries of `b`; `timed`: a batch's round, which marks its clock between
 int32_t launch_shortest(oxhip_prm* h, const PrmBatchArgs& b, const PrmShortestArgs& sa, uint32_t group, bool timed) {
     launch_batch_flags(h, b);
     launch_prm_shortest_init(h->so3, b, sa, h->stream);
-    if (timed) HIP_TRY(hipEventRecord(h->bev[1], h->stream));
+    if (timed) HIP_TRY(h->batch.clk.mark(kFlagsEnd, h->stream));
     launch_prm_shortest_labels(b, sa, group, h->stream);
     HIP_TRY(hipGetLastError());
-    if (timed) HIP_TRY(hipEventRecord(h->sev[0], h->stream));
+    if (timed) HIP_TRY(h->batch.clk.mark(kLabelsEnd, h->stream));
     launch_prm_shortest_levels(b, sa, group, h->stream);
     HIP_TRY(hipGetLastError());
     return OXHIP_OK;
@@ -920,31 +946,32 @@ int32_t launch_shortest(oxhip_prm* h, const PrmBatchArgs& b, const PrmShortestAr
 // one round on the device: the query sets, the search, and its results copied into `br` (the search's own figures: to their queries)
 int32_t run_round(oxhip_prm* h, BatchRun& br, const PrmBatchArgs& b) {
     const uint32_t c = b.n_chunk, q0 = b.q0;
-    HIP_TRY(hipMemsetAsync(h->bd_parent.p, 0xFF, (size_t)c * br.stride * sizeof(uint32_t), h->stream));
-    HIP_TRY(hipEventRecord(h->bev[0], h->stream));
+    HIP_TRY(hipMemsetAsync(h->batch.d_parent.p, 0xFF, (size_t)c * br.stride * sizeof(uint32_t), h->stream));
+    PhaseClock& clk = h->batch.clk;
+    HIP_TRY(clk.mark(kRoundBegin, h->stream));
     if (br.mode < 0) {
         launch_batch_flags(h, b);
-        HIP_TRY(hipEventRecord(h->bev[1], h->stream));
+        HIP_TRY(clk.mark(kFlagsEnd, h->stream));
         launch_prm_batch_search(b, br.group, h->stream);
         HIP_TRY(hipGetLastError());
     } else {
         OX_TRY(launch_shortest(h, b, br.sa, br.group, true));
     }
-    HIP_TRY(hipEventRecord(h->bev[2], h->stream));
-    HIP_TRY(hipMemcpyAsync(br.res.data(), h->bd_res.p, 5 * (size_t)br.chunk * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(clk.mark(kSearchEnd, h->stream));
+    HIP_TRY(hipMemcpyAsync(br.res.data(), h->batch.d_res.p, 5 * (size_t)br.chunk * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     if (br.mode >= 0) {
-        HIP_TRY(hipMemcpyAsync(h->b_cost.data() + q0, h->bd_cost.p, (size_t)c * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->b_rounds.data() + q0, h->bd_rounds.p, (size_t)c * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(h->b_relaxed.data() + q0, h->bd_relaxed.p, (size_t)c * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->shortest.cost.data() + q0, h->shortest.d_cost.p, (size_t)c * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->shortest.rounds.data() + q0, h->shortest.d_rounds.p, (size_t)c * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(h->shortest.relaxed.data() + q0, h->shortest.d_relaxed.p, (size_t)c * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
     }
-    HIP_TRY(hipEventRecord(h->bev[3], h->stream));
+    HIP_TRY(clk.mark(kResultsEnd, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    h->batch_ms[0] += elapsed_ms(h->bev[0], h->bev[1]);
-    h->batch_ms[1] += elapsed_ms(h->bev[1], h->bev[2]);
-    h->batch_ms[3] += elapsed_ms(h->bev[2], h->bev[3]);
+    h->batch.ms[0] += clk.ms(kRoundBegin, kFlagsEnd);
+    h->batch.ms[1] += clk.ms(kFlagsEnd, kSearchEnd);
+    h->batch.ms[3] += clk.ms(kSearchEnd, kResultsEnd);
     if (br.mode < 0) return OXHIP_OK;
-    h->short_ms[2] += elapsed_ms(h->bev[1], h->sev[0]);
-    h->short_ms[3] += elapsed_ms(h->sev[0], h->bev[2]);
+    h->shortest.ms[2] += clk.ms(kFlagsEnd, kLabelsEnd);
+    h->shortest.ms[3] += clk.ms(kLabelsEnd, kSearchEnd);
     for (uint32_t i = 0; i < c; ++i)
         if ((int32_t)br.res[i] == OXHIP_ERR_HIP)   // (no query status is OXHIP_ERR_HIP otherwise)
             return fail(OXHIP_ERR_HIP, "shortest-path search: a label round or level cap was hit, which cannot happen");
@@ -955,38 +982,38 @@ int32_t run_round(oxhip_prm* h, BatchRun& br, const PrmBatchArgs& b) {
 uint64_t scatter_round(oxhip_prm* h, BatchRun& br, uint32_t q0, uint32_t c) {
     const size_t chunk = br.chunk;
     uint64_t rows = 0;
-    const uint64_t row0 = h->b_off[q0];
+    const uint64_t row0 = h->batch.off[q0];
     for (uint32_t i = 0; i < c; ++i) {
-        h->b_status[q0 + i] = (int32_t)br.res[i];
-        h->b_len[q0 + i] = br.res[chunk + i];
-        h->b_goal_node[q0 + i] = (int32_t)br.res[2 * chunk + i];
-        h->b_nstart[q0 + i] = br.res[3 * chunk + i];
-        h->b_ngoal[q0 + i] = br.res[4 * chunk + i];
+        h->batch.status[q0 + i] = (int32_t)br.res[i];
+        h->batch.len[q0 + i] = br.res[chunk + i];
+        h->batch.goal_node[q0 + i] = (int32_t)br.res[2 * chunk + i];
+        h->batch.nstart[q0 + i] = br.res[3 * chunk + i];
+        h->batch.ngoal[q0 + i] = br.res[4 * chunk + i];
         br.off[i] = rows;
         rows += br.res[chunk + i];
-        h->b_off[q0 + i + 1] = row0 + rows;
+        h->batch.off[q0 + i + 1] = row0 + rows;
     }
     return rows;
 }
 
-// the `rows` path rows of the round, extracted on the device and appended to b_nodes / b_rows
+// the `rows` path rows of the round, extracted on the device and appended to batch.nodes / batch.rows
 int32_t extract_round_paths(oxhip_prm* h, const BatchRun& br, const PrmBatchArgs& b, uint64_t rows) {
     const uint32_t dim = h->cfg.dim;
-    const uint64_t row0 = h->b_off[b.q0];
-    HIP_TRY(h->bd_nodes.reserve((size_t)rows)); HIP_TRY(h->bd_rows.reserve((size_t)rows * dim));
-    h->b_nodes.resize((size_t)(row0 + rows)); h->b_rows.resize((size_t)(row0 + rows) * dim);
-    HIP_TRY(hipMemcpyAsync(h->bd_off.p, br.off.data(), (size_t)b.n_chunk * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipEventRecord(h->bev[4], h->stream));
-    launch_prm_batch_paths(b, h->bd_off.p, h->bd_nodes.p, h->bd_rows.p, h->stream);
+    const uint64_t row0 = h->batch.off[b.q0];
+    HIP_TRY(h->batch.d_nodes.reserve((size_t)rows)); HIP_TRY(h->batch.d_rows.reserve((size_t)rows * dim));
+    h->batch.nodes.resize((size_t)(row0 + rows)); h->batch.rows.resize((size_t)(row0 + rows) * dim);
+    HIP_TRY(hipMemcpyAsync(h->batch.d_off.p, br.off.data(), (size_t)b.n_chunk * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h->batch.clk.mark(kPathsBegin, h->stream));
+    launch_prm_batch_paths(b, h->batch.d_off.p, h->batch.d_nodes.p, h->batch.d_rows.p, h->stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->bev[5], h->stream));
-    HIP_TRY(hipMemcpyAsync(h->b_nodes.data() + row0, h->bd_nodes.p, (size_t)rows * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->b_rows.data() + (size_t)row0 * dim, h->bd_rows.p, (size_t)rows * dim * sizeof(double), hipMemcpyDeviceToHost,
+    HIP_TRY(h->batch.clk.mark(kPathsEnd, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->batch.nodes.data() + row0, h->batch.d_nodes.p, (size_t)rows * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->batch.rows.data() + (size_t)row0 * dim, h->batch.d_rows.p, (size_t)rows * dim * sizeof(double), hipMemcpyDeviceToHost,
                            h->stream));
-    HIP_TRY(hipEventRecord(h->bev[6], h->stream));
+    HIP_TRY(h->batch.clk.mark(kRowsEnd, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    h->batch_ms[2] += elapsed_ms(h->bev[4], h->bev[5]);
-    h->batch_ms[3] += elapsed_ms(h->bev[5], h->bev[6]);
+    h->batch.ms[2] += h->batch.clk.ms(kPathsBegin, kPathsEnd);
+    h->batch.ms[3] += h->batch.clk.ms(kPathsEnd, kRowsEnd);
     return OXHIP_OK;
 }
 
@@ -1008,14 +1035,14 @@ int32_t solve_batch_common(oxhip_prm* h, uint32_t n_queries, const double* start
             OX_TRY(run_round(h, br, b));
             const uint64_t rows = scatter_round(h, br, q0, c);
             if (rows) OX_TRY(extract_round_paths(h, br, b, rows));
-            ++h->batch_rounds;
+            ++h->batch.rounds;
             answered = q0 + c;
         }
-        for (uint32_t q = answered + 1; q <= br.Q; ++q) h->b_off[q] = h->b_off[answered];   // (the rounds not begun add no rows)
+        for (uint32_t q = answered + 1; q <= br.Q; ++q) h->batch.off[q] = h->batch.off[answered];   // (the rounds not begun add no rows)
     }
-    if (mode >= 0) { h->short_ms[1] = h->batch_ms[0]; h->short_ms[4] = h->batch_ms[2]; h->short_ms[5] = h->batch_ms[3]; }
-    h->batch_valid = true;
-    if (status_out) for (uint32_t q = 0; q < br.Q; ++q) status_out[q] = h->b_status[q];
+    if (mode >= 0) { h->shortest.ms[1] = h->batch.ms[0]; h->shortest.ms[4] = h->batch.ms[2]; h->shortest.ms[5] = h->batch.ms[3]; }
+    h->batch.valid = true;
+    if (status_out) for (uint32_t q = 0; q < br.Q; ++q) status_out[q] = h->batch.status[q];
     return OXHIP_OK;
 }
 
@@ -1037,21 +1064,21 @@ int32_t oxhip_prm_solve_batch_shortest(oxhip_prm* h, uint32_t n_queries, const d
 
 int32_t oxhip_prm_batch_get_costs(oxhip_prm* h, double* cost) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
-    if (!h->batch_valid) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "no batch was solved on this roadmap");
-    if (h->batch_mode < 0) return fail(OXHIP_ERR_BAD_ARG, "the last batch was not a shortest-path batch");
-    if (cost && !h->b_cost.empty()) std::memcpy(cost, h->b_cost.data(), h->b_cost.size() * sizeof(double));
+    if (!h->batch.valid) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "no batch was solved on this roadmap");
+    if (h->batch.mode < 0) return fail(OXHIP_ERR_BAD_ARG, "the last batch was not a shortest-path batch");
+    if (cost && !h->shortest.cost.empty()) std::memcpy(cost, h->shortest.cost.data(), h->shortest.cost.size() * sizeof(double));
     return OXHIP_OK;
 }
 
 int32_t oxhip_prm_batch_get_labels(oxhip_prm* h, uint32_t query, double* cost, uint32_t* hops, uint32_t* parent, uint32_t cap) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
-    if (!h->batch_valid) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "no batch was solved on this roadmap");
-    if (h->batch_mode < 0) return fail(OXHIP_ERR_BAD_ARG, "the last batch was not a shortest-path batch");
-    if (query >= h->b_status.size()) return fail(OXHIP_ERR_BAD_ARG, "query index beyond the last batch");
-    const uint32_t n = h->n;
+    if (!h->batch.valid) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "no batch was solved on this roadmap");
+    if (h->batch.mode < 0) return fail(OXHIP_ERR_BAD_ARG, "the last batch was not a shortest-path batch");
+    if (query >= h->batch.status.size()) return fail(OXHIP_ERR_BAD_ARG, "query index beyond the last batch");
+    const uint32_t n = h->rm.n;
     if ((cost || hops || parent) && cap < n) return fail(OXHIP_ERR_CAPACITY, "label buffers too small");
     if (!cost && !hops && !parent) return OXHIP_OK;
-    if (h->b_status[query] == OXHIP_ERR_INVALID_START_STATE || h->b_status[query] == OXHIP_ERR_TIMEOUT) {   // no search ran
+    if (h->batch.status[query] == OXHIP_ERR_INVALID_START_STATE || h->batch.status[query] == OXHIP_ERR_TIMEOUT) {   // no search ran
         for (uint32_t i = 0; i < n; ++i) {
             if (cost) cost[i] = std::numeric_limits<double>::infinity();
             if (hops) hops[i] = 0xFFFFFFFFu;
@@ -1062,15 +1089,15 @@ int32_t oxhip_prm_batch_get_labels(oxhip_prm* h, uint32_t query, double* cost, u
     // the labels are not kept per query: flags, initial labels, label rounds and levels run again for this one (same kernels, and
     // a fixed point that does not depend on the order of arrival: same bits) into workspace row 0
     OX_TRY(select_device(h->cfg.device));
-    const PrmBatchArgs b = batch_args(h, query, 1, (uint32_t)(h->bd_res.n / 5));
-    const PrmShortestArgs sa = shortest_args(h, h->batch_mode);
-    const uint32_t group = prm_batch_group(n, h->n_keys);
+    const PrmBatchArgs b = batch_args(h, query, 1, (uint32_t)(h->batch.d_res.n / 5));
+    const PrmShortestArgs sa = shortest_args(h, h->batch.mode);
+    const uint32_t group = prm_batch_group(n, h->rm.n_keys);
     OX_TRY(launch_shortest(h, b, sa, group, false));
     int32_t status = 0;
-    HIP_TRY(hipMemcpyAsync(&status, h->bd_res.p, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    if (cost) HIP_TRY(hipMemcpyAsync(cost, h->bd_label.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (hops) HIP_TRY(hipMemcpyAsync(hops, h->bd_stamp.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    if (parent) HIP_TRY(hipMemcpyAsync(parent, h->bd_parent.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(&status, h->batch.d_res.p, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (cost) HIP_TRY(hipMemcpyAsync(cost, h->shortest.d_label.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (hops) HIP_TRY(hipMemcpyAsync(hops, h->shortest.d_stamp.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (parent) HIP_TRY(hipMemcpyAsync(parent, h->batch.d_parent.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (status == OXHIP_ERR_HIP) return fail(OXHIP_ERR_HIP, "shortest-path search: a label round or level cap was hit, which cannot happen");
     return OXHIP_OK;
@@ -1078,45 +1105,45 @@ int32_t oxhip_prm_batch_get_labels(oxhip_prm* h, uint32_t query, double* cost, u
 
 int32_t oxhip_prm_batch_get_search_stats(oxhip_prm* h, uint32_t* label_rounds, uint64_t* relaxations, double* phase_ms) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
-    if (!h->batch_valid) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "no batch was solved on this roadmap");
-    if (h->batch_mode < 0) return fail(OXHIP_ERR_BAD_ARG, "the last batch was not a shortest-path batch");
-    const size_t Q = h->b_rounds.size();
-    if (label_rounds && Q) std::memcpy(label_rounds, h->b_rounds.data(), Q * sizeof(uint32_t));
-    if (relaxations && Q) std::memcpy(relaxations, h->b_relaxed.data(), Q * sizeof(uint64_t));
-    if (phase_ms) for (int i = 0; i < 6; ++i) phase_ms[i] = h->short_ms[i];
+    if (!h->batch.valid) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "no batch was solved on this roadmap");
+    if (h->batch.mode < 0) return fail(OXHIP_ERR_BAD_ARG, "the last batch was not a shortest-path batch");
+    const size_t Q = h->shortest.rounds.size();
+    if (label_rounds && Q) std::memcpy(label_rounds, h->shortest.rounds.data(), Q * sizeof(uint32_t));
+    if (relaxations && Q) std::memcpy(relaxations, h->shortest.relaxed.data(), Q * sizeof(uint64_t));
+    if (phase_ms) for (int i = 0; i < 6; ++i) phase_ms[i] = h->shortest.ms[i];
     return OXHIP_OK;
 }
 
 int32_t oxhip_prm_batch_get_results(oxhip_prm* h, int32_t* status, uint32_t* path_len, int32_t* goal_node, uint32_t* n_start, uint32_t* n_goal) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
-    if (!h->batch_valid) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "no batch was solved on this roadmap");
-    const size_t Q = h->b_status.size();
-    if (status && Q) std::memcpy(status, h->b_status.data(), Q * sizeof(int32_t));
-    if (path_len && Q) std::memcpy(path_len, h->b_len.data(), Q * sizeof(uint32_t));
-    if (goal_node && Q) std::memcpy(goal_node, h->b_goal_node.data(), Q * sizeof(int32_t));
-    if (n_start && Q) std::memcpy(n_start, h->b_nstart.data(), Q * sizeof(uint32_t));
-    if (n_goal && Q) std::memcpy(n_goal, h->b_ngoal.data(), Q * sizeof(uint32_t));
+    if (!h->batch.valid) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "no batch was solved on this roadmap");
+    const size_t Q = h->batch.status.size();
+    if (status && Q) std::memcpy(status, h->batch.status.data(), Q * sizeof(int32_t));
+    if (path_len && Q) std::memcpy(path_len, h->batch.len.data(), Q * sizeof(uint32_t));
+    if (goal_node && Q) std::memcpy(goal_node, h->batch.goal_node.data(), Q * sizeof(int32_t));
+    if (n_start && Q) std::memcpy(n_start, h->batch.nstart.data(), Q * sizeof(uint32_t));
+    if (n_goal && Q) std::memcpy(n_goal, h->batch.ngoal.data(), Q * sizeof(uint32_t));
     return OXHIP_OK;
 }
 
 int32_t oxhip_prm_batch_get_paths(oxhip_prm* h, uint64_t* offsets, uint32_t* nodes, double* states, uint64_t cap_rows, uint64_t* total_rows) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
-    if (!h->batch_valid) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "no batch was solved on this roadmap");
-    const uint64_t total = h->b_nodes.size();
+    if (!h->batch.valid) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "no batch was solved on this roadmap");
+    const uint64_t total = h->batch.nodes.size();
     if (total_rows) *total_rows = total;
-    if (offsets) std::memcpy(offsets, h->b_off.data(), h->b_off.size() * sizeof(uint64_t));
+    if (offsets) std::memcpy(offsets, h->batch.off.data(), h->batch.off.size() * sizeof(uint64_t));
     if ((nodes || states) && cap_rows < total) return fail(OXHIP_ERR_CAPACITY, "path buffers too small");
-    if (nodes && total) std::memcpy(nodes, h->b_nodes.data(), (size_t)total * sizeof(uint32_t));
-    if (states && total) std::memcpy(states, h->b_rows.data(), h->b_rows.size() * sizeof(double));
+    if (nodes && total) std::memcpy(nodes, h->batch.nodes.data(), (size_t)total * sizeof(uint32_t));
+    if (states && total) std::memcpy(states, h->batch.rows.data(), h->batch.rows.size() * sizeof(double));
     return OXHIP_OK;
 }
 
 int32_t oxhip_prm_batch_get_query_sets(oxhip_prm* h, uint32_t query, uint32_t* start_connections, uint32_t cap_start, uint32_t* n_start,
                                        uint32_t* goal_indices, uint32_t cap_goal, uint32_t* n_goal) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
-    if (!h->batch_valid) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "no batch was solved on this roadmap");
-    if (query >= h->b_status.size()) return fail(OXHIP_ERR_BAD_ARG, "query index beyond the last batch");
-    const uint32_t ns = h->b_nstart[query], ng = h->b_ngoal[query];
+    if (!h->batch.valid) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "no batch was solved on this roadmap");
+    if (query >= h->batch.status.size()) return fail(OXHIP_ERR_BAD_ARG, "query index beyond the last batch");
+    const uint32_t ns = h->batch.nstart[query], ng = h->batch.ngoal[query];
     if (n_start) *n_start = ns;
     if (n_goal) *n_goal = ng;
     if (start_connections && cap_start < ns) return fail(OXHIP_ERR_CAPACITY, "start_connections buffer too small");
@@ -1124,12 +1151,12 @@ int32_t oxhip_prm_batch_get_query_sets(oxhip_prm* h, uint32_t query, uint32_t* s
     if ((!start_connections && !goal_indices) || (ns == 0 && ng == 0)) return OXHIP_OK;
     // the sets are not kept per query: the flag kernel runs again for this one (same kernel, same bits) into workspace row 0
     OX_TRY(select_device(h->cfg.device));
-    const uint32_t n = h->n;
-    const PrmBatchArgs b = batch_args(h, query, 1, (uint32_t)(h->bd_res.n / 5));
+    const uint32_t n = h->rm.n;
+    const PrmBatchArgs b = batch_args(h, query, 1, (uint32_t)(h->batch.d_res.n / 5));
     launch_batch_flags(h, b);
     HIP_TRY(hipGetLastError());
     std::vector<uint8_t> flags(n);
-    HIP_TRY(hipMemcpyAsync(flags.data(), h->bd_flags.p, n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(flags.data(), h->batch.d_flags.p, n, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     uint32_t is = 0, ig = 0;
     for (uint32_t i = 0; i < n; ++i) {
@@ -1141,8 +1168,8 @@ int32_t oxhip_prm_batch_get_query_sets(oxhip_prm* h, uint32_t query, uint32_t* s
 
 int32_t oxhip_prm_batch_last_timing(oxhip_prm* h, double* phase_ms, uint32_t* rounds) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
-    if (phase_ms) for (int i = 0; i < 4; ++i) phase_ms[i] = h->batch_ms[i];
-    if (rounds) *rounds = h->batch_rounds;
+    if (phase_ms) for (int i = 0; i < 4; ++i) phase_ms[i] = h->batch.ms[i];
+    if (rounds) *rounds = h->batch.rounds;
     return OXHIP_OK;
 }
 
@@ -1165,6 +1192,22 @@ int32_t plant_verdict(oxhip_prm* h, uint32_t* d_viol, uint32_t first, uint32_t l
     for (uint32_t r = first; r < last; ++r)
         if (viol[r] != 0xFFFFFFFFu)
             return fail(OXHIP_ERR_BAD_ARG, std::string("roadmap refused: rule ") + kPlantRuleName[r] + ", lowest offending row " + std::to_string(viol[r]));
+    return OXHIP_OK;
+}
+
+// "Is every milestone valid now": is_valid(milestone i) under the obstacles as they are, by the re-check's kernel, into reval.valid;
+// reval.counters[kRevalInvalid] counts the zeros.  clk (or null): bracket the kernel with the marks begin, begin + 1.  n_invalid
+// (or null): read the count back, which synchronises the stream.  The re-check, growth's liveness mask and prune's stage 1 start here.
+int32_t milestone_validity(oxhip_prm* h, PhaseClock* clk, int begin, uint32_t* n_invalid) {
+    HIP_TRY(h->reval.valid.reserve(h->rm.n)); HIP_TRY(h->reval.counters.reserve(kRevalCounters));   // (hipMalloc blocks: reserve_prune has done it)
+    HIP_TRY(hipMemsetAsync(h->reval.counters.p, 0, kRevalCounters * sizeof(uint32_t), h->stream));
+    if (clk) HIP_TRY(clk->mark(begin, h->stream));
+    launch_prm_reval_valid(h->so3, h->dp, h->rm.ms.p, h->rm.n, h->reval.valid.p, h->reval.counters.p, h->stream);
+    HIP_TRY(hipGetLastError());
+    if (clk) HIP_TRY(clk->mark(begin + 1, h->stream));
+    if (!n_invalid) return OXHIP_OK;
+    HIP_TRY(hipMemcpyAsync(n_invalid, h->reval.counters.p + kRevalInvalid, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return OXHIP_OK;
 }
 
@@ -1204,67 +1247,63 @@ int32_t oxhip_prm_set_roadmap(oxhip_prm* h, const double* states, uint32_t n, co
     HIP_TRY(hipGetLastError());
     OX_TRY(plant_verdict(h, s_viol.p, kPlantRange, kPlantRules));
     // accepted: the staged roadmap becomes the handle's
-    HIP_TRY(hipMemcpyAsync(h->ms.p, s_ms.p, (size_t)n * dim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->offsets.p, s_off.p, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->rm.ms.p, s_ms.p, (size_t)n * dim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->rm.offsets.p, s_off.p, ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
     launch_planted_shadow(h, n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->stream));
-    std::swap(h->nbrs.p, s_nbrs.p); std::swap(h->nbrs.n, s_nbrs.n);
-    clear_roadmap(h);   // everything that belonged to the roadmap before; n_samples = redraw_batches = 0
-    h->n = n;
-    h->n_keys = n_entries;
+    h->rm.nbrs.swap(s_nbrs);
+    bind_roadmap(h);
+    clear_roadmap(h, n, n_entries);   // everything that belonged to the roadmap before; n_samples = redraw_batches = 0
     return OXHIP_OK;
 }
 
 int32_t oxhip_prm_revalidate(oxhip_prm* h, uint8_t* milestone_valid, uint32_t* n_invalid_milestones, uint64_t* n_removed_entries) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
     if (!h->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
-    if (h->n == 0) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "the roadmap holds no milestones");
+    if (h->rm.n == 0) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "the roadmap holds no milestones");
     OX_TRY(select_device(h->cfg.device));
-    const uint32_t n = h->n, n_old = h->n_keys, pair_cap = n_old / 2 + 1;
+    const uint32_t n = h->rm.n, n_old = h->rm.n_keys, pair_cap = n_old / 2 + 1;
     // every buffer before the timed region: hipMalloc is a blocking call
     size_t tmp_bytes = 0;
-    HIP_TRY(h->rv_valid.reserve(n)); HIP_TRY(h->rv_counters.reserve(kRevalCounters));
     if (n_old) {
-        HIP_TRY(h->rv_keep.reserve(n_old)); HIP_TRY(h->rv_pos.reserve(n_old)); HIP_TRY(h->rv_nbrs.reserve(n_old));
+        HIP_TRY(h->reval.keep.reserve(n_old)); HIP_TRY(h->reval.pos.reserve(n_old)); HIP_TRY(h->reval.nbrs.reserve(n_old));
         OX_TRY(reserve_reval_pairs(h, pair_cap));
-        HIP_TRY(prm_reval_scan(nullptr, tmp_bytes, h->rv_keep.p, h->rv_pos.p, n_old, h->stream));
-        HIP_TRY(h->rv_tmp.reserve(tmp_bytes));
+        HIP_TRY(prm_reval_scan(nullptr, tmp_bytes, h->reval.keep.p, h->reval.pos.p, n_old, h->stream));
+        HIP_TRY(h->reval.tmp.reserve(tmp_bytes));
     }
+    PhaseClock& clk = h->reval.clk;
     uint32_t cnt[kRevalCounters] = {};
-    HIP_TRY(hipMemsetAsync(h->rv_counters.p, 0, sizeof cnt, h->stream));
-    if (n_old) HIP_TRY(hipMemsetAsync(h->rv_keep.p, 0, n_old, h->stream));
-    HIP_TRY(hipEventRecord(h->bev[0], h->stream));
-    launch_prm_reval_valid(h->so3, h->dp, h->ms.p, n, h->rv_valid.p, h->rv_counters.p, h->stream);
+    if (n_old) HIP_TRY(hipMemsetAsync(h->reval.keep.p, 0, n_old, h->stream));
+    OX_TRY(milestone_validity(h, &clk, kRvBegin, nullptr));   // kRvBegin, kRvValidEnd
+    launch_prm_reval_emit(h->rm.offsets.p, h->rm.nbrs.p, h->reval.valid.p, n, n_old, h->reval.pairs.p, reval_cand(h), pair_cap,
+                          h->reval.counters.p, h->stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->bev[1], h->stream));
-    launch_prm_reval_emit(h->offsets.p, h->nbrs.p, h->rv_valid.p, n, n_old, h->rv_pairs.p, reval_cand(h), pair_cap,
-                          h->rv_counters.p, h->stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->bev[2], h->stream));
-    HIP_TRY(hipMemcpyAsync(cnt, h->rv_counters.p, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(clk.mark(kRvEmitEnd, h->stream));
+    HIP_TRY(hipMemcpyAsync(cnt, h->reval.counters.p, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (cnt[kRevalPairs] > pair_cap) return fail(OXHIP_ERR_HIP, "revalidate: more lower-index entries than half the roadmap's, which a symmetric roadmap cannot have");
-    HIP_TRY(hipEventRecord(h->bev[3], h->stream));
+    HIP_TRY(clk.mark(kRvEdgesBegin, h->stream));
     OX_TRY(launch_reval_edges(h, cnt[kRevalPairs], n, n_old));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->bev[4], h->stream));
+    HIP_TRY(clk.mark(kRvEdgesEnd, h->stream));
     uint32_t n_new = 0;
     if (n_old) {
-        HIP_TRY(prm_reval_scan(h->rv_tmp.p, tmp_bytes, h->rv_keep.p, h->rv_pos.p, n_old, h->stream));
-        launch_prm_reval_compact(h->offsets.p, h->nbrs.p, h->rv_keep.p, h->rv_pos.p, n, n_old, h->rv_nbrs.p, h->stream);
+        HIP_TRY(prm_reval_scan(h->reval.tmp.p, tmp_bytes, h->reval.keep.p, h->reval.pos.p, n_old, h->stream));
+        launch_prm_reval_compact(h->rm.offsets.p, h->rm.nbrs.p, h->reval.keep.p, h->reval.pos.p, n, n_old, h->reval.nbrs.p, h->stream);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(h->bev[5], h->stream));
-    if (n_old) HIP_TRY(hipMemcpyAsync(&n_new, h->offsets.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    if (milestone_valid) HIP_TRY(hipMemcpyAsync(milestone_valid, h->rv_valid.p, n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(clk.mark(kRvCompactEnd, h->stream));
+    if (n_old) HIP_TRY(hipMemcpyAsync(&n_new, h->rm.offsets.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (milestone_valid) HIP_TRY(hipMemcpyAsync(milestone_valid, h->reval.valid.p, n, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (n_old) { std::swap(h->nbrs.p, h->rv_nbrs.p); std::swap(h->nbrs.n, h->rv_nbrs.n); }
-    h->reval_ms[0] = elapsed_ms(h->bev[0], h->bev[1]);
-    h->reval_ms[1] = elapsed_ms(h->bev[1], h->bev[2]);
-    h->reval_ms[2] = elapsed_ms(h->bev[3], h->bev[4]);
-    h->reval_ms[3] = elapsed_ms(h->bev[4], h->bev[5]);
-    h->n_keys = n_new;
+    h->reval.ms[0] = clk.ms(kRvBegin, kRvValidEnd);
+    h->reval.ms[1] = clk.ms(kRvValidEnd, kRvEmitEnd);
+    h->reval.ms[2] = clk.ms(kRvEdgesBegin, kRvEdgesEnd);
+    h->reval.ms[3] = clk.ms(kRvEdgesEnd, kRvCompactEnd);
+    if (n_old) h->rm.nbrs.swap(h->reval.nbrs);
+    bind_roadmap(h);
+    h->rm.n_keys = n_new;
     drop_derived(h);   // the host copy (the single solve searches it), the last solve's sets, the last batch, the edge weights
     if (n_invalid_milestones) *n_invalid_milestones = cnt[kRevalInvalid];
     if (n_removed_entries) *n_removed_entries = (uint64_t)n_old - n_new;
@@ -1273,7 +1312,7 @@ int32_t oxhip_prm_revalidate(oxhip_prm* h, uint8_t* milestone_valid, uint32_t* n
 
 int32_t oxhip_prm_revalidate_last_timing(oxhip_prm* h, double* phase_ms) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
-    if (phase_ms) for (int i = 0; i < 4; ++i) phase_ms[i] = h->reval_ms[i];
+    if (phase_ms) for (int i = 0; i < 4; ++i) phase_ms[i] = h->reval.ms[i];
     return OXHIP_OK;
 }
 
@@ -1283,95 +1322,75 @@ int32_t oxhip_prm_revalidate_last_timing(oxhip_prm* h, double* phase_ms) {
 
 namespace {
 
-// which earlier milestones are live: is_valid(milestone i) now, by the re-check's own kernel, into rv_valid; n_dead = its zeros
-int32_t liveness_mask(oxhip_prm* h, uint32_t& n_dead) {
-    uint32_t cnt[kRevalCounters] = {};
-    HIP_TRY(h->rv_valid.reserve(h->n)); HIP_TRY(h->rv_counters.reserve(kRevalCounters));
-    HIP_TRY(hipMemsetAsync(h->rv_counters.p, 0, sizeof cnt, h->stream));
-    HIP_TRY(hipEventRecord(h->ev[0], h->stream));
-    launch_prm_reval_valid(h->so3, h->dp, h->ms.p, h->n, h->rv_valid.p, h->rv_counters.p, h->stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-    HIP_TRY(hipMemcpyAsync(cnt, h->rv_counters.p, sizeof cnt, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    h->grow_ms[0] = elapsed_ms(h->ev[0], h->ev[1]);
-    n_dead = cnt[kRevalInvalid];
-    return OXHIP_OK;
-}
-
 // every buffer alloc_prm sizes by the capacity, moved to `cap` with the roadmap's part of its contents (the query flags hold
 // nothing between calls)
 int32_t grow_capacity(oxhip_prm* h, uint32_t cap) {
-    const size_t dim = h->cfg.dim, n = h->n;
+    const size_t dim = h->cfg.dim, n = h->rm.n;
     DevBuf<double> ms;
     DevBuf<float> ms32;
     DevBuf<uint8_t> flags;
     DevBuf<uint32_t> offsets;
     HIP_TRY(ms.alloc(dim * cap)); HIP_TRY(flags.alloc(cap)); HIP_TRY(offsets.alloc((size_t)cap + 1));
     if (!h->so3) HIP_TRY(ms32.alloc(dim * cap));
-    HIP_TRY(hipMemcpyAsync(ms.p, h->ms.p, n * dim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    if (!h->so3) HIP_TRY(hipMemcpyAsync(ms32.p, h->ms32.p, n * dim * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(offsets.p, h->offsets.p, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(ms.p, h->rm.ms.p, n * dim * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    if (!h->so3) HIP_TRY(hipMemcpyAsync(ms32.p, h->rm.ms32.p, n * dim * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(offsets.p, h->rm.offsets.p, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    std::swap(ms.p, h->ms.p); std::swap(ms.n, h->ms.n);
-    std::swap(ms32.p, h->ms32.p); std::swap(ms32.n, h->ms32.n);
-    std::swap(flags.p, h->flags.p); std::swap(flags.n, h->flags.n);
-    std::swap(offsets.p, h->offsets.p); std::swap(offsets.n, h->offsets.n);
-    h->args.ms = h->ms.p; h->args.ms32 = h->ms32.p; h->args.cap = cap;
+    h->rm.ms.swap(ms); h->rm.ms32.swap(ms32); h->rm.offsets.swap(offsets); h->single.flags.swap(flags);
+    h->args.cap = cap;
+    bind_roadmap(h);
     return OXHIP_OK;
 }
 
 // the directed keys of the roadmap as it stands, under the current capacity's shift: what this call's edge keys are appended to
 int32_t keys_from_csr(oxhip_prm* h) {
-    HIP_TRY(h->keys.reserve(std::max<size_t>(h->n_keys, 1)));
-    h->args.keys = h->keys.p;
-    HIP_TRY(hipEventRecord(h->ev[0], h->stream));
-    launch_prm_grow_keys(h->offsets.p, h->nbrs.p, h->n, h->n_keys, prm_key_shift(h->args.cap), h->keys.p, h->stream);
+    HIP_TRY(h->work.keys.reserve(std::max<size_t>(h->rm.n_keys, 1)));
+    h->args.keys = h->work.keys.p;
+    HIP_TRY(h->grow.tally.clk.mark(kBegin, h->stream));
+    launch_prm_grow_keys(h->rm.offsets.p, h->rm.nbrs.p, h->rm.n, h->rm.n_keys, prm_key_shift(h->args.cap), h->work.keys.p, h->stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev[1], h->stream));
+    HIP_TRY(h->grow.tally.clk.mark(kEnd, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    h->grow_ms[1] = elapsed_ms(h->ev[0], h->ev[1]);
+    h->grow.keys_ms = h->grow.tally.clk.ms(kBegin, kEnd);
     return OXHIP_OK;
 }
 
-// the candidates whose earlier end is live, into gw_cand: `pairs` and st.n_cand come back as what the edge step reads
+// the candidates whose earlier end is live, into grow.cand: `pairs` and st.n_cand come back as what the edge step reads (pairs phase)
 int32_t drop_dead_candidates(oxhip_prm* h, PrmState& st, uint32_t n_old, uint2*& pairs) {
     const uint32_t nc = (uint32_t)st.n_cand;
     uint32_t kept = 0;
-    HIP_TRY(h->gw_cand.reserve(std::max<uint32_t>(nc, 1))); HIP_TRY(h->gw_count.reserve(1));
-    HIP_TRY(hipMemsetAsync(h->gw_count.p, 0, sizeof(uint32_t), h->stream));
-    HIP_TRY(hipEventRecord(h->ev[2], h->stream));
-    launch_prm_grow_filter(pairs, nc, h->rv_valid.p, n_old, h->gw_cand.p, h->gw_count.p, h->stream);
+    HIP_TRY(h->grow.cand.reserve(std::max<uint32_t>(nc, 1))); HIP_TRY(h->grow.count.reserve(1));
+    HIP_TRY(hipMemsetAsync(h->grow.count.p, 0, sizeof(uint32_t), h->stream));
+    PrmBuildTally& t = h->grow.tally;
+    HIP_TRY(t.clk.mark(kBegin, h->stream));
+    launch_prm_grow_filter(pairs, nc, h->reval.valid.p, n_old, h->grow.cand.p, h->grow.count.p, h->stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev[3], h->stream));
-    HIP_TRY(hipMemcpyAsync(&kept, h->gw_count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(t.clk.mark(kEnd, h->stream));
+    HIP_TRY(hipMemcpyAsync(&kept, h->grow.count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    h->t_ms[1] += elapsed_ms(h->ev[2], h->ev[3]);
+    t.ms[1] += t.clk.ms(kBegin, kEnd);
     st.n_cand = kept;
-    pairs = h->gw_cand.p;
+    pairs = h->grow.cand.p;
     return OXHIP_OK;
 }
 
 // construction's round for the milestones [n_old, n_now) on the roadmap that exists: sample, pairs, edges, sort + CSR
 int32_t grow_round(oxhip_prm* h, PrmState& st, uint32_t n_more, uint64_t sample_limit, bool any_dead) {
-    const uint32_t n_old = h->n, knn_k = h->cfg.knn_k;
+    const uint32_t n_old = h->rm.n, knn_k = h->cfg.knn_k;
+    PrmBuildTally& t = h->grow.tally;
     OX_TRY(write_state(h, st));
-    HIP_TRY(hipEventRecord(h->ev[0], h->stream));
-    OX_TRY(sample_until(h, st, n_old + n_more, sample_limit));
-    HIP_TRY(hipEventRecord(h->ev[1], h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    h->t_ms[0] = elapsed_ms(h->ev[0], h->ev[1]);
+    OX_TRY(sample_until(h, t, st, n_old + n_more, sample_limit));
     const uint32_t n_now = st.n_milestones;
     if (n_now > n_old && n_now >= 2 && (h->thr_conn >= 0.0 || knn_k)) {   // (construct_roadmap's condition)
         if (knn_k) OX_TRY(knn_row_radii(h, st, n_old, n_now));
-        OX_TRY(find_pairs(h, st, n_old, n_now));
-        uint2* pairs = h->cand.p;
-        if (knn_k) OX_TRY(knn_select(h, st, n_old, n_now, pairs));
+        OX_TRY(find_pairs(h, t, st, n_old, n_now));
+        uint2* pairs = h->work.cand.p;
+        if (knn_k) OX_TRY(knn_select(h, t, st, n_old, n_now, pairs));
         else if (any_dead) OX_TRY(drop_dead_candidates(h, st, n_old, pairs));   // no dead milestone: exactly construction's candidates
         OX_TRY(reserve_keys(h, st));
-        OX_TRY(check_edges(h, st, pairs));
+        OX_TRY(check_edges(h, t, st, pairs));
     }
-    return build_csr(h, n_now, st.n_keys);
+    return build_csr(h, t, n_now, st.n_keys);
 }
 
 }  // namespace
@@ -1386,16 +1405,17 @@ int32_t oxhip_prm_grow_roadmap(oxhip_prm* h, const oxhip_prm_grow_config* g, uin
     if (g->n_more == 0) return fail(OXHIP_ERR_BAD_ARG, "n_more must be at least 1");
     if (g->flags & ~OXHIP_PRM_GROW_NEW_STREAM) return fail(OXHIP_ERR_BAD_ARG, "unknown flag (OXHIP_PRM_GROW_NEW_STREAM is the only one)");
     if (!h->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
-    if (h->n == 0) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "the roadmap holds no milestones: construct_roadmap() builds one");
+    if (h->rm.n == 0) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "the roadmap holds no milestones: construct_roadmap() builds one");
     const bool new_stream = (g->flags & OXHIP_PRM_GROW_NEW_STREAM) != 0;
-    if (!new_stream && !h->pos_valid)
+    if (!new_stream && !h->sampler.pos_valid)
         return fail(OXHIP_ERR_BAD_ARG, "this roadmap was not constructed by this handle, so there is no stream position to continue: "
                                        "pass OXHIP_PRM_GROW_NEW_STREAM with a stream id");
-    const uint32_t n_old = h->n;
+    const uint32_t n_old = h->rm.n;
     if ((uint64_t)n_old + g->n_more > (1ull << 26)) return fail(OXHIP_ERR_CAPACITY, "n + n_more exceeds 2^26 milestones");
     OX_TRY(select_device(h->cfg.device));
-    uint32_t n_dead = 0;
-    OX_TRY(liveness_mask(h, n_dead));
+    uint32_t n_dead = 0;   // the liveness mask: which earlier milestones are valid now, into reval.valid; n_dead = its zeros
+    OX_TRY(milestone_validity(h, &h->grow.tally.clk, kBegin, &n_dead));
+    h->grow.mask_ms = h->grow.tally.clk.ms(kBegin, kEnd);
     if (h->cfg.knn_k && n_dead)
         return fail(OXHIP_ERR_BAD_ARG, "k-nearest growth over invalid milestones is not built (" + std::to_string(n_dead) + " are invalid now)");
     if (n_old + g->n_more > h->args.cap) {
@@ -1404,39 +1424,37 @@ int32_t oxhip_prm_grow_roadmap(oxhip_prm* h, const oxhip_prm_grow_config* g, uin
         OX_TRY(grow_capacity(h, cap));
     }
     OX_TRY(keys_from_csr(h));
-    // construction's phase times are its own: this call's go to grow_ms
-    double construct_ms[6];
-    std::memcpy(construct_ms, h->t_ms, sizeof construct_ms);
-    for (double& t : h->t_ms) t = 0.0;
+    h->grow.tally.reset();   // (after the mask and the keys, which only borrow its clock)
     const uint64_t budget = g->max_samples ? g->max_samples : 4096ull * g->n_more + (1ull << 22);
-    const uint64_t sample_limit = budget > ~0ull - h->n_samples ? ~0ull : h->n_samples + budget;
+    const uint64_t sample_limit = budget > ~0ull - h->sampler.n_samples ? ~0ull : h->sampler.n_samples + budget;
     PrmState st{};
-    st.draws = new_stream ? 0 : h->pos_draws;
-    st.n_samples = h->n_samples;
+    st.draws = new_stream ? 0 : h->sampler.pos_draws;
+    st.n_samples = h->sampler.n_samples;
     st.n_milestones = n_old;
-    st.n_keys = h->n_keys;
-    st.redraw_batches = h->redraw_batches;
-    h->args.stream = new_stream ? g->stream : h->pos_stream;
+    st.n_keys = h->rm.n_keys;
+    st.redraw_batches = h->sampler.redraw_batches;
+    h->args.stream = new_stream ? g->stream : h->sampler.pos_stream;
     const int32_t status = grow_round(h, st, g->n_more, sample_limit, n_dead != 0);
     const uint64_t stream_used = h->args.stream;
     h->args.stream = h->cfg.stream;   // construct_roadmap after a setup() draws from the configured stream
-    for (int i = 0; i < 4; ++i) h->grow_ms[2 + i] = h->t_ms[i];
-    std::memcpy(h->t_ms, construct_ms, sizeof construct_ms);
+    // oxhip_prm_last_timing's candidates and oxhip_prm_knn_exact_rows count the roadmap's, not a call's: a grow adds its own to
+    // construction's, whether it succeeds or not (tests/test_gpu_prm_timing_contract.py); the phase times stay each call's own
+    h->built.candidates += h->grow.tally.candidates; h->built.exact_rows += h->grow.tally.exact_rows;
     if (status != OXHIP_OK) return status;
     *n_added = st.n_milestones - n_old;
-    *n_samples_drawn = st.n_samples - h->n_samples;
-    h->n = st.n_milestones;
-    h->n_keys = st.n_keys;
-    h->n_samples = st.n_samples;
-    h->redraw_batches = st.redraw_batches;
-    h->pos_valid = true; h->pos_stream = stream_used; h->pos_draws = st.draws;
+    *n_samples_drawn = st.n_samples - h->sampler.n_samples;
+    h->rm.n = st.n_milestones;
+    h->rm.n_keys = st.n_keys;
+    h->sampler.n_samples = st.n_samples;
+    h->sampler.redraw_batches = st.redraw_batches;
+    h->sampler.pos_valid = true; h->sampler.pos_stream = stream_used; h->sampler.pos_draws = st.draws;
     drop_derived(h);   // the host copy, the last solve's sets, the last batch, the edge weights
     return OXHIP_OK;
 }
 
 int32_t oxhip_prm_grow_last_timing(oxhip_prm* h, double* phase_ms) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
-    if (phase_ms) for (int i = 0; i < 6; ++i) phase_ms[i] = h->grow_ms[i];
+    if (phase_ms) for (int i = 0; i < 6; ++i) phase_ms[i] = i == 0 ? h->grow.mask_ms : i == 1 ? h->grow.keys_ms : h->grow.tally.ms[i - 2];
     return OXHIP_OK;
 }
 
@@ -1446,24 +1464,24 @@ int32_t oxhip_prm_grow_last_timing(oxhip_prm* h, double* phase_ms) {
 
 namespace {
 
-PrmCcBuffers cc_buffers(oxhip_prm* h) { return PrmCcBuffers{h->cc_parent.p, h->cc_label.p, h->cc_count.p, h->cc_size.p, h->cc_summary.p}; }
+PrmCcBuffers cc_buffers(oxhip_prm* h) { return PrmCcBuffers{h->cc.parent.p, h->cc.label.p, h->cc.count.p, h->cc.size.p, h->cc.summary.p}; }
 
 // the union-find's arrays for the roadmap as it stands: before any timed region (hipMalloc is a blocking call)
 int32_t reserve_components(oxhip_prm* h) {
-    const size_t n = h->n;
-    HIP_TRY(h->cc_parent.reserve(n)); HIP_TRY(h->cc_label.reserve(n)); HIP_TRY(h->cc_count.reserve(n)); HIP_TRY(h->cc_size.reserve(n));
-    HIP_TRY(h->cc_summary.reserve(kCcSummaryWords));
+    const size_t n = h->rm.n;
+    HIP_TRY(h->cc.parent.reserve(n)); HIP_TRY(h->cc.label.reserve(n)); HIP_TRY(h->cc.count.reserve(n)); HIP_TRY(h->cc.size.reserve(n));
+    HIP_TRY(h->cc.summary.reserve(kCcSummaryWords));
     return OXHIP_OK;
 }
 
-// labels, sizes and summary of the CSR into the cc_ buffers; alive (device, [n], or null): prune's stage-1 survivors.  Records
-// the events first .. first + 3 around its three phases; the kept labels are the whole roadmap's only without a mask.
-int32_t components_of(oxhip_prm* h, const uint8_t* alive, uint32_t first) {
-    h->cc_valid = false;
-    HIP_TRY(hipEventRecord(h->cev[first], h->stream));
-    launch_prm_components(h->offsets.p, h->nbrs.p, alive, h->n, h->n_keys, cc_buffers(h), h->cev[first + 1], h->cev[first + 2], h->stream);
+// labels, sizes and summary of the CSR into cc's buffers; alive (device, [n], or null): prune's stage-1 survivors.  Marks the caller's
+// clock around its three phases: first (begin), + 1 (hooked), + 2 (flat), + 3 (end); the kept labels are the whole roadmap's only without a mask.
+int32_t components_of(oxhip_prm* h, const uint8_t* alive, PhaseClock& clk, int first) {
+    h->cc.valid = false;
+    HIP_TRY(clk.mark(first, h->stream));
+    launch_prm_components(h->rm.offsets.p, h->rm.nbrs.p, alive, h->rm.n, h->rm.n_keys, cc_buffers(h), clk.event(first + 1), clk.event(first + 2), h->stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->cev[first + 3], h->stream));
+    HIP_TRY(clk.mark(first + 3, h->stream));
     return OXHIP_OK;
 }
 
@@ -1483,73 +1501,70 @@ int32_t validate_prune_args(const oxhip_prm* h, const oxhip_prm_prune_config* c,
 
 // every buffer of a prune before its timed region: masks, scans, the second buffers the compaction writes
 int32_t reserve_prune(oxhip_prm* h, uint32_t flags, size_t& tmp_bytes) {
-    const size_t n = h->n, ne = h->n_keys, dim = h->cfg.dim, cap = h->args.cap;
-    HIP_TRY(h->pr_keep.reserve(n)); HIP_TRY(h->pr_pos.reserve(n)); HIP_TRY(h->pr_index.reserve(n)); HIP_TRY(h->pr_kept.reserve(2));
-    if (flags & OXHIP_PRM_PRUNE_MASK) HIP_TRY(h->pr_mask.reserve(n));
-    if (flags & OXHIP_PRM_PRUNE_INVALID) { HIP_TRY(h->rv_valid.reserve(n)); HIP_TRY(h->rv_counters.reserve(kRevalCounters)); }
+    const size_t n = h->rm.n, ne = h->rm.n_keys, dim = h->cfg.dim, cap = h->args.cap;
+    HIP_TRY(h->prune.keep.reserve(n)); HIP_TRY(h->prune.pos.reserve(n)); HIP_TRY(h->prune.index.reserve(n)); HIP_TRY(h->prune.kept.reserve(2));
+    if (flags & OXHIP_PRM_PRUNE_MASK) HIP_TRY(h->prune.mask.reserve(n));
+    if (flags & OXHIP_PRM_PRUNE_INVALID) { HIP_TRY(h->reval.valid.reserve(n)); HIP_TRY(h->reval.counters.reserve(kRevalCounters)); }   // (milestone_validity's)
     if (flags & (OXHIP_PRM_PRUNE_MIN_SIZE | OXHIP_PRM_PRUNE_LARGEST)) OX_TRY(reserve_components(h));
-    HIP_TRY(h->pr_ekeep.reserve(std::max<size_t>(ne, 1))); HIP_TRY(h->pr_epos.reserve(std::max<size_t>(ne, 1)));
-    HIP_TRY(h->pr_nbrs.reserve(std::max<size_t>(ne, 1)));
-    if (h->pr_offsets.n != cap + 1) HIP_TRY(h->pr_offsets.alloc(cap + 1));   // swapped with offsets: the capacity's size exactly
-    if (h->pr_ms.n != dim * cap) HIP_TRY(h->pr_ms.alloc(dim * cap));
-    if (!h->so3 && h->pr_ms32.n != dim * cap) HIP_TRY(h->pr_ms32.alloc(dim * cap));
+    HIP_TRY(h->prune.ekeep.reserve(std::max<size_t>(ne, 1))); HIP_TRY(h->prune.epos.reserve(std::max<size_t>(ne, 1)));
+    HIP_TRY(h->spare.nbrs.reserve(std::max<size_t>(ne, 1)));
+    if (h->spare.offsets.n != cap + 1) HIP_TRY(h->spare.offsets.alloc(cap + 1));   // swapped with offsets: the capacity's size exactly
+    if (h->spare.ms.n != dim * cap) HIP_TRY(h->spare.ms.alloc(dim * cap));
+    if (!h->so3 && h->spare.ms32.n != dim * cap) HIP_TRY(h->spare.ms32.alloc(dim * cap));
     size_t a = 0, b = 0;
-    HIP_TRY(prm_reval_scan(nullptr, a, h->pr_keep.p, h->pr_pos.p, (uint32_t)n, h->stream));
-    if (ne) HIP_TRY(prm_reval_scan(nullptr, b, h->pr_ekeep.p, h->pr_epos.p, (uint32_t)ne, h->stream));
+    HIP_TRY(prm_reval_scan(nullptr, a, h->prune.keep.p, h->prune.pos.p, (uint32_t)n, h->stream));
+    if (ne) HIP_TRY(prm_reval_scan(nullptr, b, h->prune.ekeep.p, h->prune.epos.p, (uint32_t)ne, h->stream));
     tmp_bytes = std::max(a, b);
-    HIP_TRY(h->rv_tmp.reserve(tmp_bytes));
+    HIP_TRY(h->reval.tmp.reserve(tmp_bytes));
     return OXHIP_OK;
 }
 
-// stage 1 into pr_keep: INVALID by the re-check's own milestone kernel (as liveness_mask), MASK from the caller's bytes (pr_mask)
+// stage 1 into prune.keep: INVALID by milestone_validity (no mark, no read-back: nothing waits inside the masks phase), MASK from prune.mask
 int32_t prune_stage1_mask(oxhip_prm* h, uint32_t flags) {
     const uint8_t *valid = nullptr, *mask = nullptr;
     if (flags & OXHIP_PRM_PRUNE_INVALID) {
-        HIP_TRY(hipMemsetAsync(h->rv_counters.p, 0, kRevalCounters * sizeof(uint32_t), h->stream));
-        launch_prm_reval_valid(h->so3, h->dp, h->ms.p, h->n, h->rv_valid.p, h->rv_counters.p, h->stream);
-        HIP_TRY(hipGetLastError());
-        valid = h->rv_valid.p;
+        OX_TRY(milestone_validity(h, nullptr, 0, nullptr));
+        valid = h->reval.valid.p;
     }
-    if (flags & OXHIP_PRM_PRUNE_MASK) mask = h->pr_mask.p;
-    launch_prm_prune_stage1(valid, mask, h->n, h->pr_keep.p, h->pr_kept.p, h->stream);
+    if (flags & OXHIP_PRM_PRUNE_MASK) mask = h->prune.mask.p;
+    launch_prm_prune_stage1(valid, mask, h->rm.n, h->prune.keep.p, h->prune.kept.p, h->stream);
     HIP_TRY(hipGetLastError());
     return OXHIP_OK;
 }
 
-// stage 2 on the components of the stage-1 survivors (cc_ buffers): MIN_SIZE and LARGEST into pr_keep
+// stage 2 on the components of the stage-1 survivors (cc's buffers): MIN_SIZE and LARGEST into prune.keep
 int32_t prune_stage2_mask(oxhip_prm* h, const oxhip_prm_prune_config* c) {
-    launch_prm_prune_stage2(cc_buffers(h), h->n, (c->flags & OXHIP_PRM_PRUNE_MIN_SIZE) ? c->min_size : 0u,
-                            (c->flags & OXHIP_PRM_PRUNE_LARGEST) != 0, h->pr_keep.p, h->pr_kept.p + 1, h->stream);
+    launch_prm_prune_stage2(cc_buffers(h), h->rm.n, (c->flags & OXHIP_PRM_PRUNE_MIN_SIZE) ? c->min_size : 0u,
+                            (c->flags & OXHIP_PRM_PRUNE_LARGEST) != 0, h->prune.keep.p, h->prune.kept.p + 1, h->stream);
     HIP_TRY(hipGetLastError());
     return OXHIP_OK;
 }
 
-// the roadmap of the n_kept milestones of pr_keep, into the second buffers; the handle takes them when everything has run
+// the roadmap of the n_kept milestones of prune.keep, into the spare roadmap's buffers; the handle takes them when everything has run
 int32_t compact_roadmap(oxhip_prm* h, uint32_t n_kept, size_t tmp_bytes, int32_t* new_index, uint32_t& n_entries_new) {
-    const uint32_t n = h->n, ne = h->n_keys, dim = h->cfg.dim;
-    HIP_TRY(hipEventRecord(h->cev[6], h->stream));
-    HIP_TRY(prm_reval_scan(h->rv_tmp.p, tmp_bytes, h->pr_keep.p, h->pr_pos.p, n, h->stream));
-    launch_prm_prune_flags(h->offsets.p, h->nbrs.p, h->pr_keep.p, h->pr_pos.p, n, ne, h->pr_index.p, h->pr_ekeep.p, h->stream);
+    const uint32_t n = h->rm.n, ne = h->rm.n_keys, dim = h->cfg.dim;
+    PhaseClock& clk = h->prune.clk;
+    HIP_TRY(clk.mark(kPrScanBegin, h->stream));
+    HIP_TRY(prm_reval_scan(h->reval.tmp.p, tmp_bytes, h->prune.keep.p, h->prune.pos.p, n, h->stream));
+    launch_prm_prune_flags(h->rm.offsets.p, h->rm.nbrs.p, h->prune.keep.p, h->prune.pos.p, n, ne, h->prune.index.p, h->prune.ekeep.p, h->stream);
     HIP_TRY(hipGetLastError());
-    if (ne) HIP_TRY(prm_reval_scan(h->rv_tmp.p, tmp_bytes, h->pr_ekeep.p, h->pr_epos.p, ne, h->stream));
-    HIP_TRY(hipEventRecord(h->cev[7], h->stream));
-    if (ne) launch_prm_prune_entries(h->offsets.p, h->nbrs.p, h->pr_ekeep.p, h->pr_epos.p, h->pr_index.p, n, ne, n_kept, h->pr_offsets.p,
-                                     h->pr_nbrs.p, h->stream);
-    else HIP_TRY(hipMemsetAsync(h->pr_offsets.p, 0, ((size_t)n_kept + 1) * sizeof(uint32_t), h->stream));
+    if (ne) HIP_TRY(prm_reval_scan(h->reval.tmp.p, tmp_bytes, h->prune.ekeep.p, h->prune.epos.p, ne, h->stream));
+    HIP_TRY(clk.mark(kPrScanEnd, h->stream));
+    if (ne) launch_prm_prune_entries(h->rm.offsets.p, h->rm.nbrs.p, h->prune.ekeep.p, h->prune.epos.p, h->prune.index.p, n, ne, n_kept, h->spare.offsets.p,
+                                     h->spare.nbrs.p, h->stream);
+    else HIP_TRY(hipMemsetAsync(h->spare.offsets.p, 0, ((size_t)n_kept + 1) * sizeof(uint32_t), h->stream));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->cev[8], h->stream));
-    launch_prm_prune_states(h->ms.p, h->so3 ? nullptr : h->ms32.p, h->pr_index.p, n, dim, h->pr_ms.p, h->so3 ? nullptr : h->pr_ms32.p, h->stream);
+    HIP_TRY(clk.mark(kPrEntriesEnd, h->stream));
+    launch_prm_prune_states(h->rm.ms.p, h->so3 ? nullptr : h->rm.ms32.p, h->prune.index.p, n, dim, h->spare.ms.p, h->so3 ? nullptr : h->spare.ms32.p, h->stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->cev[9], h->stream));
+    HIP_TRY(clk.mark(kPrStatesEnd, h->stream));
     n_entries_new = 0;
-    if (ne) HIP_TRY(hipMemcpyAsync(&n_entries_new, h->pr_offsets.p + n_kept, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    if (new_index) HIP_TRY(hipMemcpyAsync(new_index, h->pr_index.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (ne) HIP_TRY(hipMemcpyAsync(&n_entries_new, h->spare.offsets.p + n_kept, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (new_index) HIP_TRY(hipMemcpyAsync(new_index, h->prune.index.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    std::swap(h->offsets.p, h->pr_offsets.p); std::swap(h->offsets.n, h->pr_offsets.n);
-    std::swap(h->nbrs.p, h->pr_nbrs.p); std::swap(h->nbrs.n, h->pr_nbrs.n);
-    std::swap(h->ms.p, h->pr_ms.p); std::swap(h->ms.n, h->pr_ms.n);
-    if (!h->so3) { std::swap(h->ms32.p, h->pr_ms32.p); std::swap(h->ms32.n, h->pr_ms32.n); }
-    h->args.ms = h->ms.p; h->args.ms32 = h->ms32.p;
+    h->rm.offsets.swap(h->spare.offsets); h->rm.nbrs.swap(h->spare.nbrs); h->rm.ms.swap(h->spare.ms);
+    if (!h->so3) h->rm.ms32.swap(h->spare.ms32);
+    bind_roadmap(h);
     return OXHIP_OK;
 }
 
@@ -1561,27 +1576,27 @@ int32_t oxhip_prm_components(oxhip_prm* h, uint32_t* label, uint32_t* size, uint
                              uint32_t* largest_size) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
     if (!h->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
-    if (h->n == 0) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "the roadmap holds no milestones");
-    if ((label || size) && cap < h->n) return fail(OXHIP_ERR_CAPACITY, "label / size buffers too small");
+    if (h->rm.n == 0) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "the roadmap holds no milestones");
+    if ((label || size) && cap < h->rm.n) return fail(OXHIP_ERR_CAPACITY, "label / size buffers too small");
     OX_TRY(select_device(h->cfg.device));
-    const uint32_t n = h->n;
-    const bool compute = !h->cc_valid;
+    const uint32_t n = h->rm.n;
+    const bool compute = !h->cc.valid;
     if (compute) {
         OX_TRY(reserve_components(h));
-        OX_TRY(components_of(h, nullptr, 0));
+        OX_TRY(components_of(h, nullptr, h->cc.clk, kCcBegin));
     }
     unsigned long long summary[kCcSummaryWords] = {};
-    HIP_TRY(hipEventRecord(h->cev[4], h->stream));
-    HIP_TRY(hipMemcpyAsync(summary, h->cc_summary.p, sizeof summary, hipMemcpyDeviceToHost, h->stream));
-    if (label) HIP_TRY(hipMemcpyAsync(label, h->cc_label.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    if (size) HIP_TRY(hipMemcpyAsync(size, h->cc_size.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipEventRecord(h->cev[5], h->stream));
+    HIP_TRY(h->cc.clk.mark(kCcCopyBegin, h->stream));
+    HIP_TRY(hipMemcpyAsync(summary, h->cc.summary.p, sizeof summary, hipMemcpyDeviceToHost, h->stream));
+    if (label) HIP_TRY(hipMemcpyAsync(label, h->cc.label.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (size) HIP_TRY(hipMemcpyAsync(size, h->cc.size.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h->cc.clk.mark(kCcCopyEnd, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    h->cc_ms[0] = compute ? elapsed_ms(h->cev[0], h->cev[1]) : 0.0;
-    h->cc_ms[1] = compute ? elapsed_ms(h->cev[1], h->cev[2]) : 0.0;
-    h->cc_ms[2] = compute ? elapsed_ms(h->cev[2], h->cev[3]) : 0.0;
-    h->cc_ms[3] = elapsed_ms(h->cev[4], h->cev[5]);
-    h->cc_valid = true;
+    h->cc.ms[0] = compute ? h->cc.clk.ms(kCcBegin, kCcHooked) : 0.0;
+    h->cc.ms[1] = compute ? h->cc.clk.ms(kCcHooked, kCcFlat) : 0.0;
+    h->cc.ms[2] = compute ? h->cc.clk.ms(kCcFlat, kCcEnd) : 0.0;
+    h->cc.ms[3] = h->cc.clk.ms(kCcCopyBegin, kCcCopyEnd);
+    h->cc.valid = true;
     if (n_components) *n_components = (uint32_t)summary[kCcRoots];
     if (largest_label) *largest_label = 0xFFFFFFFFu - (uint32_t)summary[kCcBest];
     if (largest_size) *largest_size = (uint32_t)(summary[kCcBest] >> 32);
@@ -1590,7 +1605,7 @@ int32_t oxhip_prm_components(oxhip_prm* h, uint32_t* label, uint32_t* size, uint
 
 int32_t oxhip_prm_components_last_timing(oxhip_prm* h, double* phase_ms, uint32_t* launches) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
-    if (phase_ms) for (int i = 0; i < 4; ++i) phase_ms[i] = h->cc_ms[i];
+    if (phase_ms) for (int i = 0; i < 4; ++i) phase_ms[i] = h->cc.ms[i];
     if (launches) *launches = kCcLaunches;
     return OXHIP_OK;
 }
@@ -1599,37 +1614,37 @@ int32_t oxhip_prm_prune(oxhip_prm* h, const oxhip_prm_prune_config* c, const uin
                         uint64_t* n_removed_entries) {
     OX_TRY(validate_prune_args(h, c, keep));
     if (!h->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
-    if (h->n == 0) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "the roadmap holds no milestones");
+    if (h->rm.n == 0) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "the roadmap holds no milestones");
     OX_TRY(select_device(h->cfg.device));
-    const uint32_t n = h->n, n_old = h->n_keys;
+    const uint32_t n = h->rm.n, n_old = h->rm.n_keys;
     const bool stage2 = (c->flags & (OXHIP_PRM_PRUNE_MIN_SIZE | OXHIP_PRM_PRUNE_LARGEST)) != 0;
     size_t tmp_bytes = 0;
     OX_TRY(reserve_prune(h, c->flags, tmp_bytes));
-    if (c->flags & OXHIP_PRM_PRUNE_MASK) HIP_TRY(hipMemcpyAsync(h->pr_mask.p, keep, n, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(h->pr_kept.p, 0, 2 * sizeof(uint32_t), h->stream));
-    HIP_TRY(hipEventRecord(h->cev[4], h->stream));
+    if (c->flags & OXHIP_PRM_PRUNE_MASK) HIP_TRY(hipMemcpyAsync(h->prune.mask.p, keep, n, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(h->prune.kept.p, 0, 2 * sizeof(uint32_t), h->stream));
+    PhaseClock& clk = h->prune.clk;
+    HIP_TRY(clk.mark(kPrBegin, h->stream));
     OX_TRY(prune_stage1_mask(h, c->flags));
     if (stage2) {   // (the labels of the stage-1 survivors are not the roadmap's: components_of forgets the kept ones)
-        OX_TRY(components_of(h, h->pr_keep.p, 0));
+        OX_TRY(components_of(h, h->prune.keep.p, clk, kPrCcBegin));
         OX_TRY(prune_stage2_mask(h, c));
     }
-    HIP_TRY(hipEventRecord(h->cev[5], h->stream));
+    HIP_TRY(clk.mark(kPrMasksEnd, h->stream));
     uint32_t kept[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(kept, h->pr_kept.p, sizeof kept, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(kept, h->prune.kept.p, sizeof kept, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     const uint32_t n_new = stage2 ? kept[1] : kept[0];
     if (n_new == 0) return fail(OXHIP_ERR_BAD_ARG, "would keep no milestone");   // only workspace was written so far
     uint32_t n_entries_new = 0;
     OX_TRY(compact_roadmap(h, n_new, tmp_bytes, new_index, n_entries_new));
-    // masks = stage 1 and stage 2 around the components; components = the union-find's three phases
-    const double comp = stage2 ? elapsed_ms(h->cev[0], h->cev[3]) : 0.0;
-    h->prune_ms[0] = stage2 ? elapsed_ms(h->cev[4], h->cev[0]) + elapsed_ms(h->cev[3], h->cev[5]) : elapsed_ms(h->cev[4], h->cev[5]);
-    h->prune_ms[1] = comp;
-    h->prune_ms[2] = elapsed_ms(h->cev[6], h->cev[7]);
-    h->prune_ms[3] = elapsed_ms(h->cev[7], h->cev[8]);
-    h->prune_ms[4] = elapsed_ms(h->cev[8], h->cev[9]);
-    h->n = n_new;
-    h->n_keys = n_entries_new;
+    // masks = begin -> components begin, plus components end -> masks end; components = the union-find's three phases
+    h->prune.ms[0] = stage2 ? clk.ms(kPrBegin, kPrCcBegin) + clk.ms(kPrCcEnd, kPrMasksEnd) : clk.ms(kPrBegin, kPrMasksEnd);
+    h->prune.ms[1] = stage2 ? clk.ms(kPrCcBegin, kPrCcEnd) : 0.0;
+    h->prune.ms[2] = clk.ms(kPrScanBegin, kPrScanEnd);
+    h->prune.ms[3] = clk.ms(kPrScanEnd, kPrEntriesEnd);
+    h->prune.ms[4] = clk.ms(kPrEntriesEnd, kPrStatesEnd);
+    h->rm.n = n_new;
+    h->rm.n_keys = n_entries_new;
     drop_derived(h);   // the host copy, the last solve's sets, the last batch, the edge weights, the kept component labels
     if (n_kept) *n_kept = n_new;
     if (n_removed_entries) *n_removed_entries = (uint64_t)n_old - n_entries_new;
@@ -1638,7 +1653,7 @@ int32_t oxhip_prm_prune(oxhip_prm* h, const oxhip_prm_prune_config* c, const uin
 
 int32_t oxhip_prm_prune_last_timing(oxhip_prm* h, double* phase_ms) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
-    if (phase_ms) for (int i = 0; i < 5; ++i) phase_ms[i] = h->prune_ms[i];
+    if (phase_ms) for (int i = 0; i < 5; ++i) phase_ms[i] = h->prune.ms[i];
     return OXHIP_OK;
 }
 
