@@ -292,7 +292,8 @@ int32_t oxhip_rrt_batch_set_tree(oxhip_rrt_batch* b, uint32_t problem, const dou
  *   What set_tree drops is dropped for all problems: extracted / simplified paths, the binary32 shadows, the cell grids.  The
  *     next launch rebuilds them; this call rebuilds none.
  * n_removed[P], goal_lost[P]: may be NULL.  RRTConnect and RRT* batches: OXHIP_ERR_BAD_ARG (RRT* would need its costs and wiring
- * cursors pruned as well); SE(2) / SE(3) are RRTConnect only.  Without setup(): OXHIP_ERR_PLANNER_UNINITIALISED. */
+ * cursors pruned as well); SE(2) / SE(3) are RRTConnect only.  Without setup(): OXHIP_ERR_PLANNER_UNINITIALISED.  A refused call
+ * changes nothing: extracted and simplified paths stay. */
 int32_t oxhip_rrt_batch_revalidate_trees(oxhip_rrt_batch* b, uint32_t* n_removed /*[P] or NULL*/,
                                          uint8_t* goal_lost /*[P] or NULL*/);
 /* new_index and edge_ok (edge_ok[0] = 1) of the last revalidate_trees for one problem, n_before entries each: a test hook, and

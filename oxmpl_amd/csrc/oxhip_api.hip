@@ -1492,12 +1492,13 @@ int32_t oxhip_interpolate_batch(int32_t device, uint32_t dim, const double* from
 // ------------------------------------------------------------------ re-checking the trees (rrt_revalidate.hip)
 int32_t oxhip_rrt_batch_revalidate_trees(oxhip_rrt_batch* b, uint32_t* n_removed, uint8_t* goal_lost) {
     if (!b) return fail(OXHIP_ERR_BAD_ARG, "null batch");
-    drop_paths(b);   // (and the last call's map)
     OX_TRY(setup_done(b));
     if (b->cfg.planner == OXHIP_PLANNER_RRT_CONNECT)
         return fail(OXHIP_ERR_BAD_ARG, "revalidate_trees is for the RRT planner (an RRTConnect batch keeps two trees and their connection)");
     if (b->cfg.planner != OXHIP_PLANNER_RRT)
         return fail(OXHIP_ERR_BAD_ARG, "revalidate_trees is for the RRT planner (an RRT* batch would need its costs and wiring cursors pruned as well)");
+    // below the refusals: a call refused for its planner leaves the batch's extracted and simplified paths as they were
+    drop_paths(b);   // (and the last call's map)
     OX_TRY(select_device(b->cfg.device));
     if (space_of(b).midpoint_filter) OX_TRY(refresh_filter(b));   // as solve does: the next launch reads them
     const uint32_t P = b->cfg.n_problems, cap = b->dp.cap;
