@@ -53,77 +53,190 @@ void oxhip_stream_release(int device, hipStream_t s) {
 }
 }  // namespace oxhip
 
+// ------------------------------------------------------------------ the handle, in parts
+// Each part owns its buffers, its flags and -- where it is a service with phase times -- those times and its clock.  bind() is the
+// one place that copies a part's device pointers (and counts) into DevParams; it is called where the part's buffers are allocated
+// or replaced.  (Cells carves one arena: alloc_cells computes its pointers and stores them at the same place.)
+struct Trees {                        // what the planners grow
+    DevBuf<double> tree, tree_b;      // [P][dim][cap]; tree_b: RRTConnect's goal trees
+    DevBuf<int32_t> parent, parent_b;
+    DevBuf<uint8_t> skip;
+    DevBuf<ProblemState> state;
+    ProblemState* h_states = nullptr;   // pinned: the state array as the host reads it after every launch
+    ~Trees() { if (h_states) (void)hipHostFree(h_states); }
+    void bind(DevParams& dp) const {
+        dp.tree = tree.p; dp.parent = parent.p; dp.skip = skip.p; dp.state = state.p;
+        dp.tree_b = tree_b.p; dp.parent_b = parent_b.p;
+    }
+};
+struct Goals {
+    DevBuf<double> goal_c, goal_thr, goal_r;
+    std::vector<double> starts;       // host copy, [P][dim]
+    void bind(DevParams& dp) const { dp.goal_c = goal_c.p; dp.goal_thr = goal_thr.p; dp.goal_r = goal_r.p; }
+};
+struct Obstacles {
+    uint32_t n_spheres = 0, n_boxes = 0, n_segs = 0;
+    DevBuf<double> sph_c, sph_thr, box_lo, box_hi;
+    std::vector<double> sph_centres, sph_radii;   // host copies (AoS) for the filter thresholds
+    DevBuf<double> sph_r;             // the radii as given: uploaded by upload_radii alone, when set_spheres changed them
+    bool radii_dirty = true;
+    DevBuf<double> segs;              // SE(2): segment soup
+    DevBuf<uint16_t> seg_grid;        // ... and the cells' segment lists (rrt_connect_se2.hip, seg_grid_kernel)
+    DevBuf<double> se3_body;          // SE(3): the body's spheres, SoA [4][kSe3MaxBody] (rrt_connect_se3.hip)
+    Se3Args se3{};
+    // the filters refresh_filter derives from spheres, starts and bounds before a launch reads them
+    bool filt_dirty = true;
+    DevBuf<double> sph_filt;          // the midpoint filter's thresholds
+    DevBuf<uint64_t> conn_grid;       // RRTConnect in R^2 / R^3: the spheres that reach each cell of the bounds' grid (rrt_connect.hip)
+    DevBuf<double> conn_filt;
+    // (the grids in use -- dp.seg_grid, dp.sph_grid, dp.star_sph_grid -- are decisions of the calls that build them, not bindings)
+    void bind(DevParams& dp) {
+        dp.n_spheres = n_spheres; dp.sph_c = sph_c.p; dp.sph_thr = sph_thr.p; dp.sph_r = sph_r.p; dp.sph_filt = sph_filt.p;
+        dp.n_boxes = n_boxes; dp.box_lo = box_lo.p; dp.box_hi = box_hi.p;
+        dp.n_segs = n_segs; dp.segs = segs.p;
+        se3.body = se3_body.p;
+    }
+};
+// rrt_cells.hip: cell blocks, flat lists of small trees, node-major coordinates, grid descriptors, accumulators and part
+// positions of split frozen launches, the sphere mask grid -- ONE allocation (a hipMalloc costs more than a small kernel:
+// the one-problem Planner::solve pays for every one of them), carved at 256-byte boundaries
+struct Cells {
+    DevBuf<uint8_t> arena;
+    CellMeta* meta = nullptr;
+    uint64_t* sph_grid = nullptr;
+    uint64_t* star_grid = nullptr;    // RRT*'s edge checks: the mask grid for motions up to search_radius long
+    int32_t board_last = -1;          // parity of the last frozen cells launch (its progress board: get_stamps), -1: none yet
+};
+struct Shadow {                       // stream / RRT* kernels: fl32 shadow of the tree
+    DevBuf<float> tree32;
+    DevBuf<uint32_t> state;           // [P][2]
+    void bind(DevParams& dp) const { dp.tree32 = tree32.p; dp.shadow_state = state.p; }
+};
+struct Solve {
+    uint32_t kernel_kind = OXHIP_KERNEL_STREAM;   // the kind create() resolved (KERNEL_AUTO among them): every launch uses it, last_timing reports it
+    double last_kernel_ms = 0.0;
+    uint32_t last_launches = 0;
+    enum { kBegin, kEnd };
+    PhaseClock clk{2};                // made with the handle: create() has the device current
+};
+// path_simplify.hip: the batch's solution paths as extract_paths / simplify_paths left them.  They belong to the trees as they
+// stood at that call (drop_derived, below).
+struct Paths {
+    bool ok = false, simp_ok = false;
+    std::vector<uint64_t> off;                    // [P + 1] host copy of the row offsets
+    std::vector<uint32_t> h_len;                  // [P]
+    DevBuf<uint64_t> d_off, sp_woff, sp_bits, sp_checks;
+    DevBuf<uint32_t> len, len_a, sp_par, sp_idx, sp_len;
+    DevBuf<double> rows, sp_cost, sp_raw, sp_simp;
+    double ms[3] = {0.0, 0.0, 0.0};               // extraction kernels, pair matrix, DP of the last calls
+    uint32_t rounds = 0;
+    enum { kBegin, kMid, kEnd };                  // extract_paths: kBegin .. kMid per kernel; simplify_paths: pairs, then the DP
+    std::unique_ptr<PhaseClock> clk;              // made by the first call that times itself and kept, as the workspace is
+    void drop() { ok = simp_ok = false; }         // extract_paths: the paths start over; the trees, and a map of theirs, stay
+};
+// rrt_revalidate.hip: the workspace of revalidate_trees (allocated on first use and kept) and the map of its last call, which
+// belongs to the trees as that call left them (drop_derived, below)
+struct Reval {
+    bool ok = false;
+    DevBuf<uint8_t> edge_ok, alive, goal_lost, stage;
+    DevBuf<int32_t> new_index, jump;
+    DevBuf<uint32_t> n_after, n_removed;
+    std::vector<uint32_t> n_before;               // [P] tree sizes before the last call
+    double ms[4] = {0.0, 0.0, 0.0, 0.0};          // edge checks, survival, scan, compaction + remap + skip flags
+    enum { kBegin, kEdgesEnd, kSurviveEnd, kScanEnd, kCompactEnd };   // ms[i]: mark i to mark i + 1
+    std::unique_ptr<PhaseClock> clk;              // as Paths::clk
+};
+struct Star {                         // RRT*
+    DevBuf<double> cost;              // cost-to-come
+    DevBuf<uint64_t> wire_chk;        // W of the checksum
+    DevBuf<uint32_t> nb_idx;          // the one-kernel design's neighbour scratch (rrt_star.hip)
+    DevBuf<double> nb_dist;
+    // the decoupled design (rrt_star_wire.hip): geometry by rrt_lanes.hip / rrt_cells.hip, then the wiring kernels
+    struct Wiring {
+        bool on = false;              // this design runs (else rrt_star.hip)
+        bool geo_cells = false;       // ... its geometry by rrt_cells.hip
+        DevBuf<StarEntry> pool;
+        DevBuf<StarChunk> chunks;
+        DevBuf<uint32_t> chunk_cursor, wired, nbr_cnt, nbr_off, nbr_take, nbr_total;
+        DevBuf<double> d_near, star_filt;
+        PooledStream stream2;         // the wiring of a segment runs here while the next segment's pairs are checked on the handle's stream
+        hipEvent_t ev_seg[8] = {}, ev_join = nullptr;
+        void release() {              // the buffers create() allocates for it (KERNEL_AUTO's fallback to the one-kernel design)
+            pool.release(); chunks.release(); chunk_cursor.release(); wired.release(); nbr_take.release();
+            nbr_total.release(); nbr_cnt.release(); nbr_off.release(); d_near.release();
+        }
+        ~Wiring() {
+            stream2.close();
+            for (hipEvent_t ev : ev_seg) if (ev) (void)hipEventDestroy(ev);
+            if (ev_join) (void)hipEventDestroy(ev_join);
+        }
+    } wiring;
+    void bind(DevParams& dp) const {
+        dp.cost = cost.p; dp.wire_chk = wire_chk.p; dp.nb_idx = nb_idx.p; dp.nb_dist = nb_dist.p;
+        dp.wired = wiring.wired.p; dp.nbr_cnt = wiring.nbr_cnt.p; dp.nbr_off = wiring.nbr_off.p; dp.nbr_take = wiring.nbr_take.p;
+        dp.nbr_total = wiring.nbr_total.p; dp.d_near = wiring.d_near.p; dp.pool = wiring.pool.p;
+        dp.chunks = wiring.chunks.p; dp.chunk_cursor = wiring.chunk_cursor.p;
+    }
+};
+
+// destroy() makes the device current and drains the stream; the members then go in reverse order of declaration, which is the
+// order the resources need: the second stream released, the events destroyed, the stream released, the pinned memory freed, each
+// part's buffers with it.
 struct oxhip_rrt_batch {
     oxhip_rrt_config cfg{};
     DevParams dp{};
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    DevBuf<double> tree, goal_c, goal_thr, goal_r, sph_c, sph_thr, sph_filt, box_lo, box_hi;
-    std::vector<double> sph_centres, sph_radii;  // host copies (AoS) for the filter thresholds
-    bool filt_dirty = true;
-    // rrt_cells.hip: cell blocks, flat lists of small trees, node-major coordinates, grid descriptors, accumulators and part
-    // positions of split frozen launches, the sphere mask grid -- ONE allocation (a hipMalloc costs more than a small kernel:
-    // the one-problem Planner::solve pays for every one of them), carved at 256-byte boundaries
-    DevBuf<uint8_t> cell_arena;
-    CellMeta* cell_meta_p = nullptr;
-    int32_t cells_board_last = -1;  // parity of the last frozen cells launch (its progress board: get_stamps), -1: none yet
-    uint64_t* sph_grid_p = nullptr;
-    uint64_t* star_grid_p = nullptr;   // RRT*'s edge checks: the mask grid for motions up to search_radius long
-    DevBuf<double> star_filt;
-    ProblemState* h_states = nullptr;   // pinned: the state array as the host reads it after every launch
-    DevBuf<double> tree_b;   // RRTConnect goal trees
-    DevBuf<double> segs;            // SE(2): segment soup
-    DevBuf<uint16_t> seg_grid;      // ... and the cells' segment lists (rrt_connect_se2.hip, seg_grid_kernel)
-    DevBuf<double> se3_body;        // SE(3): the body's spheres, SoA [4][kSe3MaxBody] (rrt_connect_se3.hip)
-    Se3Args se3{};
-    DevBuf<uint64_t> conn_grid;     // RRTConnect in R^2 / R^3: the spheres that reach each cell of the bounds' grid (rrt_connect.hip)
-    DevBuf<double> conn_filt;
-    DevBuf<double> cost, nb_dist;   // RRT*: cost-to-come, neighbour scratch
-    // RRT*: W of the checksum; the decoupled design's buffers (rrt_star_wire.hip)
-    DevBuf<uint64_t> wire_chk;
-    DevBuf<uint32_t> wired, nbr_cnt, nbr_off, nbr_take, nbr_total;
-    DevBuf<double> d_near, sph_r;
-    DevBuf<StarEntry> pool;
-    DevBuf<StarChunk> chunks;
-    DevBuf<uint32_t> chunk_cursor;
-    bool star_wired = false;        // RRT*: geometry by rrt_lanes.hip / rrt_cells.hip + the wiring kernels (else rrt_star.hip)
-    bool star_geo_cells = false;    // ... by rrt_cells.hip
-    hipStream_t stream2 = nullptr;  // RRT*, decoupled: the wiring of a segment runs here while the next segment's pairs are checked on `stream`
-    hipEvent_t ev_seg[8] = {}, ev_join = nullptr;
-    DevBuf<float> tree32;           // stream / RRT* kernels: fl32 shadow of the tree
-    DevBuf<uint32_t> shadow_state;  // [P][2]
-    DevBuf<uint32_t> nb_idx;
-    DevBuf<int32_t> parent;
-    DevBuf<int32_t> parent_b;
-    DevBuf<uint8_t> skip;
-    DevBuf<ProblemState> state;
-    DevBuf<uint64_t> dbg;
-    std::vector<double> starts;  // host copy, [P][dim]
     bool is_setup = false;
-    double last_kernel_ms = 0.0;
-    uint32_t last_launches = 0;
-    uint32_t kernel_kind = OXHIP_KERNEL_STREAM;   // the kind a launch uses (KERNEL_AUTO: resolved per launch, see solve)
-    uint32_t last_kind = OXHIP_KERNEL_STREAM;     // what the last launch ran
-    // path_simplify.hip: the batch's solution paths as extract_paths / simplify_paths left them.  They belong to the trees as they
-    // stood at that call: setup / solve / set_tree drop them (drop_paths).
-    bool paths_ok = false, simp_ok = false;
-    std::vector<uint64_t> path_off;               // [P + 1] host copy of the row offsets
-    std::vector<uint32_t> h_path_len;             // [P]
-    DevBuf<uint64_t> d_path_off, sp_woff, sp_bits, sp_checks;
-    DevBuf<uint32_t> path_len, path_len_a, sp_par, sp_idx, sp_len;
-    DevBuf<double> path_rows, sp_cost, sp_raw, sp_simp;
-    double paths_ms[3] = {0.0, 0.0, 0.0};         // extraction kernels, pair matrix, DP of the last calls
-    uint32_t paths_rounds = 0;
-    // rrt_revalidate.hip: the workspace of revalidate_trees (allocated on first use and kept) and the map of its last call,
-    // which belongs to the trees as that call left them: setup / solve / set_tree drop it (drop_paths)
-    bool reval_ok = false;
-    DevBuf<uint8_t> rv_edge_ok, rv_alive, rv_goal_lost, rv_stage;
-    DevBuf<int32_t> rv_new_index, rv_jump;
-    DevBuf<uint32_t> rv_n_after, rv_n_removed;
-    std::vector<uint32_t> rv_n_before;            // [P] tree sizes before the last call
-    double reval_ms[4] = {0.0, 0.0, 0.0, 0.0};    // edge checks, survival, scan, compaction + remap + skip flags
+    DevBuf<uint64_t> dbg;             // enable_stamps
+    Goals goals;
+    Obstacles obs;
+    Cells cells;
+    Shadow shadow;
+    Trees trees;
+    PooledStream stream;
+    Solve solve;
+    Paths paths;
+    Reval reval;
+    Star star;
 };
-static void drop_paths(oxhip_rrt_batch* b) { b->paths_ok = b->simp_ok = b->reval_ok = false; }
+
+// What belongs to the trees as they stood is dropped when they change.  Two rules, and every entry point that changes trees or
+// paths calls exactly one of them:
+//   drop_derived  -- setup, solve, set_tree and an accepted revalidate_trees: the extracted paths, the simplified paths and the
+//                    re-check map all go (their getters refuse until the service runs again);
+//   Paths::drop   -- extract_paths: the paths start over (simplified ones with them), the trees stay and so does their map.
+// (simplify_paths clears simp_ok alone: it keeps the paths it shortcuts.)  tests/test_gpu_rrt_handle_contract.py asserts this.
+static void drop_derived(oxhip_rrt_batch* b) { b->paths.drop(); b->reval.ok = false; }
+
+// The derived device state of `count` problems' trees from `first` on starts over: the fl32 shadows and the cell grids, which
+// the kernels rebuild from the trees.  The only place that does; setup, set_tree and revalidate_trees call it, on the stream.
+static int32_t reset_tree_caches(oxhip_rrt_batch* b, uint32_t first, uint32_t count) {
+    if (b->shadow.state.p) HIP_TRY(hipMemsetAsync(b->shadow.state.p + 2 * (size_t)first, 0, (size_t)count * 2 * sizeof(uint32_t), b->stream));
+    if (b->cells.meta) HIP_TRY(hipMemsetAsync(b->cells.meta + first, 0, (size_t)count * sizeof(CellMeta), b->stream));
+    b->dp.cells_meta_ok = 0;
+    return OXHIP_OK;
+}
+
+// sph_r's one owner: the radii travel when set_spheres changed them since the last upload, and not otherwise.
+static int32_t upload_radii(oxhip_rrt_batch* b) {
+    if (b->obs.radii_dirty) {
+        OX_TRY(upload(b->obs.sph_r, b->obs.sph_radii, b->stream));
+        b->obs.radii_dirty = false;
+        b->obs.bind(b->dp);
+    }
+    return OXHIP_OK;
+}
+
+// a service's clock: made by its first call (the device is current) and kept
+static int32_t clock_of(std::unique_ptr<PhaseClock>& clk, int n) {
+    if (!clk) clk.reset(new PhaseClock(n));
+    if (clk->made != hipSuccess) {
+        const hipError_t e = clk->made;
+        clk.reset();
+        return fail(OXHIP_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
+    }
+    return OXHIP_OK;
+}
+
 template <typename T>
 static hipError_t grow(DevBuf<T>& buf, size_t count) {   // keeps a buffer that is large enough (a round reuses the last one's)
     if (buf.p && buf.n >= count) return hipSuccess;
@@ -181,9 +294,9 @@ static const SpaceRow kSpaces[OXHIP_SPACE_SE3 + 2] = {
         "SE(3) RRTConnect runs on rrt_connect_se3.hip: kernel must be OXHIP_KERNEL_AUTO or OXHIP_KERNEL_STREAM",
         3, nullptr, "SE(3) batches take sphere obstacles (oxhip_rrt_batch_set_spheres)", kNoSegments, nullptr,
         true, true, false, kNoSimplifySe,
-        [](oxhip_rrt_batch* b) -> int32_t { launch_rrt_connect_se3(b->dp, b->se3, b->stream); return OXHIP_OK; },
-        [](oxhip_rrt_batch* b, const double* s, uint32_t n, uint8_t* out) { launch_se3_is_valid(b->dp, b->se3, s, n, out, b->stream); },
-        [](oxhip_rrt_batch* b, const double* f, const double* t, uint32_t n, uint8_t* out) { launch_se3_check_motion(b->dp, b->se3, f, t, n, out, b->stream); }},
+        [](oxhip_rrt_batch* b) -> int32_t { launch_rrt_connect_se3(b->dp, b->obs.se3, b->stream); return OXHIP_OK; },
+        [](oxhip_rrt_batch* b, const double* s, uint32_t n, uint8_t* out) { launch_se3_is_valid(b->dp, b->obs.se3, s, n, out, b->stream); },
+        [](oxhip_rrt_batch* b, const double* f, const double* t, uint32_t n, uint8_t* out) { launch_se3_check_motion(b->dp, b->obs.se3, f, t, n, out, b->stream); }},
     /* OXHIP_SPACE_SO2 */ {   // arcs: min <= normalise(v) <= max, closed; rrt_so2.hip tests every arc
         1, "SO(2) states are one angle: dim must be 1", kRrt, "SO(2) is built for RRT only",
         "SO(2) RRT runs on rrt_so2.hip: kernel must be OXHIP_KERNEL_AUTO or OXHIP_KERNEL_STREAM",
@@ -203,13 +316,17 @@ static const SpaceRow& space_of(const oxhip_rrt_batch* b) { return *space_row(b-
 
 // ------------------------------------------------------------------ the entry points' shared openings
 // The batch exists, setup() ran and `problem` (if one is given) is in range: what most entry points check first.  Pure host code.
-static int32_t setup_done(const oxhip_rrt_batch* b, int64_t problem = -1) {
-    if (!b) return fail(OXHIP_ERR_BAD_ARG, "null batch");
-    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");  // rrt.rs:160-163
+static int32_t in_range(const oxhip_rrt_batch* b, int64_t problem) {
     if (problem >= (int64_t)b->cfg.n_problems) return fail(OXHIP_ERR_BAD_ARG, "problem index out of range");
     return OXHIP_OK;
 }
-// ... and the batch's device is current.  (An entry point that reports another check in between calls the two halves itself.)
+static int32_t setup_done(const oxhip_rrt_batch* b, int64_t problem = -1) {
+    if (!b) return fail(OXHIP_ERR_BAD_ARG, "null batch");
+    if (!b->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");  // rrt.rs:160-163
+    return in_range(b, problem);
+}
+// ... and the batch's device is current.  (An entry point that reports another check in between calls the steps itself, in the
+// order its refusals always had.)
 static int32_t ready(const oxhip_rrt_batch* b, int64_t problem = -1) {
     OX_TRY(setup_done(b, problem));
     return select_device(b->cfg.device);
@@ -330,22 +447,24 @@ static void fill_params(oxhip_rrt_batch* b, const oxhip_rrt_config* cfg, const R
     dp.thr_search = sqrt_lt_threshold(cfg->search_radius);
 }
 
-// RRT*'s buffers, for the decoupled design (b->star_wired) or the one-kernel design; KERNEL_AUTO falls back from the first to
-// the second when the first's memory is not to be had.  `e` collects the first failure, as in alloc_common.
+// RRT*'s buffers (Star), for the decoupled design (Star::Wiring, `on`) or the one-kernel design; KERNEL_AUTO falls back from the
+// first to the second when the first's memory is not to be had.  `e` collects the first failure, as in alloc_common, which binds
+// what this allocates.
 static int32_t alloc_star(oxhip_rrt_batch* b, hipError_t& e) {
     const oxhip_rrt_config* cfg = &b->cfg;
     DevParams& dp = b->dp;
+    Star::Wiring& w = b->star.wiring;
     const uint32_t P = cfg->n_problems, dim = cfg->dim, cap = dp.cap;
     auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
     const bool geo_cells = cfg->kernel != OXHIP_KERNEL_LANES && cells_supported(dim, cap);
     const bool geo_lanes = cfg->kernel != OXHIP_KERNEL_CELLS && lanes_supported(dim, cap);
     const bool can_wire = star_wire_supported(dim) && (geo_cells || geo_lanes);
-    b->star_wired = cfg->kernel == OXHIP_KERNEL_LANES || cfg->kernel == OXHIP_KERNEL_CELLS || (cfg->kernel == OXHIP_KERNEL_AUTO && can_wire);
-    if (b->star_wired && !can_wire) return fail(OXHIP_ERR_BAD_ARG, "decoupled RRT*: neither geometry kernel supports this (dim, max_nodes)");
-    b->star_geo_cells = b->star_wired && geo_cells;
-    chk(b->cost.alloc((size_t)P * cap));
-    chk(b->wire_chk.alloc(P));
-    if (b->star_wired && e == hipSuccess) {
+    w.on = cfg->kernel == OXHIP_KERNEL_LANES || cfg->kernel == OXHIP_KERNEL_CELLS || (cfg->kernel == OXHIP_KERNEL_AUTO && can_wire);
+    if (w.on && !can_wire) return fail(OXHIP_ERR_BAD_ARG, "decoupled RRT*: neither geometry kernel supports this (dim, max_nodes)");
+    w.geo_cells = w.on && geo_cells;
+    chk(b->star.cost.alloc((size_t)P * cap));
+    chk(b->star.wire_chk.alloc(P));
+    if (w.on && e == hipSuccess) {
         // neighbour lists: a pool segment per problem; a round wires the longest prefix of a problem's pending nodes whose
         // lists fit (mean list length at radius 1 in configs[1]'s world: ~40), so the size bounds memory, not the result.
         // Footprint per problem: share x 16 B of pool + (share / 32 + cap) x 144 B of chunk store + 4 x cap x 4..8 B; the
@@ -358,80 +477,71 @@ static int32_t alloc_star(oxhip_rrt_batch* b, hipError_t& e) {
         dp.pool_share = (uint32_t)share;
         hipError_t ew = hipSuccess;
         auto chkw = [&](hipError_t r) { if (ew == hipSuccess) ew = r; };
-        chkw(oxhip_stream_acquire(cfg->device, &b->stream2));
-        for (auto& ev : b->ev_seg) chkw(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        chkw(hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming));
-        chkw(b->pool.alloc((size_t)P * share + 64));   // (+ padding: masked lanes of the wiring kernel read one entry past an empty list)
+        chkw(w.stream2.take(cfg->device));
+        for (auto& ev : w.ev_seg) chkw(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        chkw(hipEventCreateWithFlags(&w.ev_join, hipEventDisableTiming));
+        chkw(w.pool.alloc((size_t)P * share + 64));   // (+ padding: masked lanes of the wiring kernel read one entry past an empty list)
         dp.chunk_share = (uint32_t)(share / 32 + cap);   // enough for any set of lists that fits the pool segment (one partial chunk per node)
-        chkw(b->chunks.alloc((size_t)P * dp.chunk_share));
-        chkw(b->chunk_cursor.alloc(P));
-        chkw(b->wired.alloc(P));
-        chkw(b->nbr_take.alloc(P));
-        chkw(b->nbr_total.alloc(P));
-        chkw(b->nbr_cnt.alloc((size_t)P * cap));
-        chkw(b->nbr_off.alloc((size_t)P * cap));
-        chkw(b->d_near.alloc((size_t)P * cap));
+        chkw(w.chunks.alloc((size_t)P * dp.chunk_share));
+        chkw(w.chunk_cursor.alloc(P));
+        chkw(w.wired.alloc(P));
+        chkw(w.nbr_take.alloc(P));
+        chkw(w.nbr_total.alloc(P));
+        chkw(w.nbr_cnt.alloc((size_t)P * cap));
+        chkw(w.nbr_off.alloc((size_t)P * cap));
+        chkw(w.d_near.alloc((size_t)P * cap));
         if (ew != hipSuccess && cfg->kernel == OXHIP_KERNEL_AUTO) {
             // KERNEL_AUTO promised "whatever runs": the one-kernel design (rrt_star.hip) needs 1/60 of this memory
             (void)hipGetLastError();
-            b->pool.release(); b->chunks.release(); b->chunk_cursor.release(); b->wired.release(); b->nbr_take.release();
-            b->nbr_total.release(); b->nbr_cnt.release(); b->nbr_off.release(); b->d_near.release();
+            w.release();
             dp.pool_share = dp.chunk_share = 0;
-            b->star_wired = false;
-            b->star_geo_cells = false;
+            w.on = false;
+            w.geo_cells = false;
         } else {
             chk(ew);
         }
     }
-    if (!b->star_wired) {
-        chk(b->nb_idx.alloc((size_t)P * cap));
-        chk(b->nb_dist.alloc((size_t)P * cap));
+    if (!w.on) {
+        chk(b->star.nb_idx.alloc((size_t)P * cap));
+        chk(b->star.nb_dist.alloc((size_t)P * cap));
     }
     return OXHIP_OK;
 }
 
-// The stream, the timing events and the buffers every batch has (the planner's own among them, RRT*'s by alloc_star at the
-// place its allocations always had), then the DevParams pointers to them.
+// The stream, the solve clock's events and the buffers every batch has (the planner's own among them, RRT*'s by alloc_star at the
+// place its allocations always had), then the binds of the parts they belong to.
 static int32_t alloc_common(oxhip_rrt_batch* b) {
     const oxhip_rrt_config* cfg = &b->cfg;
-    DevParams& dp = b->dp;
-    const uint32_t P = cfg->n_problems, dim = cfg->dim, cap = dp.cap;
+    const uint32_t P = cfg->n_problems, dim = cfg->dim, cap = b->dp.cap;
     hipError_t e = hipSuccess;
     auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-    chk(oxhip_stream_acquire(cfg->device, &b->stream));
-    chk(hipEventCreate(&b->ev0));
-    chk(hipEventCreate(&b->ev1));
-    chk(b->tree.alloc((size_t)P * dim * cap));
-    chk(b->parent.alloc((size_t)P * cap));
-    chk(b->skip.alloc((size_t)P * cap));
+    chk(b->stream.take(cfg->device));
+    chk(b->solve.clk.made);   // an event that could not be made refuses the create, as a buffer does
+    chk(b->trees.tree.alloc((size_t)P * dim * cap));
+    chk(b->trees.parent.alloc((size_t)P * cap));
+    chk(b->trees.skip.alloc((size_t)P * cap));
     if (cfg->planner == OXHIP_PLANNER_RRT_CONNECT) {
-        chk(b->tree_b.alloc((size_t)P * dim * cap));
-        chk(b->parent_b.alloc((size_t)P * cap));
+        chk(b->trees.tree_b.alloc((size_t)P * dim * cap));
+        chk(b->trees.parent_b.alloc((size_t)P * cap));
     }
     if (cfg->planner == OXHIP_PLANNER_RRT_STAR) OX_TRY(alloc_star(b, e));
-    chk(b->state.alloc(P));
-    chk(b->goal_c.alloc((size_t)P * dim));
-    chk(b->goal_thr.alloc(P));
-    chk(b->goal_r.alloc(P));
+    chk(b->trees.state.alloc(P));
+    chk(b->goals.goal_c.alloc((size_t)P * dim));
+    chk(b->goals.goal_thr.alloc(P));
+    chk(b->goals.goal_r.alloc(P));
     if (!space_of(b).no_body && e == hipSuccess) {   // the default body: one sphere of radius 0 at the origin (a point)
-        if (upload(b->se3_body, std::vector<double>(4 * (size_t)kSe3MaxBody, 0.0), b->stream) != OXHIP_OK) e = hipErrorOutOfMemory;
-        b->se3.body = b->se3_body.p;
-        b->se3.n_body = 1;
+        if (upload(b->obs.se3_body, std::vector<double>(4 * (size_t)kSe3MaxBody, 0.0), b->stream) != OXHIP_OK) e = hipErrorOutOfMemory;
+        b->obs.se3.n_body = 1;
     }
     if (e != hipSuccess) return alloc_failed(e);
-    dp.tree = b->tree.p; dp.parent = b->parent.p; dp.skip = b->skip.p; dp.state = b->state.p;
-    dp.tree_b = b->tree_b.p; dp.parent_b = b->parent_b.p;
-    dp.cost = b->cost.p; dp.nb_idx = b->nb_idx.p; dp.nb_dist = b->nb_dist.p;
-    dp.wire_chk = b->wire_chk.p; dp.wired = b->wired.p; dp.nbr_cnt = b->nbr_cnt.p; dp.nbr_off = b->nbr_off.p;
-    dp.nbr_take = b->nbr_take.p; dp.nbr_total = b->nbr_total.p; dp.d_near = b->d_near.p; dp.pool = b->pool.p;
-    dp.chunks = b->chunks.p; dp.chunk_cursor = b->chunk_cursor.p;
-    dp.goal_c = b->goal_c.p; dp.goal_thr = b->goal_thr.p; dp.goal_r = b->goal_r.p;
+    b->trees.bind(b->dp); b->goals.bind(b->dp); b->star.bind(b->dp); b->obs.bind(b->dp);
     return OXHIP_OK;
 }
 
-// rrt_cells.hip's arena (the comment at oxhip_rrt_batch::cell_arena) and the DevParams fields that describe it.
+// rrt_cells.hip's arena (the comment at Cells) and the DevParams fields that describe it.
 static int32_t alloc_cells(oxhip_rrt_batch* b) {
     DevParams& dp = b->dp;
+    Cells& c = b->cells;
     const uint32_t P = b->cfg.n_problems, dim = b->cfg.dim, cap = dp.cap;
     dp.cell_level_max = cells_level_max(dim, cap);
     // head blocks for the finest grid this capacity reaches + the overflow blocks (n nodes overflow into at most n / 7)
@@ -449,20 +559,20 @@ static int32_t alloc_cells(oxhip_rrt_batch* b) {
     const size_t o_board = carve(2 * kCellsBoardWords * sizeof(uint64_t));   // the frozen launches' progress boards: zero before the first
     const size_t zero_bytes = off;
     const size_t o_pos = carve((size_t)P * 64 * sizeof(uint64_t)), o_grid = carve(grid_cells * sizeof(uint64_t));
-    const size_t o_grid2 = carve(b->star_wired ? grid_cells * sizeof(uint64_t) : 0);
+    const size_t o_grid2 = carve(b->star.wiring.on ? grid_cells * sizeof(uint64_t) : 0);
     const size_t o_flat = carve((size_t)P * 4096 * 4 * sizeof(float)), o_xyz = carve((size_t)P * cap * 4 * sizeof(double));
     const size_t o_blk = carve((size_t)P * dp.cell_blocks * sizeof(CellBlock));
-    hipError_t e = b->cell_arena.alloc(off);
-    if (e == hipSuccess) e = hipMemset(b->cell_arena.p, 0, zero_bytes);
+    hipError_t e = c.arena.alloc(off);
+    if (e == hipSuccess) e = hipMemset(c.arena.p, 0, zero_bytes);
     if (e != hipSuccess) return alloc_failed(e);
-    uint8_t* base = b->cell_arena.p;
-    b->cell_meta_p = reinterpret_cast<CellMeta*>(base + o_meta);
-    b->sph_grid_p = reinterpret_cast<uint64_t*>(base + o_grid);
-    if (b->star_wired) b->star_grid_p = reinterpret_cast<uint64_t*>(base + o_grid2);
+    uint8_t* base = c.arena.p;
+    c.meta = reinterpret_cast<CellMeta*>(base + o_meta);
+    c.sph_grid = reinterpret_cast<uint64_t*>(base + o_grid);
+    if (b->star.wiring.on) c.star_grid = reinterpret_cast<uint64_t*>(base + o_grid2);
     dp.cell_blk = reinterpret_cast<CellBlock*>(base + o_blk); dp.cell_flat = reinterpret_cast<float*>(base + o_flat);
-    dp.cell_xyz = reinterpret_cast<double*>(base + o_xyz); dp.cell_meta = b->cell_meta_p;
+    dp.cell_xyz = reinterpret_cast<double*>(base + o_xyz); dp.cell_meta = c.meta;
     dp.cell_acc = reinterpret_cast<CellAcc*>(base + o_acc); dp.cell_part_pos = reinterpret_cast<uint64_t*>(base + o_pos);
-    dp.sph_grid = b->sph_grid_p;
+    dp.sph_grid = c.sph_grid;
     dp.cell_board = reinterpret_cast<uint64_t*>(base + o_board);
     dp.cells_parity = 0;
     return OXHIP_OK;
@@ -472,12 +582,11 @@ static int32_t alloc_cells(oxhip_rrt_batch* b) {
 // maintain themselves.
 static int32_t alloc_shadow(oxhip_rrt_batch* b) {
     const size_t P = b->cfg.n_problems;
-    hipError_t e = b->tree32.alloc(P * b->cfg.dim * b->dp.cap);
-    if (e == hipSuccess) e = b->shadow_state.alloc(P * 2);
-    if (e == hipSuccess) e = hipMemset(b->shadow_state.p, 0, P * 2 * sizeof(uint32_t));
+    hipError_t e = b->shadow.tree32.alloc(P * b->cfg.dim * b->dp.cap);
+    if (e == hipSuccess) e = b->shadow.state.alloc(P * 2);
+    if (e == hipSuccess) e = hipMemset(b->shadow.state.p, 0, P * 2 * sizeof(uint32_t));
     if (e != hipSuccess) return alloc_failed(e);
-    b->dp.tree32 = b->tree32.p;
-    b->dp.shadow_state = b->shadow_state.p;
+    b->shadow.bind(b->dp);
     return OXHIP_OK;
 }
 
@@ -489,7 +598,7 @@ static int32_t op_batch(int32_t device, const double* a, const double* b, const 
                         size_t w_a, size_t w_b, size_t w_out, bool b_uploaded, bool t_uploaded, Launch launch) {
     if (n == 0) return OXHIP_OK;
     OX_TRY(select_device(device));
-    TmpStream ts;
+    PooledStream ts;
     OX_TRY(ts.acquire(device));
     DevBuf<double> da, db, dt, dout;
     OX_TRY(to_device(da, a, w_a * n, ts.s));
@@ -547,7 +656,7 @@ int32_t oxhip_rrt_batch_create(const oxhip_rrt_config* cfg, oxhip_rrt_batch** ou
     const uint32_t dim = cfg->dim, cap = b->dp.cap;
     uint32_t kind = cfg->kernel;
     if (space_of(b.get()).one_kernel) kind = OXHIP_KERNEL_STREAM;   // (e.g. rrt_so3.hip: the space's one kernel, reported as the streaming kind)
-    if (cfg->planner != OXHIP_PLANNER_RRT) kind = b->star_wired ? (b->star_geo_cells ? OXHIP_KERNEL_CELLS : OXHIP_KERNEL_LANES) : OXHIP_KERNEL_STREAM;
+    if (cfg->planner != OXHIP_PLANNER_RRT) kind = b->star.wiring.on ? (b->star.wiring.geo_cells ? OXHIP_KERNEL_CELLS : OXHIP_KERNEL_LANES) : OXHIP_KERNEL_STREAM;
     if (kind == OXHIP_KERNEL_AUTO) {
         // rrt_cells.hip (one wave per problem, R^2 / R^3, trees up to 64,512 nodes) wherever it exists: since its rounds
         // repair overtaken queries in place it grows ONE tree to 10,000 nodes in 4.3 ms -- faster than rrt_lanes.hip, which gives
@@ -561,7 +670,7 @@ int32_t oxhip_rrt_batch_create(const oxhip_rrt_config* cfg, oxhip_rrt_batch** ou
         return fail(OXHIP_ERR_BAD_ARG, "resident (lane-per-query) kernel does not support this (dim, max_nodes)");
     if (kind == OXHIP_KERNEL_RESIDENT && !resident_supported(dim, cap))
         return fail(OXHIP_ERR_BAD_ARG, "resident kernel does not support this (dim, max_nodes)");
-    b->kernel_kind = b->last_kind = kind;
+    b->solve.kernel_kind = kind;
     if (kind == OXHIP_KERNEL_CELLS) OX_TRY(alloc_cells(b.get()));
     // (a space with a kernel of its own keeps no shadow; RRT* does on every kind)
     if ((cfg->planner == OXHIP_PLANNER_RRT && kind == OXHIP_KERNEL_STREAM && !space_of(b.get()).one_kernel) || cfg->planner == OXHIP_PLANNER_RRT_STAR)
@@ -574,14 +683,7 @@ int32_t oxhip_rrt_batch_destroy(oxhip_rrt_batch* b) {
     if (!b) return OXHIP_OK;
     (void)hipSetDevice(b->cfg.device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
-    if (b->stream2) oxhip_stream_release(b->cfg.device, b->stream2);
-    for (auto ev : b->ev_seg) if (ev) (void)hipEventDestroy(ev);
-    if (b->ev_join) (void)hipEventDestroy(b->ev_join);
-    if (b->ev0) (void)hipEventDestroy(b->ev0);
-    if (b->ev1) (void)hipEventDestroy(b->ev1);
-    if (b->stream) oxhip_stream_release(b->cfg.device, b->stream);
-    if (b->h_states) (void)hipHostFree(b->h_states);
-    delete b;
+    delete b;   // (the order of what goes: the comment at oxhip_rrt_batch)
     return OXHIP_OK;
 }
 
@@ -600,16 +702,15 @@ int32_t oxhip_rrt_batch_set_spheres(oxhip_rrt_batch* b, const double* centres, c
         }
         thr[j] = sqrt_le_threshold(radii[j]);
     }
-    OX_TRY(upload(b->sph_c, c, b->stream));
-    OX_TRY(upload(b->sph_thr, thr, b->stream));
-    b->dp.n_spheres = n; b->dp.sph_c = b->sph_c.p; b->dp.sph_thr = b->sph_thr.p;
-    if (row.radii_uploaded) {
-        OX_TRY(upload(b->sph_r, std::vector<double>(radii, radii + n), b->stream));
-        b->dp.sph_r = b->sph_r.p;
-    }
-    b->sph_centres.assign(centres, centres + (size_t)n * dim);
-    b->sph_radii.assign(radii, radii + n);
-    b->filt_dirty = true;
+    Obstacles& o = b->obs;
+    OX_TRY(upload(o.sph_c, c, b->stream));
+    OX_TRY(upload(o.sph_thr, thr, b->stream));
+    o.n_spheres = n;
+    o.bind(b->dp);
+    o.sph_centres.assign(centres, centres + (size_t)n * dim);
+    o.sph_radii.assign(radii, radii + n);
+    o.filt_dirty = o.radii_dirty = true;
+    if (row.radii_uploaded) OX_TRY(upload_radii(b));
     return OXHIP_OK;
 }
 
@@ -624,9 +725,10 @@ int32_t oxhip_rrt_batch_set_boxes(oxhip_rrt_batch* b, const double* lo, const do
             l[(size_t)k * n + j] = lo[(size_t)j * dim + k];
             h[(size_t)k * n + j] = hi[(size_t)j * dim + k];
         }
-    OX_TRY(upload(b->box_lo, l, b->stream));
-    OX_TRY(upload(b->box_hi, h, b->stream));
-    b->dp.n_boxes = n; b->dp.box_lo = b->box_lo.p; b->dp.box_hi = b->box_hi.p;
+    OX_TRY(upload(b->obs.box_lo, l, b->stream));
+    OX_TRY(upload(b->obs.box_hi, h, b->stream));
+    b->obs.n_boxes = n;
+    b->obs.bind(b->dp);
     return OXHIP_OK;
 }
 
@@ -637,21 +739,21 @@ int32_t oxhip_rrt_batch_set_segments(oxhip_rrt_batch* b, const double* segments,
     OX_TRY(select_device(b->cfg.device));
     std::vector<double> v(segments, segments + (size_t)4 * n);
     for (double x : v) if (!(std::fabs(x) <= kMaxMagnitude)) return fail(OXHIP_ERR_BAD_ARG, "segment endpoint not finite / too large");
-    OX_TRY(upload(b->segs, v, b->stream));
-    b->dp.segs = b->segs.p;
-    b->dp.n_segs = n;
+    OX_TRY(upload(b->obs.segs, v, b->stream));
+    b->obs.n_segs = n;
+    b->obs.bind(b->dp);
     b->dp.seg_thr = sqrt_le_threshold(clearance);
     // the grid the motion check looks its segments up in: over the (x, y) bounds, which are finite here (create() refused others)
     b->dp.seg_grid = nullptr;
     const double wx = b->dp.hi[0] - b->dp.lo[0], wy = b->dp.hi[1] - b->dp.lo[1];
     if (n > 0 && (b->cfg.debug_flags & OXHIP_DEBUG_SE2_NO_SEGMENT_GRID) == 0 && std::isfinite(wx) && std::isfinite(wy) && wx > 0.0 && wy > 0.0) {
         const uint32_t G = seg_grid_side();
-        if (b->seg_grid.n != (size_t)G * G * 8) HIP_TRY(b->seg_grid.alloc((size_t)G * G * 8));
+        if (b->obs.seg_grid.n != (size_t)G * G * 8) HIP_TRY(b->obs.seg_grid.alloc((size_t)G * G * 8));
         b->dp.seg_grid_G = G;
         b->dp.seg_grid_inv[0] = (double)G / wx;
         b->dp.seg_grid_inv[1] = (double)G / wy;
-        launch_seg_grid(b->dp, b->seg_grid.p, clearance, b->stream);
-        b->dp.seg_grid = b->seg_grid.p;
+        launch_seg_grid(b->dp, b->obs.seg_grid.p, clearance, b->stream);
+        b->dp.seg_grid = b->obs.seg_grid.p;
     }
     return OXHIP_OK;
 }
@@ -671,16 +773,16 @@ int32_t oxhip_rrt_batch_set_body(oxhip_rrt_batch* b, const double* centres, cons
         v[3 * (size_t)kSe3MaxBody + j] = radii[j];
     }
     OX_TRY(select_device(b->cfg.device));
-    OX_TRY(upload(b->se3_body, v, b->stream));
-    b->se3.body = b->se3_body.p;
-    b->se3.n_body = n;
+    OX_TRY(upload(b->obs.se3_body, v, b->stream));
+    b->obs.se3.n_body = n;
+    b->obs.bind(b->dp);
     return OXHIP_OK;
 }
 
 int32_t oxhip_rrt_batch_setup(oxhip_rrt_batch* b, const double* starts, const double* goal_centres,
                               const double* goal_radii) {
     if (!b || !starts || !goal_centres || !goal_radii) return fail(OXHIP_ERR_BAD_ARG, "null argument");
-    drop_paths(b);
+    drop_derived(b);
     OX_TRY(select_device(b->cfg.device));
     const uint32_t P = b->cfg.n_problems, dim = b->cfg.dim, cap = b->dp.cap;
     for (size_t i = 0; i < (size_t)P * dim; ++i)
@@ -689,8 +791,8 @@ int32_t oxhip_rrt_batch_setup(oxhip_rrt_batch* b, const double* starts, const do
     if (b->cfg.goal_sampler == OXHIP_GOAL_SAMPLE_UNIFORM_DISC)
         for (uint32_t p = 0; p < P; ++p)
             if (!(goal_radii[p] >= 0.0 && goal_radii[p] <= kMaxMagnitude)) return fail(OXHIP_ERR_BAD_ARG, "disc sampler: goal radius must be finite and >= 0");
-    b->starts.assign(starts, starts + (size_t)P * dim);
-    b->filt_dirty = true;
+    b->goals.starts.assign(starts, starts + (size_t)P * dim);
+    b->obs.filt_dirty = true;
     std::vector<double> thr(P);
     // R^n: satisfied iff d2 <= T(radius); SE(2) / SO(3) / SE(3): the space's distance is compared with the radius itself
     for (uint32_t p = 0; p < P; ++p) thr[p] = space_of(b).goal_is_radius ? goal_radii[p] : sqrt_le_threshold(goal_radii[p]);
@@ -705,34 +807,33 @@ int32_t oxhip_rrt_batch_setup(oxhip_rrt_batch* b, const double* starts, const do
         s.stop_reason = OXHIP_STOP_NONE;
     }
     std::vector<int32_t> root(1, -1);
-    HIP_TRY(hipMemcpyAsync(b->goal_c.p, goal_centres, (size_t)P * dim * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    HIP_TRY(hipMemcpyAsync(b->goal_thr.p, thr.data(), P * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    HIP_TRY(hipMemcpyAsync(b->goal_r.p, goal_radii, P * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    HIP_TRY(hipMemcpyAsync(b->state.p, states.data(), P * sizeof(ProblemState), hipMemcpyHostToDevice, b->stream));
+    Trees& t = b->trees;
+    HIP_TRY(hipMemcpyAsync(b->goals.goal_c.p, goal_centres, (size_t)P * dim * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(b->goals.goal_thr.p, thr.data(), P * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(b->goals.goal_r.p, goal_radii, P * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(t.state.p, states.data(), P * sizeof(ProblemState), hipMemcpyHostToDevice, b->stream));
     // tree.clear(); tree.push(Node{start_states[0], None})   rrt.rs:147-155
     // node 0 of coordinate k of problem p lives at tree[(p*dim + k)*cap]: strided 2-D copy
-    HIP_TRY(hipMemcpy2DAsync(b->tree.p, (size_t)cap * sizeof(double), starts, sizeof(double), sizeof(double),
+    HIP_TRY(hipMemcpy2DAsync(t.tree.p, (size_t)cap * sizeof(double), starts, sizeof(double), sizeof(double),
                              (size_t)P * dim, hipMemcpyHostToDevice, b->stream));
-    HIP_TRY(hipMemsetAsync(b->skip.p, 0, (size_t)P * cap, b->stream));
-    if (b->shadow_state.p) HIP_TRY(hipMemsetAsync(b->shadow_state.p, 0, (size_t)P * 2 * sizeof(uint32_t), b->stream));  // shadows start over
-    if (b->cell_meta_p) HIP_TRY(hipMemsetAsync(b->cell_meta_p, 0, (size_t)P * sizeof(CellMeta), b->stream));              // the grids too
-    b->dp.cells_meta_ok = 0;
+    HIP_TRY(hipMemsetAsync(t.skip.p, 0, (size_t)P * cap, b->stream));
+    OX_TRY(reset_tree_caches(b, 0, P));
     std::vector<int32_t> minus1(P, -1);
-    HIP_TRY(hipMemcpy2DAsync(b->parent.p, (size_t)cap * sizeof(int32_t), minus1.data(), sizeof(int32_t),
+    HIP_TRY(hipMemcpy2DAsync(t.parent.p, (size_t)cap * sizeof(int32_t), minus1.data(), sizeof(int32_t),
                              sizeof(int32_t), P, hipMemcpyHostToDevice, b->stream));
     if (b->cfg.planner == OXHIP_PLANNER_RRT_CONNECT) {
         // goal_tree.push(Node{goal.sample_goal(), None})  rrt_connect.rs:218-224 (the ball goal samples its centre)
-        HIP_TRY(hipMemcpy2DAsync(b->tree_b.p, (size_t)cap * sizeof(double), goal_centres, sizeof(double), sizeof(double),
+        HIP_TRY(hipMemcpy2DAsync(t.tree_b.p, (size_t)cap * sizeof(double), goal_centres, sizeof(double), sizeof(double),
                                  (size_t)P * dim, hipMemcpyHostToDevice, b->stream));
-        HIP_TRY(hipMemcpy2DAsync(b->parent_b.p, (size_t)cap * sizeof(int32_t), minus1.data(), sizeof(int32_t),
+        HIP_TRY(hipMemcpy2DAsync(t.parent_b.p, (size_t)cap * sizeof(int32_t), minus1.data(), sizeof(int32_t),
                                  sizeof(int32_t), P, hipMemcpyHostToDevice, b->stream));
     }
     if (b->cfg.planner == OXHIP_PLANNER_RRT_STAR) {   // start node: cost 0.0 (rrt_star.rs:163-167)
-        HIP_TRY(hipMemsetAsync(b->cost.p, 0, (size_t)P * cap * sizeof(double), b->stream));
-        HIP_TRY(hipMemsetAsync(b->wire_chk.p, 0, (size_t)P * sizeof(uint64_t), b->stream));
-        if (b->star_wired) {
+        HIP_TRY(hipMemsetAsync(b->star.cost.p, 0, (size_t)P * cap * sizeof(double), b->stream));
+        HIP_TRY(hipMemsetAsync(b->star.wire_chk.p, 0, (size_t)P * sizeof(uint64_t), b->stream));
+        if (b->star.wiring.on) {
             std::vector<uint32_t> one(P, 1u);   // the start node needs no wiring
-            HIP_TRY(hipMemcpyAsync(b->wired.p, one.data(), (size_t)P * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
+            HIP_TRY(hipMemcpyAsync(b->star.wiring.wired.p, one.data(), (size_t)P * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
             HIP_TRY(hipStreamSynchronize(b->stream));
         }
     }
@@ -741,92 +842,86 @@ int32_t oxhip_rrt_batch_setup(oxhip_rrt_batch* b, const double* starts, const do
     return OXHIP_OK;
 }
 
-// Conservative midpoint filter of the resident kernel's motion check.  Every state the check
-// interpolates lies within max_distance/2 (+ rounding) of the segment midpoint, so
-// d2(centre, mid) > (r + h)^2 proves sphere (centre, r) valid for the whole motion.  h carries a
-// relative 1e-6 and an absolute 1e-9 * (largest coordinate magnitude) margin, orders of magnitude
-// above the few-ulp rounding of the interpolation; the filter never decides a motion invalid.
-static int32_t refresh_filter(oxhip_rrt_batch* b) {
-    if (!b->filt_dirty) return OXHIP_OK;
-    const uint32_t n = b->dp.n_spheres, dim = b->cfg.dim;
-    if (b->cfg.planner == OXHIP_PLANNER_RRT_CONNECT && b->cfg.space == OXHIP_SPACE_REAL_VECTOR) {
-        // rrt_connect.hip's motion check looks a state's spheres up (R^2 / R^3, up to 64 spheres, finite bounds): bit j of a cell's
-        // mask = sphere j reaches the cell's box (sphere_grid_kernel: squared distance centre - box, the box taken 2^-9 of a cell
-        // wider, compared with the sphere's own validity threshold and a relative 1e-9 of slack).  A sphere that is not listed
-        // contains no state of the cell: its test would say "no hit".
-        b->dp.sph_grid = nullptr;
-        bool ok = (dim == 2 || dim == 3) && n >= 1 && n <= 64 && (b->cfg.debug_flags & OXHIP_DEBUG_SE2_NO_SEGMENT_GRID) == 0;
-        for (uint32_t k = 0; ok && k < dim; ++k) ok = std::isfinite(b->dp.lo[k]) && std::isfinite(b->dp.hi[k]) && b->dp.hi[k] > b->dp.lo[k];
-        if (ok) {
-            const uint32_t G = sphere_grid_side(dim);
-            const size_t cells = dim == 2 ? (size_t)G * G : (size_t)G * G * G;
-            if (b->conn_grid.n != cells) HIP_TRY(b->conn_grid.alloc(cells));
-            std::vector<double> f(n);
-            for (uint32_t j = 0; j < n; ++j) {
-                const double t = sqrt_le_threshold(b->sph_radii[j]);   // valid iff d2 > t
-                f[j] = std::isfinite(t) ? (t > 0.0 ? t * (1.0 + 1e-9) : t) : t;
-            }
-            OX_TRY(upload(b->conn_filt, f, b->stream));
-            b->dp.sph_grid_G = G;
-            launch_sphere_grid(b->dp, b->conn_grid.p, b->conn_filt.p, b->stream);
-            b->dp.sph_grid = b->conn_grid.p;
-        }
-        b->filt_dirty = false;
-        return OXHIP_OK;
-    }
-    double maxabs = 1.0;
-    for (uint32_t k = 0; k < 2 * dim; ++k) maxabs = std::fmax(maxabs, std::fabs(b->cfg.bounds[k]));
-    for (double v : b->starts) maxabs = std::fmax(maxabs, std::fabs(v));
-    for (double v : b->sph_centres) maxabs = std::fmax(maxabs, std::fabs(v));
+// ---- the filters a launch reads (the thresholds' arithmetic: oxhip_host.hpp), each built under its own condition by refresh_filter
+// rrt_connect.hip's motion check looks a state's spheres up (R^2 / R^3, up to 64 spheres, finite bounds): bit j of a cell's
+// mask = sphere j reaches the cell's box (sphere_grid_kernel: squared distance centre - box, the box taken 2^-9 of a cell
+// wider, compared with connect_grid_threshold).
+static int32_t connect_sphere_grid(oxhip_rrt_batch* b) {
+    Obstacles& o = b->obs;
+    const uint32_t n = o.n_spheres, dim = b->cfg.dim;
+    b->dp.sph_grid = nullptr;
+    bool ok = (dim == 2 || dim == 3) && n >= 1 && n <= 64 && (b->cfg.debug_flags & OXHIP_DEBUG_SE2_NO_SEGMENT_GRID) == 0;
+    for (uint32_t k = 0; ok && k < dim; ++k) ok = std::isfinite(b->dp.lo[k]) && std::isfinite(b->dp.hi[k]) && b->dp.hi[k] > b->dp.lo[k];
+    if (!ok) return OXHIP_OK;
+    const uint32_t G = sphere_grid_side(dim);
+    const size_t cells = dim == 2 ? (size_t)G * G : (size_t)G * G * G;
+    if (o.conn_grid.n != cells) HIP_TRY(o.conn_grid.alloc(cells));
+    std::vector<double> f(n);
+    for (uint32_t j = 0; j < n; ++j) f[j] = connect_grid_threshold(o.sph_radii[j]);
+    OX_TRY(upload(o.conn_filt, f, b->stream));
+    b->dp.sph_grid_G = G;
+    launch_sphere_grid(b->dp, o.conn_grid.p, o.conn_filt.p, b->stream);
+    b->dp.sph_grid = o.conn_grid.p;
+    return OXHIP_OK;
+}
+// The midpoint filter of a planner's motion check (midpoint_threshold, h for a motion of max_distance), and rrt_cells.hip's grid
+// of it.
+static int32_t midpoint_filter(oxhip_rrt_batch* b, double maxabs) {
+    Obstacles& o = b->obs;
+    const uint32_t n = o.n_spheres;
     const double h = 0.5 * b->cfg.max_distance * (1.0 + 1e-6) + 1e-9 * maxabs;
     std::vector<double> f(n);
-    for (uint32_t j = 0; j < n; ++j) {
-        const double r = b->sph_radii[j];
-        if (std::isnan(r) || std::isinf(r)) f[j] = r < 0.0 ? -1.0 : std::numeric_limits<double>::infinity();
-        else if (r < 0.0) f[j] = -1.0;                       // distance > negative radius always holds
-        else f[j] = (r + h) * (r + h) * (1.0 + 1e-9);
+    for (uint32_t j = 0; j < n; ++j) f[j] = midpoint_threshold(o.sph_radii[j], h);
+    OX_TRY(upload(o.sph_filt, f, b->stream));
+    o.bind(b->dp);
+    if (b->cells.sph_grid && n > 0) launch_sphere_grid(b->dp, b->cells.sph_grid, o.sph_filt.p, b->stream);   // (rrt_cells.hip looks the midpoint filter up)
+    return OXHIP_OK;
+}
+// Decoupled RRT*: motion_seq.hpp filters motions of any length, so it takes the radii as given and the absolute margin; the edge
+// kernel's grid is built for motions up to search_radius long (star_edge_threshold).
+static int32_t star_edge_filter(oxhip_rrt_batch* b, double maxabs) {
+    Obstacles& o = b->obs;
+    const uint32_t n = o.n_spheres;
+    OX_TRY(upload_radii(b));
+    b->dp.filt_abs = 1e-9 * maxabs;
+    b->dp.star_sph_grid = nullptr;
+    if (!b->cells.star_grid || n == 0) return OXHIP_OK;
+    const double h_lo = b->dp.filt_abs, h_hi = 0.5 * b->cfg.search_radius * (1.0 + 1e-6) + b->dp.filt_abs;
+    std::vector<double> sf(n);
+    for (uint32_t j = 0; j < n; ++j) sf[j] = star_edge_threshold(o.sph_radii[j], h_lo, h_hi);
+    OX_TRY(upload(b->star.wiring.star_filt, sf, b->stream));
+    launch_sphere_grid(b->dp, b->cells.star_grid, b->star.wiring.star_filt.p, b->stream);
+    b->dp.star_sph_grid = b->cells.star_grid;
+    return OXHIP_OK;
+}
+// Before a launch of a space whose kernels read them (SpaceRow::midpoint_filter): whatever spheres, starts or bounds changed.
+static int32_t refresh_filter(oxhip_rrt_batch* b) {
+    if (!b->obs.filt_dirty) return OXHIP_OK;
+    if (b->cfg.planner == OXHIP_PLANNER_RRT_CONNECT && b->cfg.space == OXHIP_SPACE_REAL_VECTOR) {
+        OX_TRY(connect_sphere_grid(b));
+    } else {
+        const double maxabs = filter_maxabs(b->cfg, b->obs.sph_centres, &b->goals.starts);
+        OX_TRY(midpoint_filter(b, maxabs));
+        if (b->star.wiring.on) OX_TRY(star_edge_filter(b, maxabs));
     }
-    OX_TRY(upload(b->sph_filt, f, b->stream));
-    b->dp.sph_filt = b->sph_filt.p;
-    if (b->sph_grid_p && n > 0) launch_sphere_grid(b->dp, b->sph_grid_p, b->sph_filt.p, b->stream);   // (rrt_cells.hip looks the midpoint filter up)
-    if (b->star_wired) {   // motion_seq.hpp filters motions of any length: it takes the radii as given and this absolute margin
-        OX_TRY(upload(b->sph_r, b->sph_radii, b->stream));
-        b->dp.sph_r = b->sph_r.p;
-        b->dp.filt_abs = 1e-9 * maxabs;
-        b->dp.star_sph_grid = nullptr;
-        if (b->star_grid_p && n > 0) {
-            // the edge kernel's midpoint filter keeps sphere j when d2(centre, mid) <= (r_j + h)^2 (1 + 1e-9), h = dist / 2 (1 + 1e-6)
-            // + filt_abs, dist < search_radius: the grid is built for the largest such ball (either end of h's range when r_j < 0)
-            const double h_lo = b->dp.filt_abs, h_hi = 0.5 * b->cfg.search_radius * (1.0 + 1e-6) + b->dp.filt_abs;
-            std::vector<double> sf(n);
-            for (uint32_t j = 0; j < n; ++j) {
-                const double r = b->sph_radii[j];
-                const double a = (r + h_lo) * (r + h_lo), c = (r + h_hi) * (r + h_hi);
-                sf[j] = (std::isnan(r) || std::isinf(r)) ? std::numeric_limits<double>::infinity()
-                                                         : std::fmax(a, c) * (1.0 + 1e-9) * (1.0 + 1e-12);
-            }
-            OX_TRY(upload(b->star_filt, sf, b->stream));
-            launch_sphere_grid(b->dp, b->star_grid_p, b->star_filt.p, b->stream);
-            b->dp.star_sph_grid = b->star_grid_p;
-        }
-    }
-    b->filt_dirty = false;
+    b->obs.filt_dirty = false;
     return OXHIP_OK;
 }
 
 static int32_t read_states(oxhip_rrt_batch* b, std::vector<ProblemState>& states) {
+    Trees& t = b->trees;
     states.resize(b->cfg.n_problems);
-    if (!b->h_states) HIP_TRY(hipHostMalloc((void**)&b->h_states, states.size() * sizeof(ProblemState), hipHostMallocDefault));
-    HIP_TRY(hipMemcpyAsync(b->h_states, b->state.p, states.size() * sizeof(ProblemState), hipMemcpyDeviceToHost, b->stream));
+    if (!t.h_states) HIP_TRY(hipHostMalloc((void**)&t.h_states, states.size() * sizeof(ProblemState), hipHostMallocDefault));
+    HIP_TRY(hipMemcpyAsync(t.h_states, t.state.p, states.size() * sizeof(ProblemState), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
-    std::memcpy(states.data(), b->h_states, states.size() * sizeof(ProblemState));
+    std::memcpy(states.data(), t.h_states, states.size() * sizeof(ProblemState));
     return OXHIP_OK;
 }
 
 int32_t oxhip_rrt_batch_set_tree(oxhip_rrt_batch* b, uint32_t problem, const double* states_in, const int32_t* parents_in,
                                  uint32_t n) {
     if (!b || !states_in || !parents_in) return fail(OXHIP_ERR_BAD_ARG, "null argument");
-    drop_paths(b);
+    drop_derived(b);
     OX_TRY(setup_done(b, problem));
     if (n == 0 || n > b->cfg.max_nodes) return fail(OXHIP_ERR_BAD_ARG, "n_nodes must be in 1..max_nodes");
     if (b->cfg.planner != OXHIP_PLANNER_RRT) return fail(OXHIP_ERR_BAD_ARG, "set_tree is for the RRT planner");
@@ -862,18 +957,15 @@ int32_t oxhip_rrt_batch_set_tree(oxhip_rrt_batch* b, uint32_t problem, const dou
             if (same) skip[order[j]] = 1;  // order[j-1] has the lower index among equals (ties sort by index)
         }
     }
-    HIP_TRY(hipMemcpy2DAsync(b->tree.p + (size_t)problem * dim * cap, (size_t)cap * sizeof(double), soa.data(),
+    HIP_TRY(hipMemcpy2DAsync(b->trees.tree.p + (size_t)problem * dim * cap, (size_t)cap * sizeof(double), soa.data(),
                              (size_t)n * sizeof(double), (size_t)n * sizeof(double), dim, hipMemcpyHostToDevice, b->stream));
-    HIP_TRY(hipMemcpyAsync(b->parent.p + (size_t)problem * cap, parents_in, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, b->stream));
-    HIP_TRY(hipMemcpyAsync(b->skip.p + (size_t)problem * cap, skip.data(), n, hipMemcpyHostToDevice, b->stream));
-    if (b->shadow_state.p)   // this problem's fl32 shadow starts over
-        HIP_TRY(hipMemsetAsync(b->shadow_state.p + 2 * (size_t)problem, 0, 2 * sizeof(uint32_t), b->stream));
-    if (b->cell_meta_p) HIP_TRY(hipMemsetAsync(b->cell_meta_p + problem, 0, sizeof(CellMeta), b->stream));   // ... and its cell grid
-    b->dp.cells_meta_ok = 0;
+    HIP_TRY(hipMemcpyAsync(b->trees.parent.p + (size_t)problem * cap, parents_in, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(b->trees.skip.p + (size_t)problem * cap, skip.data(), n, hipMemcpyHostToDevice, b->stream));
+    OX_TRY(reset_tree_caches(b, problem, 1));
     std::vector<ProblemState> states;
     OX_TRY(read_states(b, states));
     states[problem].n_nodes = n;
-    HIP_TRY(hipMemcpyAsync(b->state.p + problem, &states[problem], sizeof(ProblemState), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(b->trees.state.p + problem, &states[problem], sizeof(ProblemState), hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return OXHIP_OK;
 }
@@ -881,12 +973,13 @@ int32_t oxhip_rrt_batch_set_tree(oxhip_rrt_batch* b, uint32_t problem, const dou
 // Decoupled RRT*: parents and costs of the nodes the RRT kernel just inserted (rrt_star_wire.hip).  A round wires, per
 // problem, the longest prefix of its pending nodes whose neighbour lists fit the problem's pool segment; usually one round.
 static int32_t wire_new_nodes(oxhip_rrt_batch* b) {
+    Star::Wiring& w = b->star.wiring;
     const uint32_t P = b->cfg.n_problems;
     std::vector<ProblemState> states;
     std::vector<uint32_t> wired(P), take(P), total(P), chunks_used(P);
     for (;;) {
         OX_TRY(read_states(b, states));
-        HIP_TRY(hipMemcpyAsync(wired.data(), b->wired.p, (size_t)P * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+        HIP_TRY(hipMemcpyAsync(wired.data(), w.wired.p, (size_t)P * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
         HIP_TRY(hipStreamSynchronize(b->stream));
         uint32_t max_pending = 0;
         for (uint32_t p = 0; p < P; ++p) {
@@ -897,12 +990,12 @@ static int32_t wire_new_nodes(oxhip_rrt_batch* b) {
         uint32_t max_n = 0;
         for (uint32_t p = 0; p < P; ++p) max_n = states[p].n_nodes > max_n ? states[p].n_nodes : max_n;
         launch_star_shadow(b->dp, max_n, b->stream);
-        HIP_TRY(hipMemsetAsync(b->chunk_cursor.p, 0, (size_t)P * sizeof(uint32_t), b->stream));
+        HIP_TRY(hipMemsetAsync(w.chunk_cursor.p, 0, (size_t)P * sizeof(uint32_t), b->stream));
         launch_star_count(b->dp, max_pending, b->stream);
         launch_star_scan(b->dp, b->stream);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(take.data(), b->nbr_take.p, (size_t)P * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
-        HIP_TRY(hipMemcpyAsync(total.data(), b->nbr_total.p, (size_t)P * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+        HIP_TRY(hipMemcpyAsync(take.data(), w.nbr_take.p, (size_t)P * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+        HIP_TRY(hipMemcpyAsync(total.data(), w.nbr_total.p, (size_t)P * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
         HIP_TRY(hipStreamSynchronize(b->stream));
         uint32_t max_take = 0, max_total = 0;
         for (uint32_t p = 0; p < P; ++p) {
@@ -912,7 +1005,7 @@ static int32_t wire_new_nodes(oxhip_rrt_batch* b) {
         if (max_take == 0) return fail(OXHIP_ERR_HIP, "RRT* wiring: no node fits the neighbour pool");   // (a list is at most cap <= pool_share long)
         // every pending node of every problem fits this round and the counting pass could keep all it found: the lists are
         // built from its chunks; otherwise (a pool segment or the chunk store ran out) the round searches a second time
-        HIP_TRY(hipMemcpyAsync(chunks_used.data(), b->chunk_cursor.p, (size_t)P * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+        HIP_TRY(hipMemcpyAsync(chunks_used.data(), w.chunk_cursor.p, (size_t)P * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
         HIP_TRY(hipStreamSynchronize(b->stream));
         bool one_pass = (b->dp.dbg_flags & OXHIP_DEBUG_STAR_TWO_PASS) == 0;
         uint32_t max_chunks = 0;
@@ -931,23 +1024,23 @@ static int32_t wire_new_nodes(oxhip_rrt_batch* b) {
             b->dp.seg_index = sgi;
             b->dp.seg_count = segs;
             launch_star_edges(b->dp, max_total / segs + 2u, b->stream);
-            HIP_TRY(hipEventRecord(b->ev_seg[sgi], b->stream));
-            HIP_TRY(hipStreamWaitEvent(b->stream2, b->ev_seg[sgi], 0));
-            launch_star_wire(b->dp, b->stream2);
+            HIP_TRY(hipEventRecord(w.ev_seg[sgi], b->stream));
+            HIP_TRY(hipStreamWaitEvent(w.stream2, w.ev_seg[sgi], 0));
+            launch_star_wire(b->dp, w.stream2);
         }
-        HIP_TRY(hipEventRecord(b->ev_join, b->stream2));
-        HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_join, 0));
+        HIP_TRY(hipEventRecord(w.ev_join, w.stream2));
+        HIP_TRY(hipStreamWaitEvent(b->stream, w.ev_join, 0));
         HIP_TRY(hipGetLastError());
     }
 }
 
 // R^n's launch: by planner and by the kernel kind create() resolved (KERNEL_AUTO among them), for frozen and growing launches alike
 static int32_t solve_real_vector(oxhip_rrt_batch* b) {
-    const uint32_t kind = b->kernel_kind;
+    const uint32_t kind = b->solve.kernel_kind;
     if (b->cfg.planner == OXHIP_PLANNER_RRT_CONNECT) launch_rrt_connect(b->dp, b->stream);
-    else if (b->cfg.planner == OXHIP_PLANNER_RRT_STAR && b->star_wired) {
+    else if (b->cfg.planner == OXHIP_PLANNER_RRT_STAR && b->star.wiring.on) {
         // geometry: exactly RRT's loop on the same stream (rrt_star_wire.hip's header); then wire the new nodes
-        if (b->star_geo_cells) { launch_rrt_cells(b->dp, b->stream); b->dp.cells_meta_ok = 1; } else launch_rrt_lanes(b->dp, b->stream);
+        if (b->star.wiring.geo_cells) { launch_rrt_cells(b->dp, b->stream); b->dp.cells_meta_ok = 1; } else launch_rrt_lanes(b->dp, b->stream);
         HIP_TRY(hipGetLastError());
         OX_TRY(wire_new_nodes(b));
     }
@@ -955,7 +1048,7 @@ static int32_t solve_real_vector(oxhip_rrt_batch* b) {
     else if (kind == OXHIP_KERNEL_CELLS) {
         launch_rrt_cells(b->dp, b->stream);
         b->dp.cells_meta_ok = 1;
-        if (b->dp.freeze) { b->cells_board_last = (int32_t)b->dp.cells_parity; b->dp.cells_parity ^= 1u; }   // (the next frozen launch counts on the board this one cleared)
+        if (b->dp.freeze) { b->cells.board_last = (int32_t)b->dp.cells_parity; b->dp.cells_parity ^= 1u; }   // (the next frozen launch counts on the board this one cleared)
     }
     else if (kind == OXHIP_KERNEL_LANES) launch_rrt_lanes(b->dp, b->stream);
     else if (kind == OXHIP_KERNEL_RESIDENT) launch_rrt_resident(b->dp, b->stream);
@@ -966,7 +1059,7 @@ static int32_t solve_real_vector(oxhip_rrt_batch* b) {
 int32_t oxhip_rrt_batch_solve(oxhip_rrt_batch* b, uint64_t max_iterations, double timeout_s, uint32_t freeze,
                               int32_t* status_out) {
     if (!b) return fail(OXHIP_ERR_BAD_ARG, "null batch");
-    drop_paths(b);
+    drop_derived(b);
     OX_TRY(ready(b));
     if (b->cfg.planner != OXHIP_PLANNER_RRT && freeze) return fail(OXHIP_ERR_BAD_ARG, "freeze is for the RRT planner");
     if (space_of(b).midpoint_filter) OX_TRY(refresh_filter(b));
@@ -981,24 +1074,24 @@ int32_t oxhip_rrt_batch_solve(oxhip_rrt_batch* b, uint64_t max_iterations, doubl
     const uint64_t kChunk = has_timeout ? 2048 : 65536;
     const uint64_t chunk = max_iterations < kChunk ? max_iterations : kChunk;
     uint64_t remaining = max_iterations;
-    b->last_kernel_ms = 0.0;
-    b->last_launches = 0;
+    Solve& sv = b->solve;
+    sv.last_kernel_ms = 0.0;
+    sv.last_launches = 0;
     bool timed_out = false;
     std::vector<ProblemState> states;
     while (remaining > 0) {
         uint64_t step = remaining < chunk ? remaining : chunk;
         b->dp.budget = step;
         b->dp.freeze = freeze ? 1 : 0;
-        b->last_kind = b->kernel_kind;
-        HIP_TRY(hipEventRecord(b->ev0, b->stream));
+        HIP_TRY(sv.clk.mark(Solve::kBegin, b->stream));
         OX_TRY(space_of(b).solve(b));
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(b->ev1, b->stream));
+        HIP_TRY(sv.clk.mark(Solve::kEnd, b->stream));
         OX_TRY(read_states(b, states));   // (the launch's one synchronisation: the stop reasons come with it)
         float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, b->ev0, b->ev1));
-        b->last_kernel_ms += ms;
-        b->last_launches++;
+        HIP_TRY(hipEventElapsedTime(&ms, sv.clk.event(Solve::kBegin), sv.clk.event(Solve::kEnd)));
+        sv.last_kernel_ms += ms;
+        sv.last_launches++;
         remaining -= step;
         if (remaining == 0) break;
         bool any_running = false;
@@ -1014,7 +1107,7 @@ int32_t oxhip_rrt_batch_solve(oxhip_rrt_batch* b, uint64_t max_iterations, doubl
         if (s.stop_reason == OXHIP_STOP_INTERNAL) return fail(OXHIP_ERR_HIP, "resident kernel: scanner/resolver hand-off stalled");
     if (timed_out) {
         for (auto& s : states) if (s.stop_reason == OXHIP_STOP_ITERATIONS) s.stop_reason = OXHIP_STOP_TIMEOUT;
-        HIP_TRY(hipMemcpyAsync(b->state.p, states.data(), states.size() * sizeof(ProblemState), hipMemcpyHostToDevice, b->stream));
+        HIP_TRY(hipMemcpyAsync(b->trees.state.p, states.data(), states.size() * sizeof(ProblemState), hipMemcpyHostToDevice, b->stream));
         HIP_TRY(hipStreamSynchronize(b->stream));
     }
     if (status_out)
@@ -1033,7 +1126,7 @@ int32_t oxhip_rrt_batch_get_counts(oxhip_rrt_batch* b, uint64_t* iterations, uin
     OX_TRY(read_states(b, states));
     if (b->cfg.planner == OXHIP_PLANNER_RRT_STAR) {   // reported checksum = H (iterations) + W (wiring), DESIGN.md section 10
         std::vector<uint64_t> w(b->cfg.n_problems);
-        HIP_TRY(hipMemcpyAsync(w.data(), b->wire_chk.p, w.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
+        HIP_TRY(hipMemcpyAsync(w.data(), b->star.wire_chk.p, w.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
         HIP_TRY(hipStreamSynchronize(b->stream));
         for (uint32_t p = 0; p < b->cfg.n_problems; ++p) states[p].checksum += w[p];
     }
@@ -1051,8 +1144,8 @@ int32_t oxhip_rrt_batch_get_counts(oxhip_rrt_batch* b, uint64_t* iterations, uin
 static int32_t fetch_tree(oxhip_rrt_batch* b, uint32_t problem, uint32_t n, std::vector<double>& soa,
                           std::vector<int32_t>& parents, bool goal_tree = false) {
     const uint32_t dim = b->cfg.dim, cap = b->dp.cap;
-    const double* tree_base = goal_tree ? b->tree_b.p : b->tree.p;
-    const int32_t* parent_base = goal_tree ? b->parent_b.p : b->parent.p;
+    const double* tree_base = goal_tree ? b->trees.tree_b.p : b->trees.tree.p;
+    const int32_t* parent_base = goal_tree ? b->trees.parent_b.p : b->trees.parent.p;
     soa.resize((size_t)dim * n);
     parents.resize(n);
     // [dim][n] out of [dim][cap]
@@ -1070,7 +1163,8 @@ static int32_t copy_tree(oxhip_rrt_batch* b, uint32_t problem, bool goal_tree, d
     if (!b || !n_nodes) return fail(OXHIP_ERR_BAD_ARG, "null argument");
     OX_TRY(setup_done(b));
     if (goal_tree && b->cfg.planner != OXHIP_PLANNER_RRT_CONNECT) return fail(OXHIP_ERR_BAD_ARG, "not an RRTConnect batch");
-    OX_TRY(ready(b, problem));
+    OX_TRY(in_range(b, problem));
+    OX_TRY(select_device(b->cfg.device));
     std::vector<ProblemState> states;
     OX_TRY(read_states(b, states));
     const uint32_t n = goal_tree ? states[problem].n_nodes_b : states[problem].n_nodes, dim = b->cfg.dim;
@@ -1157,14 +1251,15 @@ int32_t oxhip_rrt_batch_get_costs(oxhip_rrt_batch* b, uint32_t problem, double* 
     if (!b || !n_nodes) return fail(OXHIP_ERR_BAD_ARG, "null argument");
     OX_TRY(setup_done(b));
     if (b->cfg.planner != OXHIP_PLANNER_RRT_STAR) return fail(OXHIP_ERR_BAD_ARG, "not an RRT* batch");
-    OX_TRY(ready(b, problem));
+    OX_TRY(in_range(b, problem));
+    OX_TRY(select_device(b->cfg.device));
     std::vector<ProblemState> states;
     OX_TRY(read_states(b, states));
     const uint32_t n = states[problem].n_nodes;
     *n_nodes = n;
     if (!costs) return OXHIP_OK;
     if (n > cap_nodes) return fail(OXHIP_ERR_CAPACITY, "cost buffer too small");
-    HIP_TRY(hipMemcpyAsync(costs, b->cost.p + (size_t)problem * b->dp.cap, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(costs, b->star.cost.p + (size_t)problem * b->dp.cap, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return OXHIP_OK;
 }
@@ -1173,55 +1268,58 @@ int32_t oxhip_rrt_batch_get_costs(oxhip_rrt_batch* b, uint32_t problem, double* 
 
 int32_t oxhip_rrt_batch_extract_paths(oxhip_rrt_batch* b) {
     OX_TRY(ready(b));
-    b->paths_ok = b->simp_ok = false;   // (the trees stay: a revalidation map stays with them)
+    Paths& ps = b->paths;
+    ps.drop();
     const uint32_t P = b->cfg.n_problems, dim = b->cfg.dim;
-    HIP_TRY(grow(b->path_len, P));
-    HIP_TRY(grow(b->path_len_a, P));
-    HIP_TRY(grow(b->d_path_off, (size_t)P + 1));
-    PathArgs a{b->d_path_off.p, b->path_len.p, b->path_len_a.p, nullptr};
+    OX_TRY(clock_of(ps.clk, 3));
+    PhaseClock& clk = *ps.clk;
+    HIP_TRY(grow(ps.len, P));
+    HIP_TRY(grow(ps.len_a, P));
+    HIP_TRY(grow(ps.d_off, (size_t)P + 1));
+    PathArgs a{ps.d_off.p, ps.len.p, ps.len_a.p, nullptr};
     // lengths first, one prefix sum, then the rows
-    HIP_TRY(hipEventRecord(b->ev0, b->stream));
+    HIP_TRY(clk.mark(Paths::kBegin, b->stream));
     launch_path_len(b->dp, a, b->stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(b->ev1, b->stream));
-    b->h_path_len.resize(P);
-    HIP_TRY(hipMemcpyAsync(b->h_path_len.data(), b->path_len.p, (size_t)P * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(clk.mark(Paths::kMid, b->stream));
+    ps.h_len.resize(P);
+    HIP_TRY(hipMemcpyAsync(ps.h_len.data(), ps.len.p, (size_t)P * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, b->ev0, b->ev1));
-    b->paths_ms[0] = ms;
-    b->path_off.assign((size_t)P + 1, 0);
+    HIP_TRY(hipEventElapsedTime(&ms, clk.event(Paths::kBegin), clk.event(Paths::kMid)));
+    ps.ms[0] = ms;
+    ps.off.assign((size_t)P + 1, 0);
     for (uint32_t p = 0; p < P; ++p) {
-        if (b->h_path_len[p] == 0xFFFFFFFFu) return fail(OXHIP_ERR_HIP, "parent chain is cyclic or leaves the tree (corrupt tree)");
-        b->path_off[p + 1] = b->path_off[p] + b->h_path_len[p];
+        if (ps.h_len[p] == 0xFFFFFFFFu) return fail(OXHIP_ERR_HIP, "parent chain is cyclic or leaves the tree (corrupt tree)");
+        ps.off[p + 1] = ps.off[p] + ps.h_len[p];
     }
-    const uint64_t total = b->path_off[P];
-    HIP_TRY(grow(b->path_rows, (size_t)total * dim));
-    HIP_TRY(hipMemcpyAsync(b->d_path_off.p, b->path_off.data(), ((size_t)P + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, b->stream));
-    a.rows = b->path_rows.p;
-    HIP_TRY(hipEventRecord(b->ev0, b->stream));
+    const uint64_t total = ps.off[P];
+    HIP_TRY(grow(ps.rows, (size_t)total * dim));
+    HIP_TRY(hipMemcpyAsync(ps.d_off.p, ps.off.data(), ((size_t)P + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, b->stream));
+    a.rows = ps.rows.p;
+    HIP_TRY(clk.mark(Paths::kBegin, b->stream));
     launch_path_rows(b->dp, a, b->stream);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(b->ev1, b->stream));
+    HIP_TRY(clk.mark(Paths::kMid, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
-    HIP_TRY(hipEventElapsedTime(&ms, b->ev0, b->ev1));
-    b->paths_ms[0] += ms;
-    b->paths_ok = true;
+    HIP_TRY(hipEventElapsedTime(&ms, clk.event(Paths::kBegin), clk.event(Paths::kMid)));
+    ps.ms[0] += ms;
+    ps.ok = true;
     return OXHIP_OK;
 }
 
 int32_t oxhip_rrt_batch_get_paths(oxhip_rrt_batch* b, uint64_t* offsets_out, double* states_out, uint64_t cap_states, uint64_t* total_out) {
     if (!b || !total_out) return fail(OXHIP_ERR_BAD_ARG, "null argument");
     OX_TRY(setup_done(b));
-    if (!b->paths_ok) return fail(OXHIP_ERR_BAD_ARG, "no extracted paths: call oxhip_rrt_batch_extract_paths after the last setup / solve / set_tree");
+    if (!b->paths.ok) return fail(OXHIP_ERR_BAD_ARG, "no extracted paths: call oxhip_rrt_batch_extract_paths after the last setup / solve / set_tree");
     OX_TRY(select_device(b->cfg.device));
     const uint32_t P = b->cfg.n_problems;
-    const uint64_t total = b->path_off[P];
+    const uint64_t total = b->paths.off[P];
     *total_out = total;
-    if (offsets_out) std::memcpy(offsets_out, b->path_off.data(), ((size_t)P + 1) * sizeof(uint64_t));
+    if (offsets_out) std::memcpy(offsets_out, b->paths.off.data(), ((size_t)P + 1) * sizeof(uint64_t));
     if (total > cap_states) return fail(OXHIP_ERR_CAPACITY, "path buffer too small");
     if (!states_out || total == 0) return OXHIP_OK;
-    HIP_TRY(hipMemcpyAsync(states_out, b->path_rows.p, (size_t)total * b->cfg.dim * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(states_out, b->paths.rows.p, (size_t)total * b->cfg.dim * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return OXHIP_OK;
 }
@@ -1233,14 +1331,8 @@ static constexpr uint64_t kPairWordsMax = (1ull << 30) / sizeof(uint64_t);
 static int32_t pair_params(oxhip_rrt_batch* b, double& filt_base) {
     filt_base = 0.0;
     if (!space_of(b).midpoint_filter) return OXHIP_OK;
-    if (b->dp.n_spheres != 0) {
-        OX_TRY(upload(b->sph_r, b->sph_radii, b->stream));
-        b->dp.sph_r = b->sph_r.p;
-    }
-    double maxabs = 1.0;
-    for (uint32_t k = 0; k < 2 * b->cfg.dim; ++k) maxabs = std::fmax(maxabs, std::fabs(b->cfg.bounds[k]));
-    for (double v : b->sph_centres) maxabs = std::fmax(maxabs, std::fabs(v));
-    filt_base = 1e-9 * maxabs;
+    if (b->obs.n_spheres != 0) OX_TRY(upload_radii(b));
+    filt_base = 1e-9 * filter_maxabs(b->cfg, b->obs.sph_centres, nullptr);   // (no starts: the kernel widens it per motion)
     return OXHIP_OK;
 }
 
@@ -1255,55 +1347,56 @@ int32_t oxhip_rrt_batch_simplify_paths(oxhip_rrt_batch* b, uint32_t max_span, ui
     OX_TRY(setup_done(b));
     OX_TRY(simplify_supported(b));
     OX_TRY(select_device(b->cfg.device));
-    b->simp_ok = false;
-    if (!b->paths_ok) OX_TRY(oxhip_rrt_batch_extract_paths(b));
+    Paths& ps = b->paths;
+    ps.simp_ok = false;
+    if (!ps.ok) OX_TRY(oxhip_rrt_batch_extract_paths(b));
     const uint32_t P = b->cfg.n_problems;
-    const uint64_t total = b->path_off[P];
+    const uint64_t total = ps.off[P];
     double filt_base = 0.0;
     OX_TRY(pair_params(b, filt_base));
-    HIP_TRY(grow(b->sp_cost, total));
-    HIP_TRY(grow(b->sp_par, total));
-    HIP_TRY(grow(b->sp_idx, total));
-    HIP_TRY(grow(b->sp_len, P));
-    HIP_TRY(grow(b->sp_raw, P));
-    HIP_TRY(grow(b->sp_simp, P));
-    HIP_TRY(grow(b->sp_checks, P));
-    const SimplifyOut out{b->sp_cost.p, b->sp_par.p, b->sp_idx.p, b->sp_len.p, b->sp_raw.p, b->sp_simp.p, b->sp_checks.p};
-    enum { kPairsBegin, kPairsEnd, kDpEnd };
-    PhaseClock clk(3);
-    b->paths_ms[1] = b->paths_ms[2] = 0.0;
-    b->paths_rounds = 0;
+    HIP_TRY(grow(ps.sp_cost, total));
+    HIP_TRY(grow(ps.sp_par, total));
+    HIP_TRY(grow(ps.sp_idx, total));
+    HIP_TRY(grow(ps.sp_len, P));
+    HIP_TRY(grow(ps.sp_raw, P));
+    HIP_TRY(grow(ps.sp_simp, P));
+    HIP_TRY(grow(ps.sp_checks, P));
+    const SimplifyOut out{ps.sp_cost.p, ps.sp_par.p, ps.sp_idx.p, ps.sp_len.p, ps.sp_raw.p, ps.sp_simp.p, ps.sp_checks.p};
+    OX_TRY(clock_of(ps.clk, 3));
+    PhaseClock& clk = *ps.clk;
+    ps.ms[1] = ps.ms[2] = 0.0;
+    ps.rounds = 0;
     std::vector<uint64_t> woff;
     for (uint32_t q0 = 0; q0 < P;) {
         // a round: as many problems as the bit workspace (and the caller's override) allows, at least one
         woff.assign(1, 0);
         uint32_t q1 = q0;
         while (q1 < P && (chunk_problems == 0 || q1 - q0 < chunk_problems)) {
-            const uint64_t w = path_pair_words(b->h_path_len[q1], max_span);
+            const uint64_t w = path_pair_words(ps.h_len[q1], max_span);
             if (w > kPairWordsMax) return fail(OXHIP_ERR_CAPACITY, "a path's pair matrix exceeds the 1 GiB workspace: pass a max_span");
             if (q1 > q0 && woff.back() + w > kPairWordsMax) break;
             woff.push_back(woff.back() + w);
             ++q1;
         }
         const uint32_t n_chunk = q1 - q0;
-        HIP_TRY(grow(b->sp_woff, (size_t)n_chunk + 1));
-        HIP_TRY(grow(b->sp_bits, woff.back()));
-        HIP_TRY(hipMemcpyAsync(b->sp_woff.p, woff.data(), woff.size() * sizeof(uint64_t), hipMemcpyHostToDevice, b->stream));
-        const PairArgs a{b->d_path_off.p, b->path_len.p, b->path_rows.p, b->sp_woff.p, b->sp_bits.p, woff.back(), q0, n_chunk, max_span, 0, filt_base};
-        HIP_TRY(clk.mark(kPairsBegin, b->stream));
+        HIP_TRY(grow(ps.sp_woff, (size_t)n_chunk + 1));
+        HIP_TRY(grow(ps.sp_bits, woff.back()));
+        HIP_TRY(hipMemcpyAsync(ps.sp_woff.p, woff.data(), woff.size() * sizeof(uint64_t), hipMemcpyHostToDevice, b->stream));
+        const PairArgs a{ps.d_off.p, ps.len.p, ps.rows.p, ps.sp_woff.p, ps.sp_bits.p, woff.back(), q0, n_chunk, max_span, 0, filt_base};
+        HIP_TRY(clk.mark(Paths::kBegin, b->stream));
         launch_path_pairs(b->dp, a, b->stream);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(clk.mark(kPairsEnd, b->stream));
+        HIP_TRY(clk.mark(Paths::kMid, b->stream));
         launch_path_dp(b->dp, a, out, b->stream);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(clk.mark(kDpEnd, b->stream));
+        HIP_TRY(clk.mark(Paths::kEnd, b->stream));
         HIP_TRY(hipStreamSynchronize(b->stream));   // (woff is rebuilt by the next round)
-        b->paths_ms[1] += clk.ms(kPairsBegin, kPairsEnd);
-        b->paths_ms[2] += clk.ms(kPairsEnd, kDpEnd);
-        b->paths_rounds++;
+        ps.ms[1] += clk.ms(Paths::kBegin, Paths::kMid);
+        ps.ms[2] += clk.ms(Paths::kMid, Paths::kEnd);
+        ps.rounds++;
         q0 = q1;
     }
-    b->simp_ok = true;
+    ps.simp_ok = true;
     return OXHIP_OK;
 }
 
@@ -1311,12 +1404,12 @@ int32_t oxhip_rrt_batch_get_simplified_paths(oxhip_rrt_batch* b, uint64_t* offse
                                              uint64_t cap_states, uint64_t* total_out) {
     if (!b || !total_out) return fail(OXHIP_ERR_BAD_ARG, "null argument");
     OX_TRY(setup_done(b));
-    if (!b->simp_ok || !b->paths_ok)
+    if (!b->paths.simp_ok || !b->paths.ok)
         return fail(OXHIP_ERR_BAD_ARG, "no simplified paths: call oxhip_rrt_batch_simplify_paths after the last setup / solve / set_tree");
     OX_TRY(select_device(b->cfg.device));
     const uint32_t P = b->cfg.n_problems, dim = b->cfg.dim;
     std::vector<uint32_t> slen(P);
-    HIP_TRY(hipMemcpyAsync(slen.data(), b->sp_len.p, (size_t)P * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(slen.data(), b->paths.sp_len.p, (size_t)P * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     std::vector<uint64_t> soff((size_t)P + 1, 0);
     for (uint32_t p = 0; p < P; ++p) soff[p + 1] = soff[p] + slen[p];
@@ -1326,33 +1419,34 @@ int32_t oxhip_rrt_batch_get_simplified_paths(oxhip_rrt_batch* b, uint64_t* offse
     if (total > cap_states) return fail(OXHIP_ERR_CAPACITY, "path buffer too small");
     if ((!states_out && !indices_out) || total == 0) return OXHIP_OK;
     // one copy of the raw rows and of the index lists; the simplified rows are gathered from them
-    const uint64_t raw_total = b->path_off[P];
+    const std::vector<uint64_t>& off = b->paths.off;
+    const uint64_t raw_total = off[P];
     std::vector<uint32_t> idx(raw_total);
     std::vector<double> rows;
-    HIP_TRY(hipMemcpyAsync(idx.data(), b->sp_idx.p, (size_t)raw_total * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(idx.data(), b->paths.sp_idx.p, (size_t)raw_total * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
     if (states_out) {
         rows.resize((size_t)raw_total * dim);
-        HIP_TRY(hipMemcpyAsync(rows.data(), b->path_rows.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        HIP_TRY(hipMemcpyAsync(rows.data(), b->paths.rows.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     }
     HIP_TRY(hipStreamSynchronize(b->stream));
     for (uint32_t p = 0; p < P; ++p)
         for (uint32_t t = 0; t < slen[p]; ++t) {
-            const uint32_t i = idx[b->path_off[p] + t];
+            const uint32_t i = idx[off[p] + t];
             if (indices_out) indices_out[soff[p] + t] = i;
-            if (states_out) std::memcpy(states_out + (soff[p] + t) * dim, rows.data() + (b->path_off[p] + i) * dim, dim * sizeof(double));
+            if (states_out) std::memcpy(states_out + (soff[p] + t) * dim, rows.data() + (off[p] + i) * dim, dim * sizeof(double));
         }
     return OXHIP_OK;
 }
 
 int32_t oxhip_rrt_batch_get_simplify_results(oxhip_rrt_batch* b, double* raw_cost, double* simplified_cost, uint64_t* checks) {
     OX_TRY(setup_done(b));
-    if (!b->simp_ok || !b->paths_ok)
+    if (!b->paths.simp_ok || !b->paths.ok)
         return fail(OXHIP_ERR_BAD_ARG, "no simplified paths: call oxhip_rrt_batch_simplify_paths after the last setup / solve / set_tree");
     OX_TRY(select_device(b->cfg.device));
     const size_t P = b->cfg.n_problems;
-    if (raw_cost) HIP_TRY(hipMemcpyAsync(raw_cost, b->sp_raw.p, P * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    if (simplified_cost) HIP_TRY(hipMemcpyAsync(simplified_cost, b->sp_simp.p, P * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    if (checks) HIP_TRY(hipMemcpyAsync(checks, b->sp_checks.p, P * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
+    if (raw_cost) HIP_TRY(hipMemcpyAsync(raw_cost, b->paths.sp_raw.p, P * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (simplified_cost) HIP_TRY(hipMemcpyAsync(simplified_cost, b->paths.sp_simp.p, P * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (checks) HIP_TRY(hipMemcpyAsync(checks, b->paths.sp_checks.p, P * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return OXHIP_OK;
 }
@@ -1362,9 +1456,9 @@ int32_t oxhip_rrt_batch_path_valid_matrix(oxhip_rrt_batch* b, uint32_t problem, 
     if (!b || !len_out) return fail(OXHIP_ERR_BAD_ARG, "null argument");
     OX_TRY(setup_done(b, problem));
     OX_TRY(simplify_supported(b));
-    if (!b->paths_ok) return fail(OXHIP_ERR_BAD_ARG, "no extracted paths: call oxhip_rrt_batch_extract_paths after the last setup / solve / set_tree");
+    if (!b->paths.ok) return fail(OXHIP_ERR_BAD_ARG, "no extracted paths: call oxhip_rrt_batch_extract_paths after the last setup / solve / set_tree");
     OX_TRY(select_device(b->cfg.device));
-    const uint32_t L = b->h_path_len[problem];
+    const uint32_t L = b->paths.h_len[problem];
     *len_out = L;
     if ((uint64_t)L * L > cap_bytes) return fail(OXHIP_ERR_CAPACITY, "matrix buffer too small");
     if (!out || L == 0) return OXHIP_OK;
@@ -1377,7 +1471,7 @@ int32_t oxhip_rrt_batch_path_valid_matrix(oxhip_rrt_batch* b, uint32_t problem, 
     const uint64_t woff[2] = {0, words};
     OX_TRY(to_device(d_woff, woff, 2, b->stream));
     HIP_TRY(d_bits.alloc(words ? words : 1));
-    const PairArgs a{b->d_path_off.p, b->path_len.p, b->path_rows.p, d_woff.p, d_bits.p, words, problem, 1, max_span, 0, filt_base};
+    const PairArgs a{b->paths.d_off.p, b->paths.len.p, b->paths.rows.p, d_woff.p, d_bits.p, words, problem, 1, max_span, 0, filt_base};
     launch_path_pairs(b->dp, a, b->stream);
     HIP_TRY(hipGetLastError());
     std::vector<uint64_t> bits(words);
@@ -1394,18 +1488,18 @@ int32_t oxhip_rrt_batch_path_valid_matrix(oxhip_rrt_batch* b, uint32_t problem, 
 
 int32_t oxhip_rrt_batch_paths_last_timing(oxhip_rrt_batch* b, double* extract_ms, double* pairs_ms, double* dp_ms, uint32_t* rounds) {
     if (!b) return fail(OXHIP_ERR_BAD_ARG, "null batch");
-    if (extract_ms) *extract_ms = b->paths_ms[0];
-    if (pairs_ms) *pairs_ms = b->paths_ms[1];
-    if (dp_ms) *dp_ms = b->paths_ms[2];
-    if (rounds) *rounds = b->paths_rounds;
+    if (extract_ms) *extract_ms = b->paths.ms[0];
+    if (pairs_ms) *pairs_ms = b->paths.ms[1];
+    if (dp_ms) *dp_ms = b->paths.ms[2];
+    if (rounds) *rounds = b->paths.rounds;
     return OXHIP_OK;
 }
 
 int32_t oxhip_rrt_batch_last_timing(oxhip_rrt_batch* b, double* kernel_ms, uint32_t* launches, uint32_t* kernel_kind) {
     if (!b) return fail(OXHIP_ERR_BAD_ARG, "null batch");
-    if (kernel_ms) *kernel_ms = b->last_kernel_ms;
-    if (launches) *launches = b->last_launches;
-    if (kernel_kind) *kernel_kind = b->cfg.planner == OXHIP_PLANNER_RRT ? b->last_kind : b->kernel_kind;
+    if (kernel_ms) *kernel_ms = b->solve.last_kernel_ms;
+    if (launches) *launches = b->solve.last_launches;
+    if (kernel_kind) *kernel_kind = b->solve.kernel_kind;
     return OXHIP_OK;
 }
 
@@ -1430,10 +1524,10 @@ int32_t oxhip_rrt_batch_get_stamps(oxhip_rrt_batch* b, uint64_t* out, uint32_t c
     const uint32_t n = cap_words < OXHIP_STAMP_WORDS ? cap_words : OXHIP_STAMP_WORDS;
     if (n) HIP_TRY(hipMemcpyAsync(out, b->dbg.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
-    if (n > OXHIP_STAMP_CELLS_BOARD && b->dp.cell_board && b->cells_board_last >= 0) {
+    if (n > OXHIP_STAMP_CELLS_BOARD && b->dp.cell_board && b->cells.board_last >= 0) {
         // rrt_cells.hip: what the last frozen launch's progress board holds, summed over the XCDs
         std::vector<uint64_t> board(kCellsBoardWords);
-        HIP_TRY(hipMemcpy(board.data(), b->dp.cell_board + (size_t)b->cells_board_last * kCellsBoardWords, kCellsBoardWords * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(board.data(), b->dp.cell_board + (size_t)b->cells.board_last * kCellsBoardWords, kCellsBoardWords * sizeof(uint64_t), hipMemcpyDeviceToHost));
         uint64_t sum = 0;
         for (uint32_t x = 0; x < 8; ++x) sum += board[x * (kCellsBoardWords / 8)];
         out[OXHIP_STAMP_CELLS_BOARD] = sum;
@@ -1456,7 +1550,7 @@ int32_t oxhip_nn_argmin_batch(int32_t device, uint32_t dim, const double* nodes,
         offsets[q] = total;
         total += n_nodes[q];
     }
-    TmpStream ts;
+    PooledStream ts;
     OX_TRY(ts.acquire(device));
     DevBuf<double> d_nodes, d_q, d_dist;
     DevBuf<uint64_t> d_off;
@@ -1498,7 +1592,7 @@ int32_t oxhip_rrt_batch_revalidate_trees(oxhip_rrt_batch* b, uint32_t* n_removed
     if (b->cfg.planner != OXHIP_PLANNER_RRT)
         return fail(OXHIP_ERR_BAD_ARG, "revalidate_trees is for the RRT planner (an RRT* batch would need its costs and wiring cursors pruned as well)");
     // below the refusals: a call refused for its planner leaves the batch's extracted and simplified paths as they were
-    drop_paths(b);   // (and the last call's map)
+    drop_derived(b);   // (the last call's map with them)
     OX_TRY(select_device(b->cfg.device));
     if (space_of(b).midpoint_filter) OX_TRY(refresh_filter(b));   // as solve does: the next launch reads them
     const uint32_t P = b->cfg.n_problems, cap = b->dp.cap;
@@ -1507,59 +1601,57 @@ int32_t oxhip_rrt_batch_revalidate_trees(oxhip_rrt_batch* b, uint32_t* n_removed
     OX_TRY(pair_params(b, a.filt_base));   // (R^n: the radii and the absolute margin of motion_seq.hpp's midpoint filter)
     std::vector<ProblemState> states;
     OX_TRY(read_states(b, states));        // one read of the state array: the node counts
-    b->rv_n_before.resize(P);
+    Reval& rv = b->reval;
+    rv.n_before.resize(P);
     uint32_t max_n = 1;
     for (uint32_t p = 0; p < P; ++p) {
-        b->rv_n_before[p] = states[p].n_nodes;
+        rv.n_before[p] = states[p].n_nodes;
         if (states[p].n_nodes == 0 || states[p].n_nodes > cap) return fail(OXHIP_ERR_HIP, "revalidate_trees: a tree size outside 1..capacity");
         max_n = std::max(max_n, states[p].n_nodes);
     }
     a.tiles = (max_n + 255u) / 256u;
     if ((uint64_t)P * a.tiles * 256u > 0x7FFFFFFFull) return fail(OXHIP_ERR_CAPACITY, "revalidate_trees: more than 2^31 node slots");
     const size_t slots = (size_t)P * cap;
-    HIP_TRY(grow(b->rv_edge_ok, slots));
-    HIP_TRY(grow(b->rv_alive, slots));
-    HIP_TRY(grow(b->rv_new_index, slots));
-    HIP_TRY(grow(b->rv_jump, slots));
-    HIP_TRY(grow(b->rv_n_after, P));
-    HIP_TRY(grow(b->rv_n_removed, P));
-    HIP_TRY(grow(b->rv_goal_lost, P));
+    HIP_TRY(grow(rv.edge_ok, slots));
+    HIP_TRY(grow(rv.alive, slots));
+    HIP_TRY(grow(rv.new_index, slots));
+    HIP_TRY(grow(rv.jump, slots));
+    HIP_TRY(grow(rv.n_after, P));
+    HIP_TRY(grow(rv.n_removed, P));
+    HIP_TRY(grow(rv.goal_lost, P));
     if (so3) {
         // 65 bytes per staged edge (two rows and a verdict) out of 6 bytes per slot: with the 10 above, 16 bytes per slot
         // (one block of 64 edges at the least)
         const size_t edges = std::max<size_t>(64, std::min<size_t>(slots * 6 / 65, (size_t)P * a.tiles * 256u));
-        HIP_TRY(grow(b->rv_stage, edges * 65));
+        HIP_TRY(grow(rv.stage, edges * 65));
         a.stage_cap = (uint32_t)std::min<size_t>(edges, 0x7FFFFF00u);
-        a.stage_from = reinterpret_cast<double*>(b->rv_stage.p);
+        a.stage_from = reinterpret_cast<double*>(rv.stage.p);
         a.stage_to = a.stage_from + (size_t)a.stage_cap * 4;
         a.stage_out = reinterpret_cast<uint8_t*>(a.stage_to + (size_t)a.stage_cap * 4);
     }
-    a.tree = b->tree.p; a.parent = b->parent.p; a.skip = b->skip.p; a.state = b->state.p;
-    a.goal_c = b->goal_c.p; a.goal_thr = b->goal_thr.p;
-    a.edge_ok = b->rv_edge_ok.p; a.alive = b->rv_alive.p; a.new_index = b->rv_new_index.p; a.jump = b->rv_jump.p;
-    a.n_after = b->rv_n_after.p; a.n_removed = b->rv_n_removed.p; a.goal_lost = b->rv_goal_lost.p;
+    a.tree = b->trees.tree.p; a.parent = b->trees.parent.p; a.skip = b->trees.skip.p; a.state = b->trees.state.p;
+    a.goal_c = b->goals.goal_c.p; a.goal_thr = b->goals.goal_thr.p;
+    a.edge_ok = rv.edge_ok.p; a.alive = rv.alive.p; a.new_index = rv.new_index.p; a.jump = rv.jump.p;
+    a.n_after = rv.n_after.p; a.n_removed = rv.n_removed.p; a.goal_lost = rv.goal_lost.p;
     a.cap = cap;
-    enum { kBegin, kEdgesEnd, kSurviveEnd, kScanEnd, kCompactEnd };   // reval_ms[i]: mark i to mark i + 1
-    PhaseClock clk(5);
-    HIP_TRY(clk.mark(kBegin, b->stream));
+    OX_TRY(clock_of(rv.clk, 5));
+    PhaseClock& clk = *rv.clk;
+    HIP_TRY(clk.mark(Reval::kBegin, b->stream));
     launch_rrt_reval_edges(b->dp, a, P, b->stream);
-    HIP_TRY(clk.mark(kEdgesEnd, b->stream));
+    HIP_TRY(clk.mark(Reval::kEdgesEnd, b->stream));
     launch_rrt_reval_survive(a, P, b->stream);
-    HIP_TRY(clk.mark(kSurviveEnd, b->stream));
+    HIP_TRY(clk.mark(Reval::kSurviveEnd, b->stream));
     launch_rrt_reval_scan(a, P, b->stream);
-    HIP_TRY(clk.mark(kScanEnd, b->stream));
+    HIP_TRY(clk.mark(Reval::kScanEnd, b->stream));
     launch_rrt_reval_compact(b->dp, a, P, b->stream);
-    HIP_TRY(clk.mark(kCompactEnd, b->stream));
+    HIP_TRY(clk.mark(Reval::kCompactEnd, b->stream));
     HIP_TRY(hipGetLastError());
-    // what set_tree drops, for every problem: the fl32 shadows start over, the cell grids too
-    if (b->shadow_state.p) HIP_TRY(hipMemsetAsync(b->shadow_state.p, 0, (size_t)P * 2 * sizeof(uint32_t), b->stream));
-    if (b->cell_meta_p) HIP_TRY(hipMemsetAsync(b->cell_meta_p, 0, (size_t)P * sizeof(CellMeta), b->stream));
-    b->dp.cells_meta_ok = 0;
-    if (n_removed) HIP_TRY(hipMemcpyAsync(n_removed, b->rv_n_removed.p, (size_t)P * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
-    if (goal_lost) HIP_TRY(hipMemcpyAsync(goal_lost, b->rv_goal_lost.p, P, hipMemcpyDeviceToHost, b->stream));
+    OX_TRY(reset_tree_caches(b, 0, P));   // (the trees were compacted in place)
+    if (n_removed) HIP_TRY(hipMemcpyAsync(n_removed, rv.n_removed.p, (size_t)P * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+    if (goal_lost) HIP_TRY(hipMemcpyAsync(goal_lost, rv.goal_lost.p, P, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
-    for (int i = kBegin; i < kCompactEnd; ++i) b->reval_ms[i] = clk.ms(i, i + 1);
-    b->reval_ok = true;
+    for (int i = Reval::kBegin; i < Reval::kCompactEnd; ++i) rv.ms[i] = clk.ms(i, i + 1);
+    rv.ok = true;
     return OXHIP_OK;
 }
 
@@ -1567,22 +1659,22 @@ int32_t oxhip_rrt_batch_get_revalidate_map(oxhip_rrt_batch* b, uint32_t problem,
                                            uint32_t* n_before) {
     if (!b || !n_before) return fail(OXHIP_ERR_BAD_ARG, "null argument");
     OX_TRY(setup_done(b, problem));
-    if (!b->reval_ok)
+    if (!b->reval.ok)
         return fail(OXHIP_ERR_BAD_ARG, "no revalidation map: call oxhip_rrt_batch_revalidate_trees after the last setup / solve / set_tree");
     OX_TRY(select_device(b->cfg.device));
-    const uint32_t n = b->rv_n_before[problem];
+    const uint32_t n = b->reval.n_before[problem];
     *n_before = n;
     if (cap < n) return fail(OXHIP_ERR_CAPACITY, "map buffer too small");
     const size_t base = (size_t)problem * b->dp.cap;
-    if (new_index) HIP_TRY(hipMemcpyAsync(new_index, b->rv_new_index.p + base, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
-    if (edge_ok) HIP_TRY(hipMemcpyAsync(edge_ok, b->rv_edge_ok.p + base, n, hipMemcpyDeviceToHost, b->stream));
+    if (new_index) HIP_TRY(hipMemcpyAsync(new_index, b->reval.new_index.p + base, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+    if (edge_ok) HIP_TRY(hipMemcpyAsync(edge_ok, b->reval.edge_ok.p + base, n, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return OXHIP_OK;
 }
 
 int32_t oxhip_rrt_batch_revalidate_last_timing(oxhip_rrt_batch* b, double* phase_ms) {
     if (!b || !phase_ms) return fail(OXHIP_ERR_BAD_ARG, "null argument");
-    for (int i = 0; i < 4; ++i) phase_ms[i] = b->reval_ms[i];
+    for (int i = 0; i < 4; ++i) phase_ms[i] = b->reval.ms[i];
     return OXHIP_OK;
 }
 
@@ -1647,7 +1739,7 @@ int32_t oxhip_rng_u64_batch(int32_t device, uint64_t seed, uint64_t stream, uint
     if (!out) return fail(OXHIP_ERR_BAD_ARG, "null argument");
     if (n == 0) return OXHIP_OK;
     OX_TRY(select_device(device));
-    TmpStream ts;
+    PooledStream ts;
     OX_TRY(ts.acquire(device));
     DevBuf<uint64_t> dout;
     HIP_TRY(dout.alloc(n));

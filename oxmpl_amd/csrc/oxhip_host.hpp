@@ -1,12 +1,16 @@
 // oxhip_host.hpp -- host-side helpers shared by the C-ABI translation units (oxhip_api.hip: RRT /
 // RRTConnect batches and primitives; oxhip_prm_api.hip: PRM).  Not installed.
 //
-// What oxhip_api.hip builds from them: the table of spaces (kSpaces, one row per oxhip_space) and create() in its steps --
-// validate_config (pure host code: space_resolution, se_space_resolution, so3_space_resolution and so2_space_resolution below), fill_params,
-// alloc_common (alloc_star at its place), the kernel kind, alloc_cells, alloc_shadow -- and the entry points' shared openings
-// (setup_done / ready) and bodies (copy_tree, op_batch with a TmpStream).  oxhip_prm_api.hip takes the same resolution helpers for
-// validate_prm_config, DevBuf for its workspaces and its roadmap, prm_bfs_path, the graph search of Planner::solve, and a PhaseClock
-// per service for its phase times (two calls of oxhip_api.hip time themselves with a local one).  No device code.
+// What oxhip_api.hip builds from them: the table of spaces (kSpaces, one row per oxhip_space); the RRT batch handle in parts (Trees,
+// Goals, Obstacles, Cells, Shadow, Solve, Paths, Reval, Star with Star::Wiring), each a set of DevBufs with a bind(DevParams&), a
+// PooledStream for the handle and one for the wiring, a PhaseClock per timed service (Solve's made with the handle, Paths' and
+// Reval's by their first call); create() in its steps -- validate_config (pure host code: space_resolution, se_space_resolution,
+// so3_space_resolution and so2_space_resolution below), fill_params, alloc_common (alloc_star at its place, then the binds), the
+// kernel kind, alloc_cells, alloc_shadow --; the filters of refresh_filter (connect_sphere_grid, midpoint_filter, star_edge_filter)
+// and pair_params over the pure threshold functions below; and the entry points' shared openings (setup_done / in_range / ready),
+// rules (drop_derived, reset_tree_caches, upload_radii) and bodies (copy_tree, op_batch with a PooledStream).  oxhip_prm_api.hip takes
+// the same resolution helpers for validate_prm_config, DevBuf for its workspaces and its roadmap, prm_bfs_path, the graph search of
+// Planner::solve, and a PhaseClock per service for its phase times.  No device code.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -89,6 +93,41 @@ inline uint64_t bernoulli_p_int(double p) {
 
 constexpr double kMaxMagnitude = 1e150;  // keeps every squared difference finite
 
+// ---- the RRT batch's obstacle filters (oxhip_api.hip: refresh_filter, pair_params): pure arithmetic, tests/cpp/test_rrt_filter_host.cpp
+// rrt_connect.hip's sphere grid lists sphere j in a cell when the squared distance centre - cell box is <= this: the sphere's own
+// validity threshold (valid iff d2 > t) with a relative 1e-9 of slack.  A sphere that is not listed contains no state of the cell.
+inline double connect_grid_threshold(double r) {
+    const double t = sqrt_le_threshold(r);
+    return std::isfinite(t) ? (t > 0.0 ? t * (1.0 + 1e-9) : t) : t;
+}
+// Conservative midpoint filter of a motion check.  Every state the check interpolates lies within h of the segment's midpoint --
+// h = half the motion's length with a relative 1e-6, plus an absolute 1e-9 * (largest coordinate magnitude in play), orders of
+// magnitude above the few-ulp rounding of the interpolation -- so d2(centre, mid) > (r + h)^2 proves sphere (centre, r) valid for
+// the whole motion.  The filter never decides a motion invalid.  A negative radius is never hit (-1: no d2 is below it).
+inline double midpoint_threshold(double r, double h) {
+    if (std::isnan(r) || std::isinf(r)) return r < 0.0 ? -1.0 : std::numeric_limits<double>::infinity();
+    if (r < 0.0) return -1.0;                      // distance > negative radius always holds
+    return (r + h) * (r + h) * (1.0 + 1e-9);
+}
+// RRT*'s edge kernel keeps sphere j when d2(centre, mid) <= (r_j + h)^2 (1 + 1e-9) with h anywhere in [h_lo, h_hi] (motions up to
+// search_radius long): its grid is built for the largest such ball (either end of h's range when r_j < 0).
+inline double star_edge_threshold(double r, double h_lo, double h_hi) {
+    const double a = (r + h_lo) * (r + h_lo), c = (r + h_hi) * (r + h_hi);
+    return (std::isnan(r) || std::isinf(r)) ? std::numeric_limits<double>::infinity() : std::fmax(a, c) * (1.0 + 1e-9) * (1.0 + 1e-12);
+}
+// The largest coordinate magnitude the midpoint filter's absolute margin (1e-9 of it) has to cover, at least 1: the bounds, the
+// sphere centres and, where given, the starts.  A planner's launch passes the starts: its thresholds are fixed before the launch
+// and a start may lie outside the bounds, whereas every other tree node lies inside them.  The kernels that check motions between
+// states a caller may have planted (path_simplify.hip, rrt_revalidate.hip) pass null: they widen this base per motion by both of
+// its ends (SeqSpace::motion_margin, seq_space.hpp), so the starts are in play there without being named here.
+inline double filter_maxabs(const oxhip_rrt_config& cfg, const std::vector<double>& centres, const std::vector<double>* starts) {
+    double maxabs = 1.0;
+    for (uint32_t k = 0; k < 2 * cfg.dim; ++k) maxabs = std::fmax(maxabs, std::fabs(cfg.bounds[k]));
+    if (starts) for (double v : *starts) maxabs = std::fmax(maxabs, std::fabs(v));
+    for (double v : centres) maxabs = std::fmax(maxabs, std::fabs(v));
+    return maxabs;
+}
+
 template <typename T>
 struct DevBuf {
     T* p = nullptr;
@@ -105,8 +144,8 @@ struct DevBuf {
     void swap(DevBuf& o) { std::swap(p, o.p); std::swap(n, o.n); }
 };
 
-// The clock of one service of a handle, or of one call: n events, made with their owner (which create() builds, and a call declares,
-// once the device is current) and destroyed with it: like DevBuf, after destroy() has made the device current.  The owner names its
+// The clock of one service of a handle: n events, made with their owner (which create(), or the service's first call, builds once
+// the device is current) and destroyed with it: like DevBuf, after destroy() has made the device current.  The owner names its
 // marks with an enum.  mark(i) records mark i on the stream; once the stream is synchronised, ms(i, j) is the GPU time from mark i
 // to mark j (0 where the runtime refuses).  A service reads only marks that it recorded itself, in the same call.  `made` is the
 // first error of making the events, for the owner's create() to refuse with; event(i) is for a launcher that records a mark itself.
@@ -136,14 +175,18 @@ inline int32_t alloc_failed(hipError_t e) { return fail(OXHIP_ERR_HIP, std::stri
 hipError_t oxhip_stream_acquire(int device, hipStream_t* out);   // non-blocking streams; `device` is the current device
 void oxhip_stream_release(int device, hipStream_t s);            // synchronises s first
 
-struct TmpStream {   // a pooled stream for one call of a stand-alone primitive
+struct PooledStream {   // a pooled stream, held by one call of a stand-alone primitive or by a handle, and given back with its holder
     hipStream_t s = nullptr;
     int device = 0;
-    ~TmpStream() { if (s) oxhip_stream_release(device, s); }
-    int32_t acquire(int dev) {   // `dev` is the current device
-        hipError_t e = oxhip_stream_acquire(dev, &s);
+    PooledStream() = default;
+    PooledStream(const PooledStream&) = delete;
+    ~PooledStream() { close(); }
+    void close() { if (s) oxhip_stream_release(device, s); s = nullptr; }
+    operator hipStream_t() const { return s; }
+    hipError_t take(int dev) { device = dev; return oxhip_stream_acquire(dev, &s); }   // `dev` is the current device
+    int32_t acquire(int dev) {
+        hipError_t e = take(dev);
         if (e != hipSuccess) return fail(OXHIP_ERR_HIP, std::string("oxhip_stream_acquire(device, &ts.s): ") + hipGetErrorString(e));
-        device = dev;
         return OXHIP_OK;
     }
 };
