@@ -30,7 +30,25 @@ class RealVectorState:
         return "<RealVectorState values=%r>" % (self._values,)
 
 
-class RealVectorStateSpace:
+def _device_distance(op, state1, state2):
+    """`op` of the two states as one-row arrays, on the device -> the one result"""
+    return float(op(np.array([state1.values], dtype=np.float64), np.array([state2.values], dtype=np.float64))[0])
+
+
+class _StateSpace:
+    """What the four state spaces share.  Each sets `dimension` (the width of a state's `values`) and
+    `longest_valid_segment_fraction` (0.05, as the reference) in its constructor."""
+
+    def set_longest_valid_segment_fraction(self, fraction):
+        if 0.0 < fraction <= 1.0:
+            self.longest_valid_segment_fraction = float(fraction)
+        elif fraction <= 0.0:
+            self.longest_valid_segment_fraction = 0.0
+        else:
+            self.longest_valid_segment_fraction = 1.0
+
+
+class RealVectorStateSpace(_StateSpace):
     """oxmpl_py.base.RealVectorStateSpace (oxmpl-py/src/base/real_vector_state_space.rs:15-57).
     Construction errors are ValueError with the reference's messages (error.rs:40-52)."""
 
@@ -53,9 +71,7 @@ class RealVectorStateSpace:
         self.longest_valid_segment_fraction = 0.05
 
     def distance(self, state1, state2):
-        a = np.array([state1.values], dtype=np.float64)
-        b = np.array([state2.values], dtype=np.float64)
-        return float(capi.distance_batch(a, b)[0])
+        return _device_distance(capi.distance_batch, state1, state2)
 
     def get_maximum_extent(self):
         if any((not math.isfinite(lo)) or (not math.isfinite(hi)) for lo, hi in self.bounds):
@@ -64,14 +80,6 @@ class RealVectorStateSpace:
         z = np.zeros((1, self.dimension))
         w = np.array([[hi - lo for lo, hi in self.bounds]], dtype=np.float64)
         return float(capi.distance_batch(w, z)[0])
-
-    def set_longest_valid_segment_fraction(self, fraction):
-        if 0.0 < fraction <= 1.0:
-            self.longest_valid_segment_fraction = float(fraction)
-        elif fraction <= 0.0:
-            self.longest_valid_segment_fraction = 0.0
-        else:
-            self.longest_valid_segment_fraction = 1.0
 
 
 class SphereBoxValidityChecker:
@@ -107,7 +115,7 @@ class SO3State:
         return "<SO3State x=%r, y=%r, z=%r, w=%r>" % (self.x, self.y, self.z, self.w)
 
 
-class SO3StateSpace:
+class SO3StateSpace(_StateSpace):
     """oxmpl_py.base.SO3StateSpace (oxmpl-py/src/base/so3_state_space.rs): SO3StateSpace(bounds=None | (SO3State, max_angle)).
     None: the identity and PI, every rotation.  A negative max_angle is ValueError (StateSpaceError::InvalidAngularDistance);
     max_angle is clamped to PI (oxmpl/src/base/spaces/so3_state_space.rs:57-76).  `distance` is evaluated by the HIP library."""
@@ -128,20 +136,10 @@ class SO3StateSpace:
         self.longest_valid_segment_fraction = 0.05
 
     def distance(self, state1, state2):
-        a = np.array([state1.values], dtype=np.float64)
-        b = np.array([state2.values], dtype=np.float64)
-        return float(capi.so3_op_batch(0, a, b)[0])
+        return _device_distance(lambda a, b: capi.so3_op_batch(0, a, b), state1, state2)
 
     def get_maximum_extent(self):
         return 0.5 * math.pi
-
-    def set_longest_valid_segment_fraction(self, fraction):
-        if 0.0 < fraction <= 1.0:
-            self.longest_valid_segment_fraction = float(fraction)
-        elif fraction <= 0.0:
-            self.longest_valid_segment_fraction = 0.0
-        else:
-            self.longest_valid_segment_fraction = 1.0
 
     def config_bounds(self):
         """the C ABI's reading of oxhip_rrt_config.bounds for SO(3): (cx, cy, cz, cw, max_angle)"""
@@ -188,7 +186,7 @@ class SO2State:
         return "<SO2State value=%r>" % self.value
 
 
-class SO2StateSpace:
+class SO2StateSpace(_StateSpace):
     """oxmpl_py.base.SO2StateSpace: SO2StateSpace(bounds=None | (lo, hi)).  None: the full circle (-PI, PI).  lo >= hi is
     ValueError (StateSpaceError::InvalidBound); the bounds are clamped to [-PI, PI]
     (oxmpl/src/base/spaces/so2_state_space.rs:57-74).  `distance` is add, subtract and fmod only: evaluated here, the bits
@@ -207,14 +205,6 @@ class SO2StateSpace:
 
     def get_maximum_extent(self):
         return math.pi
-
-    def set_longest_valid_segment_fraction(self, fraction):
-        if 0.0 < fraction <= 1.0:
-            self.longest_valid_segment_fraction = float(fraction)
-        elif fraction <= 0.0:
-            self.longest_valid_segment_fraction = 0.0
-        else:
-            self.longest_valid_segment_fraction = 1.0
 
     def config_bounds(self):
         """the C ABI's reading of oxhip_rrt_config.bounds for SO(2): (lo, hi)"""
@@ -258,7 +248,7 @@ class SE3State:
         return "<SE3State x=%r, y=%r, z=%r, rotation=%r>" % (self.x, self.y, self.z, self.rotation)
 
 
-class SE3StateSpace:
+class SE3StateSpace(_StateSpace):
     """SE(3) = R^3 x SO(3), assembled from the reference's RealVectorStateSpace(3) and SO3StateSpace with OMPL's weights
     (include/oxmpl_hip.h, OXHIP_SPACE_SE3): SE3StateSpace(bounds_xyz, rotation_bounds=None | (SO3State, max_angle)).
     distance = distance_R3 + distance_SO3, evaluated by the HIP library; extent = extent_R3 + 0.5 * PI."""
@@ -270,20 +260,10 @@ class SE3StateSpace:
         self.longest_valid_segment_fraction = 0.05
 
     def distance(self, state1, state2):
-        a = np.array([state1.values], dtype=np.float64)
-        b = np.array([state2.values], dtype=np.float64)
-        return float(capi.se3_op_batch(0, a, b)[0])
+        return _device_distance(lambda a, b: capi.se3_op_batch(0, a, b), state1, state2)
 
     def get_maximum_extent(self):
         return self.position.get_maximum_extent() + 0.5 * math.pi
-
-    def set_longest_valid_segment_fraction(self, fraction):
-        if 0.0 < fraction <= 1.0:
-            self.longest_valid_segment_fraction = float(fraction)
-        elif fraction <= 0.0:
-            self.longest_valid_segment_fraction = 0.0
-        else:
-            self.longest_valid_segment_fraction = 1.0
 
     def config_bounds(self):
         """the C ABI's reading of oxhip_rrt_config.bounds for SE(3): the (lo, hi) pairs of x, y, z, then (cx, cy, cz, cw, max_angle)"""
@@ -318,53 +298,43 @@ class ProblemDefinition:
         self.space, self.start_state, self.goal = space, start_state, goal
 
     @staticmethod
+    def _from(space_cls, state_cls, space, start_state, goal):
+        """the body of the four from_* constructors: a space_cls, a ball goal and two state_cls states -> ProblemDefinition"""
+        if not isinstance(space, space_cls):   # ("an SO3StateSpace", "a RealVectorStateSpace")
+            raise TypeError("space must be %s %s" % ("an" if space_cls.__name__.startswith("S") else "a", space_cls.__name__))
+        if not hasattr(goal, "target") or not hasattr(goal, "radius"):
+            raise TypeError("the GPU path needs a ball goal: an object with `target` and `radius` attributes")
+        if state_cls is RealVectorState:       # as the reference: any state of the space's width
+            if len(start_state.values) != space.dimension or len(goal.target.values) != space.dimension:
+                raise ValueError("state dimension does not match the space")
+        elif not isinstance(start_state, state_cls) or not isinstance(goal.target, state_cls):
+            raise TypeError("start_state and goal.target must be %s" % state_cls.__name__)
+        return ProblemDefinition(space, start_state, goal)
+
+    @staticmethod
     def from_real_vector(space, start_state, goal):
         """`goal` is any object with a `target` (RealVectorState) and a `radius`: the reference's
         CircularGoal classes qualify as they are.  is_satisfied(s) = distance(s, target) <= radius;
         the device goal sampler returns `target` (README.md:160-162), `goal.sample_goal` is not called."""
-        if not isinstance(space, RealVectorStateSpace):
-            raise TypeError("space must be a RealVectorStateSpace")
-        if not hasattr(goal, "target") or not hasattr(goal, "radius"):
-            raise TypeError("the GPU path needs a ball goal: an object with `target` and `radius` attributes")
-        if len(start_state.values) != space.dimension or len(goal.target.values) != space.dimension:
-            raise ValueError("state dimension does not match the space")
-        return ProblemDefinition(space, start_state, goal)
+        return ProblemDefinition._from(RealVectorStateSpace, RealVectorState, space, start_state, goal)
 
     @staticmethod
     def from_so3(space, start_state, goal):
         """oxmpl_py ProblemDefinition.from_so3 (oxmpl-py/src/base/problem_definition.rs:105-131).  `goal`: any object with a
         `target` (SO3State) and a `radius`; is_satisfied(s) = distance(s, target) <= radius, sample_goal() = target."""
-        if not isinstance(space, SO3StateSpace):
-            raise TypeError("space must be an SO3StateSpace")
-        if not hasattr(goal, "target") or not hasattr(goal, "radius"):
-            raise TypeError("the GPU path needs a ball goal: an object with `target` and `radius` attributes")
-        if not isinstance(start_state, SO3State) or not isinstance(goal.target, SO3State):
-            raise TypeError("start_state and goal.target must be SO3State")
-        return ProblemDefinition(space, start_state, goal)
+        return ProblemDefinition._from(SO3StateSpace, SO3State, space, start_state, goal)
 
     @staticmethod
     def from_so2(space, start_state, goal):
         """oxmpl_py ProblemDefinition.from_so2.  `goal`: any object with a `target` (SO2State) and a `radius`;
         is_satisfied(s) = distance(s, target) <= radius, sample_goal() = target (the fixture's arc sampler is not built)."""
-        if not isinstance(space, SO2StateSpace):
-            raise TypeError("space must be an SO2StateSpace")
-        if not hasattr(goal, "target") or not hasattr(goal, "radius"):
-            raise TypeError("the GPU path needs a ball goal: an object with `target` and `radius` attributes")
-        if not isinstance(start_state, SO2State) or not isinstance(goal.target, SO2State):
-            raise TypeError("start_state and goal.target must be SO2State")
-        return ProblemDefinition(space, start_state, goal)
+        return ProblemDefinition._from(SO2StateSpace, SO2State, space, start_state, goal)
 
     @staticmethod
     def from_se3(space, start_state, goal):
         """`goal`: any object with a `target` (SE3State) and a `radius`; is_satisfied(s) = distance(s, target) <= radius in the
         SE(3) distance, sample_goal() = target."""
-        if not isinstance(space, SE3StateSpace):
-            raise TypeError("space must be an SE3StateSpace")
-        if not hasattr(goal, "target") or not hasattr(goal, "radius"):
-            raise TypeError("the GPU path needs a ball goal: an object with `target` and `radius` attributes")
-        if not isinstance(start_state, SE3State) or not isinstance(goal.target, SE3State):
-            raise TypeError("start_state and goal.target must be SE3State")
-        return ProblemDefinition(space, start_state, goal)
+        return ProblemDefinition._from(SE3StateSpace, SE3State, space, start_state, goal)
 
 
 class Path:

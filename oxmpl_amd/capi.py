@@ -4,6 +4,7 @@ Mirrors the header one to one; numpy arrays in, numpy arrays out.  Nothing here 
 every call goes into the HIP library, and a missing library or GPU raises.
 """
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -254,7 +255,76 @@ def _p(a, t=_dp):
     return a.ctypes.data_as(t)
 
 
-class RRTBatch:
+_POINTER = {np.float64: _dp, np.uint8: _u8p, np.uint32: _u32p, np.int32: _i32p, np.uint64: _u64p}
+
+
+def _sized(fn, lead, buffers, count_type=C.c_uint32, capacity=lambda n: n, fill_empty=True):
+    """The ABI's size-then-fill protocol: `fn(*lead, <buffers>, capacity, &count)` is called with null buffers and capacity 0,
+    which writes the count (OK or ERR_CAPACITY), then with one array per (dtype, row width; 0: no second axis) of `buffers`.
+    An array holds at least one element, so that an empty result still hands the library a buffer.  -> the arrays, cut to
+    capacity(count) rows.  fill_empty=False leaves the second call out for a count of 0."""
+    n = count_type()
+    st = fn(*lead, *([None] * len(buffers)), 0, C.byref(n))
+    if st not in (OK, ERR_CAPACITY):
+        _check(st)
+    cap = capacity(n.value)
+    out = [np.zeros((max(cap, 1), width) if width else max(cap, 1), dtype=dtype) for dtype, width in buffers]
+    if cap or fill_empty:
+        _check(fn(*lead, *[_p(a, _POINTER[dtype]) for a, (dtype, _) in zip(out, buffers)], cap, C.byref(n)))
+    return [a[:cap] for a in out]
+
+
+def _phase_ms(fn, h, n_phases, *scalars):
+    """a *_last_timing entry point: n_phases HIP-event times in ms, then `scalars` (ctypes objects, written in place)"""
+    ms = np.zeros(n_phases, dtype=np.float64)
+    _check(fn(h, _p(ms), *[C.byref(x) for x in scalars]))
+    return ms
+
+
+def _fill_bounds(cfg, dim, bounds, space, se3=False):
+    """cfg.dim and cfg.bounds of a Config / PrmConfig from a flat or nested `bounds`: how many values the space kind asks for is
+    checked here, what they are by the library.  se3: the entry point reads SE(3)'s eleven values (one that does not gets dim
+    pairs and refuses the kind itself)."""
+    cfg.dim = dim
+    b = _f64(bounds).reshape(-1)
+    if space == SPACE_SO3:
+        if b.size != 5:
+            raise OxhipError(ERR_BAD_ARG, "SO(3) bounds are (cx, cy, cz, cw, max_angle)")
+    elif se3 and space == SPACE_SE3:
+        if b.size != 11:
+            raise OxhipError(ERR_BAD_ARG, "SE(3) bounds are (x lo, x hi, y lo, y hi, z lo, z hi, cx, cy, cz, cw, max_angle)")
+    elif b.size != 2 * dim:
+        raise OxhipError(ERR_BAD_ARG, "bounds must hold dim (lo,hi) pairs")  # StateSpaceError::DimensionMismatch
+    for i, v in enumerate(b[:2 * MAX_DIM]):  # dim > MAX_DIM is rejected by the library
+        cfg.bounds[i] = v
+
+
+class _Handle:
+    """What RRTBatch and PRMRoadmap share: the life of the library's handle and the sphere / box uploads.  `_ABI` is the
+    prefix of the class's entry points."""
+
+    def _fn(self, name):
+        return getattr(lib(), self._ABI + name)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._fn("destroy")(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def set_spheres(self, centres, radii):
+        r = _f64(radii).reshape(-1)
+        c = _f64(centres, (r.size, 3 if self.space == SPACE_SE3 else self.dim))
+        _check(self._fn("set_spheres")(self._h, _p(c), _p(r), r.size))
+
+    def set_boxes(self, lo, hi):
+        lo = _f64(lo).reshape(-1, self.dim)
+        hi = _f64(hi, lo.shape)
+        _check(self._fn("set_boxes")(self._h, _p(lo), _p(hi), lo.shape[0]))
+
+
+class RRTBatch(_Handle):
     """P independent oxmpl RRT planners (RealVectorStateSpace, ball goal, sphere/box validity)
     grown on one GPU.  Thin wrapper of the oxhip_rrt_batch_* entry points.
 
@@ -268,6 +338,7 @@ class RRTBatch:
     space=SPACE_SE3 (dim 7, states (x, y, z, qx, qy, qz, qw); planner=PLANNER_RRT_CONNECT): `bounds` holds eleven values, the
     (lo, hi) pairs of x, y, z and then (cx, cy, cz, cw, max_angle) of the rotation; set_body gives the rigid body's spheres
     and set_spheres the world's (3-wide centres)."""
+    _ABI = "oxhip_rrt_batch_"
 
     def __init__(self, dim, bounds, max_distance, goal_bias, n_problems, max_nodes=10000,
                  lvs_fraction=0.05, stop_at_goal=True, seed=0, first_problem_id=0, device=0,
@@ -275,19 +346,7 @@ class RRTBatch:
                  goal_sampler=GOAL_SAMPLE_CENTRE, debug_flags=0, star_pool_share=0, frozen_split=0):
         cfg = Config()
         cfg.struct_size = C.sizeof(Config)
-        cfg.dim = dim
-        b = _f64(bounds).reshape(-1)
-        if space == SPACE_SO3:
-            if b.size != 5:
-                raise OxhipError(ERR_BAD_ARG, "SO(3) bounds are (cx, cy, cz, cw, max_angle)")
-            b = np.concatenate([b, np.zeros(2 * dim - 5 if dim >= 3 else 0)])
-        elif space == SPACE_SE3:
-            if b.size != 11:
-                raise OxhipError(ERR_BAD_ARG, "SE(3) bounds are (x lo, x hi, y lo, y hi, z lo, z hi, cx, cy, cz, cw, max_angle)")
-        elif b.size != 2 * dim:
-            raise OxhipError(ERR_BAD_ARG, "bounds must hold dim (lo,hi) pairs")  # StateSpaceError::DimensionMismatch
-        for i, v in enumerate(b[:2 * MAX_DIM]):  # dim > MAX_DIM is rejected by the library
-            cfg.bounds[i] = v
+        _fill_bounds(cfg, dim, bounds, space, se3=True)
         cfg.max_distance, cfg.goal_bias, cfg.lvs_fraction = max_distance, goal_bias, lvs_fraction
         cfg.n_problems, cfg.max_nodes = n_problems, max_nodes
         cfg.stop_at_goal, cfg.kernel = int(bool(stop_at_goal)), kernel
@@ -301,23 +360,6 @@ class RRTBatch:
         self.dim, self.n_problems, self.max_nodes = dim, n_problems, max_nodes
         self._h = C.c_void_p()
         _check(lib().oxhip_rrt_batch_create(C.byref(cfg), C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().oxhip_rrt_batch_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
-
-    def set_spheres(self, centres, radii):
-        r = _f64(radii).reshape(-1)
-        c = _f64(centres, (r.size, 3 if self.space == SPACE_SE3 else self.dim))
-        _check(lib().oxhip_rrt_batch_set_spheres(self._h, _p(c), _p(r), r.size))
-
-    def set_boxes(self, lo, hi):
-        lo = _f64(lo).reshape(-1, self.dim)
-        hi = _f64(hi, lo.shape)
-        _check(lib().oxhip_rrt_batch_set_boxes(self._h, _p(lo), _p(hi), lo.shape[0]))
 
     def set_segments(self, segments, clearance):
         """SE(2) batches: the segment-soup checker (disc robot of radius `clearance`)"""
@@ -360,22 +402,11 @@ class RRTBatch:
         return out
 
     def tree(self, problem):
-        n = C.c_uint32()
-        st = lib().oxhip_rrt_batch_get_tree(self._h, problem, None, None, 0, C.byref(n))
-        if st not in (OK, ERR_CAPACITY):
-            _check(st)
-        states = np.empty((n.value, self.dim), dtype=np.float64)
-        parents = np.empty(n.value, dtype=np.int32)
-        _check(lib().oxhip_rrt_batch_get_tree(self._h, problem, _p(states), _p(parents, _i32p), n.value, C.byref(n)))
-        return states, parents
+        return tuple(_sized(lib().oxhip_rrt_batch_get_tree, (self._h, problem), [(np.float64, self.dim), (np.int32, 0)]))
 
     def costs(self, problem):
         """RRT*: Node::cost of every node (rrt_star.rs:26)"""
-        n = C.c_uint32()
-        _check(lib().oxhip_rrt_batch_get_costs(self._h, problem, None, 0, C.byref(n)))
-        out = np.empty(n.value, dtype=np.float64)
-        _check(lib().oxhip_rrt_batch_get_costs(self._h, problem, _p(out), n.value, C.byref(n)))
-        return out
+        return _sized(lib().oxhip_rrt_batch_get_costs, (self._h, problem), [(np.float64, 0)])[0]
 
     def goal_counts(self):
         """RRTConnect: goal-tree sizes and the last goal-tree node of each solution"""
@@ -385,24 +416,10 @@ class RRTBatch:
         return dict(nodes=nodes, end_node=end)
 
     def goal_tree(self, problem):
-        n = C.c_uint32()
-        st = lib().oxhip_rrt_batch_get_goal_tree(self._h, problem, None, None, 0, C.byref(n))
-        if st not in (OK, ERR_CAPACITY):
-            _check(st)
-        states = np.empty((n.value, self.dim), dtype=np.float64)
-        parents = np.empty(n.value, dtype=np.int32)
-        _check(lib().oxhip_rrt_batch_get_goal_tree(self._h, problem, _p(states), _p(parents, _i32p), n.value, C.byref(n)))
-        return states, parents
+        return tuple(_sized(lib().oxhip_rrt_batch_get_goal_tree, (self._h, problem), [(np.float64, self.dim), (np.int32, 0)]))
 
     def path(self, problem):
-        ln = C.c_uint32()
-        st = lib().oxhip_rrt_batch_get_path(self._h, problem, None, 0, C.byref(ln))
-        if st not in (OK, ERR_CAPACITY):
-            _check(st)
-        out = np.empty((ln.value, self.dim), dtype=np.float64)
-        if ln.value:
-            _check(lib().oxhip_rrt_batch_get_path(self._h, problem, _p(out), ln.value, C.byref(ln)))
-        return out
+        return _sized(lib().oxhip_rrt_batch_get_path, (self._h, problem), [(np.float64, self.dim)], fill_empty=False)[0]
 
     # ---- the whole batch's paths: extraction and shortcutting on the device
 
@@ -413,13 +430,8 @@ class RRTBatch:
     def paths(self):
         """(offsets [P+1] u64, rows [total][dim]): problem p's path is rows offsets[p] .. offsets[p+1], bit for bit path(p)"""
         offsets = np.zeros(self.n_problems + 1, dtype=np.uint64)
-        total = C.c_uint64()
-        st = lib().oxhip_rrt_batch_get_paths(self._h, _p(offsets, _u64p), None, 0, C.byref(total))
-        if st not in (OK, ERR_CAPACITY):
-            _check(st)
-        rows = np.zeros((max(total.value, 1), self.dim), dtype=np.float64)
-        _check(lib().oxhip_rrt_batch_get_paths(self._h, _p(offsets, _u64p), _p(rows), total.value, C.byref(total)))
-        return offsets, rows[:total.value]
+        rows, = _sized(lib().oxhip_rrt_batch_get_paths, (self._h, _p(offsets, _u64p)), [(np.float64, self.dim)], C.c_uint64)
+        return offsets, rows
 
     def simplify_paths(self, max_span=0, chunk_problems=0):
         """Shortcut every path over its own waypoints (include/oxmpl_hip.h states the semantics); extracts the paths first
@@ -431,28 +443,18 @@ class RRTBatch:
         checks [P] u64)"""
         P = self.n_problems
         offsets = np.zeros(P + 1, dtype=np.uint64)
-        total = C.c_uint64()
-        st = lib().oxhip_rrt_batch_get_simplified_paths(self._h, _p(offsets, _u64p), None, None, 0, C.byref(total))
-        if st not in (OK, ERR_CAPACITY):
-            _check(st)
-        rows = np.zeros((max(total.value, 1), self.dim), dtype=np.float64)
-        idx = np.zeros(max(total.value, 1), dtype=np.uint32)
-        _check(lib().oxhip_rrt_batch_get_simplified_paths(self._h, _p(offsets, _u64p), _p(rows), _p(idx, _u32p), total.value,
-                                                          C.byref(total)))
+        rows, idx = _sized(lib().oxhip_rrt_batch_get_simplified_paths, (self._h, _p(offsets, _u64p)),
+                           [(np.float64, self.dim), (np.uint32, 0)], C.c_uint64)
         raw, simp, checks = np.zeros(P), np.zeros(P), np.zeros(P, dtype=np.uint64)
         _check(lib().oxhip_rrt_batch_get_simplify_results(self._h, _p(raw), _p(simp), _p(checks, _u64p)))
-        return offsets, rows[:total.value], idx[:total.value], raw, simp, checks
+        return offsets, rows, idx, raw, simp, checks
 
     def path_valid_matrix(self, problem, max_span=0):
         """test hook: valid(i, j) of the extracted path of `problem` as the pair kernel evaluates it, [L][L] bool (i < j)"""
-        ln = C.c_uint32()
-        st = lib().oxhip_rrt_batch_path_valid_matrix(self._h, problem, int(max_span), None, 0, C.byref(ln))
-        if st not in (OK, ERR_CAPACITY):
-            _check(st)
-        L = ln.value
-        out = np.zeros(max(L * L, 1), dtype=np.uint8)
-        _check(lib().oxhip_rrt_batch_path_valid_matrix(self._h, problem, int(max_span), _p(out, _u8p), L * L, C.byref(ln)))
-        return out[:L * L].reshape(L, L).astype(bool)
+        out, = _sized(lib().oxhip_rrt_batch_path_valid_matrix, (self._h, problem, int(max_span)), [(np.uint8, 0)],
+                      capacity=lambda L: L * L)    # the count is the path's length L, the buffer holds L * L verdicts
+        L = math.isqrt(out.size)
+        return out.reshape(L, L).astype(bool)
 
     def paths_last_timing(self):
         """dict(extract_ms, pairs_ms, dp_ms, rounds): HIP-event times of the last extract_paths / simplify_paths"""
@@ -473,20 +475,12 @@ class RRTBatch:
     def revalidate_map(self, problem):
         """(new_index [n_before] i32, edge_ok [n_before] bool) of the last revalidate_trees: where every old node went (-1:
         removed) and the verdict of its edge from its parent (the root's is True)"""
-        n = C.c_uint32()
-        st = lib().oxhip_rrt_batch_get_revalidate_map(self._h, problem, None, None, 0, C.byref(n))
-        if st not in (OK, ERR_CAPACITY):
-            _check(st)
-        new_index = np.zeros(max(n.value, 1), dtype=np.int32)
-        edge_ok = np.zeros(max(n.value, 1), dtype=np.uint8)
-        _check(lib().oxhip_rrt_batch_get_revalidate_map(self._h, problem, _p(new_index, _i32p), _p(edge_ok, _u8p), n.value, C.byref(n)))
-        return new_index[:n.value], edge_ok[:n.value].astype(bool)
+        new_index, edge_ok = _sized(lib().oxhip_rrt_batch_get_revalidate_map, (self._h, problem), [(np.int32, 0), (np.uint8, 0)])
+        return new_index, edge_ok.astype(bool)
 
     def revalidate_last_timing(self):
         """dict(phase_ms=[edge checks, survival, scan, compaction + remap + skip flags]) of the last revalidate_trees"""
-        ms = np.zeros(4)
-        _check(lib().oxhip_rrt_batch_revalidate_last_timing(self._h, _p(ms)))
-        return dict(phase_ms=ms)
+        return dict(phase_ms=_phase_ms(lib().oxhip_rrt_batch_revalidate_last_timing, self._h, 4))
 
     def last_timing(self):
         ms, launches, kind = C.c_double(), C.c_uint32(), C.c_uint32()
@@ -595,25 +589,18 @@ def se3_op_batch(op, a, b, t=None, device=0):
     return out
 
 
-class PRMRoadmap:
+class PRMRoadmap(_Handle):
     """oxmpl's PRM (prm.rs) on one GPU: roadmap construction and queries.  Thin wrapper of oxhip_prm_*.
 
     space=SPACE_SO3 (dim 4, quaternions (x, y, z, w)): `bounds` is (cx, cy, cz, cw, max_angle), as for RRTBatch, and
     set_spheres takes the forbidden cones (centre quaternion, radius in the SO(3) distance)."""
+    _ABI = "oxhip_prm_"
 
     def __init__(self, dim, bounds, connection_radius, max_milestones, timeout=0.0, lvs_fraction=0.05,
                  max_samples=0, seed=0, stream=0, device=0, knn_k=0, space=SPACE_REAL_VECTOR):
         cfg = PrmConfig()
         cfg.struct_size = C.sizeof(PrmConfig)
-        cfg.dim = dim
-        b = _f64(bounds).reshape(-1)
-        if space == SPACE_SO3:
-            if b.size != 5:
-                raise OxhipError(ERR_BAD_ARG, "SO(3) bounds are (cx, cy, cz, cw, max_angle)")
-        elif b.size != 2 * dim:
-            raise OxhipError(ERR_BAD_ARG, "bounds must hold dim (lo,hi) pairs")
-        for i, v in enumerate(b[:2 * MAX_DIM]):
-            cfg.bounds[i] = v
+        _fill_bounds(cfg, dim, bounds, space)
         cfg.timeout, cfg.connection_radius, cfg.lvs_fraction = timeout, connection_radius, lvs_fraction
         cfg.max_milestones, cfg.device, cfg.max_samples = max_milestones, device, max_samples
         cfg.seed, cfg.stream = seed, stream
@@ -622,23 +609,6 @@ class PRMRoadmap:
         self.dim, self.space = dim, space
         self._h = C.c_void_p()
         _check(lib().oxhip_prm_create(C.byref(cfg), C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().oxhip_prm_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
-
-    def set_spheres(self, centres, radii):
-        r = _f64(radii).reshape(-1)
-        c = _f64(centres, (r.size, self.dim))
-        _check(lib().oxhip_prm_set_spheres(self._h, _p(c), _p(r), r.size))
-
-    def set_boxes(self, lo, hi):
-        lo = _f64(lo).reshape(-1, self.dim)
-        hi = _f64(hi, lo.shape)
-        _check(lib().oxhip_prm_set_boxes(self._h, _p(lo), _p(hi), lo.shape[0]))
 
     def setup(self, start, goal_centre, goal_radius):
         s, g = _f64(start, (self.dim,)), _f64(goal_centre, (self.dim,))
@@ -696,20 +666,22 @@ class PRMRoadmap:
 
     def last_timing(self):
         """dict(phase_ms=[sample, pairs, edges, sort+csr, query, bfs], candidates, redraw_batches)"""
-        ms = np.zeros(6, dtype=np.float64)
         c, r = C.c_uint64(), C.c_uint32()
-        _check(lib().oxhip_prm_last_timing(self._h, _p(ms), C.byref(c), C.byref(r)))
-        return dict(phase_ms=[float(v) for v in ms], candidates=c.value, redraw_batches=r.value)
+        ms = _phase_ms(lib().oxhip_prm_last_timing, self._h, 6, c, r)
+        return dict(phase_ms=ms.tolist(), candidates=c.value, redraw_batches=r.value)
 
     # ---- a batch of queries on the roadmap as it stands: flags, breadth-first search and paths on the device
 
     def solve_batch(self, starts, goal_centres, goal_radii, timeout_s=0.0, chunk_queries=0):
         """Q (start, ball goal) queries in one call, each answered exactly as set_problem + solve answer it.
         Returns the per-query statuses [Q] (OK, ERR_INVALID_START_STATE, ERR_NO_SOLUTION_FOUND, ERR_TIMEOUT)."""
+        return self._solve_batch(lib().oxhip_prm_solve_batch, starts, goal_centres, goal_radii, timeout_s, chunk_queries)
+
+    def _solve_batch(self, fn, starts, goal_centres, goal_radii, timeout_s, *options):
         r = _f64(goal_radii).reshape(-1)
         s, g = _f64(starts, (r.size, self.dim)), _f64(goal_centres, (r.size, self.dim))
         status = np.zeros(max(r.size, 1), dtype=np.int32)
-        _check(lib().oxhip_prm_solve_batch(self._h, r.size, _p(s), _p(g), _p(r), timeout_s, chunk_queries, _p(status, _i32p)))
+        _check(fn(self._h, r.size, _p(s), _p(g), _p(r), timeout_s, *options, _p(status, _i32p)))
         self._batch_q = r.size
         return status[:r.size]
 
@@ -744,10 +716,9 @@ class PRMRoadmap:
 
     def batch_last_timing(self):
         """dict(phase_ms=[flags, search, paths, copies], rounds) of the last batch"""
-        ms = np.zeros(4, dtype=np.float64)
         r = C.c_uint32()
-        _check(lib().oxhip_prm_batch_last_timing(self._h, _p(ms), C.byref(r)))
-        return dict(phase_ms=[float(v) for v in ms], rounds=r.value)
+        ms = _phase_ms(lib().oxhip_prm_batch_last_timing, self._h, 4, r)
+        return dict(phase_ms=ms.tolist(), rounds=r.value)
 
     # ---- the same batch answered with shortest paths (DESIGN.md section 19)
 
@@ -755,13 +726,8 @@ class PRMRoadmap:
         """Q queries in one call, each answered with a shortest path on the roadmap: weights 0 = the space's distance, 1 = unit
         (fewest hops), 2 = zero (test only).  Statuses and query sets are solve_batch's; batch_results / batch_paths /
         batch_query_sets / batch_last_timing serve this batch as they serve solve_batch's."""
-        r = _f64(goal_radii).reshape(-1)
-        s, g = _f64(starts, (r.size, self.dim)), _f64(goal_centres, (r.size, self.dim))
-        status = np.zeros(max(r.size, 1), dtype=np.int32)
-        _check(lib().oxhip_prm_solve_batch_shortest(self._h, r.size, _p(s), _p(g), _p(r), timeout_s, chunk_queries, weights,
-                                                    _p(status, _i32p)))
-        self._batch_q = r.size
-        return status[:r.size]
+        return self._solve_batch(lib().oxhip_prm_solve_batch_shortest, starts, goal_centres, goal_radii, timeout_s, chunk_queries,
+                                 weights)
 
     def batch_costs(self):
         """the label of the goal milestone reached, per query of the last shortest-path batch (+inf unless OK)"""
@@ -814,9 +780,7 @@ class PRMRoadmap:
 
     def revalidate_last_timing(self):
         """dict(phase_ms=[milestone validity, pair emission, edge checks, compaction]) of the last revalidate"""
-        ms = np.zeros(4, dtype=np.float64)
-        _check(lib().oxhip_prm_revalidate_last_timing(self._h, _p(ms)))
-        return dict(phase_ms=[float(v) for v in ms])
+        return dict(phase_ms=_phase_ms(lib().oxhip_prm_revalidate_last_timing, self._h, 4).tolist())
 
     # ---- the roadmap grown in place (DESIGN.md section 23)
 
@@ -836,9 +800,7 @@ class PRMRoadmap:
 
     def grow_timing(self):
         """dict(phase_ms=[liveness mask, keys from CSR, sample, pairs (+ filter), edges, sort + CSR]) of the last grow"""
-        ms = np.zeros(6, dtype=np.float64)
-        _check(lib().oxhip_prm_grow_last_timing(self._h, _p(ms)))
-        return dict(phase_ms=[float(v) for v in ms])
+        return dict(phase_ms=_phase_ms(lib().oxhip_prm_grow_last_timing, self._h, 6).tolist())
 
     # ---- the roadmap as a graph: connected components, and pruning (DESIGN.md section 24)
 
@@ -854,10 +816,9 @@ class PRMRoadmap:
 
     def components_timing(self):
         """dict(phase_ms=[init + hook, flatten, sizes + summary, copies], launches) of the last components()"""
-        ms = np.zeros(4, dtype=np.float64)
         launches = C.c_uint32()
-        _check(lib().oxhip_prm_components_last_timing(self._h, _p(ms), C.byref(launches)))
-        return dict(phase_ms=[float(v) for v in ms], launches=launches.value)
+        ms = _phase_ms(lib().oxhip_prm_components_last_timing, self._h, 4, launches)
+        return dict(phase_ms=ms.tolist(), launches=launches.value)
 
     def prune(self, invalid=False, keep=None, min_size=0, largest=False):
         """Removes milestones and renumbers the rest, order kept (oxhip_prm_prune).  Stage 1: invalid=True drops the milestones
@@ -885,6 +846,4 @@ class PRMRoadmap:
 
     def prune_timing(self):
         """dict(phase_ms=[masks, components, scans, move entries, move states]) of the last prune"""
-        ms = np.zeros(5, dtype=np.float64)
-        _check(lib().oxhip_prm_prune_last_timing(self._h, _p(ms)))
-        return dict(phase_ms=[float(v) for v in ms])
+        return dict(phase_ms=_phase_ms(lib().oxhip_prm_prune_last_timing, self._h, 5).tolist())

@@ -7,11 +7,14 @@
 `RRTBatch` (oxmpl_amd.capi) is the batched form the benchmark uses; this class is the one-problem
 drop-in for users of the reference's Python API.
 """
+import collections
+import contextlib
+
 import numpy as np
 
 from . import capi
-from .base import (Path, ProblemDefinition, RealVectorState, SE3RigidBodyValidityChecker, SE3State, SE3StateSpace,
-                   SO2ArcValidityChecker, SO2State, SO2StateSpace, SO3ConeValidityChecker, SO3State, SO3StateSpace,
+from .base import (Path, ProblemDefinition, RealVectorState, RealVectorStateSpace, SE3RigidBodyValidityChecker, SE3State,
+                   SE3StateSpace, SO2ArcValidityChecker, SO2State, SO2StateSpace, SO3ConeValidityChecker, SO3State, SO3StateSpace,
                    SphereBoxValidityChecker)
 
 _MESSAGES = {  # Display strings of PlanningError (oxmpl/src/base/error.rs:110-136)
@@ -21,6 +24,133 @@ _MESSAGES = {  # Display strings of PlanningError (oxmpl/src/base/error.rs:110-1
     capi.ERR_INVALID_START_STATE: "Start state is not valid in the current StateSpace.",
     capi.ERR_UNSAMPLED_STATE_SPACE: "StateSpace is not sampled. Either Tree or Roadmap is empty.",
 }
+# statuses that are the caller's ValueError: a space the library refuses to create; an argument a roadmap call refuses
+_AT_CREATE = (capi.ERR_UNBOUNDED, capi.ERR_ZERO_VOLUME, capi.ERR_BAD_ARG)
+_REFUSED_ARGUMENT = (capi.ERR_BAD_ARG, capi.ERR_CAPACITY)
+
+
+def _ready(handle):
+    """a planner's library handle if setup() has made one, else the reference's PlannerUninitialised"""
+    if handle is None:
+        raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
+    return handle
+
+
+@contextlib.contextmanager
+def _translated(value_errors=(), messages=True):
+    """A capi.OxhipError raised inside becomes ValueError when its status is one of `value_errors`, the reference-style
+    Exception(message) when `messages` and the status is a PlanningError's; any other passes as it is."""
+    try:
+        yield
+    except capi.OxhipError as e:
+        if e.status in value_errors:
+            raise ValueError(str(e)) from None
+        if messages and e.status in _MESSAGES:
+            raise Exception(_MESSAGES[e.status]) from None
+        raise
+
+
+# ---- the state spaces of the GPU path, one row each.  A state's width in the C ABI is its space's `dimension`.
+
+def _pairs(items):
+    """[(a, b), ...] -> ([a, ...], [b, ...]): the two arguments of a handle's set_spheres / set_boxes / set_body"""
+    return [a for a, _ in items], [b for _, b in items]
+
+
+# upload(handle, checker, clear): the checker's obstacles to an RRTBatch or a PRMRoadmap.  setup() leaves an empty list out
+# (a new handle has no obstacles); revalidate() passes clear=True, because an empty list must clear the old ones.
+def _upload_real_vector(handle, checker, clear):
+    if clear or checker.spheres:
+        handle.set_spheres(*_pairs(checker.spheres))
+    if clear or checker.boxes:
+        handle.set_boxes(*_pairs(checker.boxes))
+
+
+def _upload_so2(handle, checker, clear):
+    handle.set_boxes([[lo] for lo, _ in checker.arcs], [[hi] for _, hi in checker.arcs])
+
+
+def _upload_so3(handle, checker, clear):
+    if clear or checker.cones:
+        handle.set_spheres(*_pairs(checker.cones))
+
+
+def _upload_se3(handle, checker, clear):
+    handle.set_body(*_pairs(checker.body))
+    if clear or checker.obstacles:
+        handle.set_spheres(*_pairs(checker.obstacles))
+
+
+def _so2_state(row):
+    s = SO2State(0.0)
+    s.value = float(row[0])   # a tree's states are stored as the planner made them: no second normalisation
+    return s
+
+
+_TREE_PLANNERS = (capi.PLANNER_RRT, capi.PLANNER_RRT_CONNECT, capi.PLANNER_RRT_STAR)
+_Space = collections.namedtuple("_Space", [
+    "cls",        # the space class of oxmpl_amd.base
+    "kind",       # capi.SPACE_*
+    "bounds",     # space -> the config's bounds as the C ABI reads them for this kind
+    "planners",   # the capi.PLANNER_* it is built for,
+    "prm",        # ... whether PRM takes it,
+    "refusal",    # ... and what every other planner answers
+    "checker",    # the validity checker class it accepts
+    "describe",   # what that checker describes, for setup()'s refusal of any other object
+    "recheck",    # revalidate()'s refusal of any other object; {} is "tree" or "roadmap"
+    "upload",     # (handle, checker, clear): the checker's obstacles to the device
+    "state",      # device row -> state object
+    "file_name",  # the space's name in a save_roadmap file
+])
+_SPACES = (
+    _Space(RealVectorStateSpace, capi.SPACE_REAL_VECTOR, lambda space: space.bounds, _TREE_PLANNERS, True, None,
+           SphereBoxValidityChecker, "the obstacles", "describe the obstacles with oxmpl_amd.base.SphereBoxValidityChecker",
+           _upload_real_vector, RealVectorState, "real_vector"),
+    _Space(SO2StateSpace, capi.SPACE_SO2, lambda space: space.config_bounds(), (capi.PLANNER_RRT,), False,
+           "SO(2) is built for RRT only", SO2ArcValidityChecker, "the forbidden arcs",
+           "an SO(2) {} is re-checked against an SO2ArcValidityChecker", _upload_so2, _so2_state, "so2"),
+    _Space(SO3StateSpace, capi.SPACE_SO3, lambda space: space.config_bounds(), (capi.PLANNER_RRT,), True,
+           "SO(3) is built for RRT only", SO3ConeValidityChecker, "the forbidden cones",
+           "an SO(3) {} is re-checked against an SO3ConeValidityChecker", _upload_so3, lambda row: SO3State(*row), "so3"),
+    _Space(SE3StateSpace, capi.SPACE_SE3, lambda space: space.config_bounds(), (capi.PLANNER_RRT_CONNECT,), False,
+           "SE(3) is built for RRTConnect only", SE3RigidBodyValidityChecker, "the body and the obstacles",
+           "an SE(3) {} is re-checked against an SE3RigidBodyValidityChecker", _upload_se3, SE3State.from_values, "se3"),
+)
+
+
+def _row(space):
+    for row in _SPACES:
+        if isinstance(space, row.cls):
+            return row
+    raise TypeError("no GPU planner is built for %s" % type(space).__name__)
+
+
+def _set_up(previous, row, pd, checker, create):
+    """setup() after the planner's own refusal: refuse the checker, close the planner's previous handle, create() the new
+    one, upload the obstacles, hand the problem to the library -> the new handle.  A refusal leaves `previous` open."""
+    if not isinstance(checker, row.checker):
+        raise TypeError("the GPU path cannot call a Python function per interpolated state; "
+                        "describe %s with oxmpl_amd.base.%s" % (row.describe, row.checker.__name__))
+    if previous is not None:
+        previous.close()
+    with _translated(_AT_CREATE, messages=False):
+        handle = create()
+    row.upload(handle, checker, False)
+    handle.setup(pd.start_state.values, pd.goal.target.values, float(pd.goal.radius))
+    return handle
+
+
+def _new_obstacles(handle, space, checker, what):
+    """revalidate(checker): the checker's obstacles replace the ones `handle` has (`what`: "tree" or "roadmap")"""
+    row = _row(space)
+    if not isinstance(checker, row.checker):
+        raise TypeError(row.recheck.format(what))
+    row.upload(handle, checker, True)
+
+
+def _path(space, rows):
+    state = _row(space).state
+    return Path([state(row) for row in rows])
 
 
 class RRT:
@@ -32,6 +162,7 @@ class RRT:
     declared but unused by the reference's RRT) instead of "No solution found within timeout.".  Pass a larger `max_nodes`
     for narrow-passage problems.  `solve(0)` is Timeout, as upstream."""
     _PLANNER = capi.PLANNER_RRT
+    search_radius = 0.0   # (means something to RRTStar only)
 
     def __init__(self, max_distance, goal_bias, problem_definition, max_nodes=10000, seed=0, problem_id=0, device=0,
                  goal_sampler=capi.GOAL_SAMPLE_CENTRE):
@@ -48,117 +179,22 @@ class RRT:
     def setup(self, validity_checker):
         """Planner::setup (rrt.rs:140-156).  The reference takes a Python callable here; the GPU path
         takes a SphereBoxValidityChecker (see oxmpl_amd.base), or an SO3ConeValidityChecker for an SO(3) problem (RRT only),
-        or an SO2ArcValidityChecker for an SO(2) problem (RRT only)."""
-        if isinstance(self._pd.space, SO2StateSpace):
-            return self._setup_so2(validity_checker)
-        if isinstance(self._pd.space, SO3StateSpace):
-            return self._setup_so3(validity_checker)
-        if isinstance(self._pd.space, SE3StateSpace):
-            return self._setup_se3(validity_checker)
-        if not isinstance(validity_checker, SphereBoxValidityChecker):
-            raise TypeError("the GPU path cannot call a Python function per interpolated state; "
-                            "describe the obstacles with oxmpl_amd.base.SphereBoxValidityChecker")
+        or an SO2ArcValidityChecker for an SO(2) problem (RRT only), or an SE3RigidBodyValidityChecker for an SE(3) problem
+        (RRTConnect only)."""
         pd = self._pd
-        if self._batch is not None:
-            self._batch.close()
-        try:
-            b = capi.RRTBatch(pd.space.dimension, pd.space.bounds, self.max_distance, self.goal_bias, 1,
-                              lvs_fraction=pd.space.longest_valid_segment_fraction, stop_at_goal=True,
-                              planner=self._PLANNER, search_radius=getattr(self, "search_radius", 0.0), **self._opts)
-        except capi.OxhipError as e:
-            if e.status in (capi.ERR_UNBOUNDED, capi.ERR_ZERO_VOLUME, capi.ERR_BAD_ARG):
-                raise ValueError(str(e)) from None
-            raise
-        if validity_checker.spheres:
-            b.set_spheres([c for c, _ in validity_checker.spheres], [r for _, r in validity_checker.spheres])
-        if validity_checker.boxes:
-            b.set_boxes([lo for lo, _ in validity_checker.boxes], [hi for _, hi in validity_checker.boxes])
-        b.setup(pd.start_state.values, pd.goal.target.values, float(pd.goal.radius))
-        self._batch = b
-        self._checker = validity_checker
-
-    def _setup_so3(self, validity_checker):
-        if self._PLANNER != capi.PLANNER_RRT:
-            raise TypeError("SO(3) is built for RRT only")
-        if not isinstance(validity_checker, SO3ConeValidityChecker):
-            raise TypeError("the GPU path cannot call a Python function per interpolated state; "
-                            "describe the forbidden cones with oxmpl_amd.base.SO3ConeValidityChecker")
-        pd = self._pd
-        if self._batch is not None:
-            self._batch.close()
-        try:
-            b = capi.RRTBatch(4, pd.space.config_bounds(), self.max_distance, self.goal_bias, 1,
-                              lvs_fraction=pd.space.longest_valid_segment_fraction, stop_at_goal=True, planner=capi.PLANNER_RRT,
-                              space=capi.SPACE_SO3, **self._opts)
-        except capi.OxhipError as e:
-            if e.status in (capi.ERR_ZERO_VOLUME, capi.ERR_BAD_ARG):
-                raise ValueError(str(e)) from None
-            raise
-        if validity_checker.cones:
-            b.set_spheres([c for c, _ in validity_checker.cones], [r for _, r in validity_checker.cones])
-        b.setup(pd.start_state.values, pd.goal.target.values, float(pd.goal.radius))
-        self._batch = b
-        self._checker = validity_checker
-
-    def _setup_so2(self, validity_checker):
-        if self._PLANNER != capi.PLANNER_RRT:
-            raise TypeError("SO(2) is built for RRT only")
-        if not isinstance(validity_checker, SO2ArcValidityChecker):
-            raise TypeError("the GPU path cannot call a Python function per interpolated state; "
-                            "describe the forbidden arcs with oxmpl_amd.base.SO2ArcValidityChecker")
-        pd = self._pd
-        if self._batch is not None:
-            self._batch.close()
-        try:
-            b = capi.RRTBatch(1, pd.space.config_bounds(), self.max_distance, self.goal_bias, 1,
-                              lvs_fraction=pd.space.longest_valid_segment_fraction, stop_at_goal=True, planner=capi.PLANNER_RRT,
-                              space=capi.SPACE_SO2, **self._opts)
-        except capi.OxhipError as e:
-            if e.status in (capi.ERR_ZERO_VOLUME, capi.ERR_BAD_ARG):
-                raise ValueError(str(e)) from None
-            raise
-        b.set_boxes([[lo] for lo, _ in validity_checker.arcs], [[hi] for _, hi in validity_checker.arcs])
-        b.setup(pd.start_state.values, pd.goal.target.values, float(pd.goal.radius))
-        self._batch = b
-        self._checker = validity_checker
-
-    def _so2_path(self, rows):
-        states = []
-        for row in rows:   # a tree's states are stored as the planner made them: no second normalisation
-            s = SO2State(0.0)
-            s.value = float(row[0])
-            states.append(s)
-        return Path(states)
-
-    def _setup_se3(self, validity_checker):
-        if self._PLANNER != capi.PLANNER_RRT_CONNECT:
-            raise TypeError("SE(3) is built for RRTConnect only")
-        if not isinstance(validity_checker, SE3RigidBodyValidityChecker):
-            raise TypeError("the GPU path cannot call a Python function per interpolated state; "
-                            "describe the body and the obstacles with oxmpl_amd.base.SE3RigidBodyValidityChecker")
-        pd = self._pd
-        if self._batch is not None:
-            self._batch.close()
-        try:
-            b = capi.RRTBatch(7, pd.space.config_bounds(), self.max_distance, self.goal_bias, 1,
-                              lvs_fraction=pd.space.longest_valid_segment_fraction, stop_at_goal=True,
-                              planner=capi.PLANNER_RRT_CONNECT, space=capi.SPACE_SE3, **self._opts)
-        except capi.OxhipError as e:
-            if e.status in (capi.ERR_UNBOUNDED, capi.ERR_ZERO_VOLUME, capi.ERR_BAD_ARG):
-                raise ValueError(str(e)) from None
-            raise
-        b.set_body([c for c, _ in validity_checker.body], [r for _, r in validity_checker.body])
-        if validity_checker.obstacles:
-            b.set_spheres([c for c, _ in validity_checker.obstacles], [r for _, r in validity_checker.obstacles])
-        b.setup(pd.start_state.values, pd.goal.target.values, float(pd.goal.radius))
-        self._batch = b
+        row = _row(pd.space)
+        if self._PLANNER not in row.planners:
+            raise TypeError(row.refusal)
+        self._batch = _set_up(self._batch, row, pd, validity_checker, lambda: capi.RRTBatch(
+            pd.space.dimension, row.bounds(pd.space), self.max_distance, self.goal_bias, 1,
+            lvs_fraction=pd.space.longest_valid_segment_fraction, stop_at_goal=True, planner=self._PLANNER,
+            search_radius=self.search_radius, space=row.kind, **self._opts))
         self._checker = validity_checker
 
     def solve(self, timeout_secs):
         """Planner::solve (rrt.rs:158-227); errors surface as Exception(message) like the reference
         (oxmpl-py/src/geometric/rrt.rs:117)."""
-        if self._batch is None:
-            raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
+        batch = _ready(self._batch)
         timeout_secs = float(timeout_secs)
         if timeout_secs != timeout_secs or timeout_secs < 0.0:
             # Duration::from_secs_f32 (oxmpl-py/src/geometric/rrt.rs:111) panics on NaN / negative values
@@ -166,35 +202,23 @@ class RRT:
         if timeout_secs == 0.0:
             # rrt.rs:172-174: `start_time.elapsed() > timeout` already holds at the first check
             raise Exception(_MESSAGES[capi.ERR_TIMEOUT])
-        st = self._batch.solve(1 << 40, timeout_s=timeout_secs)
+        st = batch.solve(1 << 40, timeout_s=timeout_secs)
         if st[0] != capi.OK:
             raise Exception(_MESSAGES.get(int(st[0]), capi.status_string(int(st[0]))))
-        if isinstance(self._pd.space, SO2StateSpace):
-            return self._so2_path(self._batch.path(0))
-        if isinstance(self._pd.space, SO3StateSpace):
-            return Path([SO3State(*row) for row in self._batch.path(0)])
-        if isinstance(self._pd.space, SE3StateSpace):
-            return Path([SE3State.from_values(row) for row in self._batch.path(0)])
-        return Path([RealVectorState(row) for row in self._batch.path(0)])
+        return _path(self._pd.space, batch.path(0))
 
     def simplify_solution(self, max_span=0):
         """The last solution, shortcut over its own waypoints on the device (the cheapest chain of
         waypoints whose links pass the planner's own check_motion; `max_span` bounds how many waypoints a link may skip over,
         0 = no bound) -> Path.  Not part of the reference's surface.  Raises the reference-style Exception when there is no
         solution, TypeError on SE(3), for which the shortcut is not built."""
-        if self._batch is None:
-            raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
-        if isinstance(self._pd.space, SE3StateSpace):
+        batch = _ready(self._batch)
+        if _row(self._pd.space).kind == capi.SPACE_SE3:
             raise TypeError("simplify_solution is not built for SE(3)")
-        if int(self._batch.counts()["goal_node"][0]) < 0:
+        if int(batch.counts()["goal_node"][0]) < 0:
             raise Exception(_MESSAGES[capi.ERR_NO_SOLUTION_FOUND])
-        self._batch.simplify_paths(int(max_span))
-        rows = self._batch.simplified_paths()[1]
-        if isinstance(self._pd.space, SO2StateSpace):
-            return self._so2_path(rows)
-        if isinstance(self._pd.space, SO3StateSpace):
-            return Path([SO3State(*row) for row in rows])
-        return Path([RealVectorState(row) for row in rows])
+        batch.simplify_paths(int(max_span))
+        return _path(self._pd.space, batch.simplified_paths()[1])
 
     def is_state_valid(self, state):
         """the checker's predicate, evaluated on the device (the reference calls the user's callable)"""
@@ -207,29 +231,12 @@ class RRT:
         counters and the random stream where they were.  Not part of the reference's surface.  RRT only."""
         if self._PLANNER != capi.PLANNER_RRT:
             raise TypeError("revalidate is built for RRT only (not RRTConnect, not RRTStar)")
-        if self._batch is None:
-            raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
+        batch = _ready(self._batch)
         if validity_checker is not None:
-            if isinstance(self._pd.space, SO2StateSpace):
-                if not isinstance(validity_checker, SO2ArcValidityChecker):
-                    raise TypeError("an SO(2) tree is re-checked against an SO2ArcValidityChecker")
-                self._batch.set_boxes([[lo] for lo, _ in validity_checker.arcs], [[hi] for _, hi in validity_checker.arcs])
-            elif isinstance(self._pd.space, SO3StateSpace):
-                if not isinstance(validity_checker, SO3ConeValidityChecker):
-                    raise TypeError("an SO(3) tree is re-checked against an SO3ConeValidityChecker")
-                self._batch.set_spheres([c for c, _ in validity_checker.cones], [r for _, r in validity_checker.cones])
-            else:
-                if not isinstance(validity_checker, SphereBoxValidityChecker):
-                    raise TypeError("describe the obstacles with oxmpl_amd.base.SphereBoxValidityChecker")
-                self._batch.set_spheres([c for c, _ in validity_checker.spheres], [r for _, r in validity_checker.spheres])
-                self._batch.set_boxes([lo for lo, _ in validity_checker.boxes], [hi for _, hi in validity_checker.boxes])
+            _new_obstacles(batch, self._pd.space, validity_checker, "tree")
             self._checker = validity_checker
-        try:
-            return int(self._batch.revalidate_trees()["n_removed"][0])
-        except capi.OxhipError as e:
-            if e.status in _MESSAGES:
-                raise Exception(_MESSAGES[e.status]) from None
-            raise
+        with _translated():
+            return int(batch.revalidate_trees()["n_removed"][0])
 
     @property
     def num_nodes(self):
@@ -284,52 +291,15 @@ class PRM:
 
     def setup(self, validity_checker):
         """Planner::setup (prm.rs:217-225): stores problem and checker, clears the roadmap.  An SO(3) problem takes an
-        SO3ConeValidityChecker (the radius rule; milestones and path states are SO3State).  SO(2) is built for RRT only."""
-        if isinstance(self._pd.space, SO2StateSpace):
-            raise TypeError("SO(2) is built for RRT only")
-        if isinstance(self._pd.space, SO3StateSpace):
-            return self._setup_so3(validity_checker)
-        if not isinstance(validity_checker, SphereBoxValidityChecker):
-            raise TypeError("the GPU path cannot call a Python function per interpolated state; "
-                            "describe the obstacles with oxmpl_amd.base.SphereBoxValidityChecker")
+        SO3ConeValidityChecker (the radius rule; milestones and path states are SO3State).  SO(2) is built for RRT only,
+        SE(3) for RRTConnect only."""
         pd = self._pd
-        if self._prm is not None:
-            self._prm.close()
-        try:
-            g = capi.PRMRoadmap(pd.space.dimension, pd.space.bounds, self.connection_radius, timeout=self.timeout,
-                                lvs_fraction=pd.space.longest_valid_segment_fraction, **self._opts)
-        except capi.OxhipError as e:
-            if e.status in (capi.ERR_UNBOUNDED, capi.ERR_ZERO_VOLUME, capi.ERR_BAD_ARG):
-                raise ValueError(str(e)) from None
-            raise
-        if validity_checker.spheres:
-            g.set_spheres([c for c, _ in validity_checker.spheres], [r for _, r in validity_checker.spheres])
-        if validity_checker.boxes:
-            g.set_boxes([lo for lo, _ in validity_checker.boxes], [hi for _, hi in validity_checker.boxes])
-        g.setup(pd.start_state.values, pd.goal.target.values, float(pd.goal.radius))
-        self._prm = g
-
-    def _setup_so3(self, validity_checker):
-        if not isinstance(validity_checker, SO3ConeValidityChecker):
-            raise TypeError("the GPU path cannot call a Python function per interpolated state; "
-                            "describe the forbidden cones with oxmpl_amd.base.SO3ConeValidityChecker")
-        pd = self._pd
-        if self._prm is not None:
-            self._prm.close()
-        try:
-            g = capi.PRMRoadmap(4, pd.space.config_bounds(), self.connection_radius, timeout=self.timeout,
-                                lvs_fraction=pd.space.longest_valid_segment_fraction, space=capi.SPACE_SO3, **self._opts)
-        except capi.OxhipError as e:
-            if e.status in (capi.ERR_ZERO_VOLUME, capi.ERR_BAD_ARG):
-                raise ValueError(str(e)) from None
-            raise
-        if validity_checker.cones:
-            g.set_spheres([c for c, _ in validity_checker.cones], [r for _, r in validity_checker.cones])
-        g.setup(pd.start_state.values, pd.goal.target.values, float(pd.goal.radius))
-        self._prm = g
-
-    def _state(self, row):
-        return SO3State(*row) if isinstance(self._pd.space, SO3StateSpace) else RealVectorState(row)
+        row = _row(pd.space)
+        if not row.prm:
+            raise TypeError(row.refusal)
+        self._prm = _set_up(self._prm, row, pd, validity_checker, lambda: capi.PRMRoadmap(
+            pd.space.dimension, row.bounds(pd.space), self.connection_radius, timeout=self.timeout,
+            lvs_fraction=pd.space.longest_valid_segment_fraction, space=row.kind, **self._opts))
 
     def set_problem_definition(self, problem_definition):
         """PRM::set_problem_definition (prm.rs:88-90): new start / goal on the roadmap already built"""
@@ -341,19 +311,15 @@ class PRM:
                                   float(problem_definition.goal.radius))
 
     def construct_roadmap(self):
-        if self._prm is None:
-            raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
-        self._prm.construct_roadmap()
+        _ready(self._prm).construct_roadmap()
 
     def solve(self, timeout_secs):
         """Planner::solve (prm.rs:227-307); errors surface as Exception(message) like the reference
         (oxmpl-py/src/geometric/prm.rs:120-145)"""
-        if self._prm is None:
-            raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
-        st, path = self._prm.solve(float(timeout_secs))
+        st, path = _ready(self._prm).solve(float(timeout_secs))
         if st != capi.OK:
             raise Exception(_MESSAGES.get(int(st), capi.status_string(int(st))))
-        return Path([self._state(row) for row in path])
+        return _path(self._pd.space, path)
 
     def solve_batch(self, problem_definitions, timeout_secs, shortest=False):
         """Many problem definitions on the roadmap already built, in one device call (oxhip_prm_solve_batch: start
@@ -363,87 +329,56 @@ class PRM:
         definition is left as it is.  All problems must share the planner's space.  shortest=True answers every problem with
         a shortest path on the roadmap in the space's distance (oxhip_prm_solve_batch_shortest) instead of the reference's
         fewest-hop path; the statuses are the same."""
-        if self._prm is None:
-            raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
+        prm = _ready(self._prm)
         pds = list(problem_definitions)
         for pd in pds:
             if not isinstance(pd, ProblemDefinition):
                 raise TypeError("problem_definitions must hold ProblemDefinition objects")
             if type(pd.space) is not type(self._pd.space) or len(pd.start_state.values) != len(self._pd.start_state.values):
                 raise ValueError("every problem of a batch must share the planner's state space")
-        try:
-            run = self._prm.solve_batch_shortest if shortest else self._prm.solve_batch
+        with _translated():
+            run = prm.solve_batch_shortest if shortest else prm.solve_batch
             status = run([pd.start_state.values for pd in pds], [pd.goal.target.values for pd in pds],
                          [float(pd.goal.radius) for pd in pds], float(timeout_secs))
-        except capi.OxhipError as e:
-            if e.status in _MESSAGES:
-                raise Exception(_MESSAGES[e.status]) from None
-            raise
-        offsets, _, rows = self._prm.batch_paths()
+        offsets, _, rows = prm.batch_paths()
         out = []
         for q, st in enumerate(status):
             if st != capi.OK:
                 out.append(Exception(_MESSAGES.get(int(st), capi.status_string(int(st)))))
             else:
-                out.append(Path([self._state(row) for row in rows[int(offsets[q]):int(offsets[q + 1])]]))
+                out.append(_path(self._pd.space, rows[int(offsets[q]):int(offsets[q + 1])]))
         return out
 
     def get_roadmap(self):
         """PRM::get_roadmap (prm.rs:82-84) as (states, offsets, neighbours): node i's edges are
-        neighbours[offsets[i]:offsets[i+1]].  SO(3) problems: states is a list of SO3State."""
+        neighbours[offsets[i]:offsets[i+1]].  SO(3) problems: states is a list of SO3State; a real-vector roadmap's states
+        stay the [n][dim] array."""
         states, offsets, nbrs = self._prm.roadmap()
-        if isinstance(self._pd.space, SO3StateSpace):
-            states = [SO3State(*row) for row in states]
+        row = _row(self._pd.space)
+        if row.kind != capi.SPACE_REAL_VECTOR:
+            states = [row.state(r) for r in states]
         return states, offsets, nbrs
 
     # ---- a roadmap that outlives its planner, and one that follows its scene (oxhip_prm_set_roadmap / oxhip_prm_revalidate)
-
-    def _space_kind(self):
-        return "so3" if isinstance(self._pd.space, SO3StateSpace) else "real_vector"
-
-    def _space_dim(self):
-        return 4 if isinstance(self._pd.space, SO3StateSpace) else int(self._pd.space.dimension)
 
     def set_roadmap(self, states, offsets, neighbours):
         """Replaces the roadmap with the caller's, in the layout get_roadmap returns (states: rows or state objects).  The
         library checks the structure on the GPU and raises ValueError, naming the rule and the lowest offending row, when it is
         not a symmetric roadmap with ascending rows; the planner's roadmap is then unchanged."""
-        if self._prm is None:
-            raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
+        prm = _ready(self._prm)
         rows = [s.values if hasattr(s, "values") else s for s in states]
-        try:
-            self._prm.set_roadmap(rows, offsets, neighbours)
-        except capi.OxhipError as e:
-            if e.status in (capi.ERR_BAD_ARG, capi.ERR_CAPACITY):
-                raise ValueError(str(e)) from None
-            raise
+        with _translated(_REFUSED_ARGUMENT, messages=False):
+            prm.set_roadmap(rows, offsets, neighbours)
 
     def revalidate(self, validity_checker=None):
         """Re-checks every milestone and edge of the roadmap against the obstacles as they are now -- `validity_checker`'s when
         one is given (it replaces the planner's), else the ones already set.  Milestone indices are stable: an invalid
         milestone keeps its place and loses its edges.  Returns (valid_mask [n] bool, removed edge entries)."""
-        if self._prm is None:
-            raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
+        prm = _ready(self._prm)
         if validity_checker is not None:
-            if isinstance(self._pd.space, SO2StateSpace):
-                if not isinstance(validity_checker, SO2ArcValidityChecker):
-                    raise TypeError("an SO(2) tree is re-checked against an SO2ArcValidityChecker")
-                self._batch.set_boxes([[lo] for lo, _ in validity_checker.arcs], [[hi] for _, hi in validity_checker.arcs])
-            elif isinstance(self._pd.space, SO3StateSpace):
-                if not isinstance(validity_checker, SO3ConeValidityChecker):
-                    raise TypeError("an SO(3) roadmap is re-checked against an SO3ConeValidityChecker")
-                self._prm.set_spheres([c for c, _ in validity_checker.cones], [r for _, r in validity_checker.cones])
-            else:
-                if not isinstance(validity_checker, SphereBoxValidityChecker):
-                    raise TypeError("describe the obstacles with oxmpl_amd.base.SphereBoxValidityChecker")
-                self._prm.set_spheres([c for c, _ in validity_checker.spheres], [r for _, r in validity_checker.spheres])
-                self._prm.set_boxes([lo for lo, _ in validity_checker.boxes], [hi for _, hi in validity_checker.boxes])
-        try:
-            return self._prm.revalidate()
-        except capi.OxhipError as e:
-            if e.status in _MESSAGES:
-                raise Exception(_MESSAGES[e.status]) from None
-            raise
+            _new_obstacles(prm, self._pd.space, validity_checker, "roadmap")
+        with _translated():
+            return prm.revalidate()
 
     def grow_roadmap(self, n_more, max_samples=0, new_stream=None):
         """Adds up to n_more milestones to the roadmap as it stands -- built, loaded or re-checked -- under the obstacles as they
@@ -451,29 +386,17 @@ class PRM:
         gets no new edge.  new_stream=None continues the planner's own sampler where construct_roadmap or the last grow
         stopped; a loaded roadmap has no such position and needs new_stream=<stream id>.  ValueError for a refused argument or
         too many milestones.  Returns (milestones added, samples drawn)."""
-        if self._prm is None:
-            raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
-        try:
-            return self._prm.grow(int(n_more), int(max_samples), None if new_stream is None else int(new_stream))
-        except capi.OxhipError as e:
-            if e.status in (capi.ERR_BAD_ARG, capi.ERR_CAPACITY):
-                raise ValueError(str(e)) from None
-            if e.status in _MESSAGES:
-                raise Exception(_MESSAGES[e.status]) from None
-            raise
+        prm = _ready(self._prm)
+        with _translated(_REFUSED_ARGUMENT):
+            return prm.grow(int(n_more), int(max_samples), None if new_stream is None else int(new_stream))
 
     def components(self):
         """The roadmap's connected components (oxhip_prm_components): (label [n], size [n], n_components, largest_label,
         largest_size), label[i] being the lowest milestone index of i's component.  Two milestones can be joined by a path
         on the roadmap iff their labels are equal."""
-        if self._prm is None:
-            raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
-        try:
-            return self._prm.components()
-        except capi.OxhipError as e:
-            if e.status in _MESSAGES:
-                raise Exception(_MESSAGES[e.status]) from None
-            raise
+        prm = _ready(self._prm)
+        with _translated():
+            return prm.components()
 
     def prune_roadmap(self, invalid=False, keep=None, min_size=0, largest=False):
         """Removes milestones from the roadmap and renumbers the rest in their old order (oxhip_prm_prune): first the ones that
@@ -481,37 +404,26 @@ class PRM:
         components below min_size milestones and, with largest=True, all but the largest component.  No edge is re-checked.
         ValueError for a refused argument or a call that would keep no milestone.  Returns (new_index [n before] with -1 =
         dropped, milestones kept, edge entries removed)."""
-        if self._prm is None:
-            raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
-        try:
-            return self._prm.prune(bool(invalid), keep, int(min_size), bool(largest))
-        except capi.OxhipError as e:
-            if e.status in (capi.ERR_BAD_ARG, capi.ERR_CAPACITY):
-                raise ValueError(str(e)) from None
-            if e.status in _MESSAGES:
-                raise Exception(_MESSAGES[e.status]) from None
-            raise
+        prm = _ready(self._prm)
+        with _translated(_REFUSED_ARGUMENT):
+            return prm.prune(bool(invalid), keep, int(min_size), bool(largest))
 
     def save_roadmap(self, path):
         """The roadmap as a .npz file: states, offsets, neighbours, the space's kind and the width of a state."""
-        import numpy as np
-        if self._prm is None:
-            raise Exception(_MESSAGES[capi.ERR_PLANNER_UNINITIALISED])
-        states, offsets, nbrs = self._prm.roadmap()
+        states, offsets, nbrs = _ready(self._prm).roadmap()
         with open(path, "wb") as f:
-            np.savez(f, states=states, offsets=offsets, neighbours=nbrs, space=np.array(self._space_kind()),
-                     dim=np.array(self._space_dim(), dtype=np.uint32))
+            np.savez(f, states=states, offsets=offsets, neighbours=nbrs, space=np.array(_row(self._pd.space).file_name),
+                     dim=np.array(int(self._pd.space.dimension), dtype=np.uint32))
 
     def load_roadmap(self, path):
         """Plants the roadmap of a save_roadmap file.  ValueError -- before any device call -- when the file's space or
         dimension is not the planner's."""
-        import numpy as np
         with np.load(path, allow_pickle=False) as z:
             space, dim = str(z["space"]), int(z["dim"])
             states, offsets, nbrs = z["states"], z["offsets"], z["neighbours"]
-        if space != self._space_kind() or dim != self._space_dim():
-            raise ValueError("roadmap file is for %s dim %d, the planner's space is %s dim %d"
-                             % (space, dim, self._space_kind(), self._space_dim()))
+        own = (_row(self._pd.space).file_name, int(self._pd.space.dimension))
+        if (space, dim) != own:
+            raise ValueError("roadmap file is for %s dim %d, the planner's space is %s dim %d" % ((space, dim) + own))
         if states.ndim != 2 or states.shape[1] != dim or offsets.shape != (states.shape[0] + 1,):
             raise ValueError("roadmap file is malformed: states %s, offsets %s" % (states.shape, offsets.shape))
         self.set_roadmap(states, offsets, nbrs)
