@@ -455,6 +455,7 @@ class PRM {
         int32_t st = shortest ? oxhip_prm_solve_batch_shortest(prm_, (uint32_t)q, starts.data(), centres.data(), radii.data(), timeout_.count(), 0, 0,
                                                                status.data())
                               : oxhip_prm_solve_batch(prm_, (uint32_t)q, starts.data(), centres.data(), radii.data(), timeout_.count(), 0, status.data());
+        if (st == OXHIP_OK) last_batch_ = q;   // (a refused call leaves the library's last batch, and so this count, as they were)
         std::vector<uint64_t> off(q + 1);
         uint64_t total = 0;
         if (st == OXHIP_OK) st = oxhip_prm_batch_get_paths(prm_, off.data(), nullptr, nullptr, 0, &total);
@@ -474,6 +475,53 @@ class PRM {
     }
 
   public:
+    // The planner's own StateValidityChecker and check_motion on the device, against the obstacles as they are now
+    // (oxhip_prm_is_valid / oxhip_prm_check_motion); false before setup().
+    bool is_valid(const base::RealVectorState& state) {
+        uint8_t ok = 0;
+        if (!prm_ || !pd_ || state.values.size() != pd_->space->dimension) return false;
+        return oxhip_prm_is_valid(prm_, state.values.data(), 1, &ok) == OXHIP_OK && ok != 0;
+    }
+    bool check_motion(const base::RealVectorState& from, const base::RealVectorState& to) {
+        uint8_t ok = 0;
+        if (!prm_ || !pd_ || from.values.size() != pd_->space->dimension || to.values.size() != from.values.size()) return false;
+        return oxhip_prm_check_motion(prm_, from.values.data(), to.values.data(), 1, &ok) == OXHIP_OK && ok != 0;
+    }
+    // The answered paths of the last solve_batch / solve_batch_shortest, shortcut on the device
+    // (oxhip_prm_batch_simplify_paths): every edge is first cut into `subdivide` equal parts, then the cheapest chain of the
+    // resulting points whose links pass the planner's own check_motion is taken; max_span bounds a link in original edges,
+    // 0 = no bound.  Per problem of that batch the simplified path, or the batch's own error for one it did not answer.  A
+    // refused call (no batch, subdivide outside 1..256, a path too large) gives every entry that error and leaves the planner
+    // usable; last_simplify_status() holds the library's status either way (an empty result with OXHIP_OK: an empty batch).
+    std::vector<Result<base::Path, base::PlanningError>> simplify_batch(uint32_t subdivide = 1, uint32_t max_span = 0) {
+        const std::size_t n_problems = last_batch_;   // the library's last accepted batch: what its getters write
+        std::vector<Result<base::Path, base::PlanningError>> out;
+        out.reserve(n_problems);
+        int32_t st = prm_ && pd_ ? oxhip_prm_batch_simplify_paths(prm_, subdivide, max_span, 0) : (int32_t)OXHIP_ERR_PLANNER_UNINITIALISED;
+        simplify_status_ = st;
+        std::vector<int32_t> status(n_problems ? n_problems : 1);
+        if (st == OXHIP_OK) st = oxhip_prm_batch_get_results(prm_, status.data(), nullptr, nullptr, nullptr, nullptr);
+        std::vector<uint64_t> off(n_problems + 1);
+        uint64_t total = 0;
+        if (st == OXHIP_OK) st = oxhip_prm_batch_get_simplified_paths(prm_, off.data(), nullptr, nullptr, 0, &total);
+        const std::size_t dim = pd_ ? pd_->space->dimension : 0;
+        std::vector<double> flat((std::size_t)total * dim + 1);
+        if (st == OXHIP_OK) st = oxhip_prm_batch_get_simplified_paths(prm_, off.data(), flat.data(), nullptr, total, &total);
+        for (std::size_t i = 0; i < n_problems; ++i) {
+            if (st != OXHIP_OK || status[i] != OXHIP_OK) {
+                out.emplace_back(to_error(st != OXHIP_OK ? st : status[i]));
+                continue;
+            }
+            base::Path path;
+            for (uint64_t r = off[i]; r < off[i + 1]; ++r)
+                path.states.emplace_back(std::vector<double>(flat.begin() + r * dim, flat.begin() + (r + 1) * dim));
+            out.emplace_back(std::move(path));
+        }
+        if (simplify_status_ == OXHIP_OK) simplify_status_ = st;
+        return out;
+    }
+    int32_t last_simplify_status() const { return simplify_status_; }
+
     // PRM::get_roadmap (prm.rs:82-84): milestone count and, per node, its `edges`
     uint32_t num_milestones() const {
         uint32_t n = 0;
@@ -620,9 +668,11 @@ class PRM {
         prm_ = nullptr;
     }
     oxhip_prm* prm_ = nullptr;
+    std::size_t last_batch_ = 0;   // problems of the last solve_batch / solve_batch_shortest
     std::shared_ptr<base::ProblemDefinition> pd_;
     int32_t last_status_ = OXHIP_ERR_PLANNER_UNINITIALISED;
     int32_t set_roadmap_status_ = OXHIP_OK;
+    int32_t simplify_status_ = OXHIP_OK;
     int32_t grow_status_ = OXHIP_OK;
     int32_t prune_status_ = OXHIP_OK;
 };

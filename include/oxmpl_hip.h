@@ -729,6 +729,61 @@ int32_t oxhip_prm_prune(oxhip_prm* prm, const oxhip_prm_prune_config* c, const u
 /* HIP-event times (ms) of the last oxhip_prm_prune: phase_ms[5] = {masks, components, scans, move entries, move states} */
 int32_t oxhip_prm_prune_last_timing(oxhip_prm* prm, double* phase_ms /*[5]*/);
 
+/* ---- the handle's own checker, and the last batch's paths subdivided and shortcut (prm_path_simplify.hip) ----
+ * is_valid / check_motion: the handle's StateValidityChecker and the check_motion that construction uses, over caller rows
+ * ([n][dim]; SO(3): quaternions), against the obstacles as they are at the call; for every handle kind (radius, k-nearest,
+ * SO(3)), with or without a roadmap.  Without setup(): OXHIP_ERR_PLANNER_UNINITIALISED. */
+int32_t oxhip_prm_is_valid(oxhip_prm* prm, const double* states /*[n][dim]*/, uint32_t n, uint8_t* out /*[n]*/);
+int32_t oxhip_prm_check_motion(oxhip_prm* prm, const double* from /*[n][dim]*/, const double* to /*[n][dim]*/, uint32_t n,
+                               uint8_t* out /*[n]*/);
+/* oxhip_prm_batch_simplify_paths shortcuts every OXHIP_OK path of the last batch (oxhip_prm_solve_batch or _shortest) on the
+ * device.  The semantics are this build's own, as section 18's are:
+ *   The dense path.  Query q has the raw path p_0 .. p_{L-1} of oxhip_prm_batch_get_paths and m = subdivide >= 1.  The dense path
+ *     has M = (L - 1) m + 1 points: q_{k m} = p_k, copied as 64-bit words (a -0.0 or an unnormalised quaternion keeps its bits),
+ *     and q_{k m + r} = interpolate(p_k, p_{k+1}, t) for 0 < r < m with t = (double)r / (double)m, one correctly rounded divide;
+ *     the interpolation is the space's own, unfused: the bits of oxhip_interpolate_batch for R^n and of the interpolate op of
+ *     oxhip_so3_op_batch for SO(3).
+ *   Window.  S = L - 1 when max_span == 0, else min(max_span, L - 1), counted in original edges; W = S m in dense indices.
+ *     max_span == 1 with m == 1 leaves the path as it is.
+ *   valid(u, v) for u < v <= u + W.  True without a check when both points lie on one original edge, floor(u / m) ==
+ *     floor((v - 1) / m): the roadmap accepted that motion and this is a part of it (for m == 1: "adjacent is valid").
+ *     Otherwise the handle's check_motion, from = q_u, to = q_v, in path order, against the obstacles as they are at the call:
+ *     the verdict of oxhip_prm_check_motion on the same two rows.
+ *   Cost.  cost[0] = 0; cost[v] = the minimum of fl(cost[u] + distance(q_u, q_v)) over u in [v - W, v - 1] with valid(u, v),
+ *     u scanned ascending with strict '<' (ties keep the lowest u); the distance is the space's own (the bits of
+ *     oxhip_distance_batch / oxhip_so3_op_batch op 0).
+ *   Outputs.  The simplified path is the parent chain from M - 1, with its dense indices; both ends are kept.
+ *     simplified_cost = cost[M - 1]; raw_cost = the left-to-right sum over the original edges p_k -> p_{k+1} (after a
+ *     weights = 0 shortest batch: oxhip_prm_batch_get_costs's c[goal] bit for bit); simplified_cost <= raw_cost holds exactly,
+ *     since every hop q_{k m} -> q_{(k+1) m} is in the window and rounding is monotone.  checks = the number of pairs of the
+ *     window that are not on one edge.  A query whose status is not OXHIP_OK has length 0, both costs 0.0 and checks 0.
+ * Spaces: R^1 .. R^8 (spheres and boxes; radius and k-nearest handles) and SO(3).  subdivide 0 or above 256 is
+ * OXHIP_ERR_BAD_ARG.  chunk_queries: queries per device round, 0 = automatic (a round's bit matrices -- bit (d - 2) M + u for
+ * d = v - u in [2, W], whole 64-bit words per query -- stay within 1 GiB; one path whose matrix is larger is
+ * OXHIP_ERR_CAPACITY: pass a max_span or a smaller subdivide); results never depend on it.
+ * Without setup(): OXHIP_ERR_PLANNER_UNINITIALISED.  Without a current batch (none yet, or after setup()) simplify and its
+ * getters answer OXHIP_ERR_UNSAMPLED_STATE_SPACE, as the batch getters do; with a batch but no simplify since it the getters
+ * return OXHIP_ERR_BAD_ARG ("no simplified paths").  A new batch, setup() and every call that changes the roadmap (set_roadmap,
+ * revalidate, grow_roadmap, prune, construct_roadmap) drop the results; set_spheres / set_boxes do not: the next simplify
+ * reads the new obstacles.  Simplify changes neither the roadmap, the batch's own results nor the single-query state; a refused
+ * simplify (OXHIP_ERR_BAD_ARG, OXHIP_ERR_CAPACITY) leaves the last results as they were.
+ * get_simplified_paths: query q's simplified states are rows offsets[q] .. offsets[q+1] of `states`, `indices` their dense
+ * indices u; any of the three may be NULL.  get_simplify_results: any pointer may be NULL. */
+int32_t oxhip_prm_batch_simplify_paths(oxhip_prm* prm, uint32_t subdivide, uint32_t max_span, uint32_t chunk_queries);
+int32_t oxhip_prm_batch_get_simplified_paths(oxhip_prm* prm, uint64_t* offsets /*[Q+1]*/, double* states /*[total][dim]*/,
+                                             uint32_t* indices /*[total]*/, uint64_t cap_rows, uint64_t* total_rows);
+int32_t oxhip_prm_batch_get_simplify_results(oxhip_prm* prm, double* raw_cost /*[Q]*/, double* simplified_cost /*[Q]*/,
+                                             uint64_t* checks /*[Q]*/);
+/* test hook: valid(u, v) of query `query`'s dense path as the pair kernel evaluates it, out[u * M + v] for u < v within the
+ * window (same-edge pairs read 1; 0 elsewhere), M * M bytes; *len_out = M (0: no path); out == NULL only asks for M;
+ * cap_bytes < M * M is OXHIP_ERR_CAPACITY.  It leaves the last simplify's results as they are. */
+int32_t oxhip_prm_batch_path_valid_matrix(oxhip_prm* prm, uint32_t query, uint32_t subdivide, uint32_t max_span, uint8_t* out,
+                                          uint64_t cap_bytes, uint32_t* len_out);
+/* HIP-event times (ms) of the last oxhip_prm_batch_simplify_paths, summed over its rounds: phase_ms[4] = {upload + subdivide,
+ * pair matrix, DP, gather + device-to-host copies}; the number of rounds.  Either pointer may be NULL; without setup():
+ * OXHIP_ERR_PLANNER_UNINITIALISED, as the other calls of this section. */
+int32_t oxhip_prm_batch_simplify_last_timing(oxhip_prm* prm, double* phase_ms /*[4]*/, uint32_t* rounds);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,6 +57,8 @@ EXPORTS = [
     "oxhip_prm_set_roadmap", "oxhip_prm_revalidate", "oxhip_prm_revalidate_last_timing",
     "oxhip_prm_grow_roadmap", "oxhip_prm_grow_last_timing",
     "oxhip_prm_components", "oxhip_prm_components_last_timing", "oxhip_prm_prune", "oxhip_prm_prune_last_timing",
+    "oxhip_prm_is_valid", "oxhip_prm_check_motion", "oxhip_prm_batch_simplify_paths", "oxhip_prm_batch_get_simplified_paths",
+    "oxhip_prm_batch_get_simplify_results", "oxhip_prm_batch_path_valid_matrix", "oxhip_prm_batch_simplify_last_timing",
     "oxhip_rrt_batch_extract_paths", "oxhip_rrt_batch_get_paths", "oxhip_rrt_batch_simplify_paths",
     "oxhip_rrt_batch_get_simplified_paths", "oxhip_rrt_batch_get_simplify_results", "oxhip_rrt_batch_path_valid_matrix",
     "oxhip_rrt_batch_paths_last_timing",
@@ -203,6 +205,13 @@ def lib():
         L.oxhip_prm_components_last_timing.argtypes = [C.c_void_p, _dp, _u32p]
         L.oxhip_prm_prune.argtypes = [C.c_void_p, C.POINTER(PrmPruneConfig), _u8p, _i32p, _u32p, _u64p]
         L.oxhip_prm_prune_last_timing.argtypes = [C.c_void_p, _dp]
+        L.oxhip_prm_is_valid.argtypes = [C.c_void_p, _dp, C.c_uint32, _u8p]
+        L.oxhip_prm_check_motion.argtypes = [C.c_void_p, _dp, _dp, C.c_uint32, _u8p]
+        L.oxhip_prm_batch_simplify_paths.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.oxhip_prm_batch_get_simplified_paths.argtypes = [C.c_void_p, _u64p, _dp, _u32p, C.c_uint64, _u64p]
+        L.oxhip_prm_batch_get_simplify_results.argtypes = [C.c_void_p, _dp, _dp, _u64p]
+        L.oxhip_prm_batch_path_valid_matrix.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, _u8p, C.c_uint64, _u32p]
+        L.oxhip_prm_batch_simplify_last_timing.argtypes = [C.c_void_p, _dp, _u32p]
         L.oxhip_rrt_batch_extract_paths.argtypes = [C.c_void_p]
         L.oxhip_rrt_batch_get_paths.argtypes = [C.c_void_p, _u64p, _dp, C.c_uint64, _u64p]
         L.oxhip_rrt_batch_simplify_paths.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
@@ -847,3 +856,55 @@ class PRMRoadmap(_Handle):
     def prune_timing(self):
         """dict(phase_ms=[masks, components, scans, move entries, move states]) of the last prune"""
         return dict(phase_ms=_phase_ms(lib().oxhip_prm_prune_last_timing, self._h, 5).tolist())
+
+    # ---- the handle's own checker; the last batch's paths subdivided and shortcut on the device (DESIGN.md section 25)
+
+    def is_valid(self, states):
+        """the handle's StateValidityChecker over rows [n][dim], against the obstacles as they are now -> [n] bool"""
+        s = _f64(states).reshape(-1, self.dim)
+        out = np.empty(max(s.shape[0], 1), dtype=np.uint8)
+        _check(lib().oxhip_prm_is_valid(self._h, _p(s if s.size else np.zeros(1)), s.shape[0], _p(out, _u8p)))
+        return out[:s.shape[0]].astype(bool)
+
+    def check_motion(self, frm, to):
+        """the check_motion that construction uses, from[i] -> to[i] -> [n] bool"""
+        a = _f64(frm).reshape(-1, self.dim)
+        b = _f64(to, a.shape)
+        out = np.empty(max(a.shape[0], 1), dtype=np.uint8)
+        pad = np.zeros(1)
+        _check(lib().oxhip_prm_check_motion(self._h, _p(a if a.size else pad), _p(b if b.size else pad), a.shape[0], _p(out, _u8p)))
+        return out[:a.shape[0]].astype(bool)
+
+    def simplify_batch_paths(self, subdivide=1, max_span=0, chunk_queries=0):
+        """Shortcut every answered path of the last batch, each edge first cut into `subdivide` equal parts
+        (include/oxmpl_hip.h states the semantics).  max_span bounds a link in original edges, 0 = no bound.  chunk_queries:
+        queries per device round (test-only; results never depend on it)."""
+        _check(lib().oxhip_prm_batch_simplify_paths(self._h, int(subdivide), int(max_span), int(chunk_queries)))
+
+    def simplified_batch_paths(self):
+        """(offsets [Q+1] u64, states [rows][dim], indices [rows] u32 into the dense path) of the last simplify_batch_paths"""
+        offsets = np.zeros(getattr(self, "_batch_q", 0) + 1, dtype=np.uint64)
+        states, idx = _sized(lib().oxhip_prm_batch_get_simplified_paths, (self._h, _p(offsets, _u64p)),
+                             [(np.float64, self.dim), (np.uint32, 0)], C.c_uint64)
+        return offsets, states, idx
+
+    def simplify_results(self):
+        """dict(raw_cost [Q], simplified_cost [Q], checks [Q] u64) of the last simplify_batch_paths"""
+        q = getattr(self, "_batch_q", 0)
+        raw, simp, checks = np.zeros(max(q, 1)), np.zeros(max(q, 1)), np.zeros(max(q, 1), dtype=np.uint64)
+        _check(lib().oxhip_prm_batch_get_simplify_results(self._h, _p(raw), _p(simp), _p(checks, _u64p)))
+        return dict(raw_cost=raw[:q], simplified_cost=simp[:q], checks=checks[:q])
+
+    def batch_path_valid_matrix(self, query, subdivide=1, max_span=0):
+        """test hook: valid(u, v) of query `query`'s dense path as the pair kernel evaluates it, [M][M] bool (u < v; same-edge
+        pairs read True)"""
+        out, = _sized(lib().oxhip_prm_batch_path_valid_matrix, (self._h, int(query), int(subdivide), int(max_span)), [(np.uint8, 0)],
+                      capacity=lambda M: M * M, fill_empty=False)   # the count is the dense length M, the buffer holds M * M verdicts
+        M = math.isqrt(out.size)
+        return out.reshape(M, M).astype(bool)
+
+    def simplify_timing(self):
+        """dict(phase_ms=[upload + subdivide, pair matrix, DP, copies], rounds) of the last simplify_batch_paths"""
+        r = C.c_uint32()
+        ms = _phase_ms(lib().oxhip_prm_batch_simplify_last_timing, self._h, 4, r)
+        return dict(phase_ms=ms.tolist(), rounds=r.value)

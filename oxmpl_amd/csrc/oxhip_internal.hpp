@@ -338,4 +338,38 @@ uint64_t path_pair_words(uint32_t len, uint32_t max_span);   // 64-bit words of 
 void launch_path_pairs(const DevParams& p, const PairArgs& a, hipStream_t s);
 void launch_path_dp(const DevParams& p, const PairArgs& a, const SimplifyOut& o, hipStream_t s);
 
+// prm_path_simplify.hip: the answered paths of a PRM batch, subdivided into m parts per edge and shortcut on the device
+// (DESIGN.md section 25).  One round serves the queries [q0, q0 + n_chunk); row c of a per-round array is query q0 + c, and the
+// dense arrays hold the round's dense paths back to back (doff).
+struct DenseArgs {
+    const uint64_t* off;         // [Q + 1] first raw row of every query's path   (whole batch)
+    const uint32_t* len;         // [Q] raw states of the path, 0 = not answered
+    const double* rows;          // [total][width] the raw rows
+    const uint64_t* doff;        // [n_chunk + 1] first dense row of every query of the round
+    const uint64_t* woff;        // [n_chunk + 1] first word of every query's bit matrix within `bits`
+    double* dense;               // [n_rows][width] the dense paths
+    uint64_t* bits;              // bit (d - 2) * M + u of a query: check_motion(q_u, q_{u + d}), 2 <= d <= W, not on one edge
+    uint64_t n_words, n_rows;
+    uint32_t q0, n_chunk, m, max_span;
+    double filt_base;            // the midpoint filter's absolute margin from the bounds and the sphere centres (R^n)
+};
+struct DenseOut {
+    double* cost;                // [n_rows] per dense state: cost of the best chain from q_0
+    uint32_t* par;               // [n_rows] ... and the state before it on that chain
+    uint32_t* idx;               // [n_rows] the chain's dense indices in path order, at the query's dense offset
+    uint32_t* simp_len;          // [n_chunk]
+    double* raw_cost;            // [n_chunk]
+    double* simp_cost;           // [n_chunk]
+    uint64_t* checks;            // [n_chunk] pairs of the window that are not on one edge
+    const uint64_t* soff;        // [n_chunk + 1] the gather's: first compact row of every query
+    uint32_t* out_idx;           // [compact rows]
+    double* out_rows;            // [compact rows][width]
+};
+uint64_t dense_path_rows(uint32_t len, uint32_t m);                       // M = (L - 1) m + 1, 0 for no path
+uint64_t dense_pair_words(uint32_t len, uint32_t m, uint32_t max_span);   // 64-bit words of one query's bit matrix
+void launch_dense_rows(bool so3, uint32_t dim, const DenseArgs& a, hipStream_t s);
+void launch_dense_pairs(const DevParams& p, const DenseArgs& a, hipStream_t s);
+void launch_dense_dp(bool so3, uint32_t dim, const DenseArgs& a, const DenseOut& o, hipStream_t s);
+void launch_dense_gather(uint32_t width, const DenseArgs& a, const DenseOut& o, hipStream_t s);
+
 }  // namespace oxhip

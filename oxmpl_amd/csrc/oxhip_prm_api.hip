@@ -3,7 +3,7 @@
 // Host side of oxmpl's PRM (oxmpl/src/geometric/planners/prm.rs): owns the device roadmap and drives the kernels of prm_kernels.hip
 // (space = OXHIP_SPACE_SO3: prm_so3.hip).  No CPU fallback: without a HIP device every computing entry point fails.
 // The handle (struct oxhip_prm) holds the roadmap as one value (PrmRoadmap) and one member per service -- sampler, k-nearest,
-// construction's workspace and tally, single query, batch, shortest, re-check, growth, components, prune -- each with its clock
+// construction's workspace and tally, single query, batch, shortest, re-check, growth, components, prune, simplify -- each with its clock
 // (PhaseClock, oxhip_host.hpp), phase times and validity flag.  Each entry point is a sequence of named steps (DESIGN.md section 1,
 // "PRM host side"): create = validate_prm_config, select_device, fill_prm_params, alloc_prm; construct_roadmap = the reference's loop
 // over sample_until, knn_row_radii, find_pairs, knn_select, reserve_keys, check_edges, then build_csr, adding up into the tally their
@@ -12,7 +12,9 @@
 // extract_round_paths; revalidate (section 20) and the two below start from milestone_validity; grow_roadmap (section 23) = that
 // liveness mask, grow_capacity, keys_from_csr, then grow_round: construction's steps into growth's tally, with drop_dead_candidates
 // before the edges; components (section 24) = components_of, then the copies; prune = prune_stage1_mask, components_of(alive),
-// prune_stage2_mask, compact_roadmap.  The space is named by the dispatchers below the handle, the per-space part of the sampler,
+// prune_stage2_mask, compact_roadmap; batch_simplify_paths (section 25) = reserve_simplify_workspace, stage_paths, then per round
+// subdivide_round, pairs_round, dp_round, collect_round (the workspace is reserved before the paths are staged, not after as the
+// steps were first listed: the reservation is where a path too large is refused, and a refused call keeps the last results).  The space is named by the dispatchers below the handle, the per-space part of the sampler,
 // the steps of create, the two obstacle setters and the prm_shortest launches that take it as an argument.
 #include <algorithm>
 #include <chrono>
@@ -165,6 +167,19 @@ struct oxhip_prm {
         DevBuf<uint32_t> pos, epos, kept;
         DevBuf<int32_t> index;
     } prune;
+    struct {   // oxhip_prm_batch_simplify_paths: the last batch's answered paths, subdivided and shortcut
+        PhaseClock clk{8};
+        double ms[4] = {};   // upload + subdivide, pair matrix, DP, copies
+        bool valid = false;  // the results below belong to the current batch: dropped with it (drop_derived, stage_batch)
+        uint32_t rounds = 0;
+        std::vector<uint64_t> soff, checks;          // [Q + 1] row offsets of the simplified paths, [Q]
+        std::vector<uint32_t> idx;                   // dense indices of their rows
+        std::vector<double> rows, raw_cost, simp_cost;
+        // d_: the raw paths of the batch, then the per-round workspace
+        DevBuf<uint64_t> d_off, d_doff, d_woff, d_bits, d_checks, d_soff;
+        DevBuf<uint32_t> d_len, d_par, d_idx, d_simp_len, d_out_idx;
+        DevBuf<double> d_rows, d_dense, d_cost, d_raw, d_simp, d_out_rows;
+    } simplify;
 };
 
 namespace {
@@ -250,13 +265,13 @@ int32_t set_query(oxhip_prm* h, const double* start, const double* goal_centre, 
 // the kernels' view of the milestones, re-derived from the roadmap: whatever replaces one of its buffers ends here
 void bind_roadmap(oxhip_prm* h) { h->args.ms = h->rm.ms.p; h->args.ms32 = h->rm.ms32.p; }
 
-// What is derived from the roadmap as it was -- the host copy, the single query's sets, the last batch's results (batch.valid), the
+// What is derived from the roadmap as it was -- the host copy, the single query's sets, the last batch's results (batch.valid) and their shortcut (simplify.valid), the
 // edge weights (shortest.w_valid), the component labels (cc.valid) -- and so is gone when it changes: every function that changes `rm` ends here.
 void drop_derived(oxhip_prm* h) {
     h->single.host_copy = false;
     h->single.h_offsets.clear(); h->single.h_nbrs.clear(); h->single.h_states.clear();
     h->single.start_conn.clear(); h->single.goal_idx.clear();
-    h->batch.valid = h->shortest.w_valid = h->cc.valid = false;
+    h->batch.valid = h->simplify.valid = h->shortest.w_valid = h->cc.valid = false;
 }
 
 // setup: no roadmap; set_roadmap: one of n milestones that this handle did not sample.  The samples and the stream position
@@ -425,7 +440,7 @@ int32_t alloc_prm(oxhip_prm* h) {
     hipError_t e = hipSuccess;
     auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
     chk(oxhip_stream_acquire(h->cfg.device, &h->stream));
-    for (const PhaseClock* c : {&h->built.clk, &h->single.clk, &h->batch.clk, &h->shortest.clk, &h->reval.clk, &h->grow.tally.clk, &h->cc.clk, &h->prune.clk})
+    for (const PhaseClock* c : {&h->built.clk, &h->single.clk, &h->batch.clk, &h->shortest.clk, &h->reval.clk, &h->grow.tally.clk, &h->cc.clk, &h->prune.clk, &h->simplify.clk})
         chk(c->made);   // an event that could not be made refuses the create, as a buffer does
     chk(h->rm.ms.alloc((size_t)dim * cap));
     if (!h->so3) chk(h->rm.ms32.alloc((size_t)dim * cap));   // (the SO(3) pair search screens nothing)
@@ -877,7 +892,7 @@ int32_t stage_batch(oxhip_prm* h, uint32_t Q, const double* starts, const double
     const uint32_t dim = h->cfg.dim;
     OX_TRY(check_query_points(starts, goal_centres, (size_t)Q * dim));
     OX_TRY(select_device(h->cfg.device));
-    h->batch.valid = false;
+    h->batch.valid = h->simplify.valid = false;
     h->batch.rounds = 0;
     h->batch.mode = mode;
     for (double& t : h->batch.ms) t = 0.0;
@@ -1654,6 +1669,313 @@ int32_t oxhip_prm_prune(oxhip_prm* h, const oxhip_prm_prune_config* c, const uin
 int32_t oxhip_prm_prune_last_timing(oxhip_prm* h, double* phase_ms) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
     if (phase_ms) for (int i = 0; i < 5; ++i) phase_ms[i] = h->prune.ms[i];
+    return OXHIP_OK;
+}
+
+}  // extern "C"
+
+// ---- the handle's own validity checker, and the last batch's answered paths subdivided and shortcut
+
+namespace {
+
+enum SimplifyMark { kSpStageBegin, kSpStageEnd, kSpRoundBegin, kSpRowsEnd, kSpPairsEnd, kSpDpEnd, kSpCopyBegin, kSpCopyEnd };
+
+constexpr uint64_t kSimplifyMatrixBytes = 1ull << 30;   // a round's bit matrices stay within this
+
+// what every call of this service opens with: the handle, setup(), and -- for the calls that read the last batch -- the batch
+int32_t simplify_ready(const oxhip_prm* h, bool needs_batch) {
+    if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
+    if (!h->is_setup) return fail(OXHIP_ERR_PLANNER_UNINITIALISED, "setup() was not called");
+    if (needs_batch && !h->batch.valid) return fail(OXHIP_ERR_UNSAMPLED_STATE_SPACE, "no batch was solved on this roadmap");
+    return OXHIP_OK;
+}
+
+int32_t check_subdivide(uint32_t subdivide) {
+    if (subdivide == 0 || subdivide > 256u) return fail(OXHIP_ERR_BAD_ARG, "subdivide must be in 1..256");
+    return OXHIP_OK;
+}
+
+// the size of one path's dense form and matrix, refused when no round could hold it
+int32_t dense_shape(uint32_t len, uint32_t m, uint32_t max_span, uint64_t& rows, uint64_t& words) {
+    rows = dense_path_rows(len, m);
+    words = dense_pair_words(len, m, max_span);
+    if (rows > 0x7FFFFFFFull || words * 8ull > kSimplifyMatrixBytes)
+        return fail(OXHIP_ERR_CAPACITY, "one path's pair matrix is larger than 1 GiB: pass a max_span or a smaller subdivide");
+    return OXHIP_OK;
+}
+
+// one simplify while it runs: its shape, its rounds [first[r], first[r + 1]) and a round's tables on the host
+struct SimplifyRun {
+    uint32_t Q = 0, m = 1, max_span = 0, width = 0;
+    std::vector<uint32_t> first;           // the first query of every round, then Q
+    uint64_t max_rows = 0, max_words = 0;  // of the largest round
+    uint32_t max_chunk = 0;
+    std::vector<uint64_t> doff, woff, soff;
+    std::vector<uint32_t> simp_len;
+};
+
+DenseArgs dense_args(oxhip_prm* h, const SimplifyRun& run, uint32_t q0, uint32_t c) {
+    DenseArgs a{};
+    a.off = h->simplify.d_off.p; a.len = h->simplify.d_len.p; a.rows = h->simplify.d_rows.p;
+    a.doff = h->simplify.d_doff.p; a.woff = h->simplify.d_woff.p; a.dense = h->simplify.d_dense.p; a.bits = h->simplify.d_bits.p;
+    a.q0 = q0; a.n_chunk = c; a.m = run.m; a.max_span = run.max_span;
+    a.filt_base = h->dp.filt_abs;
+    return a;
+}
+
+DenseOut dense_out(oxhip_prm* h) {
+    DenseOut o{};
+    o.cost = h->simplify.d_cost.p; o.par = h->simplify.d_par.p; o.idx = h->simplify.d_idx.p; o.simp_len = h->simplify.d_simp_len.p;
+    o.raw_cost = h->simplify.d_raw.p; o.simp_cost = h->simplify.d_simp.p; o.checks = h->simplify.d_checks.p;
+    o.soff = h->simplify.d_soff.p; o.out_idx = h->simplify.d_out_idx.p; o.out_rows = h->simplify.d_out_rows.p;
+    return o;
+}
+
+// the batch's raw paths, from its host copy off / rows / len, to the device; the host side of the results starts empty
+int32_t stage_paths(oxhip_prm* h, const SimplifyRun& run) {
+    auto& sp = h->simplify;
+    const size_t total = h->batch.nodes.size();
+    sp.valid = false; sp.rounds = 0;
+    for (double& t : sp.ms) t = 0.0;
+    sp.soff.assign((size_t)run.Q + 1, 0); sp.checks.assign(run.Q, 0);
+    sp.raw_cost.assign(run.Q, 0.0); sp.simp_cost.assign(run.Q, 0.0);
+    sp.idx.clear(); sp.rows.clear();
+    if (!run.Q) return OXHIP_OK;
+    HIP_TRY(sp.d_off.reserve((size_t)run.Q + 1)); HIP_TRY(sp.d_len.reserve(run.Q)); HIP_TRY(sp.d_rows.reserve(std::max<size_t>(1, total * run.width)));
+    HIP_TRY(sp.clk.mark(kSpStageBegin, h->stream));
+    HIP_TRY(hipMemcpyAsync(sp.d_off.p, h->batch.off.data(), ((size_t)run.Q + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(sp.d_len.p, h->batch.len.data(), (size_t)run.Q * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    if (total) HIP_TRY(hipMemcpyAsync(sp.d_rows.p, h->batch.rows.data(), total * run.width * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(sp.clk.mark(kSpStageEnd, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    sp.ms[0] += sp.clk.ms(kSpStageBegin, kSpStageEnd);
+    return OXHIP_OK;
+}
+
+// The rounds -- queries are taken in order while their matrices stay within 1 GiB together and, with chunk_queries given, while
+// the round holds fewer than that many -- and every buffer the largest of them needs
+int32_t reserve_simplify_workspace(oxhip_prm* h, SimplifyRun& run, uint32_t chunk_queries) {
+    const uint32_t limit = chunk_queries ? std::min(chunk_queries, 65535u) : 65535u;
+    uint64_t rows = 0, words = 0;
+    run.first.assign(1, 0u);
+    auto close_round = [&](uint32_t q) {
+        run.max_rows = std::max(run.max_rows, rows); run.max_words = std::max(run.max_words, words);
+        run.max_chunk = std::max(run.max_chunk, q - run.first.back());
+        run.first.push_back(q);
+        rows = words = 0;
+    };
+    for (uint32_t q = 0; q < run.Q; ++q) {
+        uint64_t r = 0, w = 0;
+        OX_TRY(dense_shape(h->batch.len[q], run.m, run.max_span, r, w));
+        if (q > run.first.back() && ((words + w) * 8ull > kSimplifyMatrixBytes || q - run.first.back() >= limit)) close_round(q);
+        rows += r; words += w;
+    }
+    if (run.Q) close_round(run.Q);
+    auto& sp = h->simplify;
+    const size_t c1 = (size_t)run.max_chunk + 1, nr = std::max<size_t>(1, run.max_rows);
+    HIP_TRY(sp.d_doff.reserve(c1)); HIP_TRY(sp.d_woff.reserve(c1)); HIP_TRY(sp.d_soff.reserve(c1));
+    HIP_TRY(sp.d_simp_len.reserve(c1)); HIP_TRY(sp.d_raw.reserve(c1)); HIP_TRY(sp.d_simp.reserve(c1)); HIP_TRY(sp.d_checks.reserve(c1));
+    HIP_TRY(sp.d_dense.reserve(nr * run.width)); HIP_TRY(sp.d_out_rows.reserve(nr * run.width));
+    HIP_TRY(sp.d_cost.reserve(nr)); HIP_TRY(sp.d_par.reserve(nr)); HIP_TRY(sp.d_idx.reserve(nr)); HIP_TRY(sp.d_out_idx.reserve(nr));
+    HIP_TRY(sp.d_bits.reserve(std::max<size_t>(1, run.max_words)));
+    run.doff.resize(c1); run.woff.resize(c1); run.soff.resize(c1); run.simp_len.resize(c1);
+    return OXHIP_OK;
+}
+
+// the round's tables (where each query's dense rows and matrix words begin) and its dense paths
+int32_t subdivide_round(oxhip_prm* h, SimplifyRun& run, DenseArgs& a) {
+    auto& sp = h->simplify;
+    const uint32_t c = a.n_chunk;
+    run.doff[0] = run.woff[0] = 0;
+    for (uint32_t i = 0; i < c; ++i) {
+        const uint32_t len = h->batch.len[a.q0 + i];
+        run.doff[i + 1] = run.doff[i] + dense_path_rows(len, run.m);
+        run.woff[i + 1] = run.woff[i] + dense_pair_words(len, run.m, run.max_span);
+    }
+    a.n_rows = run.doff[c]; a.n_words = run.woff[c];
+    HIP_TRY(sp.clk.mark(kSpRoundBegin, h->stream));
+    HIP_TRY(hipMemcpyAsync(sp.d_doff.p, run.doff.data(), ((size_t)c + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(sp.d_woff.p, run.woff.data(), ((size_t)c + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+    launch_dense_rows(h->so3, h->cfg.dim, a, h->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(sp.clk.mark(kSpRowsEnd, h->stream));
+    return OXHIP_OK;
+}
+
+// check_motion per pair of the round's windows that is not on one edge, against the obstacles as they are now
+int32_t pairs_round(oxhip_prm* h, const DenseArgs& a) {
+    launch_dense_pairs(h->dp, a, h->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(h->simplify.clk.mark(kSpPairsEnd, h->stream));
+    return OXHIP_OK;
+}
+
+int32_t dp_round(oxhip_prm* h, const DenseArgs& a, const DenseOut& o) {
+    launch_dense_dp(h->so3, h->cfg.dim, a, o, h->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(h->simplify.clk.mark(kSpDpEnd, h->stream));
+    return OXHIP_OK;
+}
+
+// the round's chains: their lengths, then indices and rows compacted on the device and appended to the host side; the phase times
+int32_t collect_round(oxhip_prm* h, SimplifyRun& run, const DenseArgs& a, const DenseOut& o) {
+    auto& sp = h->simplify;
+    const uint32_t c = a.n_chunk, q0 = a.q0, width = run.width;
+    HIP_TRY(sp.clk.mark(kSpCopyBegin, h->stream));
+    HIP_TRY(hipMemcpyAsync(run.simp_len.data(), sp.d_simp_len.p, (size_t)c * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    run.soff[0] = 0;
+    for (uint32_t i = 0; i < c; ++i) {
+        run.soff[i + 1] = run.soff[i] + run.simp_len[i];
+        sp.soff[q0 + i + 1] = sp.soff[q0] + run.soff[i + 1];
+    }
+    const uint64_t n_out = run.soff[c], row0 = sp.soff[q0];
+    if (n_out > a.n_rows) return fail(OXHIP_ERR_HIP, "simplify: a chain longer than its dense path, which cannot happen");
+    sp.idx.resize((size_t)(row0 + n_out)); sp.rows.resize((size_t)(row0 + n_out) * width);
+    HIP_TRY(hipMemcpyAsync(sp.d_soff.p, run.soff.data(), ((size_t)c + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+    launch_dense_gather(width, a, o, h->stream);
+    HIP_TRY(hipGetLastError());
+    if (n_out) {
+        HIP_TRY(hipMemcpyAsync(sp.idx.data() + row0, sp.d_out_idx.p, (size_t)n_out * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(sp.rows.data() + (size_t)row0 * width, sp.d_out_rows.p, (size_t)n_out * width * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(sp.raw_cost.data() + q0, sp.d_raw.p, (size_t)c * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(sp.simp_cost.data() + q0, sp.d_simp.p, (size_t)c * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(sp.checks.data() + q0, sp.d_checks.p, (size_t)c * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(sp.clk.mark(kSpCopyEnd, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    sp.ms[0] += sp.clk.ms(kSpRoundBegin, kSpRowsEnd);
+    sp.ms[1] += sp.clk.ms(kSpRowsEnd, kSpPairsEnd);
+    sp.ms[2] += sp.clk.ms(kSpPairsEnd, kSpDpEnd);
+    sp.ms[3] += sp.clk.ms(kSpCopyBegin, kSpCopyEnd);
+    return OXHIP_OK;
+}
+
+// the handle's StateValidityChecker and check_motion over caller rows: what an RRT batch of the same space launches
+template <typename Launch>
+int32_t checker_rows(oxhip_prm* h, const double* a, const double* b, uint32_t n, uint8_t* out, Launch&& launch) {
+    OX_TRY(simplify_ready(h, false));
+    if (!a || !out) return fail(OXHIP_ERR_BAD_ARG, "null argument");
+    if (n == 0) return OXHIP_OK;
+    OX_TRY(select_device(h->cfg.device));
+    DevBuf<double> da, db;
+    DevBuf<uint8_t> dout;
+    OX_TRY(to_device(da, a, (size_t)n * h->cfg.dim, h->stream));
+    if (b) OX_TRY(to_device(db, b, (size_t)n * h->cfg.dim, h->stream));
+    HIP_TRY(dout.alloc(n));
+    launch(da.p, db.p, dout.p);
+    HIP_TRY(hipGetLastError());
+    return to_host(out, dout, n, h->stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t oxhip_prm_is_valid(oxhip_prm* h, const double* states, uint32_t n, uint8_t* out) {
+    return checker_rows(h, states, nullptr, n, out, [&](const double* s, const double*, uint8_t* o) {
+        if (h->so3) launch_so3_is_valid(h->dp, s, n, o, h->stream);
+        else launch_is_valid(h->dp, s, n, o, h->stream);
+    });
+}
+
+int32_t oxhip_prm_check_motion(oxhip_prm* h, const double* from, const double* to, uint32_t n, uint8_t* out) {
+    if (h && !to) return fail(OXHIP_ERR_BAD_ARG, "null argument");
+    return checker_rows(h, from, to, n, out, [&](const double* f, const double* t, uint8_t* o) {
+        if (h->so3) launch_so3_check_motion(h->dp, f, t, n, o, h->stream);
+        else launch_check_motion(h->dp, f, t, n, o, h->stream);
+    });
+}
+
+int32_t oxhip_prm_batch_simplify_paths(oxhip_prm* h, uint32_t subdivide, uint32_t max_span, uint32_t chunk_queries) {
+    OX_TRY(simplify_ready(h, true));
+    OX_TRY(check_subdivide(subdivide));
+    OX_TRY(select_device(h->cfg.device));
+    SimplifyRun run;
+    run.Q = (uint32_t)h->batch.status.size(); run.m = subdivide; run.max_span = max_span; run.width = h->cfg.dim;
+    OX_TRY(reserve_simplify_workspace(h, run, chunk_queries));   // (refuses a path too large before anything is staged: the last results stay)
+    OX_TRY(stage_paths(h, run));
+    const DenseOut o = dense_out(h);
+    for (size_t r = 0; r + 1 < run.first.size(); ++r) {
+        DenseArgs a = dense_args(h, run, run.first[r], run.first[r + 1] - run.first[r]);
+        OX_TRY(subdivide_round(h, run, a));
+        OX_TRY(pairs_round(h, a));
+        OX_TRY(dp_round(h, a, o));
+        OX_TRY(collect_round(h, run, a, o));
+        ++h->simplify.rounds;
+    }
+    h->simplify.valid = true;
+    return OXHIP_OK;
+}
+
+int32_t oxhip_prm_batch_get_simplified_paths(oxhip_prm* h, uint64_t* offsets, double* states, uint32_t* indices, uint64_t cap_rows,
+                                             uint64_t* total_rows) {
+    OX_TRY(simplify_ready(h, true));
+    if (!h->simplify.valid) return fail(OXHIP_ERR_BAD_ARG, "no simplified paths: call oxhip_prm_batch_simplify_paths after the last batch");
+    const uint64_t total = h->simplify.idx.size();
+    if (total_rows) *total_rows = total;
+    if (offsets) std::memcpy(offsets, h->simplify.soff.data(), h->simplify.soff.size() * sizeof(uint64_t));
+    if ((states || indices) && cap_rows < total) return fail(OXHIP_ERR_CAPACITY, "path buffers too small");
+    if (indices && total) std::memcpy(indices, h->simplify.idx.data(), (size_t)total * sizeof(uint32_t));
+    if (states && total) std::memcpy(states, h->simplify.rows.data(), h->simplify.rows.size() * sizeof(double));
+    return OXHIP_OK;
+}
+
+int32_t oxhip_prm_batch_get_simplify_results(oxhip_prm* h, double* raw_cost, double* simplified_cost, uint64_t* checks) {
+    OX_TRY(simplify_ready(h, true));
+    if (!h->simplify.valid) return fail(OXHIP_ERR_BAD_ARG, "no simplified paths: call oxhip_prm_batch_simplify_paths after the last batch");
+    const size_t Q = h->simplify.checks.size();
+    if (raw_cost && Q) std::memcpy(raw_cost, h->simplify.raw_cost.data(), Q * sizeof(double));
+    if (simplified_cost && Q) std::memcpy(simplified_cost, h->simplify.simp_cost.data(), Q * sizeof(double));
+    if (checks && Q) std::memcpy(checks, h->simplify.checks.data(), Q * sizeof(uint64_t));
+    return OXHIP_OK;
+}
+
+// test hook: the pair kernel's verdicts on one query's dense path, in buffers of its own (the last simplify's results stay)
+int32_t oxhip_prm_batch_path_valid_matrix(oxhip_prm* h, uint32_t query, uint32_t subdivide, uint32_t max_span, uint8_t* out, uint64_t cap_bytes,
+                                          uint32_t* len_out) {
+    OX_TRY(simplify_ready(h, true));
+    if (!len_out) return fail(OXHIP_ERR_BAD_ARG, "null argument");
+    OX_TRY(check_subdivide(subdivide));
+    if (query >= h->batch.status.size()) return fail(OXHIP_ERR_BAD_ARG, "query index beyond the last batch");
+    const uint32_t L = h->batch.len[query], width = h->cfg.dim, m = subdivide;
+    uint64_t M = 0, words = 0;
+    OX_TRY(dense_shape(L, m, max_span, M, words));
+    *len_out = (uint32_t)M;
+    if (!out || M == 0) return OXHIP_OK;
+    if (cap_bytes < M * M) return fail(OXHIP_ERR_CAPACITY, "matrix buffer too small");
+    OX_TRY(select_device(h->cfg.device));
+    const uint64_t off[2] = {0, L}, doff[2] = {0, M}, woff[2] = {0, words};
+    DevBuf<uint64_t> d_off, d_doff, d_woff, d_bits;
+    DevBuf<uint32_t> d_len;
+    DevBuf<double> d_rows, d_dense;
+    OX_TRY(to_device(d_off, off, 2, h->stream)); OX_TRY(to_device(d_doff, doff, 2, h->stream)); OX_TRY(to_device(d_woff, woff, 2, h->stream));
+    OX_TRY(to_device(d_len, &L, 1, h->stream));
+    OX_TRY(to_device(d_rows, h->batch.rows.data() + (size_t)h->batch.off[query] * width, (size_t)L * width, h->stream));
+    HIP_TRY(d_dense.alloc((size_t)M * width)); HIP_TRY(d_bits.alloc(std::max<size_t>(1, words)));
+    DenseArgs a{};
+    a.off = d_off.p; a.len = d_len.p; a.rows = d_rows.p; a.doff = d_doff.p; a.woff = d_woff.p; a.dense = d_dense.p; a.bits = d_bits.p;
+    a.n_words = words; a.n_rows = M; a.q0 = 0; a.n_chunk = 1; a.m = m; a.max_span = max_span; a.filt_base = h->dp.filt_abs;
+    launch_dense_rows(h->so3, width, a, h->stream);
+    launch_dense_pairs(h->dp, a, h->stream);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint64_t> bits(words);
+    OX_TRY(to_host(bits.data(), d_bits, words, h->stream));
+    const uint32_t full = L - 1u;
+    const uint64_t Wd = (uint64_t)(max_span == 0u || max_span > full ? full : max_span) * m;
+    std::memset(out, 0, (size_t)(M * M));
+    for (uint64_t u = 0; u + 1 < M; ++u)
+        for (uint64_t v = u + 1; v < M && v - u <= Wd; ++v) {
+            const uint64_t slot = (v - u - 2) * M + u;   // (read for pairs that are not on one edge only: those have d >= 2)
+            out[u * M + v] = u / m == (v - 1) / m ? 1 : (uint8_t)((bits[slot >> 6] >> (slot & 63u)) & 1ull);
+        }
+    return OXHIP_OK;
+}
+
+int32_t oxhip_prm_batch_simplify_last_timing(oxhip_prm* h, double* phase_ms, uint32_t* rounds) {
+    OX_TRY(simplify_ready(h, false));
+    if (phase_ms) for (int i = 0; i < 4; ++i) phase_ms[i] = h->simplify.ms[i];
+    if (rounds) *rounds = h->simplify.rounds;
     return OXHIP_OK;
 }
 

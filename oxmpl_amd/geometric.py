@@ -349,6 +349,31 @@ class PRM:
                 out.append(_path(self._pd.space, rows[int(offsets[q]):int(offsets[q + 1])]))
         return out
 
+    def simplify_batch(self, subdivide=1, max_span=0):
+        """The answered paths of the last solve_batch, shortcut on the device (oxhip_prm_batch_simplify_paths, DESIGN.md
+        section 25): every edge is first cut into `subdivide` equal parts, so a link may leave and join the path between its
+        milestones, and the cheapest chain of the resulting points whose links pass the planner's own check_motion is
+        returned; `max_span` bounds how many original edges a link may span, 0 = no bound.  Returns a list with a Path per
+        answered problem and None for every other one.  Not part of the reference's surface.  ValueError for a refused
+        argument or a path too large for the device's pair matrix; the reference-style Exception when no batch was solved."""
+        prm = _ready(self._prm)
+        with _translated(_REFUSED_ARGUMENT):
+            prm.simplify_batch_paths(int(subdivide), int(max_span))
+            offsets, rows, _ = prm.simplified_batch_paths()
+        return [_path(self._pd.space, rows[int(a):int(b)]) if b > a else None for a, b in zip(offsets[:-1], offsets[1:])]
+
+    def simplify_solution(self, subdivide=1, max_span=0):
+        """The planner's own problem definition answered and shortcut: it runs that query as a one-query batch, which
+        replaces "the last batch" (a solve_batch's paths are gone afterwards), and shortcuts it as simplify_batch does
+        -> Path.  Raises the reference-style Exception when the query has no solution."""
+        prm = _ready(self._prm)
+        pd = self._pd
+        with _translated():
+            status = prm.solve_batch([pd.start_state.values], [pd.goal.target.values], [float(pd.goal.radius)])
+        if status[0] != capi.OK:
+            raise Exception(_MESSAGES.get(int(status[0]), capi.status_string(int(status[0]))))
+        return self.simplify_batch(subdivide, max_span)[0]
+
     def get_roadmap(self):
         """PRM::get_roadmap (prm.rs:82-84) as (states, offsets, neighbours): node i's edges are
         neighbours[offsets[i]:offsets[i+1]].  SO(3) problems: states is a list of SO3State; a real-vector roadmap's states

@@ -328,6 +328,13 @@ extern "C" {
     pub fn oxhip_prm_components_last_timing(p: *mut OxhipPrm, phase_ms: *mut f64, launches: *mut u32) -> i32;
     pub fn oxhip_prm_prune(p: *mut OxhipPrm, c: *const OxhipPrmPruneConfig, keep: *const u8, new_index: *mut i32, n_kept: *mut u32, n_removed_entries: *mut u64) -> i32;
     pub fn oxhip_prm_prune_last_timing(p: *mut OxhipPrm, phase_ms: *mut f64) -> i32;
+    pub fn oxhip_prm_is_valid(p: *mut OxhipPrm, states: *const f64, n: u32, out: *mut u8) -> i32;
+    pub fn oxhip_prm_check_motion(p: *mut OxhipPrm, from: *const f64, to: *const f64, n: u32, out: *mut u8) -> i32;
+    pub fn oxhip_prm_batch_simplify_paths(p: *mut OxhipPrm, subdivide: u32, max_span: u32, chunk_queries: u32) -> i32;
+    pub fn oxhip_prm_batch_get_simplified_paths(p: *mut OxhipPrm, offsets: *mut u64, states: *mut f64, indices: *mut u32, cap_rows: u64, total_rows: *mut u64) -> i32;
+    pub fn oxhip_prm_batch_get_simplify_results(p: *mut OxhipPrm, raw_cost: *mut f64, simplified_cost: *mut f64, checks: *mut u64) -> i32;
+    pub fn oxhip_prm_batch_path_valid_matrix(p: *mut OxhipPrm, query: u32, subdivide: u32, max_span: u32, out: *mut u8, cap_bytes: u64, len_out: *mut u32) -> i32;
+    pub fn oxhip_prm_batch_simplify_last_timing(p: *mut OxhipPrm, phase_ms: *mut f64, rounds: *mut u32) -> i32;
     // rrt_revalidate.hip: the trees of an RRT batch re-checked against the current obstacles
     pub fn oxhip_rrt_batch_revalidate_trees(b: *mut OxhipRrtBatch, n_removed: *mut u32, goal_lost: *mut u8) -> i32;
     pub fn oxhip_rrt_batch_get_revalidate_map(b: *mut OxhipRrtBatch, problem: u32, new_index: *mut i32, edge_ok: *mut u8, cap: u32, n_before: *mut u32) -> i32;

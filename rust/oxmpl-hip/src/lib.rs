@@ -424,6 +424,8 @@ pub struct HipPRM<D: DeviceValidityChecker, G: DeviceGoal> {
     checker: Arc<D>,
     problem_def: Option<Arc<Pd<G>>>,
     prm: *mut ffi::OxhipPrm,
+    /// problems of the last `solve_batch` / `solve_batch_shortest`: what `simplify_batch` returns one entry each for
+    last_batch_len: usize,
 }
 
 impl<D: DeviceValidityChecker, G: DeviceGoal> HipPRM<D, G> {
@@ -437,6 +439,7 @@ impl<D: DeviceValidityChecker, G: DeviceGoal> HipPRM<D, G> {
             checker,
             problem_def: None,
             prm: ptr::null_mut(),
+            last_batch_len: 0,
         }
     }
 
@@ -638,6 +641,37 @@ impl<D: DeviceValidityChecker, G: DeviceGoal> HipPRM<D, G> {
         self.solve_batch_with(problems, timeout, true)
     }
 
+    /// The answered paths of the last `solve_batch` / `solve_batch_shortest`, shortcut on the device
+    /// (`oxhip_prm_batch_simplify_paths`): every edge is first cut into `subdivide` equal parts, then the cheapest chain of
+    /// the resulting points whose links pass the planner's own `check_motion` is taken; `max_span` bounds a link in original
+    /// edges, 0 = no bound.  One entry per problem of that batch, `None` for an unanswered one; `Err` carries the library's message.
+    pub fn simplify_batch(&mut self, subdivide: u32, max_span: u32) -> Result<Vec<Option<Path<RealVectorState>>>, String> {
+        let dim = match (&self.problem_def, self.prm.is_null()) {
+            (Some(pd), false) => pd.space.dimension,
+            _ => return Err("setup() was not called".to_string()),
+        };
+        if unsafe { ffi::oxhip_prm_batch_simplify_paths(self.prm, subdivide, max_span, 0) } != ffi::OXHIP_OK {
+            return Err(last_error());
+        }
+        let q = self.last_batch_len;
+        let mut offsets = vec![0u64; q + 1];
+        let mut total = 0u64;
+        if unsafe { ffi::oxhip_prm_batch_get_simplified_paths(self.prm, offsets.as_mut_ptr(), ptr::null_mut(), ptr::null_mut(), 0, &mut total) } != ffi::OXHIP_OK {
+            return Err(last_error());
+        }
+        let mut flat = vec![0.0f64; (total as usize * dim).max(1)];
+        let st = unsafe { ffi::oxhip_prm_batch_get_simplified_paths(self.prm, offsets.as_mut_ptr(), flat.as_mut_ptr(), ptr::null_mut(), total, &mut total) };
+        if st != ffi::OXHIP_OK {
+            return Err(last_error());
+        }
+        Ok((0..q)
+            .map(|i| {
+                let (a, b) = (offsets[i] as usize, offsets[i + 1] as usize);
+                (b > a).then(|| Path(flat[a * dim..b * dim].chunks(dim).map(|c| RealVectorState::new(c.to_vec())).collect()))
+            })
+            .collect())
+    }
+
     fn solve_batch_with(&mut self, problems: &[Arc<Pd<G>>], timeout: Duration, shortest: bool) -> Vec<Result<Path<RealVectorState>, PlanningError>> {
         let dim = match (&self.problem_def, self.prm.is_null()) {
             (Some(pd), false) => pd.space.dimension,
@@ -663,6 +697,7 @@ impl<D: DeviceValidityChecker, G: DeviceGoal> HipPRM<D, G> {
         if st != ffi::OXHIP_OK {
             return problems.iter().map(|_| Err(to_planning_error(st))).collect();
         }
+        self.last_batch_len = q; // the library accepted the batch; a refused call leaves its last batch, and this count, as they were
         let mut offsets = vec![0u64; q + 1];
         let mut total = 0u64;
         unsafe { ffi::oxhip_prm_batch_get_paths(self.prm, offsets.as_mut_ptr(), ptr::null_mut(), ptr::null_mut(), 0, &mut total) };
