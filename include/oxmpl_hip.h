@@ -344,7 +344,8 @@ int32_t oxhip_rrt_batch_get_goal_tree(oxhip_rrt_batch* b, uint32_t problem, doub
 int32_t oxhip_rrt_batch_get_costs(oxhip_rrt_batch* b, uint32_t problem, double* costs, uint32_t cap_nodes,
                                   uint32_t* n_nodes);
 
-/* ---- the whole batch's solution paths, extracted and shortcut on the device (path_simplify.hip) ----
+/* ---- the whole batch's solution paths, extracted and shortcut on the device (path_simplify.hip extracts, shortcut_core.hip
+ * shortcuts with every waypoint a row) ----
  * extract_paths walks the parent chain of every problem whose goal_node >= 0 on the device (RRTConnect: plus the goal-tree
  * chain, spliced as get_path splices it) and keeps the rows in path order behind a per-problem offset; an unsolved problem has
  * length 0.  Every space and planner a batch can hold.  get_paths hands everything out in one copy: problem p's path is rows
@@ -729,7 +730,8 @@ int32_t oxhip_prm_prune(oxhip_prm* prm, const oxhip_prm_prune_config* c, const u
 /* HIP-event times (ms) of the last oxhip_prm_prune: phase_ms[5] = {masks, components, scans, move entries, move states} */
 int32_t oxhip_prm_prune_last_timing(oxhip_prm* prm, double* phase_ms /*[5]*/);
 
-/* ---- the handle's own checker, and the last batch's paths subdivided and shortcut (prm_path_simplify.hip) ----
+/* ---- the handle's own checker, and the last batch's paths subdivided and shortcut (prm_path_simplify.hip subdivides and compacts,
+ * shortcut_core.hip shortcuts) ----
  * is_valid / check_motion: the handle's StateValidityChecker and the check_motion that construction uses, over caller rows
  * ([n][dim]; SO(3): quaternions), against the obstacles as they are at the call; for every handle kind (radius, k-nearest,
  * SO(3)), with or without a roadmap.  Without setup(): OXHIP_ERR_PLANNER_UNINITIALISED. */

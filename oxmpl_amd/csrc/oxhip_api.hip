@@ -119,7 +119,7 @@ struct Solve {
     enum { kBegin, kEnd };
     PhaseClock clk{2};                // made with the handle: create() has the device current
 };
-// path_simplify.hip: the batch's solution paths as extract_paths / simplify_paths left them.  They belong to the trees as they
+// path_simplify.hip, shortcut_core.hip: the batch's solution paths as extract_paths / simplify_paths left them.  They belong to the trees as they
 // stood at that call (drop_derived, below).
 struct Paths {
     bool ok = false, simp_ok = false;
@@ -1264,7 +1264,7 @@ int32_t oxhip_rrt_batch_get_costs(oxhip_rrt_batch* b, uint32_t problem, double* 
     return OXHIP_OK;
 }
 
-// ------------------------------------------------------------------ the whole batch's paths (path_simplify.hip)
+// ------------------------------------------------------------------ the whole batch's paths (path_simplify.hip, shortcut_core.hip)
 
 int32_t oxhip_rrt_batch_extract_paths(oxhip_rrt_batch* b) {
     OX_TRY(ready(b));
@@ -1324,9 +1324,6 @@ int32_t oxhip_rrt_batch_get_paths(oxhip_rrt_batch* b, uint64_t* offsets_out, dou
     return OXHIP_OK;
 }
 
-// what a round of the pair matrix may take: 1 GiB of bits
-static constexpr uint64_t kPairWordsMax = (1ull << 30) / sizeof(uint64_t);
-
 // the batch's parameters as the pair kernel reads them (R^n: the radii and the absolute margin of motion_seq.hpp's midpoint filter)
 static int32_t pair_params(oxhip_rrt_batch* b, double& filt_base) {
     filt_base = 0.0;
@@ -1361,40 +1358,36 @@ int32_t oxhip_rrt_batch_simplify_paths(oxhip_rrt_batch* b, uint32_t max_span, ui
     HIP_TRY(grow(ps.sp_raw, P));
     HIP_TRY(grow(ps.sp_simp, P));
     HIP_TRY(grow(ps.sp_checks, P));
-    const SimplifyOut out{ps.sp_cost.p, ps.sp_par.p, ps.sp_idx.p, ps.sp_len.p, ps.sp_raw.p, ps.sp_simp.p, ps.sp_checks.p};
+    std::vector<uint32_t> first;   // the rounds: as many problems each as the bit workspace (and the caller's override) allows
+    uint32_t refused = 0;
+    if (!shortcut_rounds(ps.h_len.data(), P, 1, max_span, kShortcutMatrixBytes, chunk_problems, first, refused))
+        return fail(OXHIP_ERR_CAPACITY, "a path's pair matrix exceeds the 1 GiB workspace: pass a max_span");
     OX_TRY(clock_of(ps.clk, 3));
     PhaseClock& clk = *ps.clk;
     ps.ms[1] = ps.ms[2] = 0.0;
     ps.rounds = 0;
     std::vector<uint64_t> woff;
-    for (uint32_t q0 = 0; q0 < P;) {
-        // a round: as many problems as the bit workspace (and the caller's override) allows, at least one
+    for (size_t r = 0; r + 1 < first.size(); ++r) {
+        const uint32_t q0 = first[r], n_chunk = first[r + 1] - q0;
         woff.assign(1, 0);
-        uint32_t q1 = q0;
-        while (q1 < P && (chunk_problems == 0 || q1 - q0 < chunk_problems)) {
-            const uint64_t w = path_pair_words(ps.h_len[q1], max_span);
-            if (w > kPairWordsMax) return fail(OXHIP_ERR_CAPACITY, "a path's pair matrix exceeds the 1 GiB workspace: pass a max_span");
-            if (q1 > q0 && woff.back() + w > kPairWordsMax) break;
-            woff.push_back(woff.back() + w);
-            ++q1;
-        }
-        const uint32_t n_chunk = q1 - q0;
+        for (uint32_t q = q0; q < q0 + n_chunk; ++q) woff.push_back(woff.back() + shortcut_shape(ps.h_len[q], 1, max_span).words);
         HIP_TRY(grow(ps.sp_woff, (size_t)n_chunk + 1));
         HIP_TRY(grow(ps.sp_bits, woff.back()));
         HIP_TRY(hipMemcpyAsync(ps.sp_woff.p, woff.data(), woff.size() * sizeof(uint64_t), hipMemcpyHostToDevice, b->stream));
-        const PairArgs a{ps.d_off.p, ps.len.p, ps.rows.p, ps.sp_woff.p, ps.sp_bits.p, woff.back(), q0, n_chunk, max_span, 0, filt_base};
+        // the extracted rows are the shortcut's rows (m = 1); the per-problem tables from q0 on, the per-row ones whole
+        const ShortcutArgs a{ps.len.p + q0, ps.d_off.p + q0, ps.rows.p, ps.sp_woff.p, ps.sp_bits.p, woff.back(), n_chunk, 1, max_span, 0, filt_base};
+        const ShortcutOut out{ps.sp_cost.p, ps.sp_par.p, ps.sp_idx.p, ps.sp_len.p + q0, ps.sp_raw.p + q0, ps.sp_simp.p + q0, ps.sp_checks.p + q0};
         HIP_TRY(clk.mark(Paths::kBegin, b->stream));
-        launch_path_pairs(b->dp, a, b->stream);
+        launch_shortcut_pairs(b->dp, a, false, b->stream);
         HIP_TRY(hipGetLastError());
         HIP_TRY(clk.mark(Paths::kMid, b->stream));
-        launch_path_dp(b->dp, a, out, b->stream);
+        launch_shortcut_dp(b->dp.space, b->dp.dim, a, out, b->stream);
         HIP_TRY(hipGetLastError());
         HIP_TRY(clk.mark(Paths::kEnd, b->stream));
         HIP_TRY(hipStreamSynchronize(b->stream));   // (woff is rebuilt by the next round)
         ps.ms[1] += clk.ms(Paths::kBegin, Paths::kMid);
         ps.ms[2] += clk.ms(Paths::kMid, Paths::kEnd);
         ps.rounds++;
-        q0 = q1;
     }
     ps.simp_ok = true;
     return OXHIP_OK;
@@ -1462,8 +1455,9 @@ int32_t oxhip_rrt_batch_path_valid_matrix(oxhip_rrt_batch* b, uint32_t problem, 
     *len_out = L;
     if ((uint64_t)L * L > cap_bytes) return fail(OXHIP_ERR_CAPACITY, "matrix buffer too small");
     if (!out || L == 0) return OXHIP_OK;
-    const uint64_t words = path_pair_words(L, max_span);
-    if (words > kPairWordsMax) return fail(OXHIP_ERR_CAPACITY, "a path's pair matrix exceeds the 1 GiB workspace: pass a max_span");
+    const ShortcutShape sh = shortcut_shape(L, 1, max_span);
+    const uint64_t words = sh.words;
+    if (!shortcut_fits(sh, kShortcutMatrixBytes)) return fail(OXHIP_ERR_CAPACITY, "a path's pair matrix exceeds the 1 GiB workspace: pass a max_span");
     double filt_base = 0.0;
     OX_TRY(pair_params(b, filt_base));
     // the pair kernel on a round of this one problem (its own buffers: a simplified result stays as it is)
@@ -1471,18 +1465,12 @@ int32_t oxhip_rrt_batch_path_valid_matrix(oxhip_rrt_batch* b, uint32_t problem, 
     const uint64_t woff[2] = {0, words};
     OX_TRY(to_device(d_woff, woff, 2, b->stream));
     HIP_TRY(d_bits.alloc(words ? words : 1));
-    const PairArgs a{b->paths.d_off.p, b->paths.len.p, b->paths.rows.p, d_woff.p, d_bits.p, words, problem, 1, max_span, 0, filt_base};
-    launch_path_pairs(b->dp, a, b->stream);
+    const ShortcutArgs a{b->paths.len.p + problem, b->paths.d_off.p + problem, b->paths.rows.p, d_woff.p, d_bits.p, words, 1, 1, max_span, 0, filt_base};
+    launch_shortcut_pairs(b->dp, a, false, b->stream);
     HIP_TRY(hipGetLastError());
     std::vector<uint64_t> bits(words);
     OX_TRY(to_host(bits.data(), d_bits, words, b->stream));
-    const uint32_t S = max_span == 0 || max_span > L - 1 ? L - 1 : max_span;
-    std::memset(out, 0, (size_t)L * L);
-    for (uint32_t i = 0; i + 1 < L; ++i)
-        for (uint32_t d = 1; d <= S && i + d < L; ++d) {
-            const uint64_t slot = (uint64_t)(d - 2) * L + i;
-            out[(size_t)i * L + i + d] = d == 1 ? 1 : (uint8_t)((bits[slot >> 6] >> (slot & 63)) & 1u);
-        }
+    shortcut_matrix_bytes(bits.data(), L, 1, max_span, out);
     return OXHIP_OK;
 }
 

@@ -10,12 +10,14 @@
 // and pair_params over the pure threshold functions below; and the entry points' shared openings (setup_done / in_range / ready),
 // rules (drop_derived, reset_tree_caches, upload_radii) and bodies (copy_tree, op_batch with a PooledStream).  oxhip_prm_api.hip takes
 // the same resolution helpers for validate_prm_config, DevBuf for its workspaces and its roadmap, prm_bfs_path, the graph search of
-// Planner::solve, and a PhaseClock per service for its phase times.  No device code.
+// Planner::solve, and a PhaseClock per service for its phase times.  Both take the shortcut's shape, rounds and matrix expansion
+// (shortcut_shape, shortcut_rounds, shortcut_matrix_bytes); shortcut_shape is the one piece the kernels of shortcut_core.hip call too.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <deque>
@@ -118,7 +120,7 @@ inline double star_edge_threshold(double r, double h_lo, double h_hi) {
 // The largest coordinate magnitude the midpoint filter's absolute margin (1e-9 of it) has to cover, at least 1: the bounds, the
 // sphere centres and, where given, the starts.  A planner's launch passes the starts: its thresholds are fixed before the launch
 // and a start may lie outside the bounds, whereas every other tree node lies inside them.  The kernels that check motions between
-// states a caller may have planted (path_simplify.hip, rrt_revalidate.hip) pass null: they widen this base per motion by both of
+// states a caller may have planted (shortcut_core.hip, rrt_revalidate.hip) pass null: they widen this base per motion by both of
 // its ends (SeqSpace::motion_margin, seq_space.hpp), so the starts are in play there without being named here.
 inline double filter_maxabs(const oxhip_rrt_config& cfg, const std::vector<double>& centres, const std::vector<double>* starts) {
     double maxabs = 1.0;
@@ -126,6 +128,66 @@ inline double filter_maxabs(const oxhip_rrt_config& cfg, const std::vector<doubl
     if (starts) for (double v : *starts) maxabs = std::fmax(maxabs, std::fabs(v));
     for (double v : centres) maxabs = std::fmax(maxabs, std::fabs(v));
     return maxabs;
+}
+
+// ---- the shortcut of a path (shortcut_core.hip, DESIGN.md sections 18 and 25): its shape, a batch's rounds and the bit matrix as
+// bytes.  Pure arithmetic, tests/cpp/test_shortcut_host.cpp.  A path of L original states with every edge in m parts:
+struct ShortcutShape {
+    uint64_t rows;     // M = (L - 1) m + 1 rows q_0 .. q_{M-1}, q_{k m} = p_k; 0 for no path
+    uint64_t window;   // W = span * m, span = max_span original edges (0 or beyond L - 1: all L - 1); pairs (u, v) with v - u <= W
+    uint64_t words;    // 64-bit words of the bit matrix: bit (d - 2) * M + u is check_motion(q_u, q_{u + d}), 2 <= d <= W
+    uint64_t checks;   // pairs of the window that are not on one original edge: the motion checks evaluated
+};
+__host__ __device__ inline ShortcutShape shortcut_shape(uint32_t L, uint32_t m, uint32_t max_span) {
+    if (L == 0) return ShortcutShape{0, 0, 0, 0};
+    const uint32_t full = L - 1u;
+    ShortcutShape s;
+    s.rows = (uint64_t)full * m + 1u;
+    s.window = (uint64_t)(max_span == 0u || max_span > full ? full : max_span) * m;
+    s.words = s.window < 2u ? 0u : ((s.window - 1u) * s.rows + 63u) / 64u;
+    // pairs with 1 <= d <= W: sum of (M - d); of them on one edge: m (m + 1) / 2 per original edge
+    s.checks = s.window * s.rows - s.window * (s.window + 1u) / 2u - (uint64_t)full * ((uint64_t)m * (m + 1ull) / 2ull);
+    return s;
+}
+
+constexpr uint64_t kShortcutMatrixBytes = 1ull << 30;   // a round's bit matrices stay within this
+constexpr uint64_t kShortcutRowsMax = 0x7FFFFFFFull;    // of one path: the kernels index its rows with 32 bits (an RRT path is shorter:
+                                                        // two chains of at most 2^30 nodes, less the shared connection point)
+
+// whether a round can hold this path at all
+inline bool shortcut_fits(const ShortcutShape& s, uint64_t budget_bytes) { return s.rows <= kShortcutRowsMax && s.words <= budget_bytes / 8u; }
+
+// The rounds of a batch of n paths: paths are taken in order while their matrices stay within budget_bytes together and, with
+// max_paths given (not 0), while the round holds fewer than that many; a round holds at least one path.  first = the first path of
+// every round, then n (empty for n = 0).  False, with `refused` the first such path, when a path does not fit a round of its own.
+inline bool shortcut_rounds(const uint32_t* len, uint32_t n, uint32_t m, uint32_t max_span, uint64_t budget_bytes, uint32_t max_paths,
+                            std::vector<uint32_t>& first, uint32_t& refused) {
+    first.clear();
+    uint64_t words = 0;
+    for (uint32_t q = 0; q < n; ++q) {
+        const ShortcutShape s = shortcut_shape(len[q], m, max_span);
+        if (!shortcut_fits(s, budget_bytes)) { refused = q; return false; }
+        if (q == 0 || (words + s.words) * 8u > budget_bytes || (max_paths != 0 && q - first.back() >= max_paths)) {
+            first.push_back(q);
+            words = 0;
+        }
+        words += s.words;
+    }
+    if (n) first.push_back(n);
+    return true;
+}
+
+// The bit matrix of one path as the M x M byte matrix of the test hooks: out[u * M + v] for u < v <= u + W is 1 on one original
+// edge and the pair's bit otherwise; every other byte is 0.
+inline void shortcut_matrix_bytes(const uint64_t* bits, uint32_t L, uint32_t m, uint32_t max_span, uint8_t* out) {
+    const ShortcutShape s = shortcut_shape(L, m, max_span);
+    const uint64_t M = s.rows;
+    std::fill(out, out + M * M, (uint8_t)0);
+    for (uint64_t u = 0; u + 1 < M; ++u)
+        for (uint64_t v = u + 1; v < M && v - u <= s.window; ++v) {
+            const uint64_t slot = (v - u - 2) * M + u;   // (read for pairs that are not on one edge only: those have d >= 2)
+            out[u * M + v] = u / m == (v - 1) / m ? 1 : (uint8_t)((bits[slot >> 6] >> (slot & 63u)) & 1ull);
+        }
 }
 
 template <typename T>

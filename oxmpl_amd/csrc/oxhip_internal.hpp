@@ -305,71 +305,61 @@ void launch_prm_shortest_init(bool so3, const PrmBatchArgs& b, const PrmShortest
 void launch_prm_shortest_labels(const PrmBatchArgs& b, const PrmShortestArgs& a, uint32_t group, hipStream_t s);
 void launch_prm_shortest_levels(const PrmBatchArgs& b, const PrmShortestArgs& a, uint32_t group, hipStream_t s);
 
-// path_simplify.hip: the solution paths of an RRT / RRTConnect / RRT* batch, extracted and shortcut on the device (DESIGN.md
-// section 18).  Problem p's raw path is rows off[p] .. off[p] + len[p] of `rows`.
+// shortcut_core.hip: the pair matrix and the shortest chain over it, for a round of n_chunk paths (DESIGN.md sections 18 and 25).
+// Every pointer is already at the round's first path: path c of the round has len[c] original states, every edge in m parts, and
+// its rows, costs, parents and indices begin at row_off[c] of `rows` / cost / par / idx (ShortcutShape, oxhip_host.hpp).
+struct ShortcutArgs {
+    const uint32_t* len;         // [n_chunk] original states of the path, 0 = none
+    const uint64_t* row_off;     // [n_chunk] first row of the path
+    const double* rows;          // the paths' rows, (L - 1) m + 1 per path
+    const uint64_t* woff;        // [n_chunk + 1] first word of every path's bit matrix within `bits`
+    uint64_t* bits;              // bit (d - 2) * M + u of a path: check_motion(q_u, q_{u + d}), 2 <= d <= W, not on one edge
+    uint64_t n_words;
+    uint32_t n_chunk, m, max_span, pad;
+    double filt_base;            // the midpoint filter's absolute margin from the bounds and the sphere centres (R^n)
+};
+struct ShortcutOut {
+    double* cost;                // per row: cost of the best chain from q_0
+    uint32_t* par;               // per row: the row before it on that chain
+    uint32_t* idx;               // the chain's rows in path order, at the path's first row
+    uint32_t* simp_len;          // [n_chunk]
+    double* raw_cost;            // [n_chunk]
+    double* simp_cost;           // [n_chunk]
+    uint64_t* checks;            // [n_chunk] motion checks evaluated
+};
+// subdivided = false: m is 1 and the space may be SO(2) (an RRT batch); true: R^1 .. R^8 and SO(3) with any m (a PRM batch)
+void launch_shortcut_pairs(const DevParams& p, const ShortcutArgs& a, bool subdivided, hipStream_t s);
+void launch_shortcut_dp(uint32_t space, uint32_t dim, const ShortcutArgs& a, const ShortcutOut& o, hipStream_t s);
+
+// path_simplify.hip: the solution paths of an RRT / RRTConnect / RRT* batch, extracted on the device.  Problem p's raw path is rows off[p] .. off[p] + len[p] of `rows`.
 struct PathArgs {
     const uint64_t* off;         // [P + 1] first row of every problem's path (read by the rows kernel only)
     uint32_t* len;               // [P] states of the path, 0 = unsolved (0xFFFFFFFF from the length kernel: corrupt chain)
     uint32_t* len_a;             // [P] of which from the start tree
     double* rows;                // [total][dim]
 };
-struct PairArgs {                // one round: the problems [q0, q0 + n_chunk)
-    const uint64_t* off;
-    const uint32_t* len;
-    const double* rows;
-    const uint64_t* woff;        // [n_chunk + 1] first word of every problem's bit matrix within `bits`
-    uint64_t* bits;              // bit (d - 2) * L + i of a problem: check_motion(p_i, p_{i + d}), 2 <= d <= span
-    uint64_t n_words;
-    uint32_t q0, n_chunk, max_span, pad;
-    double filt_base;            // the midpoint filter's absolute margin from the bounds and the sphere centres (R^n)
-};
-struct SimplifyOut {
-    double* cost;                // [total] per raw state: cost of the best chain from p_0
-    uint32_t* par;               // [total] ... and the state before it on that chain
-    uint32_t* idx;               // [total] the simplified path's indices into the raw path, at the raw path's offset
-    uint32_t* simp_len;          // [P]
-    double* raw_cost;            // [P]
-    double* simp_cost;           // [P]
-    uint64_t* checks;            // [P] motion checks evaluated
-};
 void launch_path_len(const DevParams& p, const PathArgs& a, hipStream_t s);
 void launch_path_rows(const DevParams& p, const PathArgs& a, hipStream_t s);
-uint64_t path_pair_words(uint32_t len, uint32_t max_span);   // 64-bit words of one problem's bit matrix
-void launch_path_pairs(const DevParams& p, const PairArgs& a, hipStream_t s);
-void launch_path_dp(const DevParams& p, const PairArgs& a, const SimplifyOut& o, hipStream_t s);
 
-// prm_path_simplify.hip: the answered paths of a PRM batch, subdivided into m parts per edge and shortcut on the device
-// (DESIGN.md section 25).  One round serves the queries [q0, q0 + n_chunk); row c of a per-round array is query q0 + c, and the
-// dense arrays hold the round's dense paths back to back (doff).
+// prm_path_simplify.hip: the answered paths of a PRM batch, subdivided into m parts per edge for shortcut_core.hip and the chains
+// compacted after it.  One round serves the queries [q0, q0 + n_chunk); the dense arrays hold the round's
+// dense paths back to back (doff).
 struct DenseArgs {
     const uint64_t* off;         // [Q + 1] first raw row of every query's path   (whole batch)
-    const uint32_t* len;         // [Q] raw states of the path, 0 = not answered
     const double* rows;          // [total][width] the raw rows
     const uint64_t* doff;        // [n_chunk + 1] first dense row of every query of the round
-    const uint64_t* woff;        // [n_chunk + 1] first word of every query's bit matrix within `bits`
     double* dense;               // [n_rows][width] the dense paths
-    uint64_t* bits;              // bit (d - 2) * M + u of a query: check_motion(q_u, q_{u + d}), 2 <= d <= W, not on one edge
-    uint64_t n_words, n_rows;
-    uint32_t q0, n_chunk, m, max_span;
-    double filt_base;            // the midpoint filter's absolute margin from the bounds and the sphere centres (R^n)
+    uint64_t n_rows;
+    uint32_t q0, n_chunk, m, pad;
 };
 struct DenseOut {
-    double* cost;                // [n_rows] per dense state: cost of the best chain from q_0
-    uint32_t* par;               // [n_rows] ... and the state before it on that chain
-    uint32_t* idx;               // [n_rows] the chain's dense indices in path order, at the query's dense offset
-    uint32_t* simp_len;          // [n_chunk]
-    double* raw_cost;            // [n_chunk]
-    double* simp_cost;           // [n_chunk]
-    uint64_t* checks;            // [n_chunk] pairs of the window that are not on one edge
-    const uint64_t* soff;        // [n_chunk + 1] the gather's: first compact row of every query
+    const uint32_t* simp_len;    // [n_chunk] the chains' lengths ...
+    const uint32_t* idx;         // [n_rows] ... and their dense indices in path order, at the query's dense offset
+    const uint64_t* soff;        // [n_chunk + 1] first compact row of every query
     uint32_t* out_idx;           // [compact rows]
     double* out_rows;            // [compact rows][width]
 };
-uint64_t dense_path_rows(uint32_t len, uint32_t m);                       // M = (L - 1) m + 1, 0 for no path
-uint64_t dense_pair_words(uint32_t len, uint32_t m, uint32_t max_span);   // 64-bit words of one query's bit matrix
 void launch_dense_rows(bool so3, uint32_t dim, const DenseArgs& a, hipStream_t s);
-void launch_dense_pairs(const DevParams& p, const DenseArgs& a, hipStream_t s);
-void launch_dense_dp(bool so3, uint32_t dim, const DenseArgs& a, const DenseOut& o, hipStream_t s);
-void launch_dense_gather(uint32_t width, const DenseArgs& a, const DenseOut& o, hipStream_t s);
+void launch_dense_gather(uint32_t width, const DenseArgs& a, const DenseOut& g, hipStream_t s);
 
 }  // namespace oxhip

@@ -1680,8 +1680,6 @@ namespace {
 
 enum SimplifyMark { kSpStageBegin, kSpStageEnd, kSpRoundBegin, kSpRowsEnd, kSpPairsEnd, kSpDpEnd, kSpCopyBegin, kSpCopyEnd };
 
-constexpr uint64_t kSimplifyMatrixBytes = 1ull << 30;   // a round's bit matrices stay within this
-
 // what every call of this service opens with: the handle, setup(), and -- for the calls that read the last batch -- the batch
 int32_t simplify_ready(const oxhip_prm* h, bool needs_batch) {
     if (!h) return fail(OXHIP_ERR_BAD_ARG, "null handle");
@@ -1695,13 +1693,8 @@ int32_t check_subdivide(uint32_t subdivide) {
     return OXHIP_OK;
 }
 
-// the size of one path's dense form and matrix, refused when no round could hold it
-int32_t dense_shape(uint32_t len, uint32_t m, uint32_t max_span, uint64_t& rows, uint64_t& words) {
-    rows = dense_path_rows(len, m);
-    words = dense_pair_words(len, m, max_span);
-    if (rows > 0x7FFFFFFFull || words * 8ull > kSimplifyMatrixBytes)
-        return fail(OXHIP_ERR_CAPACITY, "one path's pair matrix is larger than 1 GiB: pass a max_span or a smaller subdivide");
-    return OXHIP_OK;
+int32_t path_too_large() {
+    return fail(OXHIP_ERR_CAPACITY, "one path's pair matrix is larger than 1 GiB: pass a max_span or a smaller subdivide");
 }
 
 // one simplify while it runs: its shape, its rounds [first[r], first[r + 1]) and a round's tables on the host
@@ -1714,19 +1707,32 @@ struct SimplifyRun {
     std::vector<uint32_t> simp_len;
 };
 
+// a round's three views of the handle's workspaces: the subdivision, the shortcut over the dense rows, the gather
 DenseArgs dense_args(oxhip_prm* h, const SimplifyRun& run, uint32_t q0, uint32_t c) {
     DenseArgs a{};
-    a.off = h->simplify.d_off.p; a.len = h->simplify.d_len.p; a.rows = h->simplify.d_rows.p;
-    a.doff = h->simplify.d_doff.p; a.woff = h->simplify.d_woff.p; a.dense = h->simplify.d_dense.p; a.bits = h->simplify.d_bits.p;
-    a.q0 = q0; a.n_chunk = c; a.m = run.m; a.max_span = run.max_span;
+    a.off = h->simplify.d_off.p; a.rows = h->simplify.d_rows.p; a.doff = h->simplify.d_doff.p; a.dense = h->simplify.d_dense.p;
+    a.q0 = q0; a.n_chunk = c; a.m = run.m;
+    return a;
+}
+
+ShortcutArgs shortcut_args(oxhip_prm* h, const SimplifyRun& run, const DenseArgs& d) {
+    ShortcutArgs a{};
+    a.len = h->simplify.d_len.p + d.q0; a.row_off = d.doff; a.rows = d.dense; a.woff = h->simplify.d_woff.p; a.bits = h->simplify.d_bits.p;
+    a.n_words = run.woff[d.n_chunk]; a.n_chunk = d.n_chunk; a.m = run.m; a.max_span = run.max_span;
     a.filt_base = h->dp.filt_abs;
     return a;
 }
 
-DenseOut dense_out(oxhip_prm* h) {
-    DenseOut o{};
+ShortcutOut shortcut_out(oxhip_prm* h) {
+    ShortcutOut o{};
     o.cost = h->simplify.d_cost.p; o.par = h->simplify.d_par.p; o.idx = h->simplify.d_idx.p; o.simp_len = h->simplify.d_simp_len.p;
     o.raw_cost = h->simplify.d_raw.p; o.simp_cost = h->simplify.d_simp.p; o.checks = h->simplify.d_checks.p;
+    return o;
+}
+
+DenseOut dense_out(oxhip_prm* h) {
+    DenseOut o{};
+    o.simp_len = h->simplify.d_simp_len.p; o.idx = h->simplify.d_idx.p;
     o.soff = h->simplify.d_soff.p; o.out_idx = h->simplify.d_out_idx.p; o.out_rows = h->simplify.d_out_rows.p;
     return o;
 }
@@ -1752,25 +1758,21 @@ int32_t stage_paths(oxhip_prm* h, const SimplifyRun& run) {
     return OXHIP_OK;
 }
 
-// The rounds -- queries are taken in order while their matrices stay within 1 GiB together and, with chunk_queries given, while
-// the round holds fewer than that many -- and every buffer the largest of them needs
+// The rounds (shortcut_rounds: at most 65,535 queries each, fewer with chunk_queries given) and every buffer the largest needs
 int32_t reserve_simplify_workspace(oxhip_prm* h, SimplifyRun& run, uint32_t chunk_queries) {
-    const uint32_t limit = chunk_queries ? std::min(chunk_queries, 65535u) : 65535u;
-    uint64_t rows = 0, words = 0;
-    run.first.assign(1, 0u);
-    auto close_round = [&](uint32_t q) {
+    uint32_t refused = 0;
+    if (!shortcut_rounds(h->batch.len.data(), run.Q, run.m, run.max_span, kShortcutMatrixBytes,
+                         chunk_queries ? std::min(chunk_queries, 65535u) : 65535u, run.first, refused))
+        return path_too_large();
+    for (size_t r = 0; r + 1 < run.first.size(); ++r) {
+        uint64_t rows = 0, words = 0;
+        for (uint32_t q = run.first[r]; q < run.first[r + 1]; ++q) {
+            const ShortcutShape s = shortcut_shape(h->batch.len[q], run.m, run.max_span);
+            rows += s.rows; words += s.words;
+        }
         run.max_rows = std::max(run.max_rows, rows); run.max_words = std::max(run.max_words, words);
-        run.max_chunk = std::max(run.max_chunk, q - run.first.back());
-        run.first.push_back(q);
-        rows = words = 0;
-    };
-    for (uint32_t q = 0; q < run.Q; ++q) {
-        uint64_t r = 0, w = 0;
-        OX_TRY(dense_shape(h->batch.len[q], run.m, run.max_span, r, w));
-        if (q > run.first.back() && ((words + w) * 8ull > kSimplifyMatrixBytes || q - run.first.back() >= limit)) close_round(q);
-        rows += r; words += w;
+        run.max_chunk = std::max(run.max_chunk, run.first[r + 1] - run.first[r]);
     }
-    if (run.Q) close_round(run.Q);
     auto& sp = h->simplify;
     const size_t c1 = (size_t)run.max_chunk + 1, nr = std::max<size_t>(1, run.max_rows);
     HIP_TRY(sp.d_doff.reserve(c1)); HIP_TRY(sp.d_woff.reserve(c1)); HIP_TRY(sp.d_soff.reserve(c1));
@@ -1788,11 +1790,11 @@ int32_t subdivide_round(oxhip_prm* h, SimplifyRun& run, DenseArgs& a) {
     const uint32_t c = a.n_chunk;
     run.doff[0] = run.woff[0] = 0;
     for (uint32_t i = 0; i < c; ++i) {
-        const uint32_t len = h->batch.len[a.q0 + i];
-        run.doff[i + 1] = run.doff[i] + dense_path_rows(len, run.m);
-        run.woff[i + 1] = run.woff[i] + dense_pair_words(len, run.m, run.max_span);
+        const ShortcutShape s = shortcut_shape(h->batch.len[a.q0 + i], run.m, run.max_span);
+        run.doff[i + 1] = run.doff[i] + s.rows;
+        run.woff[i + 1] = run.woff[i] + s.words;
     }
-    a.n_rows = run.doff[c]; a.n_words = run.woff[c];
+    a.n_rows = run.doff[c];
     HIP_TRY(sp.clk.mark(kSpRoundBegin, h->stream));
     HIP_TRY(hipMemcpyAsync(sp.d_doff.p, run.doff.data(), ((size_t)c + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(sp.d_woff.p, run.woff.data(), ((size_t)c + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
@@ -1803,15 +1805,15 @@ int32_t subdivide_round(oxhip_prm* h, SimplifyRun& run, DenseArgs& a) {
 }
 
 // check_motion per pair of the round's windows that is not on one edge, against the obstacles as they are now
-int32_t pairs_round(oxhip_prm* h, const DenseArgs& a) {
-    launch_dense_pairs(h->dp, a, h->stream);
+int32_t pairs_round(oxhip_prm* h, const ShortcutArgs& a) {
+    launch_shortcut_pairs(h->dp, a, true, h->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(h->simplify.clk.mark(kSpPairsEnd, h->stream));
     return OXHIP_OK;
 }
 
-int32_t dp_round(oxhip_prm* h, const DenseArgs& a, const DenseOut& o) {
-    launch_dense_dp(h->so3, h->cfg.dim, a, o, h->stream);
+int32_t dp_round(oxhip_prm* h, const ShortcutArgs& a, const ShortcutOut& o) {
+    launch_shortcut_dp(h->dp.space, h->cfg.dim, a, o, h->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(h->simplify.clk.mark(kSpDpEnd, h->stream));
     return OXHIP_OK;
@@ -1895,13 +1897,15 @@ int32_t oxhip_prm_batch_simplify_paths(oxhip_prm* h, uint32_t subdivide, uint32_
     run.Q = (uint32_t)h->batch.status.size(); run.m = subdivide; run.max_span = max_span; run.width = h->cfg.dim;
     OX_TRY(reserve_simplify_workspace(h, run, chunk_queries));   // (refuses a path too large before anything is staged: the last results stay)
     OX_TRY(stage_paths(h, run));
-    const DenseOut o = dense_out(h);
+    const ShortcutOut o = shortcut_out(h);
+    const DenseOut g = dense_out(h);
     for (size_t r = 0; r + 1 < run.first.size(); ++r) {
-        DenseArgs a = dense_args(h, run, run.first[r], run.first[r + 1] - run.first[r]);
-        OX_TRY(subdivide_round(h, run, a));
+        DenseArgs d = dense_args(h, run, run.first[r], run.first[r + 1] - run.first[r]);
+        OX_TRY(subdivide_round(h, run, d));
+        const ShortcutArgs a = shortcut_args(h, run, d);
         OX_TRY(pairs_round(h, a));
         OX_TRY(dp_round(h, a, o));
-        OX_TRY(collect_round(h, run, a, o));
+        OX_TRY(collect_round(h, run, d, g));
         ++h->simplify.rounds;
     }
     h->simplify.valid = true;
@@ -1939,8 +1943,9 @@ int32_t oxhip_prm_batch_path_valid_matrix(oxhip_prm* h, uint32_t query, uint32_t
     OX_TRY(check_subdivide(subdivide));
     if (query >= h->batch.status.size()) return fail(OXHIP_ERR_BAD_ARG, "query index beyond the last batch");
     const uint32_t L = h->batch.len[query], width = h->cfg.dim, m = subdivide;
-    uint64_t M = 0, words = 0;
-    OX_TRY(dense_shape(L, m, max_span, M, words));
+    const ShortcutShape sh = shortcut_shape(L, m, max_span);
+    const uint64_t M = sh.rows, words = sh.words;
+    if (!shortcut_fits(sh, kShortcutMatrixBytes)) return path_too_large();
     *len_out = (uint32_t)M;
     if (!out || M == 0) return OXHIP_OK;
     if (cap_bytes < M * M) return fail(OXHIP_ERR_CAPACITY, "matrix buffer too small");
@@ -1953,22 +1958,15 @@ int32_t oxhip_prm_batch_path_valid_matrix(oxhip_prm* h, uint32_t query, uint32_t
     OX_TRY(to_device(d_len, &L, 1, h->stream));
     OX_TRY(to_device(d_rows, h->batch.rows.data() + (size_t)h->batch.off[query] * width, (size_t)L * width, h->stream));
     HIP_TRY(d_dense.alloc((size_t)M * width)); HIP_TRY(d_bits.alloc(std::max<size_t>(1, words)));
-    DenseArgs a{};
-    a.off = d_off.p; a.len = d_len.p; a.rows = d_rows.p; a.doff = d_doff.p; a.woff = d_woff.p; a.dense = d_dense.p; a.bits = d_bits.p;
-    a.n_words = words; a.n_rows = M; a.q0 = 0; a.n_chunk = 1; a.m = m; a.max_span = max_span; a.filt_base = h->dp.filt_abs;
-    launch_dense_rows(h->so3, width, a, h->stream);
-    launch_dense_pairs(h->dp, a, h->stream);
+    DenseArgs d{};
+    d.off = d_off.p; d.rows = d_rows.p; d.doff = d_doff.p; d.dense = d_dense.p; d.n_rows = M; d.q0 = 0; d.n_chunk = 1; d.m = m;
+    const ShortcutArgs a{d_len.p, d_doff.p, d_dense.p, d_woff.p, d_bits.p, words, 1, m, max_span, 0, h->dp.filt_abs};
+    launch_dense_rows(h->so3, width, d, h->stream);
+    launch_shortcut_pairs(h->dp, a, true, h->stream);
     HIP_TRY(hipGetLastError());
     std::vector<uint64_t> bits(words);
     OX_TRY(to_host(bits.data(), d_bits, words, h->stream));
-    const uint32_t full = L - 1u;
-    const uint64_t Wd = (uint64_t)(max_span == 0u || max_span > full ? full : max_span) * m;
-    std::memset(out, 0, (size_t)(M * M));
-    for (uint64_t u = 0; u + 1 < M; ++u)
-        for (uint64_t v = u + 1; v < M && v - u <= Wd; ++v) {
-            const uint64_t slot = (v - u - 2) * M + u;   // (read for pairs that are not on one edge only: those have d >= 2)
-            out[u * M + v] = u / m == (v - 1) / m ? 1 : (uint8_t)((bits[slot >> 6] >> (slot & 63u)) & 1ull);
-        }
+    shortcut_matrix_bytes(bits.data(), L, m, max_span, out);
     return OXHIP_OK;
 }
 

@@ -1,5 +1,6 @@
 // seq_space.hpp -- the state space as ONE thread sees it: the kernels in which a thread owns a state or a motion of its own (PRM's
-// query sets, the re-check, the shortcutter's pair matrix, the shortest paths' weights) are written once over SeqSpace<DIM>.
+// query sets, the re-check, the shortcut's pair matrix and DP -- shortcut_core.hip, one pair of kernels for an RRT batch's paths and a
+// PRM batch's --, the shortest paths' weights) are written once over SeqSpace<DIM>.
 // DIM = 1..8 is R^DIM, DIM = 0 is SO(3) (unit quaternions among forbidden cones), DIM = -1 is SO(2) (one angle among forbidden
 // arcs).  The members forward to motion_seq.hpp / so3_motion_seq.hpp / so3_device.hpp / so2_device.hpp, so every bit is the one
 // those functions give.  space_dispatch is the host's way in: R^n or SO(3), and SO(2) for the callers that ask for it.
@@ -114,7 +115,7 @@ struct SeqSpace<-1> {                              // SO(2)
 // The host's way to an instantiation: f(std::integral_constant<int, D>{}) with D = dim in LO..8 (a caller that never sees R^1
 // passes LO = 2) -- for kernels that exist over R^n only -- and space_dispatch below it, which takes the oxhip_space_kind: D = 0
 // for SO(3) and, for a caller that opts in with SO2 = true, D = -1 for SO(2).  Without the opt-in nothing is instantiated over
-// SO(2): the PRM files do not ask (no roadmap is built over SO(2)), the RRT re-check and the shortcutter do.
+// SO(2): the PRM files do not ask (no roadmap is built over SO(2)), the RRT re-check and the shortcut's RRT entry do.
 template <int LO = 1, typename F>
 void dim_dispatch(uint32_t dim, F&& f) {
     if constexpr (LO <= 1)

@@ -229,7 +229,7 @@ extern "C" {
     pub fn oxhip_rrt_batch_get_goal_tree(b: *mut OxhipRrtBatch, problem: u32, states: *mut f64, parents: *mut i32, cap_nodes: u32, n_nodes: *mut u32) -> i32;
     pub fn oxhip_rrt_batch_get_costs(b: *mut OxhipRrtBatch, problem: u32, costs: *mut f64, cap_nodes: u32, n_nodes: *mut u32) -> i32;
     pub fn oxhip_rrt_batch_last_timing(b: *mut OxhipRrtBatch, kernel_ms: *mut f64, launches: *mut u32, kernel_kind: *mut u32) -> i32;
-    // the whole batch's solution paths, extracted and shortcut on the device (path_simplify.hip)
+    // the whole batch's solution paths, extracted and shortcut on the device (path_simplify.hip, shortcut_core.hip)
     pub fn oxhip_rrt_batch_extract_paths(b: *mut OxhipRrtBatch) -> i32;
     pub fn oxhip_rrt_batch_get_paths(b: *mut OxhipRrtBatch, offsets: *mut u64, states: *mut f64, cap_states: u64, total_out: *mut u64) -> i32;
     pub fn oxhip_rrt_batch_simplify_paths(b: *mut OxhipRrtBatch, max_span: u32, chunk_problems: u32) -> i32;

@@ -177,7 +177,7 @@ def test_prm_components_kernels_resource_shape(tmp_path):
 
 def test_new_kernels_live_in_their_own_file_and_the_makefile_builds_it():
     assert re.search(r"^SRCS\s*:=.*\bprm_components\.hip\b", open(os.path.join(CSRC, "Makefile")).read(), re.M)
-    for other in ("prm_kernels.hip", "prm_batch.hip", "prm_shortest.hip", "prm_revalidate.hip", "prm_grow.hip", "path_simplify.hip"):
+    for other in ("prm_kernels.hip", "prm_batch.hip", "prm_shortest.hip", "prm_revalidate.hip", "prm_grow.hip", "path_simplify.hip", "shortcut_core.hip"):
         text = open(os.path.join(CSRC, other)).read()
         assert "prm_cc_" not in text and "prm_prune_" not in text, other
     # the hook kernel's forest is read and written through agent-scope atomics only: the find and the swap name them

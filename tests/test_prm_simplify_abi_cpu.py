@@ -1,11 +1,12 @@
 """CPU: the PRM handle's checker and shortcut entry points (oxhip_prm_is_valid .. oxhip_prm_batch_simplify_last_timing,
-prm_path_simplify.hip).
+prm_path_simplify.hip and shortcut_core.hip).
 (i)   header, capi.EXPORTS, the library and rust/oxmpl-hip/src/ffi.rs agree on the seven names and their arity; the ABI version
       and both configuration structs are what they were;
 (ii)  null handles and null pointers are OXHIP_ERR_BAD_ARG;
 (iii) the Python mirror's simplify calls before setup() carry the reference's "uninitialised" message;
-(iv)  prm_path_simplify.hip compiles for gfx950 with exactly the instantiations D = 1 .. 8 and 0 of every templated kernel,
-      without scratch or VGPR spills (from the code object's metadata alone)."""
+(iv)  prm_path_simplify.hip compiles for gfx950 with exactly the instantiations D = 1 .. 8 and 0 of its templated kernel, and
+      shortcut_core.hip with the subdivided pair matrix in the same spaces, without scratch or VGPR spills (from the code objects'
+      metadata alone)."""
 import ctypes as C
 import os
 import re
@@ -93,17 +94,26 @@ def _kernels(asm):
     return meta
 
 
-def test_prm_path_simplify_kernels_resource_shape(tmp_path):
-    out = str(tmp_path / "prm_path_simplify.s")
+def _compile(tmp_path, src):
+    out = str(tmp_path / (src[:-4] + ".s"))
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
-                           "-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, "prm_path_simplify.hip")], stderr=subprocess.DEVNULL)
-    meta = _kernels(open(out).read())
-    templated = ("dense_rows_kernel", "dense_pairs_kernel", "dense_dp_kernel")
-    for kernel in templated:
-        got = sorted(re.search(kernel + r"ILi(n?\d+)E", k).group(1) for k in meta if kernel in k)
-        assert got == sorted(str(d) for d in range(0, 9)), (kernel, got)      # D = 1 .. 8 and 0 (SO(3)); no SO(2) ("n1")
-    assert sum("dense_gather_kernel" in k for k in meta) == 1 and len(meta) == 9 * len(templated) + 1
-    for name, m in meta.items():
+                           "-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, src)], stderr=subprocess.DEVNULL)
+    return _kernels(open(out).read())
+
+
+def test_prm_path_simplify_kernels_resource_shape(tmp_path):
+    meta = _compile(tmp_path, "prm_path_simplify.hip")
+    got = sorted(re.search(r"dense_rows_kernelILi(n?\d+)E", k).group(1) for k in meta if "dense_rows_kernel" in k)
+    assert got == sorted(str(d) for d in range(0, 9)), got                    # D = 1 .. 8 and 0 (SO(3)); no SO(2) ("n1")
+    assert sum("dense_gather_kernel" in k for k in meta) == 1 and len(meta) == 9 + 1
+    # the pair matrix and the DP over the dense rows are shortcut_core.hip's: subdivided in the same spaces, and the DP in SO(2) too
+    core = _compile(tmp_path, "shortcut_core.hip")
+    for kernel, suffix, dims in (("shortcut_pairs_kernel", "Lb1", range(0, 9)), ("shortcut_dp_kernel", "", range(-1, 9))):
+        got = sorted(re.search(kernel + r"ILi(n?\d+)E" + suffix + "E", k).group(1) for k in core if re.search(kernel + r"ILin?\d+E" + suffix + "E", k))
+        assert got == sorted(str(d).replace("-", "n") for d in dims), (kernel, got)
+    for name, m in list(meta.items()) + list(core.items()):
         assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0, (name, m)
-        assert m["max_flat_workgroup_size"] == (64 if "dense_dp_kernel" in name or "dense_gather_kernel" in name else 256), (name, m)
-    assert re.search(r"^SRCS\s*:=.*\bprm_path_simplify\.hip\b", open(os.path.join(CSRC, "Makefile")).read(), re.M)
+        assert m["max_flat_workgroup_size"] == (64 if "shortcut_dp_kernel" in name or "dense_gather_kernel" in name else 256), (name, m)
+    makefile = open(os.path.join(CSRC, "Makefile")).read()
+    for src in ("prm_path_simplify.hip", "shortcut_core.hip"):
+        assert re.search(r"^SRCS\s*:=.*\b" + re.escape(src) + r"\b", makefile, re.M), src

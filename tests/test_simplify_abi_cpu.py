@@ -1,11 +1,12 @@
 """CPU: the path entry points of the RRT batch (oxhip_rrt_batch_extract_paths .. oxhip_rrt_batch_paths_last_timing,
-path_simplify.hip).
+path_simplify.hip and shortcut_core.hip).
 (i)   header, capi.EXPORTS, the library and rust/oxmpl-hip/src/ffi.rs agree on the names and their arity; the ABI version and
       both configuration structs are what they were;
 (ii)  null handles and null pointers are OXHIP_ERR_BAD_ARG;
 (iii) without a device the Python mirror reaches ERR_NO_DEVICE at setup, not a crash, and simplify_solution before setup() is
       the reference's "uninitialised" message;
-(iv)  path_simplify.hip compiles for gfx950 without scratch, VGPR spills or flat / scratch memory instructions."""
+(iv)  path_simplify.hip and shortcut_core.hip compile for gfx950 with exactly their instantiations, without scratch, VGPR spills or
+      flat / scratch memory instructions, and every shortcut kernel is a symbol of one object of the library alone."""
 import ctypes as C
 import os
 import re
@@ -96,19 +97,41 @@ def _kernels(asm):
     return meta
 
 
-def test_path_simplify_kernels_resource_shape(tmp_path):
-    out = str(tmp_path / "path_simplify.s")
+def _compile(tmp_path, src):
+    out = str(tmp_path / (src[:-4] + ".s"))
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
-                           "-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, "path_simplify.hip")], stderr=subprocess.DEVNULL)
+                           "-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, src)], stderr=subprocess.DEVNULL)
     asm = open(out).read()
-    meta = _kernels(asm)
-    # chain walk (2), pair matrix in R^2 .. R^8, SO(3) and SO(2), DP in R^n, SO(3) and SO(2)
-    assert sum("path_len_kernel" in k or "path_rows_kernel" in k for k in meta) == 2
-    assert sum("path_pairs_kernel" in k for k in meta) == 9 and sum("path_pairs_kernelILi0E" in k for k in meta) == 1   # (D = 0: SO(3))
-    assert sum("path_pairs_kernelILin1E" in k for k in meta) == 1                                                        # (D = -1: SO(2))
-    assert sum("path_dp_kernel" in k for k in meta) == 3 and len(meta) == 14
-    for name, m in meta.items():
-        assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0, (name, m)
-        body = asm.split("\n" + name + ":")[1].split("s_endpgm")[0]
-        assert len(body) > 200, name
-        assert "flat_load" not in body and "scratch_" not in body, name
+    return asm, _kernels(asm)
+
+
+def _instances(meta, kernel, suffix=""):
+    """the D of every kernel<D, ...suffix> in the metadata ("n1" is -1)"""
+    return sorted(re.search(kernel + r"ILi(n?\d+)E" + suffix + "E", k).group(1) for k in meta if re.search(kernel + r"ILin?\d+E" + suffix + "E", k))
+
+
+def test_path_simplify_kernels_resource_shape(tmp_path, L):
+    asm, meta = _compile(tmp_path, "path_simplify.hip")
+    assert sorted(re.search(r"path_\w+_kernel", k).group(0) for k in meta) == ["path_len_kernel", "path_rows_kernel"]   # the chain walks alone
+    core_asm, core = _compile(tmp_path, "shortcut_core.hip")
+    # the pair matrix with m = 1 in R^2 .. R^8, SO(3) and SO(2), subdivided in R^1 .. R^8 and SO(3); the DP in all of them
+    rn = [str(d) for d in range(2, 9)]
+    assert _instances(core, "shortcut_pairs_kernel", "Lb0") == sorted(rn + ["0", "n1"])
+    assert _instances(core, "shortcut_pairs_kernel", "Lb1") == sorted(rn + ["0", "1"])
+    assert _instances(core, "shortcut_dp_kernel") == sorted(rn + ["0", "1", "n1"])
+    assert len(core) == 9 + 9 + 10 and all("shortcut_pairs_kernel" in k or "shortcut_dp_kernel" in k for k in core)
+    for text, kernels in ((asm, meta), (core_asm, core)):
+        for name, m in kernels.items():
+            assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0, (name, m)
+            assert m["max_flat_workgroup_size"] == (256 if "shortcut_pairs_kernel" in name else 64), (name, m)
+            body = text.split("\n" + name + ":")[1].split("s_endpgm")[0]
+            assert len(body) > 200, name
+            assert "flat_load" not in body and "scratch_" not in body, name
+    # one definition: every shortcut kernel is a symbol of exactly one of the library's objects
+    srcs = re.search(r"^SRCS\s*:=(.*)$", open(os.path.join(CSRC, "Makefile")).read(), re.M).group(1).split()
+    assert "shortcut_core.hip" in srcs and "path_simplify.hip" in srcs
+    objects = {src: open(os.path.join(CSRC, src[:-4] + ".o"), "rb").read() for src in srcs}   # (the fixture built them)
+    for name in core:
+        assert [src for src, blob in objects.items() if name.encode() in blob] == ["shortcut_core.hip"], name
+    for gone in (b"path_pairs_kernel", b"path_dp_kernel", b"dense_pairs_kernel", b"dense_dp_kernel"):
+        assert not [src for src, blob in objects.items() if gone in blob], gone

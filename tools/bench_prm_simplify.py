@@ -8,7 +8,7 @@ planning"; the mean and worst simplified_cost / raw_cost.  One warm-up, then the
 The host route -- batch_paths, one oxhip_prm_check_motion call over all pairs of the dense paths, the DP in Python -- is timed
 on the first 32 answered queries and extrapolated to the batch by the number of checks: stated as extrapolated.
 
-Usage: bench_prm_simplify.py [Q=1024] [milestones=50000]     writes profiles/prm_simplify/bench.json"""
+Usage: bench_prm_simplify.py [Q=1024] [milestones=50000] [--out FILE]     writes FILE, by default profiles/prm_simplify/bench.json"""
 import json
 import os
 import statistics
@@ -20,11 +20,14 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 from oxmpl_amd import capi, scenarios  # noqa: E402
 
-Q = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-N = int(sys.argv[2]) if len(sys.argv) > 2 else 50000
+argv = [a for a in sys.argv[1:] if not a.startswith("--")]
+OUT = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "prm_simplify", "bench.json")
+if OUT in argv:
+    argv.remove(OUT)
+Q = int(argv[0]) if len(argv) > 0 else 1024
+N = int(argv[1]) if len(argv) > 1 else 50000
 SEED, REP, HOST_QUERIES = 42, 5, 32
 SUBDIVIDE = (1, 4, 16)
-OUT = os.path.join(ROOT, "profiles", "prm_simplify", "bench.json")
 
 
 def median_spread(v):
@@ -123,7 +126,7 @@ def main():
     g.close()
     text = json.dumps(out, indent=1)
     print(text)
-    os.makedirs(os.path.dirname(OUT), exist_ok=True)
+    os.makedirs(os.path.dirname(os.path.abspath(OUT)), exist_ok=True)
     with open(OUT, "w") as f:
         f.write(text + "\n")
 
